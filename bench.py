@@ -26,9 +26,16 @@ Ranks: `python bench.py --gpus N` starts N fresh child processes by itself (one 
 the GPU, torch or HIP) unless it is already running under a launcher (WORLD_SIZE set, e.g. torch.distributed.run),
 in which case --gpus must equal WORLD_SIZE.  Rank 0 prints ONE JSON line (contract in the task statement) with
   roofline      dominant kernel (encoder MFMA GEMM, HIP events around every launch of the last timed step, on the
-                stream the kernels run on) + per-phase fractions and their time-weighted mean
-  cpu_baseline  the CPU oracle (oracle/, a C restatement of the reference's candle CPU path) timed on a bounded
+                stream the kernels run on) + per-phase fractions and their time-weighted mean (with several batches in
+                flight the per-phase figures need a pass of their own: --full)
+  cpu_baseline  --full: the CPU oracle (oracle/, a C restatement of the reference's candle CPU path) timed on a bounded
                 sample of the same workload on the box's host cores (rank 0, N = 1, default workload only)
+
+A plain run sets up, warms up, times --steps steps and prints the line.  `--full` adds what takes passes of its own after
+the timed region: the one-batch-at-a-time pass (per-phase times, parity of every pipelined batch against it), the
+128-new-token and host-PCM rates, and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step returned
+(token ids, avg_logprob, no_speech_prob, no_speech_exit per clip) as finite float64 .npy files, non-finite values as codes
+beside them (dump_outputs); inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -99,7 +106,15 @@ def parse_args(argv=None):
                     help="no GPU work: the ranks rendezvous (gloo), partition the job, exchange placeholder results "
                          "through the real gather and print the JSON line with value null (CPU rehearsal of the N > 1 path)")
     ap.add_argument("--print-tokens-hash", action="store_true", help="add a hash of the gathered token ids to the line")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run what the headline does not need: the one-batch-at-a-time pass "
+                         "(per-phase roofline, results under load), the 128-new-token and host-PCM rates, the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the results of the last timed step as DIR/<name>.npy (float64, one row per clip)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -177,6 +192,54 @@ def tokens_hash(results):
     for r in results:
         h.update((",".join(map(str, r["tokens"])) + ";").encode())
     return h.hexdigest()[:16]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+NONFINITE_CODES = {"nan": 1.0, "+inf": 2.0, "-inf": 3.0}
+
+
+def split_nonfinite(a):
+    """A float array as two finite ones, losslessly: the values with every non-finite entry set to 0, and a code per entry
+    (0 finite, NONFINITE_CODES otherwise).  avg_logprob is NaN by contract whenever a step had every candidate masked
+    (model.rs:364-365 takes ln(-inf)), which the headline's random weights do on every clip."""
+    import numpy as np
+    a = np.asarray(a, np.float64)
+    code = np.zeros_like(a)
+    code[np.isnan(a)] = NONFINITE_CODES["nan"]
+    code[np.isposinf(a)] = NONFINITE_CODES["+inf"]
+    code[np.isneginf(a)] = NONFINITE_CODES["-inf"]
+    return np.where(code == 0, a, 0.0), code
+
+
+def dump_outputs(out_dir, results, ctx_len):
+    """--dump-outputs: the per-clip results a caller of the timed path receives, as finite float64 arrays (token ids are
+    exact in float64): tokens [n, ctx_len] padded with -1, n_tokens, avg_logprob and no_speech_prob (each with a
+    <name>_nonfinite code array: split_nonfinite), no_speech_exit (0/1), and `row`, the index of each row in the step's
+    results.  Beyond DUMP_LIMIT_BYTES a fixed, seeded sample of the rows is written."""
+    import numpy as np
+    n = len(results)
+    width = max([ctx_len] + [len(r["tokens"]) for r in results])
+    per_row = (width + 7) * 8
+    rows = np.arange(n)
+    if n * per_row > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // per_row, replace=False))
+    tokens = np.full((len(rows), width), -1.0)
+    for i, k in enumerate(rows):
+        t = results[k]["tokens"]
+        tokens[i, :len(t)] = t
+    arrays = {"tokens": tokens, "n_tokens": np.array([len(results[k]["tokens"]) for k in rows], np.float64)}
+    for name in ("avg_logprob", "no_speech_prob"):
+        arrays[name], arrays[name + "_nonfinite"] = split_nonfinite([results[k][name] for k in rows])
+    arrays["no_speech_exit"] = np.array([float(results[k]["no_speech_exit"]) for k in rows], np.float64)
+    arrays["row"] = rows.astype(np.float64)
+    bad = [name for name, a in arrays.items() if not np.isfinite(a).all()]
+    if bad:
+        raise RuntimeError(f"bench.py --dump-outputs: non-finite values in {bad}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -287,7 +350,7 @@ def worker(args):
             h.set_option(hip.NH_OPT_FUSE_DECODE_LAYERNORM, 0)
         hms.append(h)
     hm = hms[0]
-    want_cpu = (not args.no_cpu_baseline) and headline and world == 1 and rank == 0
+    want_cpu = args.full and (not args.no_cpu_baseline) and headline and world == 1 and rank == 0
     om = None
     if want_cpu:
         from oracle import oracle as O
@@ -401,10 +464,13 @@ def worker(args):
         dt = float(t.item())
     audio_s = total_chunks * 30.0 * args.steps
     value = audio_s / dt
+    if args.dump_outputs and rank == 0:
+        # pipeline 0's last timed batch (strong workloads: the gathered job); every step of a run transcribes the same clips
+        dump_outputs(args.dump_outputs, res, C)
 
     extra = {}
     single_ms = dt / args.steps * 1e3     # wall time of a step with one batch on the GPU (the H2D comparison below)
-    if (P > 1 or G > 1) and B:
+    if args.full and (P > 1 or G > 1) and B:
         # one batch at a time, untimed by the contract: the per-phase times (and their roofline fractions below) are taken
         # from this pass, where no other batch shares the GPU; with several batches in flight a phase's wall time
         # includes the kernels of the other batches interleaved with it
@@ -429,7 +495,7 @@ def worker(args):
             single_ms = (time.perf_counter() - t1) / n1 * 1e3
             extra["xrt_one_batch_at_a_time_per_gpu"] = B * 30.0 / (single_ms * 1e-3)
         tm = hm.timings()
-    if headline and world == 1:
+    if args.full and headline and world == 1:
         # second decode-length protocol: 128 new tokens per clip, untimed by the contract
         if args.max_new_tokens == 0:
             barrier()
@@ -473,9 +539,11 @@ def worker(args):
         if tm and tm is not tm_timed and tm["gemm_ms"] > 0:   # the same launches with nothing else on the GPU (no queueing behind other contexts)
             extra["gemm_tflops_one_batch_at_a_time"] = tm["gemm_flops"] / (tm["gemm_ms"] * 1e-3) / 1e12
         n_tok = int(np.mean([len(r["tokens"]) for r in res])) if res else 0
-        # per-phase roofline fractions of the last timed step of rank 0 (algorithmic work / phase time / nominal peak)
+        # per-phase roofline fractions of a step of rank 0 with ONE batch on the GPU (algorithmic work / phase time / nominal
+        # peak): the last timed step when one batch is in flight, else the --full pass after the timed region
+        one_batch_tm = tm if tm and (tm is not tm_timed or (P == 1 and G == 1)) else None
         phases = []
-        if tm:
+        if one_batch_tm:
             prompt = 3 if (multilingual or tk.en >= 0) else 2
             steps_dec = max(tm["decode_steps"], 1)
             dec_bytes = sum(decode_step_bytes(cfg, B, t) for t in range(steps_dec))
@@ -513,7 +581,7 @@ def worker(args):
                        "decode_tokens": n_tok, "parallelism": f"chunk-dp{world}", "batches_in_flight_per_gpu": P * G, "pipelines_per_gpu": P,
                        "encoder_batches_per_decode": G,
                        "weight_sets_per_gpu": P if args.private_weights else 1},
-            "phases_ms": {k: tm[k] for k in ("mel_ms", "encoder_ms", "cross_kv_ms", "decode_ms")} if tm else None,
+            "phases_ms": {k: tm[k] for k in ("mel_ms", "encoder_ms", "cross_kv_ms", "decode_ms")} if one_batch_tm else None,
             "decode_steps": tm["decode_steps"] if tm else 0,
             "roofline": {"bound": "mfma", "kernel": "gemm256_f16_kernel", "achieved": gemm_tflops, "peak": MFMA_PEAK_TFLOPS,
                          "unit": "TFLOP/s", "frac": gemm_tflops / MFMA_PEAK_TFLOPS, "traffic": traffic,
@@ -525,10 +593,11 @@ def worker(args):
                          "launches": tm_timed["gemm_launches"] if tm_timed else 0,
                          "avg_launch_ms": tm_timed["gemm_ms"] / max(tm_timed["gemm_launches"], 1) if tm_timed else None,
                          "flops_per_step": tm_timed["gemm_flops"] if tm_timed else None,
-                         "phases_note": "per-phase times of a step with ONE batch on the GPU" + (" (measured after the timed region; "
-                                        f"the timed region keeps {P} batches in flight)" if P > 1 else ""),
+                         "phases_note": ("per-phase times of a step with ONE batch on the GPU" + (" (measured after the timed region; "
+                                         f"the timed region keeps {P} batches in flight)" if P > 1 else "")) if one_batch_tm else
+                                        "per-phase times need a step with ONE batch on the GPU after the timed region: --full",
                          "phases": phases, "time_weighted_frac": time_weighted},
-            "extra": extra, "model_build_s": t_build,
+            "extra": extra, "model_build_s": t_build, "full": args.full,
         }
         if args.rank_share:
             sr, sn = (int(x) for x in args.rank_share.split("/"))
@@ -807,6 +876,9 @@ def worker_varlen(args, cfg, tk, world, rank, local_rank, dev, backend, gather_d
                   "wasted_row_step_frac": 1.0 - need_stream / max(fed[1][0], 1.0), "decode_steps_launched": fed[1][1],
                   "encoder_submissions": fed[1][2], "same_tokens_and_logprobs_as_lockstep": fed[1][3] == world}
         t_val = (fed[0] / args.steps if (args.pool_fed and fed is not None) else t_p / args.steps if args.pool else (t_b if args.balance else t_a))
+        if args.dump_outputs:   # the pass `value` times: the job of its last step in chunk order, or a pool's whole stream
+            dump_outputs(args.dump_outputs, res_f if (args.pool_fed and fed is not None) else res_p if args.pool else
+                         res_b if args.balance else res_a, C)
         gemm_tflops = tm["gemm_flops"] / (tm["gemm_ms"] * 1e-3) / 1e12 if tm["gemm_ms"] > 0 else 0.0
         out = {"metric": "audio-sec/wall-sec (xRT) distil-large-v3 fp16, variable decode lengths", "value": job * 30.0 / t_val,
                "unit": "audio-sec/wall-sec", "n_gpus": world, "steps": args.steps, "warmup": 1, "ms_per_step": t_val * 1e3,

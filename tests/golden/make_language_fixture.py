@@ -2,7 +2,7 @@
 """tests/golden/language_tokens.json: the language tokens in `Language::iter()` order, derived from the reference's
 src/models/whisper/languages.rs (enum variant order, lines 7-107, joined with the `token()` match arms, lines 122+).
 model.rs:204 and multilingual.rs:395-398 index the language logits in exactly this order.  Data only: 99 strings.
-Run in the build container (needs /root/reference):  python tests/golden/make_language_fixture.py"""
+Usage:  python tests/golden/make_language_fixture.py <the reference's src/models/whisper/languages.rs>"""
 import json
 import os
 import re
@@ -21,7 +21,9 @@ def parse(path):
 
 
 if __name__ == "__main__":
-    ref = sys.argv[1] if len(sys.argv) > 1 else "/root/reference/src/models/whisper/languages.rs"
+    if len(sys.argv) != 2:
+        raise SystemExit(__doc__.splitlines()[-1].strip())
+    ref = sys.argv[1]
     toks = parse(ref)
     with open(os.path.join(HERE, "language_tokens.json"), "w") as f:
         json.dump({"source": "src/models/whisper/languages.rs (MikeIvanichev/norma @ 2024_10_08)", "tokens": toks}, f, indent=0)

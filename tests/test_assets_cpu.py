@@ -127,16 +127,22 @@ def test_malformed_checkpoints_are_rejected_not_read_past_the_mapping(L, tmp_pat
     assert L.nm_gguf_list(str(bad2).encode(), lib_buf, len(lib_buf)) == -1
 
 
-def test_language_table_is_the_references_language_iter_order(L):
+def test_language_table_is_the_references_language_iter_order(L, tmp_path):
     with open(os.path.join(GOLD, "language_tokens.json")) as f:
         want = json.load(f)["tokens"]
     assert len(want) == 99 and want[0] == "<|en|>" and want[-1] == "<|su|>"
-    ref = "/root/reference/src/models/whisper/languages.rs"
-    if os.path.exists(ref):                                         # build container: re-derive from the reference file itself
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("mlf", os.path.join(GOLD, "make_language_fixture.py"))
-        m = importlib.util.module_from_spec(spec); spec.loader.exec_module(m)
-        assert m.parse(ref) == want
+    # the fixture's generator (make_language_fixture.parse) takes the order from the enum, not from the match arms: a
+    # source of the same shape with the arms sorted must give the fixture back
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("mlf", os.path.join(GOLD, "make_language_fixture.py"))
+    m = importlib.util.module_from_spec(spec); spec.loader.exec_module(m)
+    names = [t[2:-2].capitalize() for t in want]
+    src = ("pub enum Language {\n" + "".join(f"    {n},\n" for n in names) + "}\n\nimpl Language {\n    pub fn token(&self) -> &str {\n"
+           "        match self {\n" + "".join(f'            Language::{n} => "{t}",\n' for n, t in sorted(zip(names, want))) +
+           "        }\n    }\n}\n")
+    src_path = tmp_path / "languages.rs"
+    src_path.write_text(src)
+    assert m.parse(str(src_path)) == want
     got = []
     for i in range(99):
         got.append("<|" + L.nm_language_code(i).decode() + "|>")

@@ -77,3 +77,65 @@ def test_rank_share_and_length_bucket_helpers():
     run_a, need = shard.wasted_row_steps(arrival, steps)
     run_b, need_b = shard.wasted_row_steps(buckets, steps)
     assert need == need_b == sum(steps) and run_a == 4 * 400 + 4 * 380 and run_b == 4 * 45 + 4 * 400 and run_b < run_a
+
+
+def test_plain_run_options_and_steps_floor():
+    sys.path.insert(0, common.ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert a.steps == 5 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    b = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert b.full is True and b.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_writes_every_result_as_float64(tmp_path):
+    import numpy as np
+    sys.path.insert(0, common.ROOT)
+    import bench
+    res = [dict(tokens=[50258, 50259, 50359] + [100 + k] * k, avg_logprob=-0.25 * k, no_speech_prob=0.01 * k,
+                no_speech_exit=(k == 2)) for k in range(4)]
+    bench.dump_outputs(str(tmp_path), res, 8)
+    names = ("tokens", "n_tokens", "avg_logprob", "avg_logprob_nonfinite", "no_speech_prob", "no_speech_prob_nonfinite",
+             "no_speech_exit", "row")
+    assert sorted(f.name for f in tmp_path.iterdir()) == sorted(f"{n}.npy" for n in names)
+    got = {n: np.load(tmp_path / f"{n}.npy") for n in names}
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in got.values())
+    assert (got["avg_logprob_nonfinite"] == 0).all() and (got["no_speech_prob_nonfinite"] == 0).all()
+    assert got["tokens"].shape == (4, 8) and got["row"].tolist() == [0, 1, 2, 3]
+    for k, r in enumerate(res):
+        n = len(r["tokens"])
+        assert got["n_tokens"][k] == n and got["tokens"][k, :n].tolist() == r["tokens"] and (got["tokens"][k, n:] == -1).all()
+        assert got["avg_logprob"][k] == r["avg_logprob"] and got["no_speech_prob"][k] == r["no_speech_prob"]
+    assert got["no_speech_exit"].tolist() == [0, 0, 1, 0]
+
+
+def test_dump_outputs_samples_the_same_rows_beyond_the_size_limit(tmp_path, monkeypatch):
+    import numpy as np
+    sys.path.insert(0, common.ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10 * (8 + 7) * 8)    # room for 10 rows of width 8
+    res = [dict(tokens=[k, k + 1], avg_logprob=float(-k), no_speech_prob=0.0, no_speech_exit=False) for k in range(100)]
+    bench.dump_outputs(str(tmp_path / "a"), res, 8)
+    bench.dump_outputs(str(tmp_path / "b"), res, 8)
+    rows = np.load(tmp_path / "a" / "row.npy")
+    assert len(rows) == 10 and (np.diff(rows) > 0).all() and (rows == np.load(tmp_path / "b" / "row.npy")).all()
+    assert (np.load(tmp_path / "a" / "avg_logprob.npy") == -rows).all()
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_LIMIT_BYTES + 8 * 256
+
+
+def test_dump_outputs_writes_non_finite_results_as_finite_values_and_codes(tmp_path):
+    """avg_logprob is NaN whenever a step had every candidate masked (ln(-inf), as in the reference): the dump stays finite and
+    keeps which entries were NaN / +inf / -inf, so a build that changed them still compares different."""
+    import numpy as np
+    sys.path.insert(0, common.ROOT)
+    import bench
+    lp = [float("nan"), -0.5, float("-inf"), float("inf")]
+    res = [dict(tokens=[1, 2, 51865], avg_logprob=v, no_speech_prob=0.125, no_speech_exit=False) for v in lp]
+    bench.dump_outputs(str(tmp_path), res, 8)
+    assert all(np.isfinite(np.load(f)).all() for f in tmp_path.iterdir())
+    assert np.load(tmp_path / "avg_logprob.npy").tolist() == [0.0, -0.5, 0.0, 0.0]
+    assert np.load(tmp_path / "avg_logprob_nonfinite.npy").tolist() == [1.0, 0.0, 3.0, 2.0]
+    assert np.load(tmp_path / "no_speech_prob.npy").tolist() == [0.125] * 4
+    assert np.load(tmp_path / "no_speech_prob_nonfinite.npy").tolist() == [0.0] * 4
