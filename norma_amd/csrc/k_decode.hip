@@ -654,6 +654,7 @@ static void launch_skinny_ncb(const SkinnyParams &p, hipStream_t st) {
             }
             // `lds` is what the kernel uses; it is given the whole LDS of the CU (NH_LDS_EXCLUSIVE, see there)
             hipLaunchKernelGGL((skinny_lds_kernel<NCB>), dim3(256), dim3(512), lds_exclusive_bytes(lds), st, p);
+            return;
         } else if (NCB >= 3 && p.Wt && !p.ln_x && tiles <= LP_MT * 2048) {
             // 33 .. 96 rows: K in phases through the LDS (skinny_ldsp_kernel); as few phases as 144 KiB of LDS allow, balanced
             const int steps = p.K >> 5, spmax = (144 * 1024) / (16 * NCB * 64);
@@ -668,11 +669,14 @@ static void launch_skinny_ncb(const SkinnyParams &p, hipStream_t st) {
             }
             // the kernel uses sp * 16 NCB * 64 bytes; it is given the whole LDS of the CU (NH_LDS_EXCLUSIVE, see there)
             hipLaunchKernelGGL((skinny_ldsp_kernel<NCB>), dim3(256), dim3(512), lds_exclusive_bytes((size_t)sp * 16 * NCB * 64), st, p, sp);
+            return;
         } else if constexpr (NCB <= 4) {
             int waves = (tiles + 1) / 2;
             hipLaunchKernelGGL((skinny_gemm_kernel<NCB, 1, 2>), dim3((waves + 1) / 2), dim3(128), 0, st, p);
+            return;
         }
-        return;
+        // 65 .. 96 rows without the tile-major repack: no full-row form exists for NCB 5, 6 (its registers would not fit);
+        // the split-row K-sliced form below handles any number of tiles
     }
     // waves per workgroup: every wave keeps a whole number of 32-deep k-steps, and at most ~10 of them (one group of
     // loads in flight = one memory round trip per wave).  r01 split the long-K layer (fc2, K = 4 d) across workgroups
@@ -700,7 +704,10 @@ static void launch_skinny_ncb(const SkinnyParams &p, hipStream_t st) {
 #undef SKG
 }
 
-void launch_skinny(const SkinnyParams &p_in, hipStream_t st) {
+bool launch_skinny(const SkinnyParams &p_in, hipStream_t st) {
+    // the fused LayerNorm exists for the shapes skinny_ln_supported names only: any other kernel would read x instead of ln_x
+    if (p_in.ln_x && !skinny_ln_supported(p_in.R, p_in.N, p_in.K)) return false;
+    if (p_in.R < 1 || p_in.R > 96) return false;
     SkinnyParams p = p_in;
     p.ln_rk = 1.0f / (float)p.K;
     int ncb = (p.R + 15) / 16;
@@ -710,6 +717,7 @@ void launch_skinny(const SkinnyParams &p_in, hipStream_t st) {
     else if (ncb == 4) launch_skinny_ncb<4>(p, st);
     else if (ncb == 5) launch_skinny_ncb<5>(p, st);
     else launch_skinny_ncb<6>(p, st);   // R <= 96 (nh_create rejects a larger max_batch)
+    return true;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -893,7 +893,12 @@ static void skinny(nh_ctx *ctx, const half_t *x, long ldx, const LinW &W, int R,
     p.pos_ptr = pos_ptr; p.ln_x = ln_x; p.ln_w = ln_w; p.ln_b = ln_b;
     p.x = x; p.ldx = ldx; p.W = W.w; p.Wt = W.wt; p.bias = W.b; p.R = R; p.N = N; p.K = K; p.epi = epi;
     p.out[0] = o0; p.out[1] = o1; p.out[2] = o2; p.ldo = ldo; p.d = ctx->c.d_model; p.t0 = t0; p.Tn = 1; p.ctx = ctxlen;
-    launch_skinny(p, ctx->sd);
+    // every caller checks skinny_ln_supported before it passes ln_x, and R <= max_batch <= 96: a refusal is a broken invariant,
+    // and going on would leave the output as it was
+    if (!launch_skinny(p, ctx->sd)) {
+        fprintf(stderr, "norma_hip: launch_skinny refused R=%d N=%d K=%d (ln_x %s)\n", R, N, K, ln_x ? "set" : "unset");
+        abort();
+    }
 }
 
 // every decoder LayerNorm uses the "sliced" summation tree (nh_kernels.h) when the width allows, so that the fused and
@@ -1275,6 +1280,9 @@ extern "C" int nh_set_languages(nh_ctx *ctx, const int32_t *langs) {
 
 extern "C" int nh_detect_language(nh_ctx *ctx, const int32_t *lang_tokens, int n, int32_t *out_lang, float *out_probs) {
     if (!ctx || !lang_tokens || !out_lang || n < 1 || n > 256) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_detect_language: bad arguments (1 <= n <= 256)") : NH_ERR_INVALID;
+    // the probe overwrites tokens and self-K/V of rows [0, cur_batch): the busy rows of a pool would decode on from that
+    // (a pool detects languages on its encoder contexts: nh_pool_admit_from takes the language per row)
+    if (ctx->pool_rows > 0) return ctx->fail(NH_ERR_STATE, "nh_detect_language: the context runs a decode pool (nh_pool_begin)");
     if (!ctx->have_enc) return ctx->fail(NH_ERR_STATE, "nh_detect_language: call nh_encode first");
     if (!ctx->have_tokens) return ctx->fail(NH_ERR_STATE, "nh_detect_language: call nh_set_tokens first");
     hipSetDevice(ctx->dev);
@@ -1321,6 +1329,7 @@ extern "C" int nh_synchronize(nh_ctx *ctx) {
 
 extern "C" int nh_decoder_forward(nh_ctx *ctx, const int32_t *tokens, int T, float *hidden_out) {
     if (!ctx || !tokens || !hidden_out) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_decoder_forward: bad arguments") : NH_ERR_INVALID;
+    if (ctx->pool_rows > 0) return ctx->fail(NH_ERR_STATE, "nh_decoder_forward: the context runs a decode pool (nh_pool_begin)");
     if (!ctx->have_enc) return ctx->fail(NH_ERR_STATE, "nh_decoder_forward: call nh_encode first");
     const int B = ctx->cur_batch, C = ctx->c.max_target_positions, d = ctx->c.d_model, V = ctx->c.vocab_size;
     if (T < 1 || T > C) return ctx->fail(NH_ERR_INVALID, "nh_decoder_forward: T out of range");
@@ -1408,6 +1417,8 @@ extern "C" int nh_set_option(nh_ctx *ctx, int option, int value) {
     }
     else if (option == NH_OPT_ABSORBED_XATTN) {
         if (value < 0 || value > 2) return ctx->fail(NH_ERR_INVALID, "nh_set_option: NH_OPT_ABSORBED_XATTN takes 0, 1 or 2");
+        // pool steps would read xa16 rows that admission never fills (it copies the cross K/V only); nh_pool_begin refuses the reverse order
+        if (value && ctx->pool_rows > 0) return ctx->fail(NH_ERR_STATE, "nh_set_option: NH_OPT_ABSORBED_XATTN covers lockstep decodes only, and the context runs a decode pool");
         if (value == 2 && !xabs_fast_supported(ctx->c.d_model, ctx->c.decoder_attention_heads)) value = 1;   // widths the one-pass kernel is not built for
         hipSetDevice(ctx->dev);
         if (value && !ctx->xabs_u) {

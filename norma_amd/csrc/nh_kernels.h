@@ -152,7 +152,8 @@ __device__ __forceinline__ f32x4 ln_apply(const f32x4 &x, float mean, float inv,
 #endif
 // stand-alone kernel with that arithmetic (K % 128 == 0, K <= 1280); returns false when the shape is not covered
 bool launch_layernorm_sliced(const float *x, const float *w, const float *b, half_t *y, float *y32, int M, int K, hipStream_t st);
-void launch_skinny(const SkinnyParams &p, hipStream_t st);
+// false (and nothing launched) when the shape is not covered: R outside 1..96, or ln_x set where skinny_ln_supported says no
+[[nodiscard]] bool launch_skinny(const SkinnyParams &p, hipStream_t st);
 // out: ceil(N/16) * 16 * K halfs.  Tile-major: the MFMA A fragment of (16-row tile, 32-deep k-step) is 1 KiB contiguous, so a
 // GEMV streams its weights like a memcpy (the row-major form reads 16 x 64 B per wave instruction: 3.7 vs 5.1 TB/s).
 void launch_repack_tiles(const half_t *W, half_t *out, int N, int K, hipStream_t st);
@@ -190,7 +191,8 @@ void launch_mel_finish_ex(float *mel32, const unsigned *chunk_max, half_t *img, 
 
 // ---- encoder attention ---------------------------------------------------------------------------------
 // q,k: fp16 [B*S][ld] (head h at column h*64), q PRE-SCALED by NH_ENC_Q_SCALE (GemmParams::seg0_scale);
-// vt: fp16 [B][H][64][SP]; out: fp16 [B*S][ldo]
+// vt: fp16 [B][H][64][SP]; out: fp16 [B*S][ldo].  The pad columns S..SP-1 of vt are masked (their weights are exactly 0) but still
+// multiplied: they must hold finite values.  The V^T epilogue of launch_gemm never writes them; the context zeroes them once.
 #define NH_ENC_Q_SCALE (0.125f * 1.4426950408889634f)   // dh^-1/2 * log2(e), dh = 64
 void launch_enc_attention(const half_t *q, const half_t *k, long ld, const half_t *vt, half_t *out, long ldo,
                           int B, int S, int H, hipStream_t st);

@@ -120,6 +120,18 @@ def test_a_pool_fed_by_encoder_contexts_of_the_same_weight_set_gives_the_lockste
         hp.pool_admit_from(other, 0, 0)
     with pytest.raises(hip.HipError):
         hp.pool_admit_from(encs[0], batch + 3, 0)
+    # calls that would overwrite the tokens / self-K/V of busy rows, or make pool steps read xa16 rows admission never filled
+    NHS = 3  # NH_ERR_STATE
+    with pytest.raises(hip.HipError, match="decode pool") as e:
+        hp.detect_language([tk.en, tk.en + 1])
+    assert e.value.code == NHS
+    with pytest.raises(hip.HipError, match="decode pool") as e:
+        hp.decoder_forward(np.full((hp.batch, 2), tk.sot, dtype=np.int32))
+    assert e.value.code == NHS
+    with pytest.raises(hip.HipError, match="decode pool") as e:
+        hp.set_option(hip.NH_OPT_ABSORBED_XATTN, 1)
+    assert e.value.code == NHS
+    hp.set_option(hip.NH_OPT_ABSORBED_XATTN, 0)   # switching it off stays allowed
     other.close(); hp.close()
     for h in encs:
         h.close()
