@@ -1496,6 +1496,8 @@ void launch_sample_rules(const float *probs_in, int32_t *token_out, const int32_
 // probabilities round to the same value would tie in the reference and resolve to the higher index;
 // here the larger logit wins.  That needs a relative gap < 6e-8 and is far below the fp16 noise floor.)
 #define LSPLIT 8
+constexpr int LMAX = 32;  // logits per thread: ceil(51866 / 8 / 256) = 26 for the largest Whisper vocabulary
+static_assert(NH_MAX_VOCAB == LSPLIT * 256 * LMAX, "logit_step_kernel holds exactly NH_MAX_VOCAB logits in registers");
 
 __device__ __forceinline__ void merge_ms(float &m, float &s, float &ts, float m2, float s2, float ts2) {
     float mn = fmaxf(m, m2);
@@ -1518,7 +1520,6 @@ __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict
     const int per = (V + LSPLIT - 1) / LSPLIT, lo = part * per, hi = min(V, lo + per);
     // fetch the whole slice first: the statistics below are a dependent chain, the loads are not
     // (they are issued before the per-sequence state is even looked at -- one memory round trip for both)
-    constexpr int LMAX = 32;  // ceil(51866 / 8 / 256) = 26 elements per thread
     float lv[LMAX]; unsigned char sv[LMAX];
 #pragma unroll
     for (int u = 0; u < LMAX; u++) {  // unconditional (clamped) loads: a guarded load makes hipcc wait vmcnt(0) per element
@@ -1534,6 +1535,8 @@ __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict
     const int have_last = s.have_last[b], last_ts = s.last_ts[b];
     const double sum_lp_in = s.sum_logprob[b];  // prefetched for the bookkeeping at the end
     const int l1 = toks[n >= 1 ? n - 1 : 0], l2 = toks[n >= 2 ? n - 2 : 0];  // unconditional: one round trip for both
+    const float l_nt = lg[tk.no_timestamps];           // no_timestamps is text to supress_past_timestamps only (see below)
+    const int sup_nt = s.suppress[tk.no_timestamps];
     if (done) return;
     // mode 2 (decode pool): sequences join a running decode, so each is in its own phase -- position 0 of its prompt is the
     // no-speech probe, the other prompt positions only feed the caches (their next token is given), then it generates
@@ -1556,10 +1559,6 @@ __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict
     else kind = 3;
     float m = -INFINITY, se = 0.f, ts = 0.f, tsinf = 0.f, av = -INFINITY, bv = -INFINITY;
     int ai = -1, bi = -1;
-    for (int i0 = lo + 256 * LMAX; i0 < hi; i0 += 256) {  // vocabularies beyond 8 * 256 * LMAX tokens (none today)
-        int i = i0 + tid;
-        if (i < hi) { float l = lg[i]; if (l > m) { float f = __expf(m - l); se = se * f + 1.f; ts = ts * f; m = l; if (i > NT) ts += 1.f; } else { float e = __expf(l - m); se += e; if (i > NT) ts += e; } }
-    }
     // slice maximum first, then one exp per element against it (the slice lives in registers)
 #pragma unroll
     for (int u = 0; u < LMAX; u++) m = fmaxf(m, lv[u]);
@@ -1576,8 +1575,8 @@ __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict
         if (kind == 0) { if (i >= tk.zero_sec && i <= tk.one_sec) better(av, ai, l, i); }
         else if (kind == 1) { if (!is_ts && !sup) better(av, ai, l, i); }
         else if (kind == 2) { if (is_ts && i > last_ts && !sup) better(bv, bi, l, i); }
-        else if (kind == 3) {
-            if (!is_ts && !sup) better(av, ai, l, i);
+        else if (kind == 3) {  // max_text of model.rs:267-270 runs over i < no_timestamps
+            if (i < NT && !sup) better(av, ai, l, i);
             else if (is_ts && i > last_ts && !sup) better(bv, bi, l, i);
         }
     }
@@ -1658,7 +1657,10 @@ __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict
         float sum_ts = tsinf > 0.f ? -INFINITY : ts / se;          // probabilities, as the reference compares them
         float max_text = ai >= 0 ? expf(av - m) / se : -INFINITY;
         if (sum_ts >= max_text) { next = bi; lnext = bv; }          // supress_non_timestamps
-        else { next = ai; lnext = av; better(lnext, next, bv, bi); }  // supress_past_timestamps only
+        else {                                                      // supress_past_timestamps only
+            next = ai; lnext = av; better(lnext, next, bv, bi);
+            if (!sup_nt) better(lnext, next, l_nt, NT);             // left unmasked when suppress lacks it
+        }
     }
     float pv;
     if (next < 0) { next = V - 1; pv = -INFINITY; }  // every candidate masked: all -inf, last index wins (H3)

@@ -386,6 +386,11 @@ extern "C" int nh_create(int device_ordinal, const nh_config *cfg, int max_batch
                          "max_source_positions 1500, num_mel_bins 80|128, max_batch <= 96)";
         return NH_ERR_INVALID;
     }
+    if (cfg->vocab_size < 1 || cfg->vocab_size > NH_MAX_VOCAB) {
+        g_create_error = "nh_create: unsupported vocab_size " + std::to_string(cfg->vocab_size) + " (the vocabulary must hold 1 to " +
+                         std::to_string(NH_MAX_VOCAB) + " tokens: the decode step keeps a row of logits in registers)";
+        return NH_ERR_INVALID;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device_ordinal < 0 || device_ordinal >= ndev) {
         g_create_error = "nh_create: no HIP device with ordinal " + std::to_string(device_ordinal) +

@@ -17,6 +17,7 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 #define NH_SP 1536    // encoder sequence padded to a multiple of 64 for the V^T image
 #define NH_DH 64      // head dim of every Whisper size
 #define NH_MAX_DEVICES 64  // per-device caches of the launchers (one process may hold contexts on several GPUs)
+#define NH_MAX_VOCAB 65536 // launch_logit_step holds a row in registers: LSPLIT (8) workgroups x 256 threads x LMAX (32)
 
 // ---- big MFMA GEMM: C[M][N] = A[M][K] . W[N][K]^T (+bias), fp16 in, fp32 accumulate ------------
 enum GemmEpi {
@@ -236,6 +237,7 @@ struct RuleTokens { int sot, eot, lang, task, no_speech, no_timestamps, zero_sec
 // token is given), otherwise generate
 // partials: f32 [B][8][8] scratch, tickets: u32 [B] zero-initialised (the kernel re-zeroes them)
 // pos_ptr != nullptr: i32 [B], the position of every sequence; the kernel advances those it stepped
+// 1 <= V <= NH_MAX_VOCAB (nh_create refuses larger vocabularies)
 void launch_logit_step(const float *logits, int V, DecodeState s, RuleTokens tk, int B, int ctx, int cap,
                        int max_new, int prompt_len, int mode, float *partials, unsigned *tickets, int32_t *pos_ptr,
                        hipStream_t st);

@@ -21,7 +21,7 @@ ENC_Q_SCALE = float(np.float32(np.float32(0.125) * np.float32(1.4426950408889634
 SK_F16, SK_GELU_F16, SK_RESID_F32, SK_F32, SK_QKV = 0, 1, 2, 3, 4
 EPI_F16, EPI_GELU_F16, EPI_RESID_F32, EPI_CONV2_F32 = 0, 1, 2, 3
 WRAPPERS = ["kref_skinny", "kref_skinny_ln_supported", "kref_dec_attention", "kref_xabs_attention", "kref_enc_attention",
-            "kref_gemm", "kref_layernorm", "kref_embed"]
+            "kref_gemm", "kref_layernorm", "kref_embed", "kref_logit_step", "kref_sample_step", "kref_lang_detect"]
 
 # ---- loader ----------------------------------------------------------------------------------------------------------------
 _lib = None
@@ -55,6 +55,10 @@ def _argtypes():
     L.kref_gemm.argtypes = [i, vp, z, l, i, l, vp, vp, i, i, i, i, vp, vp, vp, z, i, l, i, l, l, i, i, f, i, i, vp]
     L.kref_layernorm.argtypes = [i, vp, vp, vp, vp, vp, i, i]
     L.kref_embed.argtypes = [vp, i, vp, i, vp, i, vp, i, i, i, vp, i]
+    L.kref_logit_step.argtypes = [vp, i, i, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp, vp]
+    L.kref_sample_step.argtypes = [vp, i, i, i, i, i, i, i, f, C.c_ulonglong, C.c_uint, C.c_uint, vp, vp, vp, vp, vp, vp, vp,
+                                   vp, vp]
+    L.kref_lang_detect.argtypes = [vp, i, i, vp, i, vp, vp]
     return L
 
 
@@ -354,3 +358,642 @@ def within(got, ref, bound, what):
         i = np.unravel_index(np.argmax(np.where(bad, err / bound, 0)), err.shape)
         raise AssertionError(f"{what}: {int(bad.sum())} of {err.size} outside the bound; worst at {i}: got {d64(got)[i]!r}, "
                              f"ref {d64(ref)[i]!r}, bound {bound[i]!r}")
+
+
+# ---- token selection: logit_step_kernel, sample_step_kernel, lang_detect_kernel (k_decode.hip) -------------------------------
+# model.rs:212-277, 293-370 restated literally on fp64 PROBABILITIES.  Token outputs are discrete, so the bound becomes a
+# margin: a step is *decidable* when its outcome cannot change under the kernel's arithmetic error, and the kernel must then
+# match exactly; an undecidable step accepts either candidate.  The error model, per path (PATHS):
+#   exp      logit_step_kernel takes e_i = __expf(l_i - m_t) against its thread's maximum m_t: the f32 subtraction (u|x|),
+#            v_exp_f32's scaling of the argument by log2 e (u|x|) and v_exp_f32 itself (<= 2 u) give (2|x| + 4) u with
+#            x = l_i - m <= 0 against the row maximum m.  Every merge (6 lane levels, 3 waves, 8 partials: 17 rescalings)
+#            multiplies by another __expf(m_a - m_b) of error (2|m_a - m_b| + 4) u; the maxima rise monotonically, so the
+#            |m_a - m_b| telescope to m - m_t <= |x|: per term (4|x| + 68) u  ->  a = 4, c = 68.  sample_step_kernel and
+#            lang_detect_kernel use expf (correctly rounded to ~1 ulp) on the f32 difference: (|x| + 3) u -> a = 1, c = 3.
+#   sums     all terms are positive, so a summation of depth D (roundings on the way of any partial sum) is off by <= D u
+#            relative.  logit_step: <= LMAX = 32 adds per thread + 17 merges of 3 roundings (two products, one add): D = 83.
+#            sample_step: ceil(V / 1024) adds per thread + block_sum (6 shuffles + 16 waves): D = ceil(V / 1024) + 22.
+#            lang_detect: 4 per lane + 6 shuffles: D = 10.  The f32 CPU path (numpy softmax, pairwise sums) D = 64, and the
+#            C oracle's timestamp sum is sequential: D_ts = V - no_timestamps.
+#   se       eps_se = (D + c + a sum_i p_i |x_i|) u (each term's exp error weighted by its share of the sum) + V 2^-126 (terms
+#            that flush to zero below 2^-126, against se >= 1)
+#   p_i      expf(x_i) / se: rel(i) = eps_se + (|x_i| + 3) u (expf, the f32 difference, the division)
+#   sum_ts   ts / se: eps_se + (D_ts + c + a mean_ts|x|) u + u, mean_ts weighted by the timestamps' own probabilities
+# The top two allowed candidates are decided when p1 (1 - rel1) > p2 (1 + rel2), or exactly when their f32 logits are equal
+# (then every path compares equal values and the tie rule alone decides); the TEXT decision when
+# |sum_ts - max_text| > sum_ts rel_ts + max_text rel_text, or exactly when either side is -inf.
+FIRST, SUP_TS, NON_TS, TEXT_NON_TS, TEXT_PAST = "FIRST", "SUP_TS", "NON_TS", "TEXT>NON_TS", "TEXT>PAST"
+RULE_STATES = (FIRST, SUP_TS, NON_TS, TEXT_NON_TS, TEXT_PAST)
+PATHS = {"logit_step": (4.0, 68.0, 83.0), "f32": (1.0, 3.0, 64.0), "lang": (1.0, 3.0, 10.0)}
+NH_MAX_VOCAB = 65536
+# plausible bugs the discrete references are rebuilt under (token_discriminates); each must change a decided outcome
+MUTATIONS = ("nt_as_text", "last_ts_lt", "text_gt", "window_lo", "window_hi", "sup_sum_ignored", "tie_low", "cap_off",
+             "max_new_off", "pos_prompt_stuck", "pos_prompt_twice", "done_touched")
+
+
+def sample_path(V):
+    return (1.0, 3.0, float(-(-V // 1024) + 22))
+
+
+def tk_array(tk):
+    """RuleTokens {sot, eot, lang, task, no_speech, no_timestamps, zero_sec, one_sec} of a vocab.SpecialTokens"""
+    return np.array([tk.sot, tk.eot, tk.en, tk.transcribe, tk.no_speech, tk.no_timestamps, tk.zero_sec, tk.one_sec],
+                    dtype=np.int32)
+
+
+def ldl_of(V):
+    return (V + 63) & ~63
+
+
+def softmax64(l):
+    """fp64 softmax of f32 logits; also x = l - max"""
+    l = d64(l)
+    x = l - l.max()
+    e = np.exp(x)
+    return e / e.sum(), x
+
+
+def _eps_se(p, x, path, V):
+    a, c, D = path[:3]
+    return (D + c + a * float(p @ np.abs(x))) * U32 + V * 2.0 ** -126
+
+
+def _rel(eps_se, x):
+    return eps_se + (np.abs(x) + 3.0) * U32
+
+
+class Step:
+    """outcome of one row's step: next token (-1 = none), acceptable tokens, decided flags, rule state, log-prob"""
+    __slots__ = ("state", "next", "ok", "decided", "lp", "lp_bound", "p")
+
+    def __init__(self, state, nxt, ok, decided, lp, lp_bound, p=None):
+        self.state, self.next, self.ok, self.decided, self.lp, self.lp_bound, self.p = state, nxt, ok, decided, lp, lp_bound, p
+
+
+def _rule_state(tok_hist, have_last, tk, NT):
+    n = len(tok_hist)
+    if not have_last:
+        return FIRST
+    l1 = tok_hist[-1]
+    if l1 > NT:
+        return SUP_TS if (n >= 2 and tok_hist[-2] >= tk[1]) else NON_TS
+    return "TEXT"
+
+
+def _allowed(rule, V, sup, tk, last_ts, mut):
+    i = np.arange(V)
+    NT, zs, os_ = int(tk[5]), int(tk[6]), int(tk[7])
+    past = (i > NT) & ((i < last_ts) if "last_ts_lt" in mut else (i <= last_ts))       # supress_past_timestamps (:225-243)
+    if rule == FIRST:                                                                  # first_token_supress (:336-337)
+        return (i >= zs + ("window_lo" in mut)) & (i <= os_ + ("window_hi" in mut))
+    if rule == SUP_TS:                                                                 # suppress + supress_timestamps
+        return ~sup & (i <= NT)
+    if rule == NON_TS:                                                                 # suppress + supress_non_timestamps
+        return ~sup & (i > NT) & ~past
+    return ~sup & ~past                                                                # PAST: suppress + past timestamps
+
+
+def _argmax_decide(p, l, allowed, rel, mut):
+    """arg max under total_cmp (the LAST maximum wins) over the allowed set; (winner, acceptable set, decided)"""
+    idx = np.nonzero(allowed)[0]
+    if idx.size == 0:
+        return len(p) - 1, {len(p) - 1}, True      # every entry -inf: the last index (H3), probability -inf
+    pa = p[idx]
+    top = pa.max()
+    ties = idx[pa == top]
+    w = int(ties[0] if "tie_low" in mut else ties[-1])
+    if idx.size == 1:
+        return w, {w}, True
+    rest = np.where(idx == w, -1.0, pa)
+    j = int(idx[int(np.argmax(rest))])
+    if l[j] == l[w]:
+        return w, {w}, True                           # an exact tie of f32 logits: the tie rule decides on every path
+    decided = p[w] * (1 - rel[w]) > p[j] * (1 + rel[j])
+    return w, ({w} if decided else {w, j}), bool(decided)
+
+
+def step_ref(l, tok_hist, have_last, last_ts, sup, tk, path, mut=()):
+    """one greedy token (model.rs:331-356) from f32 logits l [V] for a live row; returns a Step"""
+    V = len(l)
+    NT = int(tk[5])
+    p, x = softmax64(l)
+    eps = _eps_se(p, x, path, V)
+    rel = _rel(eps, x)
+    rule = _rule_state(tok_hist, have_last, tk, NT)
+    lv = d64(l)
+    if rule != "TEXT":
+        w, ok, dec = _argmax_decide(p, lv, _allowed(rule, V, sup, tk, last_ts, mut), rel, mut)
+        state = rule
+    else:                                                                              # model.rs:263-272
+        i = np.arange(V)
+        ts = i > NT
+        if sup[ts].any() and "sup_sum_ignored" not in mut:
+            sum_ts, rel_ts = -np.inf, 0.0
+        else:
+            pts = p[ts]
+            s = pts.sum()
+            D_ts = path[2] if len(path) < 4 else path[3]
+            rel_ts = eps + (D_ts + path[1] + path[0] * float(pts @ np.abs(x[ts])) / s) * U32 + U32
+            sum_ts = s
+        text = ((i <= NT) if "nt_as_text" in mut else (i < NT)) & ~sup
+        if text.any():
+            jt = int(np.nonzero(text)[0][np.argmax(p[text])])
+            max_text, rel_text = p[jt], rel[jt]
+        else:
+            max_text, rel_text = -np.inf, 0.0
+        non_ts = (sum_ts > max_text) if "text_gt" in mut else (sum_ts >= max_text)
+        if np.isinf(sum_ts) or np.isinf(max_text):
+            dec_rule = True
+        else:
+            dec_rule = abs(sum_ts - max_text) > sum_ts * rel_ts + max_text * rel_text
+        outs = {}
+        for r in (NON_TS, "PAST"):
+            outs[r] = _argmax_decide(p, lv, _allowed(r, V, sup, tk, last_ts, mut), rel, mut)
+        w, ok, dec = outs[NON_TS if non_ts else "PAST"]
+        state = TEXT_NON_TS if non_ts else TEXT_PAST
+        if not dec_rule:
+            ok = ok | outs["PAST" if non_ts else NON_TS][1]
+            dec = False
+    pw = p[w] if np.nonzero(_allowed_final(state, V, sup, tk, last_ts, mut, NT))[0].size else -np.inf
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lp = np.log(pw) if pw >= 0 else np.nan
+    lp_bound = rel[w] + 2.0 ** -50 if x[w] > -80 else np.inf                        # f32 p underflows below e^-87
+    return Step(state, w, ok, dec, lp, lp_bound, p)
+
+
+def _allowed_final(state, V, sup, tk, last_ts, mut, NT):
+    r = {FIRST: FIRST, SUP_TS: SUP_TS, NON_TS: NON_TS, TEXT_NON_TS: NON_TS, TEXT_PAST: "PAST"}[state]
+    return _allowed(r, V, sup, tk, last_ts, mut)
+
+
+class TokenCase:
+    """K launches of launch_logit_step (or sample_step) on one decode state.  logits f32 [K][B][ldl] (pad columns NaN),
+    state arrays as DecodeState holds them, modes / use_pos [K], admits [n][6] = {before launch, row, t0, t1, t2, P}"""
+
+    def __init__(self, name, V, tk, sup, logits, tokens, n_tokens, done, have_last, last_ts, ctx, cap, max_new, prompt_len,
+                 modes=None, use_pos=None, pos=None, admits=(), inv_t=0.0, seed=0, clip0=0, attempt=0, labels=None):
+        self.name, self.V, self.tk, self.sup = name, V, tk, sup
+        self.logits = logits
+        self.K, self.B = logits.shape[0], logits.shape[1]
+        self.tokens, self.n_tokens, self.done = tokens, n_tokens, done
+        self.have_last, self.last_ts = have_last, last_ts
+        self.sum_logprob = np.zeros(self.B)
+        self.no_speech = np.zeros(self.B)
+        self.ctx, self.cap, self.max_new, self.prompt_len = ctx, cap, max_new, prompt_len
+        self.modes = np.full(self.K, 1, np.int32) if modes is None else np.asarray(modes, np.int32)
+        self.use_pos = np.zeros(self.K, np.int32) if use_pos is None else np.asarray(use_pos, np.int32)
+        self.pos = pos
+        self.admits = np.asarray(admits, np.int32).reshape(-1, 6)
+        self.inv_t, self.seed, self.clip0, self.attempt = inv_t, seed, clip0, attempt
+        self.labels = labels if labels is not None else [""] * self.B
+
+    def state(self):
+        return dict(tokens=self.tokens.copy(), n_tokens=self.n_tokens.copy(), done=self.done.copy(),
+                    have_last=self.have_last.copy(), last_ts=self.last_ts.copy(), sum_logprob=self.sum_logprob.copy(),
+                    no_speech=self.no_speech.copy(), pos=None if self.pos is None else self.pos.copy())
+
+
+def _bookkeep(st, b, nxt, lp, tk, cap, max_new, prompt_len, mut):
+    """model.rs:359-370 (+ the max_new bench knob): push next, log-prob, cap at C - 1, eot, max_new"""
+    NT, eot = int(tk[5]), int(tk[1])
+    n = int(st["n_tokens"][b])
+    if nxt > NT:
+        st["last_ts"][b] = nxt
+        st["have_last"][b] = 1
+    st["tokens"][b, n] = nxt
+    n += 1
+    st["sum_logprob"][b] += lp
+    fin = 0
+    if (n > cap) if "cap_off" in mut else (n >= cap):
+        st["tokens"][b, n] = eot; n += 1; fin = 1
+    elif nxt == eot:
+        fin = 1
+    elif max_new > 0 and ((n - prompt_len > max_new) if "max_new_off" in mut else (n - prompt_len >= max_new)):
+        st["tokens"][b, n] = eot; n += 1; fin = 1
+    st["n_tokens"][b] = n
+    if fin:
+        st["done"][b] = 1
+
+
+def logit_step_ref(case, mut=(), path=None):
+    """the fp64 reference of case's K launches.  Returns (final state, per-row info): info[b] = dict(decided = every step of
+    the row decided, steps = [Step], lp_bound, ns_bound, ns_decided)"""
+    path = PATHS["logit_step"] if path is None else path
+    st = case.state()
+    st["tokens"] = np.concatenate([st["tokens"], np.zeros((case.B, 2 * case.K + 2), np.int32)], axis=1)   # room for a mutant's overrun
+    tk, P = case.tk, case.prompt_len
+    info = [dict(decided=True, steps=[], lp_bound=0.0, ns_bound=0.0, ns_decided=True) for _ in range(case.B)]
+    ad = [tuple(a) for a in case.admits]
+    for k in range(case.K + 1):
+        for a in [a for a in ad if a[0] == k]:                                        # pool_admit_kernel
+            _, row, t0, t1, t2, Pa = a
+            st["tokens"][row, :Pa] = [t0, t1, t2][:Pa]
+            st["n_tokens"][row], st["done"][row], st["have_last"][row], st["last_ts"][row] = Pa, 0, 0, 0
+            st["sum_logprob"][row] = st["no_speech"][row] = 0.0
+            st["pos"][row] = 0
+        if k == case.K:
+            break
+        pos = st["pos"] if case.use_pos[k] else None
+        for b in range(case.B):
+            if st["done"][b] and "done_touched" not in mut:
+                continue
+            mode = int(case.modes[k])
+            if mode == 2:
+                mp = int(pos[b])
+                mode = 0 if mp == 0 else (3 if mp < P - 1 else 1)
+                if mode == 3:                                                          # prompt phase: only the position
+                    if "pos_prompt_stuck" not in mut:
+                        pos[b] = mp + (2 if "pos_prompt_twice" in mut else 1)
+                    continue
+            l = case.logits[k, b, :case.V]
+            if pos is not None:
+                pos[b] += 1
+            if mode == 0:                                                              # model.rs:293-315
+                p, x = softmax64(l)
+                ns = int(tk[4])
+                rel = _rel(_eps_se(p, x, path, case.V), x[ns])
+                st["no_speech"][b] = p[ns]
+                info[b]["ns_bound"] = p[ns] * rel
+                info[b]["ns_decided"] &= bool(abs(p[ns] - 0.6) > p[ns] * rel)
+                if p[ns] > 0.6:
+                    st["done"][b] = 2
+                continue
+            n = int(st["n_tokens"][b])
+            s = step_ref(l, list(st["tokens"][b, :n]), int(st["have_last"][b]), int(st["last_ts"][b]), case.sup, tk, path, mut)
+            info[b]["steps"].append(s)
+            info[b]["decided"] &= s.decided
+            info[b]["lp_bound"] += s.lp_bound
+            _bookkeep(st, b, s.next, s.lp, tk, case.cap, case.max_new, P, mut)
+    st["tokens"] = st["tokens"][:, :case.ctx]
+    return st, info
+
+
+def _philox_u(seed, clip, step, attempt):
+    from oracle import oracle as O
+    r0 = O.philox([step, clip, attempt, 0x6e6f726d], [seed & 0xFFFFFFFF, seed >> 32])[0]
+    return (r0 >> 8) * 2.0 ** -24
+
+
+def sample_ref(q, rel_q, t, u):
+    """the seeded draw (include/norma_hip.h) in fp64: weights exp((q - max q) / t) over the allowed entries (q > -inf), the
+    first j whose running sum exceeds u total.  Its margin: the kernel's weight w'_i = sexp((q'_i - q'max) inv_t) differs from
+    w_i by eta_i relative, eta_i = q_i rel_i / t (the probabilities' error, carried by 1/t; the error of q'max shifts every
+    y alike and cancels in the normalisation) + 3 u |y_i|
+    (the f32 subtraction, the product, inv_t = f32(1 / t)) + 3 u (sexp's polynomial, the f32 weight); the f64 sums add
+    2^-52 V.  A relative perturbation eta of the weights moves every normalised boundary F_k by <= 2 sum_i pi_i eta_i
+    (pi = w / total), doubled for the second order: delta.  Returns (j, acceptable set, decided); j = -1: nothing allowed."""
+    al = np.isfinite(q)
+    if not al.any():
+        return -1, {-1}, True
+    qm = q[al].max()
+    y = np.where(al, (q - qm) / t, -np.inf)
+    w = np.exp(y)
+    T = w.sum()
+    F = np.cumsum(w) / T
+    j = int(np.searchsorted(F, u, side="right"))
+    j = min(j, len(q) - 1)
+    eta = np.where(al, np.abs(np.where(al, q, 0)) * rel_q / t + 3 * U32 * np.abs(np.where(al, y, 0)) + 3 * U32, 0.0)
+    delta = 4 * float((w / T) @ eta) + 2.0 ** -52 * len(q)
+    Fprev = np.concatenate([[0.0], F[:-1]])
+    ok = set(int(i) for i in np.nonzero(al & (Fprev - delta < u) & (u < F + delta))[0]) | {j}
+    return j, ok, len(ok) == 1
+
+
+def sample_step_ref(case, mut=()):
+    """fp64 reference of K launches of launch_sample_step (t = 1 / inv_t): rules as step_ref, then the seeded draw"""
+    path = sample_path(case.V)
+    st = case.state()
+    st["tokens"] = np.concatenate([st["tokens"], np.zeros((case.B, 2 * case.K + 2), np.int32)], axis=1)
+    tk = case.tk
+    t = 1.0 / float(np.float32(case.inv_t))
+    info = [dict(decided=True, steps=[], lp_bound=0.0) for _ in range(case.B)]
+    for k in range(case.K):
+        for b in range(case.B):
+            if st["done"][b] and "done_touched" not in mut:
+                continue
+            n = int(st["n_tokens"][b])
+            l = case.logits[k, b, :case.V]
+            s = step_ref(l, list(st["tokens"][b, :n]), int(st["have_last"][b]), int(st["last_ts"][b]), case.sup, tk, path, mut)
+            p, x = s.p, softmax64(l)[1]
+            allowed = _allowed_final(s.state, case.V, case.sup, tk, int(st["last_ts"][b]), mut, int(tk[5]))
+            q = np.where(allowed, p, -np.inf)
+            rel = _rel(_eps_se(p, x, path, case.V), x)
+            u = _philox_u(case.seed, case.clip0 + b, n, case.attempt)
+            j, ok, dec = sample_ref(q, rel, t, u)
+            s.ok = ok if s.decided else (s.ok | ok)   # an undecided rule state: the draw is checked against both
+            s.decided = s.decided and dec
+            info[b]["steps"].append(s)
+            info[b]["decided"] &= s.decided
+            if j < 0:                                                                  # :343-346 push eot, stop
+                st["tokens"][b, n] = tk[1]; st["n_tokens"][b] = n + 1; st["done"][b] = 1
+                continue
+            s.next = j
+            lp = np.log(p[j])
+            info[b]["lp_bound"] += rel[j] + 2.0 ** -50 if x[j] > -80 else np.inf
+            _bookkeep(st, b, j, lp, tk, case.cap, case.max_new, case.prompt_len, mut)
+    st["tokens"] = st["tokens"][:, :case.ctx]
+    return st, info
+
+
+def lang_ref(l, lang_tokens, mut=()):
+    """Model::detect_language (model.rs:194-210): fp64 softmax over the language tokens' logits and the FIRST maximum;
+    (probabilities, their bound, winner token, acceptable tokens, decided).  Bound: PATHS["lang"]."""
+    v = d64(l)[lang_tokens]
+    p, x = softmax64(v)
+    rel = _rel(_eps_se(p, x, PATHS["lang"], len(v)), x)
+    top = p.max()
+    ties = np.nonzero(p == top)[0]
+    w = int(ties[-1] if "tie_low" in mut else ties[0])     # the mutation for language: ties to the higher index
+    if len(v) == 1:
+        return p, p * rel, int(lang_tokens[w]), {int(lang_tokens[w])}, True
+    rest = p.copy(); rest[w] = -1
+    j = int(np.argmax(rest))
+    if v[j] == v[w]:
+        dec = True
+    else:
+        dec = bool(p[w] * (1 - rel[w]) > p[j] * (1 + rel[j]))
+    ok = {int(lang_tokens[w])} | (set() if dec else {int(lang_tokens[j])})
+    return p, p * rel, int(lang_tokens[w]), ok, dec
+
+
+# ---- token-selection cases (the suite's own data: tests/test_gpu_token_ref.py runs them, tests/test_kref_cpu.py checks that
+# every mutation changes a decided outcome on them) --------------------------------------------------------------------------
+def small_layout(V=1000):
+    """a short vocabulary with the Whisper order of specials: text, eot, sot, languages, tasks, no_speech, no_timestamps,
+    then timestamps"""
+    from norma_amd.vocab import SpecialTokens
+    eot = V - 200
+    return SpecialTokens(V, eot, eot + 1, eot + 2, eot + 42, eot + 43, eot + 46, eot + 47, eot + 48, 40)
+
+
+def token_layouts():
+    """(name, V, SpecialTokens, suppress list): the three Whisper vocabularies, the largest supported one and a short one"""
+    from norma_amd import vocab
+    out = [(n, vocab.VOCABS[n].n_vocab, vocab.VOCABS[n], vocab.default_suppress_tokens(n)) for n in ("EnV1", "V1", "V2")]
+    v2 = vocab.VOCABS["V2"]
+    out.append(("V2@65536", NH_MAX_VOCAB, v2, vocab.default_suppress_tokens("V2")))
+    sm = small_layout()
+    out.append(("small", sm.n_vocab, sm, [1, 2, 7, 8, 9, 10, 14, 25, sm.eot + 44]))
+    return out
+
+
+def sup_array(V, sup_list, nt, with_nt=True):
+    s = np.zeros(V, dtype=np.uint8)
+    s[[t for t in sup_list if 0 <= t < V]] = 1
+    if with_nt:
+        s[nt] = 1                         # monolingual.rs:386-395 (nh_set_tokens): suppress_tokens U {no_timestamps}
+    return s
+
+
+def edge_positions(V):
+    """index 0, V - 1, the first and last index of each of the LSPLIT = 8 slices, and lane / wave edges inside them"""
+    per = -(-V // 8)
+    pos = {0, V - 1}
+    for s in range(8):
+        lo, hi = s * per, min(V, (s + 1) * per) - 1
+        if lo >= V:
+            continue
+        pos |= {lo, hi} | {lo + e for e in (63, 64, 127, 128, 255, 256, 257) if lo + e <= hi}
+    return sorted(pos)
+
+
+def _hist(state, tk, rng, V):
+    """(tokens, have_last, last_ts) of a row in a rule state"""
+    NT, zs = tk.no_timestamps, tk.zero_sec
+    pr = [tk.sot, tk.en, tk.transcribe]
+    ts0 = int(rng.integers(zs, zs + 40))
+    if state == FIRST:
+        return pr, 0, 0
+    if state == SUP_TS:
+        return pr + [ts0], 1, ts0
+    if state == NON_TS:
+        ts1 = int(rng.integers(ts0 + 1, ts0 + 60))
+        return pr + [ts0, 11, ts1], 1, ts1
+    return pr + [ts0, 11], 1, ts0                                                      # the last token was text
+
+
+def _winner_ok(state, i, tk, sup, last_ts):
+    NT = tk.no_timestamps
+    if state == FIRST:
+        return tk.zero_sec <= i <= tk.one_sec
+    if sup[i]:
+        return False
+    if state == SUP_TS:
+        return i <= NT
+    if state in (NON_TS, TEXT_NON_TS):
+        return i > NT and i > last_ts
+    return i < NT or i > last_ts                                                       # TEXT>PAST
+
+
+def _row_logits(rng, V, ldl, tk, state, win, last_ts, sup, flat=False):
+    """f32 logits [ldl] (pad columns NaN) whose allowed winner in `state` is `win` (or, when win is not allowed there, a
+    decoy: the largest logit sits on win and the winner is some allowed token)"""
+    NT = tk.no_timestamps
+    l = np.full(ldl, np.nan, dtype=np.float32)
+    bg = np.zeros(V) if flat else rng.standard_normal(V)
+    if not flat:
+        if state == TEXT_NON_TS:
+            bg[NT + 1:] += 4.0          # timestamps carry the mass: sum_ts >= max_text
+        elif state == TEXT_PAST:
+            bg[NT + 1:] -= 4.0
+    top = bg.max()
+    if win is not None:
+        if _winner_ok(state, win, tk, sup, last_ts):
+            bg[win] = top + 5.0
+        else:
+            bg[win] = top + 7.0         # a decoy the rules must mask
+    l[:V] = bg
+    return l
+
+
+def greedy_cases(layout, seed=0):
+    """single-launch cases over every rule state x winner position, exact ties, flat logits and the special cases"""
+    name, V, tk, sl = layout
+    rng = np.random.default_rng(zlib_key(name, seed))
+    sup = sup_array(V, sl, tk.no_timestamps)
+    ldl = ldl_of(V)
+    ctx = 24
+    specs = []
+    for state in RULE_STATES:
+        for win in edge_positions(V) + [tk.zero_sec, tk.one_sec, tk.zero_sec - 1, tk.one_sec + 1, tk.no_timestamps, tk.eot]:
+            specs.append((state, win, False))
+        specs.append((state, None, True))                                              # flat logits
+    rows = []
+    for state, win, flat in specs:
+        toks, hl, lt = _hist(state, tk, rng, V)
+        rows.append((f"{state}@{'flat' if flat else win}", toks, hl, lt, _row_logits(rng, V, ldl, tk, state, win, lt, sup, flat)))
+    # exact ties between slices and between waves of a slice: two allowed tokens share the largest logit
+    per = -(-V // 8)
+    for state in RULE_STATES:
+        toks, hl, lt = _hist(state, tk, rng, V)
+        cand = sorted({i for i in edge_positions(V) + [tk.zero_sec, tk.zero_sec + 1, tk.one_sec - 1, tk.one_sec, V - 2]
+                       if _winner_ok(state, i, tk, sup, lt)})
+        for a_, b_ in [(cand[0], cand[-1])] + list(zip(cand[:-1], cand[1:]))[:6]:
+            l = _row_logits(rng, V, ldl, tk, state, None, lt, sup)
+            l[a_] = l[b_] = np.float32(np.nanmax(l[:V]) + 5.0)
+            rows.append((f"{state}@tie{a_}/{b_}", toks, hl, lt, l))
+    # the special cases: a suppressed timestamp in the TEXT state forces PAST; last_ts = V - 1 in NON_TS masks everything
+    for k in range(3):
+        toks, hl, lt = _hist("TEXT", tk, rng, V)
+        l = _row_logits(rng, V, ldl, tk, TEXT_NON_TS, None, lt, sup)
+        l[100 + 7 * k] = np.nanmax(l) + 1.0     # the largest logit is text, yet the timestamps' sum would beat it
+        rows.append((f"TEXT@sup_ts{k}", toks, hl, lt, l))
+    rows.append(("NON_TS@all_masked", [tk.sot, tk.en, tk.transcribe, tk.zero_sec, 11, V - 1], 1, V - 1,
+                 _row_logits(rng, V, ldl, tk, NON_TS, None, V - 1, sup)))
+    out = []
+    for B in (1, 7, 64, 96):
+        take = [rows[i % len(rows)] for i in range(B)] if B < len(rows) else rows + rows[:B - len(rows)]
+        if B == 1:
+            take = [rows[0]]
+        out.append(_pack(f"{name}/B{B}", V, tk, sup, [take], ctx, ctx - 1, 0, 3, done_every=5 if B > 1 else 0))
+    rest = rows[96:]
+    while rest:
+        out.append(_pack(f"{name}/B96+", V, tk, sup, [rest[:96]], ctx, ctx - 1, 0, 3, done_every=7))
+        rest = rest[96:]
+    # the special-case rows need their own suppression (a suppressed timestamp; no_timestamps left open)
+    s2 = sup.copy(); s2[tk.zero_sec + 45] = 1
+    tr = [r for r in rows if r[0].startswith("TEXT@sup_ts")]
+    out.append(_pack(f"{name}/sup_ts", V, tk, s2, [tr], ctx, ctx - 1, 0, 3))
+    out.append(_open_nt_case(name, V, tk, sup, rng, ctx))
+    return out
+
+
+def zlib_key(*key):
+    import zlib
+    return zlib.crc32(repr(key).encode())
+
+
+def _open_nt_case(name, V, tk, sup, rng, ctx):
+    """no_timestamps left out of the suppression (nh_set_tokens always adds it; the kernel must not rely on that): in the
+    TEXT state it is a PAST candidate but not part of max_text (model.rs:267-270 runs over i < no_timestamps)"""
+    NT = tk.no_timestamps
+    s = sup.copy(); s[NT] = 0
+    ldl = ldl_of(V)
+    rows = []
+    for k in range(4):
+        toks, hl, lt = _hist("TEXT", tk, rng, V)
+        l = np.full(ldl, np.nan, np.float32)
+        bg = rng.standard_normal(V)
+        p_ts = np.log(np.exp(bg[NT + 1:]).sum())
+        bg[NT] = p_ts + 1.5 + 0.3 * k          # above sum_ts: a mutant counting it as text would pick PAST
+        l[:V] = bg
+        rows.append((f"TEXT@open_nt{k}", toks, hl, lt, l))
+    # every text token suppressed, no_timestamps open, one timestamp suppressed: sum_ts = max_text = -inf, and >= picks NON_TS
+    s3 = s.copy(); s3[:NT] = 1; s3[NT + 3] = 1
+    toks, hl, lt = _hist("TEXT", tk, rng, V)
+    l = np.full(ldl, np.nan, np.float32)
+    bg = rng.standard_normal(V); bg[NT] = bg.max() + 5
+    l[:V] = bg
+    c1 = _pack(f"{name}/open_nt", V, tk, s, [rows], ctx, ctx - 1, 0, 3)
+    c2 = _pack(f"{name}/inf_tie", V, tk, s3, [[("TEXT@inf_tie", toks, hl, lt, l)]], ctx, ctx - 1, 0, 3)
+    c1.extra = c2
+    return c1
+
+
+def _pack(name, V, tk, sup, launches, ctx, cap, max_new, P, done_every=0, **kw):
+    """rows [(label, tokens, have_last, last_ts, logits)] per launch (the first launch's histories set the state)"""
+    K, B = len(launches), len(launches[0])
+    ldl = ldl_of(V)
+    logits = np.stack([np.stack([r[4] for r in rows]) for rows in launches]).astype(np.float32)
+    tokens = np.zeros((B, ctx), np.int32)
+    n = np.zeros(B, np.int32); hl = np.zeros(B, np.int32); lt = np.zeros(B, np.int32); done = np.zeros(B, np.int32)
+    for b, r in enumerate(launches[0]):
+        tokens[b, :len(r[1])] = r[1]; n[b] = len(r[1]); hl[b] = r[2]; lt[b] = r[3]
+        if done_every and b % done_every == done_every - 1:
+            done[b] = 1
+    assert logits.shape == (K, B, ldl)
+    c = TokenCase(name, V, tk_array(tk), sup.astype(bool), logits, tokens, n, done, hl, lt, ctx, cap, max_new, P,
+                  labels=[r[0] for r in launches[0]], **kw)
+    c.extra = None
+    return c
+
+
+def sequence_cases(layout, seed=0):
+    """K = 24 launches on a small ctx: rows reach the cap (C - 1), eot and max_new; random peaks move them through the rule
+    states; mode 2 on a pool with rows admitted in mixed phases (P = 2 and 3); the no-speech probe (mode 0)"""
+    name, V, tk, sl = layout
+    rng = np.random.default_rng(zlib_key(name, seed, "seq"))
+    sup = sup_array(V, sl, tk.no_timestamps)
+    ldl = ldl_of(V)
+    NT = tk.no_timestamps
+    out = []
+
+    def peak_logits(K, B, p_eot):
+        L = np.full((K, B, ldl), np.nan, np.float32)
+        for k in range(K):
+            for b in range(B):
+                bg = rng.standard_normal(V)
+                r = rng.random()
+                if r < p_eot:
+                    bg[tk.eot] = bg.max() + 6
+                elif r < 0.5:
+                    bg[int(rng.integers(NT + 1, V))] = bg.max() + 6 + rng.random()
+                else:
+                    bg[int(rng.integers(0, tk.eot))] = bg.max() + 9 + rng.random()
+                L[k, b, :V] = bg
+        return L
+
+    for max_new, p_eot in ((0, 0.0), (5, 0.0), (0, 0.06)):
+        ctx, K, B = 16, 24, 7
+        rows = [("SEQ", [tk.sot, tk.en, tk.transcribe], 0, 0, None) for _ in range(B)]
+        c = _pack(f"{name}/seq_mn{max_new}_eot{p_eot}", V, tk, sup, [[(r[0], r[1], r[2], r[3], np.zeros(ldl, np.float32))
+                                                                      for r in rows]], ctx, ctx - 1, max_new, 3, done_every=6)
+        c.logits = peak_logits(K, B, p_eot); c.K = K
+        c.modes = np.full(K, 1, np.int32); c.use_pos = np.ones(K, np.int32); c.pos = np.arange(B, dtype=np.int32) + 3
+        out.append(c)
+    for P in (2, 3):
+        ctx, K, B = 16, 10, 7
+        rows = [("POOL", [tk.sot, tk.en, tk.transcribe][:P], 0, 0, np.zeros(ldl, np.float32)) for _ in range(B)]
+        c = _pack(f"{name}/pool_P{P}", V, tk, sup, [rows], ctx, ctx - 1, 6, P)
+        c.done[:] = 1                                                                    # idle rows until admitted
+        c.done[B - 1] = 0                                                                # one row already generating
+        c.n_tokens[B - 1] = P + 1; c.tokens[B - 1, P] = 11
+        c.logits = peak_logits(K, B, 0.0); c.K = K
+        c.modes = np.full(K, 2, np.int32); c.use_pos = np.ones(K, np.int32)
+        c.pos = np.full(B, 5, np.int32)
+        c.admits = np.array(sorted([r % 4, r, tk.sot, tk.en if P == 3 else tk.transcribe, tk.transcribe, P]
+                                   for r in range(B - 1)), np.int32)
+        out.append(c)
+    # the no-speech probe: p(no_speech) spread over [0.3, 0.9] around the 0.6 threshold
+    B = 64
+    L = np.full((1, B, ldl), np.nan, np.float32)
+    for b in range(B):
+        bg = rng.standard_normal(V)
+        t = 0.3 + 0.6 * b / (B - 1)
+        so = np.exp(np.delete(bg, tk.no_speech).astype(np.float32).astype(np.float64)).sum()
+        bg[tk.no_speech] = np.log(t * so / (1 - t))
+        L[0, b, :V] = bg
+    rows = [("PROBE", [tk.sot, tk.en, tk.transcribe], 0, 0, L[0, b]) for b in range(B)]
+    c = _pack(f"{name}/probe", V, tk, sup, [rows], 16, 15, 0, 3, done_every=9)
+    c.modes = np.zeros(1, np.int32)
+    c.use_pos = np.ones(1, np.int32); c.pos = np.zeros(B, np.int32)
+    out.append(c)
+    return out
+
+
+def _sample_win(rng, V, tk, state):
+    return int(rng.integers(tk.no_timestamps + 1, V)) if state == TEXT_NON_TS else int(rng.integers(0, V))
+
+
+def sample_cases(layout, seed=0):
+    """launch_sample_step at t in {0.2, 0.6, 1.0} in every rule state (3 launches), and everything masked"""
+    name, V, tk, sl = layout
+    rng = np.random.default_rng(zlib_key(name, seed, "sample"))
+    sup = sup_array(V, sl, tk.no_timestamps)
+    ldl = ldl_of(V)
+    out = []
+    for t in (0.2, 0.6, 1.0):
+        rows = []
+        for state in RULE_STATES:
+            for k in range(10 if state == TEXT_NON_TS else 4):
+                toks, hl, lt = _hist(state if not state.startswith("TEXT") else "TEXT", tk, rng, V)
+                rows.append((state, toks, hl, lt, _row_logits(rng, V, ldl, tk, state, _sample_win(rng, V, tk, state), lt, sup)))
+        rows.append(("NON_TS@all_masked", [tk.sot, tk.en, tk.transcribe, tk.zero_sec, 11, V - 1], 1, V - 1,
+                     _row_logits(rng, V, ldl, tk, NON_TS, None, V - 1, sup)))
+        c = _pack(f"{name}/sample_t{t}", V, tk, sup, [rows], 24, 23, 0, 3, done_every=8,
+                  inv_t=float(np.float32(1.0) / np.float32(t)), seed=0x1234_5678_9abc + int(t * 10), clip0=3, attempt=1)
+        c.logits = np.concatenate([c.logits] + [np.stack([_row_logits(rng, V, ldl, tk, r[0], _sample_win(rng, V, tk, r[0]), r[3], sup)
+                                                          for r in rows])[None] for _ in range(2)])
+        c.K = 3
+        out.append(c)
+    return out

@@ -56,6 +56,14 @@ def test_create_rejects_unsupported_config_before_touching_the_device():
     cfg = config.preset("test-d128")
     with pytest.raises(hip.HipError):
         hip.HipWhisper(cfg, device=0, max_batch=0)
+    # the decode step holds at most NH_MAX_VOCAB = 65536 logits per row: larger (or empty) vocabularies are refused as
+    # invalid, by name, before any device is looked at (without a GPU a later refusal would be NH_ERR_HIP)
+    for v in (0, -1, 65537, 70000):
+        cfg = config.preset("test-d128")
+        cfg.vocab_size = v
+        with pytest.raises(hip.HipError) as e:
+            hip.HipWhisper(cfg, device=0, max_batch=1)
+        assert e.value.code == 1 and "vocab_size" in str(e.value), str(e.value)
 
 
 def test_struct_layouts_match_the_header():

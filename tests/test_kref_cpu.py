@@ -186,3 +186,121 @@ def test_xabs_bound_holds_for_an_f32_fp16_emulation_of_the_kernels():
             out[b, 64 * h:64 * h + 64] = (Wv @ z + bkv[d + 64 * h:d + 64 * h + 64]).astype(np.float16)
     K.within(out, ref, bound, "emulated absorbed attention")
     assert K.violation(ref, bound, K.xabs_attention(q, Wkv, bkv, xa[:, :-1], H)) > 0
+
+
+# ---- token selection -------------------------------------------------------------------------------------------------------
+def _oracle(layout_name):
+    import common
+    from norma_amd import vocab
+    from oracle import oracle as O
+    tk = vocab.VOCABS[layout_name]
+    name = "test-d128" if layout_name == "EnV1" else "test-d256-mel128"
+    cfg = common.make_config(name, encoder_layers=0, decoder_layers=0)
+    return O, O.OracleModel(cfg, tk, tk.en, tk.transcribe)
+
+
+def _f32_softmax(l):
+    l = np.asarray(l, np.float32)
+    e = np.exp(l - l.max())
+    return e / e.sum(dtype=np.float32)
+
+
+@pytest.mark.parametrize("lname", ["EnV1", "V2"])
+def test_token_reference_at_f32_agrees_with_the_oracle_rules(lname):
+    """the fp64 restatement, with the margin of an f32 evaluation (numpy softmax, the oracle's sequential timestamp sum),
+    picks what oracle.apply_rules + wo_argmax_total pick on every decided case, and the sampler's draw what
+    oracle.sample_token draws"""
+    import ctypes as C
+    O, om = _oracle(lname)
+    layout = [l for l in K.token_layouts() if l[0] == lname][0]
+    V, tk = layout[1], layout[2]
+    path = K.PATHS["f32"] + (float(V - tk.no_timestamps),)
+    first = om.mask(3)
+    n_dec = 0
+    for c in K.greedy_cases(layout)[:4]:
+        for b in range(c.B):
+            n = int(c.n_tokens[b])
+            toks, l = c.tokens[b, :n], c.logits[0, b, :V]
+            s = K.step_ref(l, list(toks), int(c.have_last[b]), int(c.last_ts[b]), c.sup, c.tk, path)
+            p32 = _f32_softmax(l)
+            q = om.apply_rules(p32, toks, int(c.last_ts[b])) if c.have_last[b] else p32 + first
+            got = O.lib().wo_argmax_total(q.ctypes.data_as(C.POINTER(C.c_float)), V)
+            assert got in s.ok, (c.labels[b], got, s.ok)
+            if s.decided:
+                n_dec += 1
+                assert got == s.next, (c.labels[b], got, s.next)
+    assert n_dec >= 100, n_dec
+    n_dec = 0
+    for c in K.sample_cases(layout):
+        t = 1.0 / float(np.float32(c.inv_t))
+        for b in range(c.B):
+            n = int(c.n_tokens[b])
+            toks, l = c.tokens[b, :n], c.logits[0, b, :V]
+            s = K.step_ref(l, list(toks), int(c.have_last[b]), int(c.last_ts[b]), c.sup, c.tk, path)
+            p32 = _f32_softmax(l)
+            q = om.apply_rules(p32, toks, int(c.last_ts[b])) if c.have_last[b] else p32 + first
+            p, x = K.softmax64(l)
+            allowed = np.isfinite(q)
+            rel = K._rel(K._eps_se(p, x, path, V), x)
+            u = K._philox_u(c.seed, c.clip0 + b, n, c.attempt)
+            j, ok, dec = K.sample_ref(np.where(allowed, p, -np.inf), rel, t, u)
+            got = O.sample_token(q, t, c.seed, c.clip0 + b, n, c.attempt)
+            assert got in ok, (c.labels[b], got, ok)
+            if dec and s.decided:
+                n_dec += 1
+                assert got == j
+    assert n_dec >= 20, n_dec
+    om.close()
+
+
+def _outcome(st, b):
+    return (tuple(st["tokens"][b, :st["n_tokens"][b]].tolist()), int(st["n_tokens"][b]), int(st["done"][b]),
+            int(st["have_last"][b]), int(st["last_ts"][b]), None if st["pos"] is None else int(st["pos"][b]))
+
+
+def test_token_mutations_change_a_decided_outcome_of_the_suite():
+    """each plausible bug of MUTATIONS, applied to the reference, changes the outcome of at least one decided case of the GPU
+    suite's own data (kref.greedy_cases / sequence_cases / lang cases), so a kernel with that bug fails the suite"""
+    caught = {m: 0 for m in K.MUTATIONS}
+    for layout in [l for l in K.token_layouts() if l[0] in ("V2", "small")]:
+        cases = []
+        for c in K.greedy_cases(layout) + K.sequence_cases(layout):
+            cases += [c] + ([c.extra] if c.extra is not None else [])
+        for c in cases:
+            ref, info = K.logit_step_ref(c)
+            for m in K.MUTATIONS:
+                mst, minfo = K.logit_step_ref(c, mut=(m,))
+                for b in range(c.B):
+                    if info[b]["decided"] and info[b]["ns_decided"] and _outcome(ref, b) != _outcome(mst, b):
+                        caught[m] += 1
+    # language detection: ties go to the FIRST index; the mutation sends them to the last
+    lt = np.array([5, 3, 9, 1], np.int32)
+    l = np.zeros(12, np.float32); l[[3, 1]] = 2.0
+    assert K.lang_ref(l, lt)[2] == 3 and K.lang_ref(l, lt, mut=("tie_low",))[2] == 1
+    missed = [m for m, v in caught.items() if not v]
+    print("mutations caught (decided rows changed):", caught)
+    assert not missed, f"no decided case of the suite distinguishes {missed}"
+
+
+def test_token_margins_flag_near_ties_and_accept_exact_ties():
+    from norma_amd import vocab
+    tk = vocab.VOCABS["V2"]
+    V = tk.n_vocab
+    sup = K.sup_array(V, vocab.default_suppress_tokens("V2"), tk.no_timestamps).astype(bool)
+    l = np.zeros(V, np.float32)
+    l[100] = l[200] = 5.0
+    s = K.step_ref(l, [tk.sot, tk.en, tk.transcribe, tk.zero_sec, 11, tk.zero_sec + 3], 1, tk.zero_sec + 3, sup,
+                   K.tk_array(tk), K.PATHS["logit_step"])
+    assert s.state == K.NON_TS
+    l2 = np.zeros(V, np.float32)
+    l2[400] = 5.0
+    l2[300] = np.nextafter(np.float32(5.0), np.float32(0))        # one ulp apart: not decidable
+    s = K.step_ref(l2, [tk.sot, tk.en, tk.transcribe], 0, 0, sup, K.tk_array(tk), K.PATHS["logit_step"])
+    assert s.state == K.FIRST and s.next == tk.one_sec              # the window only: flat -> the last index wins
+    t = K.tk_array(tk)
+    l[tk.no_timestamps + 1:] = -10.0                                 # TEXT -> PAST: max_text beats the timestamps' sum
+    s = K.step_ref(l, [tk.sot, tk.en, tk.transcribe, tk.zero_sec, 11], 1, tk.zero_sec, sup, t, K.PATHS["logit_step"])
+    assert s.next == 200 and s.decided                               # exact tie: the higher index, decided
+    l[200] = np.nextafter(np.float32(5.0), np.float32(0))
+    s = K.step_ref(l, [tk.sot, tk.en, tk.transcribe, tk.zero_sec, 11], 1, tk.zero_sec, sup, t, K.PATHS["logit_step"])
+    assert s.next == 100 and not s.decided and s.ok == {100, 200}

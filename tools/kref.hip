@@ -216,3 +216,125 @@ int kref_embed(const int32_t *tokens, int tok_stride, const void *E, int V, cons
 }
 
 }  // extern "C"
+
+// ---- token selection ------------------------------------------------------------------------------------------------------
+namespace {
+// device copies of a DecodeState's arrays (host arrays in and out, B rows of ctx tokens); tk: the 8 ints of RuleTokens
+struct KrefState {
+    DecodeState s{};
+    int32_t *tokens, *n_tokens, *done, *have_last, *last_ts;
+    double *sum_logprob, *no_speech;
+    int B, ctx;
+    KrefState(Bufs &b, int B_, int ctx_, int V, const uint8_t *suppress, int32_t *tokens_, int32_t *n_tokens_, int32_t *done_,
+              int32_t *have_last_, int32_t *last_ts_, double *sum_logprob_, double *no_speech_)
+        : tokens(tokens_), n_tokens(n_tokens_), done(done_), have_last(have_last_), last_ts(last_ts_), sum_logprob(sum_logprob_),
+          no_speech(no_speech_), B(B_), ctx(ctx_) {
+        s.tokens = b.in<int32_t>(tokens, (size_t)B * ctx * 4);
+        s.n_tokens = b.in<int32_t>(n_tokens, (size_t)B * 4);
+        s.done = b.in<int32_t>(done, (size_t)B * 4);
+        s.have_last = b.in<int32_t>(have_last, (size_t)B * 4);
+        s.last_ts = b.in<int32_t>(last_ts, (size_t)B * 4);
+        s.sum_logprob = b.in<double>(sum_logprob, (size_t)B * 8);
+        s.no_speech = b.in<double>(no_speech, (size_t)B * 8);
+        s.n_active = b.zeros<int32_t>(4);
+        s.suppress = b.in<uint8_t>(suppress, (size_t)V);
+    }
+    void out(Bufs &b) {
+        b.out(tokens, s.tokens, (size_t)B * ctx * 4);
+        b.out(n_tokens, s.n_tokens, (size_t)B * 4);
+        b.out(done, s.done, (size_t)B * 4);
+        b.out(have_last, s.have_last, (size_t)B * 4);
+        b.out(last_ts, s.last_ts, (size_t)B * 4);
+        b.out(sum_logprob, s.sum_logprob, (size_t)B * 8);
+        b.out(no_speech, s.no_speech, (size_t)B * 8);
+    }
+};
+RuleTokens rule_tokens(const int32_t *t) { return RuleTokens{t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7]}; }
+}  // namespace
+
+extern "C" {
+
+// K consecutive launch_logit_step on one state, launch k on logits [k][B][ldl] (ldl = V rounded up to 64, as the launcher
+// computes it) with mode modes[k] and pos_ptr = pos when use_pos[k] (else null).  admit [n_admit][6] = {before launch k, row,
+// t0, t1, t2, P}: launch_pool_admit calls, in order, ahead of launch k (k = K: after the last).  Every state array, pos [B]
+// (may be null), tickets [B] and partials [B][LSPLIT][8] are copied in and back.
+int kref_logit_step(const float *logits, int K, int V, int B, int ctx, int cap, int max_new, int prompt_len, const int32_t *modes,
+                    const int32_t *use_pos, const int32_t *tk, const uint8_t *suppress, int32_t *tokens, int32_t *n_tokens,
+                    int32_t *done, int32_t *have_last, int32_t *last_ts, double *sum_logprob, double *no_speech, int32_t *pos,
+                    const int32_t *admit, int n_admit, unsigned *tickets, float *partials) {
+    // refuse what would write out of bounds: a mode-2 launch or an admission without positions, a row outside [0, B), a
+    // live row whose next two writes do not fit below the cap
+    if (cap > ctx - 1 || V < 1 || V > NH_MAX_VOCAB) return -1;
+    for (int k = 0; k < K; k++) if (modes[k] == 2 && !(use_pos[k] && pos)) return -1;
+    for (int a = 0; a < n_admit; a++)
+        if (!pos || admit[6 * a + 1] < 0 || admit[6 * a + 1] >= B || (admit[6 * a + 5] != 2 && admit[6 * a + 5] != 3) ||
+            admit[6 * a + 5] >= cap || (a && admit[6 * a] < admit[6 * a - 6]))
+            return -1;
+    for (int r = 0; r < B; r++) if (!done[r] && (n_tokens[r] < 1 || n_tokens[r] >= cap)) return -1;
+    Bufs b;
+    Stream st;
+    const long ldl = (V + 63) & ~63;
+    const float *dl = b.in<float>(logits, (size_t)K * B * ldl * 4);
+    KrefState ks(b, B, ctx, V, suppress, tokens, n_tokens, done, have_last, last_ts, sum_logprob, no_speech);
+    int32_t *dpos = b.in<int32_t>(pos, (size_t)B * 4);
+    unsigned *dtick = b.in<unsigned>(tickets, (size_t)B * 4);
+    float *dpart = b.in<float>(partials, (size_t)B * 64 * 4);
+    KREF_CHECK(b);
+    const RuleTokens rt = rule_tokens(tk);
+    for (int k = 0, a = 0; k <= K; k++) {
+        for (; a < n_admit && admit[6 * a] == k; a++) {
+            const int32_t *e = admit + 6 * a;
+            launch_pool_admit(ks.s, dpos, dtick, e[1], ctx, e[2], e[3], e[4], e[5], st.s);
+        }
+        if (k == K) break;
+        launch_logit_step(dl + (long)k * B * ldl, V, ks.s, rt, B, ctx, cap, max_new, prompt_len, modes[k], dpart, dtick,
+                          use_pos[k] ? dpos : nullptr, st.s);
+    }
+    if (hipError_t e = st.finish()) return (int)e;
+    ks.out(b);
+    b.out(pos, dpos, (size_t)B * 4);
+    b.out(tickets, dtick, (size_t)B * 4);
+    b.out(partials, dpart, (size_t)B * 64 * 4);
+    return (int)b.err;
+}
+
+// K consecutive launch_sample_step on one state (logits [k][B][ldl] as above); clip0, attempt and seed as the launcher takes them
+int kref_sample_step(const float *logits, int K, int V, int B, int ctx, int cap, int max_new, int prompt_len, float inv_t,
+                     unsigned long long seed, unsigned clip0, unsigned attempt, const int32_t *tk, const uint8_t *suppress,
+                     int32_t *tokens, int32_t *n_tokens, int32_t *done, int32_t *have_last, int32_t *last_ts, double *sum_logprob,
+                     double *no_speech) {
+    if (cap > ctx - 1 || V < 1) return -1;
+    for (int r = 0; r < B; r++) if (!done[r] && (n_tokens[r] < 1 || n_tokens[r] >= cap)) return -1;
+    Bufs b;
+    Stream st;
+    const long ldl = (V + 63) & ~63;
+    const float *dl = b.in<float>(logits, (size_t)K * B * ldl * 4);
+    KrefState ks(b, B, ctx, V, suppress, tokens, n_tokens, done, have_last, last_ts, sum_logprob, no_speech);
+    KREF_CHECK(b);
+    const RuleTokens rt = rule_tokens(tk);
+    for (int k = 0; k < K; k++)
+        launch_sample_step(dl + (long)k * B * ldl, V, ks.s, rt, B, ctx, cap, max_new, prompt_len, inv_t, seed, clip0, attempt, st.s);
+    if (hipError_t e = st.finish()) return (int)e;
+    ks.out(b);
+    return (int)b.err;
+}
+
+// launch_lang_detect: logits [B][ldl], lang_tokens [n] (1 <= n <= 256, any order) -> probs [B][n], lang_out [B]
+int kref_lang_detect(const float *logits, int V, int B, const int32_t *lang_tokens, int n, float *probs, int32_t *lang_out) {
+    Bufs b;
+    Stream st;
+    if (n < 1 || n > 256) return -1;
+    const long ldl = (V + 63) & ~63;
+    const float *dl = b.in<float>(logits, (size_t)B * ldl * 4);
+    const int32_t *dlt = b.in<int32_t>(lang_tokens, (size_t)n * 4);
+    float *dp = b.in<float>(probs, (size_t)B * n * 4);
+    int32_t *dout = b.in<int32_t>(lang_out, (size_t)B * 4);
+    KREF_CHECK(b);
+    launch_lang_detect(dl, V, dlt, n, dp, dout, B, st.s);
+    if (hipError_t e = st.finish()) return (int)e;
+    b.out(probs, dp, (size_t)B * n * 4);
+    b.out(lang_out, dout, (size_t)B * 4);
+    return (int)b.err;
+}
+
+}  // extern "C"
