@@ -898,8 +898,8 @@ static void skinny(nh_ctx *ctx, const half_t *x, long ldx, const LinW &W, int R,
     p.pos_ptr = pos_ptr; p.ln_x = ln_x; p.ln_w = ln_w; p.ln_b = ln_b;
     p.x = x; p.ldx = ldx; p.W = W.w; p.Wt = W.wt; p.bias = W.b; p.R = R; p.N = N; p.K = K; p.epi = epi;
     p.out[0] = o0; p.out[1] = o1; p.out[2] = o2; p.ldo = ldo; p.d = ctx->c.d_model; p.t0 = t0; p.Tn = 1; p.ctx = ctxlen;
-    // every caller checks skinny_ln_supported before it passes ln_x, and R <= max_batch <= 96: a refusal is a broken invariant,
-    // and going on would leave the output as it was
+    // every caller checks skinny_ln_supported before it passes ln_x, R <= max_batch <= 96, and every K and N of the model is a
+    // multiple of 64 but the vocabulary (SK_F32): a refusal is a broken invariant, and going on would leave the output as it was
     if (!launch_skinny(p, ctx->sd)) {
         fprintf(stderr, "norma_hip: launch_skinny refused R=%d N=%d K=%d (ln_x %s)\n", R, N, K, ln_x ? "set" : "unset");
         abort();
@@ -952,13 +952,8 @@ static void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr = nullptr,
 // TextDecoder::final_linear on LN(dx) of the R rows of the last decoder_step(..., final_ln = false)
 static void logits_from_dx(nh_ctx *ctx, int R) {
     LinW E; E.w = ctx->tok_emb; E.wt = ctx->tok_emb_t; E.b = nullptr;  // tied embedding, no bias (final_linear)
-    const int d = ctx->c.d_model, V = ctx->c.vocab_size;
-    if (ctx->opt_fuse_ln && skinny_ln_supported(R, V, d)) {
-        skinny(ctx, nullptr, d, E, R, V, d, SK_F32, ctx->logits, nullptr, nullptr, ctx->VP, 0, 0, nullptr, ctx->dx, ctx->dec_ln.w, ctx->dec_ln.b);
-    } else {
-        dec_layernorm(ctx, ctx->dec_ln, ctx->dxn, nullptr, R, d);
-        skinny(ctx, ctx->dxn, d, E, R, V, d, SK_F32, ctx->logits, nullptr, nullptr, ctx->VP, 0, 0);
-    }
+    const int d = ctx->c.d_model;
+    ln_skinny(ctx, ctx->dec_ln, E, R, ctx->c.vocab_size, d, SK_F32, ctx->logits, nullptr, nullptr, ctx->VP, 0, 0, nullptr);
 }
 
 static void logits_from_dxn(nh_ctx *ctx, int R) {

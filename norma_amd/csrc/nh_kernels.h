@@ -4,6 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
+#include "skinny_plan.h"
+
 typedef _Float16 half_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 half8;
 typedef __attribute__((ext_vector_type(4))) _Float16 half4;
@@ -67,13 +71,7 @@ void launch_gemm(const GemmParams &p, hipStream_t st);
 void launch_gemm_128(const GemmParams &p, hipStream_t st);  // always the 128 x 128 kernel
 
 // ---- skinny GEMM for the decoder: y[R][N] = x[R][K] . W[N][K]^T, R <= 96 rows -------------------
-enum SkinnyEpi {
-    SK_F16 = 0,         // fp16 out (row stride ldo, per-row base offsets)
-    SK_GELU_F16 = 1,
-    SK_RESID_F32 = 2,   // f32 x[r][n] += acc + bias
-    SK_F32 = 3,         // f32 out = acc (+bias)  (logits)
-    SK_QKV = 4,         // self-attn fused q|k|v: q -> out[0] [R][d]; k,v -> caches at position t
-};
+// (enum SkinnyEpi, and which kernel serves which shape: skinny_plan.h)
 struct SkinnyParams {
     const half_t *x; long ldx;  // [R][K] fp16
     const half_t *W; const float *bias;
@@ -89,8 +87,9 @@ struct SkinnyParams {
     const float *ln_x, *ln_w, *ln_b;
     float ln_rk;  // 1.0f / K, filled in by launch_skinny
 };
-// true when launch_skinny can take its activations through the fused LayerNorm for this shape
-bool skinny_ln_supported(int R, int N, int K);
+// true when launch_skinny can take its activations through the fused LayerNorm for this shape: a question about (R, N, K)
+// alone, whatever the weight layout and the epilogue
+inline bool skinny_ln_supported(int R, int N, int K) { return skinny_plan(R, N, K, SK_F32, false, true).kind != SKP_NONE; }
 
 // ---- the decoder's LayerNorm arithmetic ("sliced") ------------------------------------------------
 // One fixed summation tree for every LayerNorm of a decode step, whether it runs fused inside a skinny GEMM, in the
@@ -153,11 +152,49 @@ __device__ __forceinline__ f32x4 ln_apply(const f32x4 &x, float mean, float inv,
 #endif
 // stand-alone kernel with that arithmetic (K % 128 == 0, K <= 1280); returns false when the shape is not covered
 bool launch_layernorm_sliced(const float *x, const float *w, const float *b, half_t *y, float *y32, int M, int K, hipStream_t st);
-// false (and nothing launched) when the shape is not covered: R outside 1..96, or ln_x set where skinny_ln_supported says no
+// false (and nothing launched) when skinny_plan refuses the shape: R outside 1..96, K % 64 != 0, N % 4 != 0 under an epilogue
+// other than SK_F32, or ln_x set where skinny_ln_supported says no
 [[nodiscard]] bool launch_skinny(const SkinnyParams &p, hipStream_t st);
 // out: ceil(N/16) * 16 * K halfs.  Tile-major: the MFMA A fragment of (16-row tile, 32-deep k-step) is 1 KiB contiguous, so a
 // GEMV streams its weights like a memcpy (the row-major form reads 16 x 64 B per wave instruction: 3.7 vs 5.1 TB/s).
 void launch_repack_tiles(const half_t *W, half_t *out, int N, int K, hipStream_t st);
+
+// ---- kernels that do not share their CU's LDS: skinny_lds_kernel, skinny_ldsp_kernel (k_skinny.hip: the "two logits kernels
+// above" of the finding below, written beside them) and xabs_main_kernel (k_dec_attn.hip) -----------------------------------------
+// The two logits kernels above keep their activations in LDS and feed every MFMA from a `ds_read_b128` -- 512 threads, 288-358
+// of a SIMD's 512 registers, 40-120 KB of LDS: other kernels' workgroups fit beside them on a CU.  r03 found that they must not:
+// the log-mel kernel of ANOTHER context (37 KB of LDS, 4 waves) gave wrong spectra in 1-250 frames of a clip whenever one of these
+// workgroups ran beside it (tools/dbg/stress_mel.py: 150-190 wrong clip-mels in 3200 next to 64-row decodes, 6 in 9600 next to
+// 32-row ones, none next to 16-row ones or with nothing running; `tools/ldsprobe` shows LDS allocations and barriers of
+// co-resident workgroups do stay apart).  Stripping the kernel showed what it takes: the LDS read feeding the MFMA -- without the
+// MFMAs (LDS reads into VALU adds), or with the MFMA's B operand taken from registers instead, the neighbour's results are right;
+// stores, weight loads and the staging writes do not matter.  No software contract covers that, so these kernels do not share
+// their CU's LDS: they ask for all of it, which keeps every LDS-using workgroup off the CU while they run (30 us per token).
+#define NH_LDS_EXCLUSIVE (160 * 1024)
+#ifdef __HIPCC__
+static inline size_t lds_exclusive_bytes(size_t needed) {
+#ifdef NH_DBG_SHARE_LDS   // tools/dbg/stress_mel.py's A/B switch, off in every build the Makefiles make: only what the kernel uses
+    return needed;
+#else
+    (void)needed;
+    return (size_t)NH_LDS_EXCLUSIVE;
+#endif
+}
+// launches Kernel, which uses lds_used bytes of dynamic LDS, with the whole LDS of its CU
+template <auto Kernel, class... Args>
+static void launch_lds_exclusive(dim3 grid, dim3 block, size_t lds_used, hipStream_t st, Args... args) {
+    // hipFuncSetAttribute acts on the CURRENT device: remember it per device (contexts on several GPUs of one
+    // process, each driven by its own host thread)
+    static std::atomic<bool> attr_set[NH_MAX_DEVICES];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= NH_MAX_DEVICES || !attr_set[dev].load(std::memory_order_acquire)) {
+        hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, NH_LDS_EXCLUSIVE);
+        if (dev >= 0 && dev < NH_MAX_DEVICES) attr_set[dev].store(true, std::memory_order_release);
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds_exclusive_bytes(lds_used), st, args...);
+}
+#endif
 
 // ---- elementwise / normalisation -------------------------------------------------------------------
 // LayerNorm over rows of f32 x[M][d] -> fp16 y[M][d] (and optionally f32 y32[M][d])
@@ -207,7 +244,7 @@ void launch_dec_attention(const half_t *q, const half_t *kc, const half_t *vc, h
                           int H, int d, int ctx, int Tk, const int32_t *pos_ptr, hipStream_t st, int kv_head_major = 0,
                           const int32_t *done = nullptr);
 
-// numerics prototype of cross-attention on the encoder output itself (NH_OPT_ABSORBED_XATTN; k_decode.hip): Wkv = the fused
+// numerics prototype of cross-attention on the encoder output itself (NH_OPT_ABSORBED_XATTN; k_dec_attn.hip): Wkv = the fused
 // [2 d][d] cross K/V projection (K rows first), bkv its bias, xa fp16 [B][S][d], U scratch fp16 [B][H][d]
 void launch_xabs_attention(const half_t *q, const half_t *Wkv, const float *bkv, const half_t *xa, half_t *U, half_t *out, int B, int H, int d, int S,
                            const int32_t *done, hipStream_t st);

@@ -19,8 +19,10 @@ SUB16 = 2.0 ** -25    # half the spacing of fp16 subnormals: the absolute part o
 NH_SP, NH_DH = 1536, 64
 ENC_Q_SCALE = float(np.float32(np.float32(0.125) * np.float32(1.4426950408889634)))
 SK_F16, SK_GELU_F16, SK_RESID_F32, SK_F32, SK_QKV = 0, 1, 2, 3, 4
+SKP_NONE, SKP_GEMM, SKP_LN, SKP_LDS, SKP_LDSP = 0, 1, 2, 3, 4      # SkinnyKind of norma_amd/csrc/skinny_plan.h
+PLAN_FIELDS = ("kind", "ncb", "nt", "ksplit", "sp", "grid_x", "grid_y", "block", "lds_used", "lds_exclusive")
 EPI_F16, EPI_GELU_F16, EPI_RESID_F32, EPI_CONV2_F32 = 0, 1, 2, 3
-WRAPPERS = ["kref_skinny", "kref_skinny_ln_supported", "kref_dec_attention", "kref_xabs_attention", "kref_enc_attention",
+WRAPPERS = ["kref_skinny", "kref_skinny_ln_supported", "kref_skinny_plan", "kref_dec_attention", "kref_xabs_attention", "kref_enc_attention",
             "kref_gemm", "kref_layernorm", "kref_embed", "kref_logit_step", "kref_sample_step", "kref_lang_detect"]
 
 # ---- loader ----------------------------------------------------------------------------------------------------------------
@@ -49,6 +51,7 @@ def _argtypes():
     vp, i, l, z, f = C.c_void_p, C.c_int, C.c_long, C.c_size_t, C.c_float
     L.kref_skinny.argtypes = [vp, l, i, i, i, vp, vp, i, i, vp, z, vp, vp, z, l, i, i, i, i, vp, i, vp, vp, vp]
     L.kref_skinny_ln_supported.argtypes = [i, i, i]
+    L.kref_skinny_plan.argtypes = [i, i, i, i, i, i, vp]
     L.kref_dec_attention.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, i, vp]
     L.kref_xabs_attention.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp, i]
     L.kref_enc_attention.argtypes = [vp, vp, l, vp, vp, l, i, i, i]
@@ -67,6 +70,16 @@ def lib():
     if L.kref_skinny.argtypes is None:
         _argtypes()
     return L
+
+
+def skinny_plan(R, N, Kd, epi, wt, ln):
+    """skinny_plan (norma_amd/csrc/skinny_plan.h) of a launch_skinny shape as a dict of PLAN_FIELDS; pure host code: the
+    wrapper library answers without a GPU"""
+    out = np.zeros(10, dtype=np.int32)
+    planned = lib().kref_skinny_plan(R, N, Kd, epi, int(wt), int(ln), ptr(out))
+    plan = dict(zip(PLAN_FIELDS, (int(v) for v in out)))
+    assert planned == (plan["kind"] != SKP_NONE)
+    return plan
 
 
 def check_rc(rc, what):
@@ -360,7 +373,7 @@ def within(got, ref, bound, what):
                              f"ref {d64(ref)[i]!r}, bound {bound[i]!r}")
 
 
-# ---- token selection: logit_step_kernel, sample_step_kernel, lang_detect_kernel (k_decode.hip) -------------------------------
+# ---- token selection: logit_step_kernel, sample_step_kernel, lang_detect_kernel (k_token.hip) -------------------------------
 # model.rs:212-277, 293-370 restated literally on fp64 PROBABILITIES.  Token outputs are discrete, so the bound becomes a
 # margin: a step is *decidable* when its outcome cannot change under the kernel's arithmetic error, and the kernel must then
 # match exactly; an undecidable step accepts either candidate.  The error model, per path (PATHS):

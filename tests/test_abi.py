@@ -20,7 +20,7 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_strict_memory_model_build_exists_and_exports_the_same_abi():
-    """The -DNH_STRICT_MEMORY_MODEL variant of k_decode.hip (portable release / acquire spelling of the logit step's
+    """The -DNH_STRICT_MEMORY_MODEL variant of k_token.hip (portable release / acquire spelling of the logit step's
     cross-workgroup hand-off) is compiled by every build so that it cannot rot; tests/test_gpu_kernels.py runs it."""
     assert os.path.exists(hip.STRICT_LIB_PATH), "make -C norma_amd/csrc builds libnorma_hip_strict.so"
     L = C.CDLL(hip.STRICT_LIB_PATH)

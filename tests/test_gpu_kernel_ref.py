@@ -48,17 +48,9 @@ def _skinny(x, W, bias, R, epi, out0, use_wt, ldo, ln=None, qkv=None):
     return out0
 
 
-# launch_skinny at d = 1280 over the row sweep, on every decoder shape.  Kernels reached (k_decode.hip):
-#   N <= 2560 tiles (QKV 3d, out-proj d, fc1 4d: 240 / 80 / 320 tiles):
-#     R <= 16               skinny_gemm_kernel<1, KS, 1>   (KS = 4 at K = 1280, 16 at K = 5120)
-#     R 17..64, few tiles   skinny_gemm_kernel<1, KS, 1> on the (tiles, NCB) grid (split rows)
-#     R 17..64, fc1         skinny_gemm_kernel<NCB, 4, 1> (unsplit, tiles * NCB > 640)
-#     R 65..96              skinny_gemm_kernel<1, KS, 1> split rows (NCB 5, 6)
-#   logits (>= 2048 tiles):
-#     R <= 32               skinny_lds_kernel<1|2>
-#     R 33..96, Wt          skinny_ldsp_kernel<3..6>
-#     R 33..64, no Wt       skinny_gemm_kernel<3|4, 1, 2>
-#     R 65..96, no Wt       skinny_gemm_kernel<1, 4, 1> split rows (the former hole: nothing was launched)
+# launch_skinny at d = 1280 over the row sweep, on every decoder shape.  Which kernel each (rows, shape, weight layout) reaches is
+# skinny_plan (norma_amd/csrc/skinny_plan.h; swept on the CPU by tests/test_kref_cpu.py); test_skinny_sweeps_reach_every_kernel
+# asserts through it that these sweeps reach every kernel family and form.
 SHAPES = [  # (name, N, K, epilogue)
     ("qkv-f16", 3 * D, D, K.SK_F16),
     ("outproj-resid", D, D, K.SK_RESID_F32),
@@ -80,6 +72,43 @@ def test_skinny_row_sweep_matches_fp64(name, N, Kd, epi):
 def test_skinny_width_sweep_matches_fp64(d):
     for name, N, Kd, epi in [("outproj-f16", d, d, K.SK_F16), ("fc1-gelu", 4 * d, d, K.SK_GELU_F16), ("fc2-resid", d, 4 * d, K.SK_RESID_F32)]:
         _run_skinny(f"{name}-d{d}", N, Kd, epi, WIDTH_ROWS)
+
+
+def _kernel(R, N, Kd, epi, wt, ln=0):
+    pl = K.skinny_plan(R, N, Kd, epi, wt, ln)
+    return pl["kind"], pl["ncb"], pl["nt"], pl["ksplit"], pl["grid_y"]
+
+
+def test_skinny_sweeps_reach_every_kernel():
+    """what the sweeps of this file rely on reaching, asserted through skinny_plan: (kind, ncb, nt, ksplit, grid.y)"""
+    G, LN, LDS, LDSP = K.SKP_GEMM, K.SKP_LN, K.SKP_LDS, K.SKP_LDSP
+    f16, resid, gelu, f32 = K.SK_F16, K.SK_RESID_F32, K.SK_GELU_F16, K.SK_F32
+    for wt in (0, 1):
+        # up to 2560 tiles (QKV 3d, out-proj d, fc1 4d: 240 / 80 / 320 tiles)
+        assert _kernel(16, 3 * D, D, f16, wt) == (G, 1, 1, 4, 1)               # one row block: K-sliced, 4 waves at K = 1280
+        assert _kernel(16, D, 4 * D, resid, wt) == (G, 1, 1, 16, 1)            # fc2: 16 waves at K = 5120
+        assert _kernel(33, D, D, resid, wt) == (G, 1, 1, 4, 3)                 # few tiles: rows split over grid.y
+        assert _kernel(64, D, 4 * D, resid, wt) == (G, 1, 1, 16, 4)
+        assert _kernel(33, 4 * D, D, gelu, wt) == (G, 3, 1, 4, 1)              # fc1: unsplit (tiles * NCB > 640)
+        assert _kernel(64, 3 * D, D, f16, wt) == (G, 4, 1, 4, 1)
+        for R in (65, 96):                                                      # more than 64 rows: always split
+            assert _kernel(R, 4 * D, D, gelu, wt) == (G, 1, 1, 4, (R + 15) // 16)
+        # the logits (>= 2048 tiles)
+        assert _kernel(16, 51866, D, f32, wt) == (LDS, 1, 1, 1, 1) and _kernel(32, 51865, D, f32, wt) == (LDS, 2, 1, 1, 1)
+    for R in (33, 48, 49, 64, 65, 96):
+        assert _kernel(R, 51866, D, f32, 1) == (LDSP, (R + 15) // 16, 2, 1, 1)
+    for R in (33, 64):
+        assert _kernel(R, 51866, D, f32, 0) == (G, (R + 15) // 16, 2, 1, 1)    # full rows, two tiles per wave
+    for R in (65, 80, 96):                                                      # the former hole: nothing was launched
+        assert _kernel(R, 51866, D, f32, 0) == (G, 1, 1, 4, (R + 15) // 16)
+    # the width sweep: fc2's K = 4 d takes 16 waves once it reaches 2560, 4 below
+    assert _kernel(17, 768, 4 * 768, resid, 1)[:4] == (G, 1, 1, 16) and _kernel(17, 128, 4 * 128, resid, 1)[:4] == (G, 1, 1, 4)
+    # the fused LayerNorm: one tile per workgroup up to 160 tiles, two beyond with more than one row block; the logits' staging
+    for d in LN_WIDTHS:
+        assert _kernel(17, d, d, f16, 1, ln=1) == (LN, 1, 1, d // 128, 2)
+        assert _kernel(1, 4 * d, d, gelu, 1, ln=1) == (LN, 1, 1, d // 128, 1)
+        assert _kernel(96, 4 * d, d, gelu, 0, ln=1) == (LN, 1, 2 if 4 * d // 16 > 160 else 1, d // 128, 6)
+    assert _kernel(32, 51866, D, f32, 0, ln=1) == (LDS, 2, 1, 1, 1)
 
 
 def _run_skinny(name, N, Kd, epi, rows, ln=False, bias=True):
@@ -142,7 +171,7 @@ def _run_skinny(name, N, Kd, epi, rows, ln=False, bias=True):
 
 
 # LayerNorm fused into the activation load wherever skinny_ln_supported says so: STEPS = K / 128 in {1, 2, 3, 4, 6, 8, 10}
-# (skinny_ln_kernel<1, STEPS, NT>), NT = 2 for > 160 tiles with more than one row block (fc1 at d >= 768), and the logits'
+# (skinny_ln_kernel<STEPS, NT>), NT = 2 for > 160 tiles with more than one row block (fc1 at d >= 768), and the logits'
 # skinny_lds_kernel with its LayerNorm staging (R <= 32).  Each case includes a constant row and a row 1000 + 1e-3 noise.
 LN_WIDTHS = [128, 256, 384, 512, 768, 1024, 1280]
 
@@ -191,10 +220,23 @@ def test_skinny_refuses_fused_layernorm_where_unsupported():
     W = K.f16(r.standard_normal((51866, 128)))
     lx = K.f32(r.standard_normal((33, 128)))
     lw = K.f32(np.ones(128)); lb = K.f32(np.zeros(128))
-    out = np.zeros((33, 51872), np.float32)
+    out = np.full((33, 51872), np.float32(7.25), np.float32)
     rc = L.kref_skinny(None, 128, 33, 51866, 128, K.ptr(W), None, 0, K.SK_F32, K.ptr(out), out.nbytes, None, None, 0, 51872,
                        0, 0, 1, 0, None, 0, K.ptr(lx), K.ptr(lw), K.ptr(lb))
     assert rc == -1
+    assert np.all(out == np.float32(7.25)), "a refused launch wrote to its output"
+    # what the kernels cannot compute is refused too, with the output (poisoned; the wrapper copies it back) left alone:
+    # K % 64 != 0 (the narrowest form cuts K into two slices of whole 32-deep k-steps: the tail of K would be dropped) and
+    # N % 4 != 0 under an epilogue that stores four features at a time
+    for R, N, Kd, epi in [(16, 1280, 96, K.SK_F16), (16, 6, 128, K.SK_F16)]:
+        x, W, b = _data(r, R, N, Kd)
+        for wt in (0, 1):
+            assert K.skinny_plan(R, N, Kd, epi, wt, 0)["kind"] == K.SKP_NONE
+            out = np.full((R, N), np.float16(7.25), np.float16)
+            rc = L.kref_skinny(K.ptr(x), Kd, R, N, Kd, K.ptr(W), K.ptr(b), wt, epi, K.ptr(out), out.nbytes, None, None, 0, N,
+                               0, 0, 1, 0, None, 0, None, None, None)
+            assert rc == -1, (R, N, Kd, wt)
+            assert np.all(out == np.float16(7.25)), "a refused launch wrote to its output"
 
 
 # SK_QKV: q -> out0 [R][d]; k, v -> head-major caches [B][H][ctx][64] at t0 (or pos_ptr[b]); every other position untouched

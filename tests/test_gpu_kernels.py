@@ -96,7 +96,7 @@ print("RESULT " + json.dumps(out))
 
 
 def test_strict_memory_model_build_gives_the_same_tokens_and_logprobs():
-    """k_decode.hip's one cross-workgroup hand-off (logit_step_kernel: 8 workgroups per sequence -> last arriver) has two
+    """k_token.hip's one cross-workgroup hand-off (logit_step_kernel: 8 workgroups per sequence -> last arriver) has two
     spellings: the gfx950 ISA-level default (sc1 stores, s_waitcnt vmcnt(0), relaxed ticket) and -DNH_STRICT_MEMORY_MODEL
     (RELEASE ticket + ACQUIRE fence).  The Makefile builds both on every build; this runs the strict library
     (NORMA_HIP_LIB) in a child process and compares tokens and log-probs with the default library bit for bit."""

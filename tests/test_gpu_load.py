@@ -6,7 +6,7 @@ then.  The first stage to differ was the log-mel: a log-mel workgroup (37 KB of 
 workgroup of ANOTHER context's logits kernel -- activations staged in LDS, every MFMA fed by a `ds_read_b128` -- computed wrong
 spectra in 1 to 250 frames of a clip; LDS allocations and barriers of co-resident workgroups do stay apart (tools/ldsprobe.hip),
 and it takes the LDS read feeding the MFMA: LDS reads without MFMAs, or MFMAs fed from registers, leave the neighbour alone
-(bisect: tools/dbg/stress_mel.py, k_decode.hip at NH_LDS_EXCLUSIVE).  Those kernels now take the whole LDS of their CU, so no
+(bisect: tools/dbg/stress_mel.py, nh_kernels.h at NH_LDS_EXCLUSIVE).  Those kernels now take the whole LDS of their CU, so no
 LDS-using workgroup runs beside them.  Without that, the first test below sees 150-190 wrong clip-mels in 3200.
 
 The reference has nothing comparable (one stream at a time, src/lib.rs:462-464); what is at stake is the invariant every parity

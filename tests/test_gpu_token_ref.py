@@ -1,4 +1,4 @@
-"""GPU: the token-selection kernels of k_decode.hip -- logit_step_kernel (greedy step, no-speech probe, decode-pool phases),
+"""GPU: the token-selection kernels of k_token.hip -- logit_step_kernel (greedy step, no-speech probe, decode-pool phases),
 pool_admit_kernel, sample_step_kernel, lang_detect_kernel -- called through tools/kref.hip and compared with the fp64
 restatement of model.rs:212-277, 293-370 in tests/kref.py.
 

@@ -151,15 +151,128 @@ def test_discrimination_flags_each_mutation():
         K.within(o + 3 * ab, o, ab, "shifted")
 
 
-def test_make_builds_the_wrapper_library_with_every_entry_point():
+def _make_wrapper_library():
     root = K.ROOT
-    if not os.path.exists(os.path.join(root, "norma_amd", "csrc", "build", "k_decode.o")):
+    if not os.path.exists(os.path.join(root, "norma_amd", "csrc", "build", "k_skinny.o")):
         subprocess.check_call(["make", "-C", os.path.join(root, "norma_amd", "csrc"), "-j8"])
     subprocess.check_call(["make", "-C", os.path.join(root, "tools", ), "bin/libnh_kref.so"], stdout=subprocess.DEVNULL)
+
+
+def test_make_builds_the_wrapper_library_with_every_entry_point():
+    _make_wrapper_library()
     assert os.path.exists(K.LIB_PATH)
     syms = subprocess.run(["nm", "-D", "--defined-only", K.LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = {line.split()[-1] for line in syms.splitlines() if " T " in line}
     assert set(K.WRAPPERS) <= exported, set(K.WRAPPERS) - exported
+
+
+# ---- the decode GEMV dispatch (norma_amd/csrc/skinny_plan.h), asked through the wrapper library: pure host code, no GPU ------
+PLAN_WIDTHS = [128, 256, 384, 512, 640, 768, 1024, 1280]
+
+
+def _plan_shapes(d):
+    return [(d, d), (3 * d, d), (4 * d, d), (d, 4 * d), (51864, d), (51865, d), (51866, d)]
+
+
+def _plan_epilogues(N, d):
+    """every epilogue valid for the shape: all but SK_F32 store 4 features at a time, SK_QKV cuts N into q | k | v of width d"""
+    epis = [K.SK_F32]
+    if N % 4 == 0:
+        epis += [K.SK_F16, K.SK_GELU_F16, K.SK_RESID_F32]
+    if N == 3 * d:
+        epis.append(K.SK_QKV)
+    return epis
+
+
+def _ln_expected(R, N, Kd):
+    """where a fused LayerNorm exists, written out independently of the plan: below 2048 weight tiles skinny_ln_kernel for
+    K = 128 STEPS, STEPS in {1, 2, 3, 4, 6, 8, 10}, any R <= 96; for the logits the staging pass of skinny_lds_kernel, R <= 32,
+    K = 128 steps with steps <= 10"""
+    if (N + 15) // 16 < 2048:
+        return R <= 96 and Kd % 128 == 0 and Kd // 128 in (1, 2, 3, 4, 6, 8, 10)
+    return R <= 32 and Kd % 128 == 0 and Kd <= 1280
+
+
+def _check_launchable(pl, R, N, Kd, wt, ln, what):
+    tiles = (N + 15) // 16
+    assert pl["grid_x"] >= 1 and pl["grid_y"] >= 1, what
+    assert pl["block"] in (128, 256, 512, 1024), what
+    assert 0 <= pl["lds_used"] <= 160 * 1024, what
+    assert pl["ksplit"] >= 1 and Kd % (pl["ksplit"] * 32) == 0, what
+    assert pl["grid_y"] * 16 * pl["ncb"] >= R, what
+    kind = pl["kind"]
+    if kind == K.SKP_GEMM:
+        # K-sliced: one tile per workgroup, its ksplit waves split K; full rows (ksplit 1): 2 waves of nt tiles each
+        per_wg = pl["nt"] if pl["ksplit"] > 1 else 2 * pl["nt"]
+        assert pl["block"] == (128 if pl["ksplit"] == 1 else 64 * pl["ksplit"]), what
+        assert 1 <= pl["ncb"] <= 4 and pl["lds_used"] == 0 and not pl["lds_exclusive"] and not ln, what
+    elif kind == K.SKP_LN:
+        per_wg = pl["nt"]
+        assert ln and pl["block"] == 256 and pl["ncb"] == 1 and pl["ksplit"] * 128 == Kd and pl["nt"] in (1, 2), what
+    elif kind == K.SKP_LDS:
+        per_wg = tiles                     # its 8 waves per workgroup walk the tiles grid-stride: any grid covers N
+        assert pl["block"] == 512 and pl["ncb"] in (1, 2) and pl["lds_exclusive"], what
+        assert pl["lds_used"] == (Kd // 32) * 16 * pl["ncb"] * 64 <= 96 * 1024, what
+    else:
+        assert kind == K.SKP_LDSP, what
+        per_wg = 8 * pl["nt"]              # 8 waves of at most LP_MT = nt tiles each
+        assert wt and not ln and pl["block"] == 512 and 3 <= pl["ncb"] <= 6 and pl["lds_exclusive"], what
+        assert 1 <= pl["sp"] and pl["lds_used"] == pl["sp"] * 16 * pl["ncb"] * 64 <= 144 * 1024, what
+    assert pl["grid_x"] * per_wg >= tiles, what
+
+
+def test_skinny_plan_covers_every_decoder_shape_and_is_launchable():
+    """the sweep of every row count x width x decoder shape x weight layout x epilogue, with and without the fused LayerNorm:
+    without LayerNorm nothing is refused (the hole 9a04a41 closed: 65-96 rows on >= 2048 tiles without tile-major weights had
+    no kernel); with it, exactly the shapes _ln_expected names are planned, whatever the layout and the epilogue; and every
+    plan can be launched as it stands"""
+    _make_wrapper_library()
+    L = K.lib()
+    n_plans, ln_yes, ln_no, kinds = 0, 0, 0, set()
+    for d in PLAN_WIDTHS:
+        for N, Kd in _plan_shapes(d):
+            for R in range(1, 97):
+                want_ln = _ln_expected(R, N, Kd)
+                assert bool(L.kref_skinny_ln_supported(R, N, Kd)) == want_ln, (R, N, Kd)
+                ln_yes, ln_no = ln_yes + want_ln, ln_no + (not want_ln)
+                for wt in (0, 1):
+                    for epi in _plan_epilogues(N, d):
+                        for ln in (0, 1):
+                            what = f"R={R} N={N} K={Kd} epi={epi} wt={wt} ln={ln}"
+                            pl = K.skinny_plan(R, N, Kd, epi, wt, ln)
+                            if ln:
+                                assert (pl["kind"] != K.SKP_NONE) == want_ln, what
+                                if not want_ln:
+                                    continue
+                                assert pl["kind"] in (K.SKP_LN, K.SKP_LDS), what
+                            else:
+                                assert pl["kind"] != K.SKP_NONE, what
+                            _check_launchable(pl, R, N, Kd, wt, ln, what)
+                            n_plans += 1
+                            kinds.add((pl["kind"], pl["ncb"], pl["nt"], pl["ksplit"]))
+    assert ln_yes > 0 and ln_no > 0, (ln_yes, ln_no)      # the sweep holds both outcomes (d = 640 has no skinny_ln_kernel)
+    assert not L.kref_skinny_ln_supported(17, 640, 640) and not L.kref_skinny_ln_supported(33, 51866, 1280)
+    assert L.kref_skinny_ln_supported(32, 51866, 1280) and L.kref_skinny_ln_supported(96, 3840, 1280)
+    assert {k[0] for k in kinds} == {K.SKP_GEMM, K.SKP_LN, K.SKP_LDS, K.SKP_LDSP}, kinds
+    # the former hole: K-sliced rows split over grid.y
+    for R in (65, 80, 96):
+        pl = K.skinny_plan(R, 51866, 1280, K.SK_F32, 0, 0)
+        assert (pl["kind"], pl["ncb"], pl["ksplit"], pl["grid_x"], pl["grid_y"]) == (K.SKP_GEMM, 1, 4, 3242, (R + 15) // 16), pl
+    print(f"{n_plans} plans, {len(kinds)} distinct (kind, ncb, nt, ksplit)")
+
+
+def test_skinny_plan_refuses_what_the_kernels_cannot_compute():
+    _make_wrapper_library()
+    none = K.SKP_NONE
+    assert K.skinny_plan(16, 1280, 96, K.SK_F16, 0, 0)["kind"] == none          # K % 64 != 0: the tail of K would be dropped
+    assert K.skinny_plan(16, 1280, 96, K.SK_F32, 1, 0)["kind"] == none
+    assert K.skinny_plan(16, 6, 128, K.SK_F16, 0, 0)["kind"] == none            # 4 features per store: N % 4 != 0
+    assert K.skinny_plan(16, 6, 128, K.SK_F32, 0, 0)["kind"] == K.SKP_GEMM      # SK_F32 stores the ragged tail one by one
+    assert K.skinny_plan(16, 1280, 192, K.SK_F16, 0, 0)["ksplit"] == 2          # K % 64 == 0 is enough: two slices of 3 k-steps
+    for R in (0, -1, 97):
+        assert K.skinny_plan(R, 1280, 1280, K.SK_F16, 1, 0)["kind"] == none
+    assert K.skinny_plan(33, 51866, 1280, K.SK_F32, 1, 1)["kind"] == none       # no fused LayerNorm for the phased logits kernel
+    assert K.skinny_plan(17, 640, 640, K.SK_F16, 1, 1)["kind"] == none          # K / 128 = 5: no such skinny_ln_kernel
 
 
 def test_xabs_bound_holds_for_an_f32_fp16_emulation_of_the_kernels():

@@ -83,15 +83,25 @@ int kref_skinny(const void *x, long ldx, int R, int N, int K, const void *W, con
         launch_repack_tiles(p.W, wt, N, K, st.s);
         p.Wt = wt;
     }
-    if (!launch_skinny(p, st.s)) return -1;
+    const bool launched = launch_skinny(p, st.s);
     if (hipError_t e = st.finish()) return (int)e;
+    // copied back after a refusal too: a test can see that a refused launch left the outputs alone
     b.out(out0, p.out[0], out0_bytes);
     b.out(out1, p.out[1], out12_bytes);
     b.out(out2, p.out[2], out12_bytes);
-    return (int)b.err;
+    return launched ? (int)b.err : -1;
 }
 
 int kref_skinny_ln_supported(int R, int N, int K) { return skinny_ln_supported(R, N, K) ? 1 : 0; }
+
+// skinny_plan (pure host: no GPU needed): out = {kind, ncb, nt, ksplit, sp, grid.x, grid.y, block, lds_used, lds_exclusive};
+// returns 1 when the shape is planned, 0 when it is refused (kind SKP_NONE)
+int kref_skinny_plan(int R, int N, int K, int epi, int wt, int ln, int32_t out[10]) {
+    const SkinnyPlan pl = skinny_plan(R, N, K, epi, wt != 0, ln != 0);
+    const int32_t v[10] = {pl.kind, pl.ncb, pl.nt, pl.ksplit, pl.sp, pl.grid_x, pl.grid_y, pl.block, (int32_t)pl.lds_used, pl.lds_exclusive};
+    for (int i = 0; i < 10; i++) out[i] = v[i];
+    return pl.kind != SKP_NONE;
+}
 
 // launch_dec_attention: q [B][d]; kc, vc [B][ctx][d] or head-major [B][H][ctx][64]; out [B][d] (copied in: done rows stay)
 int kref_dec_attention(const void *q, const void *kc, const void *vc, void *out, int B, int H, int d, int ctx, int Tk,

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(512) void aggressor(unsigned *sink, int words, int 
     if (acc == 0x12345u) sink[0] = acc;
 }
 
-// ---- third experiment: the aggressor as it is in the product (k_decode.hip, skinny_ldsp_kernel): every MFMA's B operand comes
+// ---- third experiment: the aggressor as it is in the product (k_skinny.hip, skinny_ldsp_kernel): every MFMA's B operand comes
 // straight from a ds_read_b128, two waves per SIMD; the victims re-read LDS they filled themselves, in three access patterns
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f4 __attribute__((ext_vector_type(4)));

@@ -1,4 +1,4 @@
-// xabs_bench: the one-pass "absorbed" cross-attention kernels of k_decode.hip (NH_OPT_ABSORBED_XATTN = 2) on random data, next to
+// xabs_bench: the one-pass "absorbed" cross-attention kernels of k_dec_attn.hip (NH_OPT_ABSORBED_XATTN = 2) on random data, next to
 // the K/V kernel they replace: time per launch group, and (built with -DXA_STAMPS) the cycle counter at eight points of one tile.
 #include "../norma_amd/csrc/nh_kernels.h"
 #include <cstdio>
