@@ -188,6 +188,15 @@ int nh_pool_step(nh_ctx *ctx, int n_steps, int32_t *done_out);
 /* Results of the n finished rows `rows[]`: out_tokens host i32 [n][max_target_positions], results [n]; the rows are free
  * for nh_pool_admit afterwards. */
 int nh_pool_collect(nh_ctx *ctx, const int32_t *rows, int n, int32_t *out_tokens, nh_decode_result *results);
+/* The clip that last decoded in `row` decodes again from position 0, every generated token SAMPLED at `temperature` (> 0)
+ * under the seeded contract of nh_decode_sampled (step = tokens so far, clip, attempt as given).  Valid on a row that
+ * nh_pool_collect has handed back and that no nh_pool_admit* has refilled since: its cross K/V and its prompt are still in
+ * place, nothing is copied.  The row is busy again afterwards; asynchronous.  This is the retry of decode_with_fallback
+ * (model.rs:164-191) for one row: the caller walks TEMPERATURES (norma_amd/pool.py does, fallback=True), an admitted row is
+ * always the t = 0 attempt.  The row's bits are those of nh_decode_sampled on a batch that holds the clip at index
+ * clip - clip0, whatever the other rows of the pool do meanwhile.  Refused (NH_ERR_INVALID / NH_ERR_STATE, nothing is
+ * launched): no pool, row out of range, row busy, row never admitted since nh_pool_begin, temperature <= 0 or not finite. */
+int nh_pool_retry(nh_ctx *ctx, int row, float temperature, uint64_t seed, uint32_t clip, uint32_t attempt);
 /* Model::decode at t > 0 (model.rs:340-348): every token is SAMPLED from softmax(q / t), q = the rule-masked
  * probabilities.  The reference draws with rand::WeightedIndex from an entropy-seeded StdRng (model.rs:30), so only its
  * distribution can be reproduced; this build fixes a seeded SAMPLING CONTRACT (the C oracle implements the same, bit for bit):

@@ -229,6 +229,58 @@ void launch_sample_step(const float *logits, int V, DecodeState s, RuleTokens tk
                        inv_t, seed, clip0, attempt);
 }
 
+// decode pool: sample_step_kernel for the rows of a pool that are sampled.  One workgroup per row; it acts on a row that has
+// inv_t > 0, is running and stands at a generation position, draws its token and keeps its books exactly as sample_step_kernel
+// does (same device functions, same order: the bits are the lockstep path's), and advances its position.  Every step it also
+// tells logit_step_kernel (mode 2, launched next on the same stream) which rows it has dealt with: handled[b].  The two
+// kernels never decide that through pos[b], which one of them has moved by then.
+__global__ __launch_bounds__(1024) void pool_sample_step_kernel(const float *__restrict__ logits, int V, int ldl, DecodeState s,
+                                                                RuleTokens tk, int ctx, int cap, int max_new, int prompt_len,
+                                                                PoolSampling ps, int32_t *pos) {
+    __shared__ SampleShared sh;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float inv_t = ps.inv_t[b];
+    const int my_pos = pos[b];  // read by every thread ahead of the first barrier; thread 0 moves it after the last
+    const bool mine = inv_t > 0.f && !s.done[b] && my_pos >= prompt_len - 1;
+    if (tid == 0) ps.handled[b] = mine ? 1 : 0;
+    if (!mine) return;
+    const float *lg = logits + (long)b * ldl;
+    float mx = -INFINITY;
+    for (int i = tid; i < V; i += 1024) mx = fmaxf(mx, lg[i]);
+    const float m = block_max(mx, sh.red);
+    float se = 0.f;
+    for (int i = tid; i < V; i += 1024) se += expf(lg[i] - m);
+    se = block_sum(se, sh.red);
+    auto probs = [&](int i) { return expf(lg[i] - m) / se; };  // model.rs:331
+    int32_t *toks = s.tokens + (long)b * ctx;
+    const int n = s.n_tokens[b], have_last = s.have_last[b], last_ts = s.last_ts[b];
+    const int rule = rules_decide(probs, V, toks, n, have_last, s.suppress, tk, sh.red);
+    auto q = [&](int i) { return masked_value(probs(i), i, rule, s.suppress, tk, last_ts); };
+    float qv;
+    const int next = sample_masked(q, V, inv_t, ps.seed[b], ps.clip[b], (unsigned)n, ps.attempt[b], sh, qv);
+    if (tid != 0) return;
+    int nn = n, fin = 0;
+    if (next < 0) { toks[nn++] = tk.eot; fin = 1; }                // :343-346 all NaN: push eot, stop (no log-prob)
+    else {
+        if (next > tk.no_timestamps) { s.last_ts[b] = next; s.have_last[b] = 1; }  // :359-361
+        toks[nn++] = next;
+        s.sum_logprob[b] += log((double)qv);                       // :364-365
+        if (nn >= cap) { toks[nn++] = tk.eot; fin = 1; }           // :367-370
+        else if (next == tk.eot) fin = 1;                          // :317
+        else if (max_new > 0 && nn - prompt_len >= max_new) { toks[nn++] = tk.eot; fin = 1; }
+    }
+    s.n_tokens[b] = nn;
+    if (fin) s.done[b] = 1;
+    pos[b] = my_pos + 1;
+}
+
+void launch_pool_sample_step(const float *logits, int V, DecodeState s, RuleTokens tk, int B, int ctx, int cap, int max_new,
+                             int prompt_len, PoolSampling ps, int32_t *pos, hipStream_t st) {
+    const int ldl = (V + 63) & ~63;
+    hipLaunchKernelGGL(pool_sample_step_kernel, dim3(B), dim3(1024), 0, st, logits, V, ldl, s, tk, ctx, cap, max_new, prompt_len,
+                       ps, pos);
+}
+
 // parity view of the sampler: rules + one draw on an already soft-maxed probability vector
 __global__ __launch_bounds__(1024) void sample_rules_kernel(const float *__restrict__ probs_in, int32_t *token_out,
                                                             const int32_t *tokens, int n, int last_ts, const uint8_t *sup,
@@ -273,7 +325,7 @@ __device__ __forceinline__ void better(float &v, int &i, float v2, int i2) {  //
 __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict__ logits, int V, int ldl,
                                                          DecodeState s, RuleTokens tk, int ctx, int cap, int max_new,
                                                          int prompt_len, int mode, float *partials, unsigned *tickets,
-                                                         int32_t *pos_ptr) {
+                                                         int32_t *pos_ptr, const int32_t *handled) {
     __shared__ float sh_f[4][6];
     __shared__ int sh_i[4][2];
     __shared__ int sh_last;
@@ -299,7 +351,8 @@ __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict
     const int l1 = toks[n >= 1 ? n - 1 : 0], l2 = toks[n >= 2 ? n - 2 : 0];  // unconditional: one round trip for both
     const float l_nt = lg[tk.no_timestamps];           // no_timestamps is text to supress_past_timestamps only (see below)
     const int sup_nt = s.suppress[tk.no_timestamps];
-    if (done) return;
+    const int taken = handled ? handled[b] : 0;  // decode pool: pool_sample_step_kernel generated this sequence's token in this step
+    if (done || taken) return;                   // (all LSPLIT workgroups leave before any takes a ticket)
     // mode 2 (decode pool): sequences join a running decode, so each is in its own phase -- position 0 of its prompt is the
     // no-speech probe, the other prompt positions only feed the caches (their next token is given), then it generates
     if (mode == 2) {
@@ -442,10 +495,10 @@ __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict
 
 void launch_logit_step(const float *logits, int V, DecodeState s, RuleTokens tk, int B, int ctx, int cap,
                        int max_new, int prompt_len, int mode, float *partials, unsigned *tickets, int32_t *pos_ptr,
-                       hipStream_t st) {
+                       hipStream_t st, const int32_t *handled) {
     int ldl = (V + 63) & ~63;
     hipLaunchKernelGGL(logit_step_kernel, dim3(LSPLIT, B), dim3(256), 0, st, logits, V, ldl, s, tk, ctx, cap, max_new,
-                       prompt_len, mode, partials, tickets, pos_ptr);
+                       prompt_len, mode, partials, tickets, pos_ptr, handled);
 }
 
 // decode pool: sequence `row` starts over with the prompt [t0, t1, (t2)] (model.rs:285-289) at position 0
@@ -458,6 +511,20 @@ __global__ void pool_admit_kernel(DecodeState s, int32_t *pos, unsigned *tickets
 }
 void launch_pool_admit(DecodeState s, int32_t *pos, unsigned *tickets, int row, int ctx, int t0, int t1, int t2, int P, hipStream_t st) {
     hipLaunchKernelGGL(pool_admit_kernel, dim3(1), dim3(1), 0, st, s, pos, tickets, row, ctx, t0, t1, t2, P);
+}
+
+// decode pool: sequence `row` decodes the clip it holds once more, sampled.  The prompt tokens [0, P) are still in place
+// (generation writes from P on; the trimming of finish_sequence works on the host copy), so is the clip's cross K/V.
+__global__ void pool_retry_kernel(DecodeState s, int32_t *pos, unsigned *tickets, PoolSampling ps, int row, int P, float inv_t,
+                                  unsigned long long seed, unsigned clip, unsigned attempt) {
+    s.n_tokens[row] = P; s.done[row] = 0; s.have_last[row] = 0; s.last_ts[row] = 0;
+    s.sum_logprob[row] = 0.0; s.no_speech[row] = 0.0;
+    pos[row] = 0; tickets[row] = 0u;
+    ps.inv_t[row] = inv_t; ps.seed[row] = seed; ps.clip[row] = clip; ps.attempt[row] = attempt;
+}
+void launch_pool_retry(DecodeState s, int32_t *pos, unsigned *tickets, PoolSampling ps, int row, int P, float inv_t,
+                       unsigned long long seed, unsigned clip, unsigned attempt, hipStream_t st) {
+    hipLaunchKernelGGL(pool_retry_kernel, dim3(1), dim3(1), 0, st, s, pos, tickets, ps, row, P, inv_t, seed, clip, attempt);
 }
 
 // Model::detect_language (model.rs:194-210) on the position-0 logits of a [sot] prompt: softmax over the language

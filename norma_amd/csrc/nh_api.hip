@@ -112,9 +112,17 @@ struct nh_ctx {
     int pool_rows = 0, pool_max_new = 0, pool_prompt = 0;
     bool pool_per_clip_language = false;
     std::vector<char> pool_busy;
+    std::vector<char> pool_held;     // the row holds a clip: admitted since nh_pool_begin (nh_pool_retry decodes that clip again)
+    std::vector<char> pool_sampled;  // the row is busy on a sampled retry (nh_pool_retry); cleared by nh_pool_collect and by an admit
+    std::vector<char> pool_inv_t;    // the row's device-side inv_t is > 0 (its last decode was a retry): the next admit zeroes it
+    PoolSampling psamp{};            // [max_batch] each: per-row temperature, seed, clip, attempt, and the step's handled flags
     hipGraphExec_t step_graph = nullptr;   // one decode step
     hipGraphExec_t multi_graph = nullptr;  // NH_GRAPH_STEPS consecutive steps (one launch gap instead of NH_GRAPH_STEPS)
     int graph_key[6] = {-1, -1, -1, -1, -1, -1};
+    // the same pair for pool steps with at least one sampled row busy: pool_sample_step_kernel ahead of logit_step_kernel.
+    // Kept beside the greedy pair, so a pool that goes back and forth between the two states captures each once.
+    hipGraphExec_t step_graph_s = nullptr, multi_graph_s = nullptr;
+    int graph_key_s[6] = {-1, -1, -1, -1, -1, -1};
     int token_gen = 0;  // bumped by nh_set_tokens; part of the graph key
     bool opt_graphs = true, opt_fuse_ln = true;  // nh_set_option
     int opt_absorbed = 0;        // NH_OPT_ABSORBED_XATTN: 1 = numerics prototype, 2 = one-pass kernels
@@ -145,10 +153,16 @@ struct nh_ctx {
 
 // the captured decode-step graphs bake in everything the step kernels take by value (batch, encoder length, the rule
 // token ids, the max_new_tokens knob): whoever changes one of those drops the graphs, the next greedy decode re-captures
+static void drop_sampled_graphs(nh_ctx *ctx) {
+    if (ctx->step_graph_s) { hipGraphExecDestroy(ctx->step_graph_s); ctx->step_graph_s = nullptr; }
+    if (ctx->multi_graph_s) { hipGraphExecDestroy(ctx->multi_graph_s); ctx->multi_graph_s = nullptr; }
+    for (int &k : ctx->graph_key_s) k = -1;
+}
 static void drop_graphs(nh_ctx *ctx) {
     if (ctx->step_graph) { hipGraphExecDestroy(ctx->step_graph); ctx->step_graph = nullptr; }
     if (ctx->multi_graph) { hipGraphExecDestroy(ctx->multi_graph); ctx->multi_graph = nullptr; }
     for (int &k : ctx->graph_key) k = -1;
+    drop_sampled_graphs(ctx);
 }
 
 template <typename T>
@@ -364,7 +378,9 @@ static int build_context(std::shared_ptr<nh_model> mdl, int max_batch, nh_ctx **
     DA(dxn, half_t, (long)B * d); DA(dq, half_t, (long)B * d); DA(datt, half_t, (long)B * d); DA(dhid, half_t, (long)B * 4 * d);
     DA(ds.tokens, int32_t, (long)B * ctxlen); DA(ds.n_tokens, int32_t, B); DA(ds.done, int32_t, B);
     DA(ds.have_last, int32_t, B); DA(ds.last_ts, int32_t, B); DA(ds.sum_logprob, double, B); DA(ds.no_speech, double, B);
-    DA(ds.n_active, int32_t, 1); DA(suppress, uint8_t, V); DA(lpart, float, (long)B * 64); DA(ltick, unsigned, B); DA(d_pos, int32_t, B); DA(d_lang_tokens, int32_t, 256); DA(d_lang_out, int32_t, B); DA(d_lang_probs, float, (long)B * 256);
+    DA(ds.n_active, int32_t, 1); DA(suppress, uint8_t, V); DA(lpart, float, (long)B * 64); DA(ltick, unsigned, B); DA(d_pos, int32_t, B);
+    DA(psamp.inv_t, float, B); DA(psamp.seed, unsigned long long, B); DA(psamp.clip, unsigned, B); DA(psamp.attempt, unsigned, B); DA(psamp.handled, int32_t, B);
+    DA(d_lang_tokens, int32_t, 256); DA(d_lang_out, int32_t, B); DA(d_lang_probs, float, (long)B * 256);
 #undef DA
     if (!ok) { ctx->err = "hipMalloc failed while sizing the context (out of device memory?)"; return bail(NH_ERR_NOMEM); }
     ctx->ds.suppress = ctx->suppress;
@@ -977,7 +993,7 @@ static void finish_sequence(nh_ctx *ctx, int32_t *t, int n, int done, double slp
     for (int i = n; i < C; i++) out_tokens[i] = 0;
 }
 
-static int capture_step_graphs(nh_ctx *ctx, int B, int max_new_tokens, int P, int mode);
+static int capture_step_graphs(nh_ctx *ctx, int B, int max_new_tokens, int P, int mode, bool sampled = false);
 
 // Model::decode (model.rs:279-389) for the whole batch.  inv_t == 0: t = 0, greedy (hipGraph replay); inv_t > 0: every
 // token is sampled at temperature 1 / inv_t under the seeded contract (eager launches: the fallback path is rare).
@@ -1102,13 +1118,15 @@ extern "C" int nh_pool_begin(nh_ctx *ctx, int rows, int max_new_tokens, int per_
     ctx->pool_rows = rows; ctx->pool_max_new = max_new_tokens;
     ctx->pool_prompt = (per_clip_language || ctx->tk.lang >= 0) ? 3 : 2;
     ctx->pool_per_clip_language = per_clip_language != 0;
-    ctx->pool_busy.assign(rows, 0);
+    const bool was_sampled = std::find(ctx->pool_inv_t.begin(), ctx->pool_inv_t.end(), 1) != ctx->pool_inv_t.end();
+    ctx->pool_busy.assign(rows, 0); ctx->pool_held.assign(rows, 0); ctx->pool_sampled.assign(rows, 0); ctx->pool_inv_t.assign(rows, 0);
     ctx->cur_batch = rows; ctx->frames = -1; ctx->S = 0; ctx->have_mel = false; ctx->have_enc = false;
     ctx->seq_lang.clear();
     for (int b = 0; b < rows; b++) ctx->h_done[128 + b] = 3;  // 3: empty row (skipped like a finished one)
     HIPCHK(hipMemcpyAsync(ctx->ds.done, ctx->h_done + 128, sizeof(int32_t) * rows, hipMemcpyHostToDevice, ctx->sd));
     HIPCHK(hipMemsetAsync(ctx->d_pos, 0, sizeof(int32_t) * rows, ctx->sd));
     HIPCHK(hipMemsetAsync(ctx->ltick, 0, sizeof(unsigned) * rows, ctx->sd));
+    if (was_sampled) HIPCHK(hipMemsetAsync(ctx->psamp.inv_t, 0, sizeof(float) * ctx->B, ctx->sd));  // rows an earlier pool left on a retry: greedy again
     HIPCHK(hipStreamSynchronize(ctx->sd));
     return NH_OK;
 }
@@ -1136,7 +1154,28 @@ static int pool_admit_impl(nh_ctx *ctx, nh_ctx *src, int src_row, int dst_row, i
     launch_pool_admit(ctx->ds, ctx->d_pos, ctx->ltick, dst_row, ctx->c.max_target_positions, ctx->tk.sot, P == 3 ? lg : ctx->tk.task,
                       ctx->tk.task, P, ctx->sd);
     HIPCHK(hipGetLastError());
-    ctx->pool_busy[dst_row] = 1;
+    if (ctx->pool_inv_t[dst_row]) {  // an admitted row is greedy (a pool that never retried launches nothing here)
+        HIPCHK(hipMemsetAsync(ctx->psamp.inv_t + dst_row, 0, sizeof(float), ctx->sd));
+        ctx->pool_inv_t[dst_row] = 0;
+    }
+    ctx->pool_busy[dst_row] = 1; ctx->pool_held[dst_row] = 1; ctx->pool_sampled[dst_row] = 0;
+    return NH_OK;
+}
+
+// The clip in `row` once more, sampled (the fallback of decode_with_fallback, model.rs:164-191, for one row of a pool): the row
+// restarts at position 0 on the cross K/V and the prompt it still holds -- nothing is copied, where an admission copies the
+// clip's cross K/V of every layer.
+extern "C" int nh_pool_retry(nh_ctx *ctx, int row, float temperature, uint64_t seed, uint32_t clip, uint32_t attempt) {
+    if (!ctx) return NH_ERR_INVALID;
+    if (ctx->pool_rows < 1) return ctx->fail(NH_ERR_STATE, "nh_pool_retry: no decode pool (nh_pool_begin)");
+    if (row < 0 || row >= ctx->pool_rows) return ctx->fail(NH_ERR_INVALID, "nh_pool_retry: row outside the pool");
+    if (ctx->pool_busy[row]) return ctx->fail(NH_ERR_STATE, "nh_pool_retry: that row is busy (nh_pool_collect hands it back first)");
+    if (!ctx->pool_held[row]) return ctx->fail(NH_ERR_STATE, "nh_pool_retry: no clip was admitted into that row since nh_pool_begin");
+    if (!(temperature > 0.f && temperature < INFINITY)) return ctx->fail(NH_ERR_INVALID, "nh_pool_retry: temperature must be > 0 and finite (an admitted row decodes at t = 0)");
+    hipSetDevice(ctx->dev);
+    launch_pool_retry(ctx->ds, ctx->d_pos, ctx->ltick, ctx->psamp, row, ctx->pool_prompt, 1.0f / temperature, seed, clip, attempt, ctx->sd);
+    HIPCHK(hipGetLastError());
+    ctx->pool_busy[row] = 1; ctx->pool_sampled[row] = 1; ctx->pool_inv_t[row] = 1;
     return NH_OK;
 }
 
@@ -1159,8 +1198,9 @@ extern "C" int nh_pool_admit_from(nh_ctx *ctx, nh_ctx *enc, int src_row, int dst
     return pool_admit_impl(ctx, enc, src_row, dst_row, lang);
 }
 
-static int capture_step_graphs(nh_ctx *ctx, int B, int max_new_tokens, int P, int mode) {
+static int capture_step_graphs(nh_ctx *ctx, int B, int max_new_tokens, int P, int mode, bool sampled) {
     const int C = ctx->c.max_target_positions, cap = C - 1, V = ctx->c.vocab_size;
+    hipGraphExec_t &one = sampled ? ctx->step_graph_s : ctx->step_graph, &multi = sampled ? ctx->multi_graph_s : ctx->multi_graph;
     for (int which = 0; which < 2; which++) {
         hipGraph_t g = nullptr;
         hipError_t ge = hipStreamBeginCapture(ctx->sd, hipStreamCaptureModeThreadLocal);
@@ -1168,19 +1208,21 @@ static int capture_step_graphs(nh_ctx *ctx, int B, int max_new_tokens, int P, in
         for (int i = 0; i < (which ? NH_GRAPH_STEPS : 1); i++) {  // every step reads and advances the device-side positions
             decoder_step(ctx, 0, ctx->d_pos, false, true);
             logits_from_dx(ctx, B);
-            launch_logit_step(ctx->logits, V, ctx->ds, ctx->tk, B, C, cap, max_new_tokens, P, mode, ctx->lpart, ctx->ltick, ctx->d_pos, ctx->sd);
+            if (sampled) launch_pool_sample_step(ctx->logits, V, ctx->ds, ctx->tk, B, C, cap, max_new_tokens, P, ctx->psamp, ctx->d_pos, ctx->sd);
+            launch_logit_step(ctx->logits, V, ctx->ds, ctx->tk, B, C, cap, max_new_tokens, P, mode, ctx->lpart, ctx->ltick, ctx->d_pos, ctx->sd,
+                              sampled ? ctx->psamp.handled : nullptr);
         }
         // the stream must leave capture mode whatever happened in between; a failed capture leaves no graph behind
         ge = hipStreamEndCapture(ctx->sd, &g);
         if (ge == hipSuccess && !g) ge = hipErrorStreamCaptureInvalidated;
         if (ge == hipSuccess) {
-            ge = hipGraphInstantiate(which ? &ctx->multi_graph : &ctx->step_graph, g, nullptr, nullptr, 0);
-            if (ge != hipSuccess) (which ? ctx->multi_graph : ctx->step_graph) = nullptr;
+            ge = hipGraphInstantiate(which ? &multi : &one, g, nullptr, nullptr, 0);
+            if (ge != hipSuccess) (which ? multi : one) = nullptr;
         }
         if (g) hipGraphDestroy(g);
         if (ge != hipSuccess) {
             (void)hipGetLastError();
-            drop_graphs(ctx);
+            if (sampled) drop_sampled_graphs(ctx); else drop_graphs(ctx);
             return ctx->fail(NH_ERR_HIP, std::string("decode-step graph capture: ") + hipGetErrorString(ge));
         }
     }
@@ -1193,8 +1235,8 @@ extern "C" int nh_pool_step(nh_ctx *ctx, int n_steps, int32_t *done_out) {
     if (n_steps < 0) return ctx->fail(NH_ERR_INVALID, "nh_pool_step: n_steps < 0");
     const int B = ctx->pool_rows, C = ctx->c.max_target_positions, cap = C - 1, V = ctx->c.vocab_size, P = ctx->pool_prompt;
     hipSetDevice(ctx->dev);
-    bool any = false;
-    for (int b = 0; b < B; b++) any = any || ctx->pool_busy[b];
+    bool any = false, sampled = false;  // sampled: a busy row is on a retry -- the steps carry pool_sample_step_kernel
+    for (int b = 0; b < B; b++) { any = any || ctx->pool_busy[b]; sampled = sampled || (ctx->pool_busy[b] && ctx->pool_sampled[b]); }
     if (any && n_steps > 0) {
         if (ctx->S < 1) return ctx->fail(NH_ERR_STATE, "nh_pool_step: rows are busy but nothing was ever encoded");
         if (ctx->opt_graphs) {
@@ -1204,15 +1246,22 @@ extern "C" int nh_pool_step(nh_ctx *ctx, int n_steps, int32_t *done_out) {
                 if (int rc = capture_step_graphs(ctx, B, ctx->pool_max_new, P, 2)) return rc;
                 memcpy(ctx->graph_key, key, sizeof(key));
             }
+            if (sampled && memcmp(key, ctx->graph_key_s, sizeof(key)) != 0) {
+                drop_sampled_graphs(ctx);
+                if (int rc = capture_step_graphs(ctx, B, ctx->pool_max_new, P, 2, true)) return rc;
+                memcpy(ctx->graph_key_s, key, sizeof(key));
+            }
         }
         for (int left = n_steps; left > 0;) {
             if (!ctx->opt_graphs) {
                 decoder_step(ctx, 0, ctx->d_pos, false, true);
                 logits_from_dx(ctx, B);
-                launch_logit_step(ctx->logits, V, ctx->ds, ctx->tk, B, C, cap, ctx->pool_max_new, P, 2, ctx->lpart, ctx->ltick, ctx->d_pos, ctx->sd);
+                if (sampled) launch_pool_sample_step(ctx->logits, V, ctx->ds, ctx->tk, B, C, cap, ctx->pool_max_new, P, ctx->psamp, ctx->d_pos, ctx->sd);
+                launch_logit_step(ctx->logits, V, ctx->ds, ctx->tk, B, C, cap, ctx->pool_max_new, P, 2, ctx->lpart, ctx->ltick, ctx->d_pos, ctx->sd,
+                                  sampled ? ctx->psamp.handled : nullptr);
                 left--;
-            } else if (left >= NH_GRAPH_STEPS) { HIPCHK(hipGraphLaunch(ctx->multi_graph, ctx->sd)); left -= NH_GRAPH_STEPS; }
-            else { HIPCHK(hipGraphLaunch(ctx->step_graph, ctx->sd)); left--; }
+            } else if (left >= NH_GRAPH_STEPS) { HIPCHK(hipGraphLaunch(sampled ? ctx->multi_graph_s : ctx->multi_graph, ctx->sd)); left -= NH_GRAPH_STEPS; }
+            else { HIPCHK(hipGraphLaunch(sampled ? ctx->step_graph_s : ctx->step_graph, ctx->sd)); left--; }
         }
         ctx->tm.decode_steps += n_steps;
     }
@@ -1244,7 +1293,7 @@ extern "C" int nh_pool_collect(nh_ctx *ctx, const int32_t *rows, int n, int32_t 
     for (int i = 0; i < n; i++) {
         const int b = rows[i];
         finish_sequence(ctx, toks.data() + (size_t)i * C, nt[b], done[b], slp[b], nsp[b], out_tokens + (size_t)i * C, results[i]);
-        ctx->pool_busy[b] = 0;
+        ctx->pool_busy[b] = 0; ctx->pool_sampled[b] = 0;
     }
     return NH_OK;
 }

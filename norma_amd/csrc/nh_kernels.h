@@ -275,11 +275,27 @@ struct RuleTokens { int sot, eot, lang, task, no_speech, no_timestamps, zero_sec
 // partials: f32 [B][8][8] scratch, tickets: u32 [B] zero-initialised (the kernel re-zeroes them)
 // pos_ptr != nullptr: i32 [B], the position of every sequence; the kernel advances those it stepped
 // 1 <= V <= NH_MAX_VOCAB (nh_create refuses larger vocabularies)
+// handled != nullptr: i32 [B], written by launch_pool_sample_step earlier in the same step; a sequence whose flag is set is left alone
 void launch_logit_step(const float *logits, int V, DecodeState s, RuleTokens tk, int B, int ctx, int cap,
                        int max_new, int prompt_len, int mode, float *partials, unsigned *tickets, int32_t *pos_ptr,
-                       hipStream_t st);
+                       hipStream_t st, const int32_t *handled = nullptr);
 // decode pool: sequence `row` restarts at position 0 with the prompt [t0, t1] (P = 2) or [t0, t1, t2] (P = 3)
 void launch_pool_admit(DecodeState s, int32_t *pos, unsigned *tickets, int row, int ctx, int t0, int t1, int t2, int P, hipStream_t st);
+// decode pool, sampled rows: how each row draws its tokens.  All device pointers, [B]; inv_t == 0: the row is greedy.
+struct PoolSampling {
+    float *inv_t;
+    unsigned long long *seed;
+    unsigned *clip, *attempt;
+    int32_t *handled;       // written every step by pool_sample_step_kernel: 1 = it generated this row's token
+};
+// decode pool: sequence `row` decodes its clip again from position 0, sampled at 1 / inv_t; its prompt tokens [0, P) stay
+void launch_pool_retry(DecodeState s, int32_t *pos, unsigned *tickets, PoolSampling ps, int row, int P, float inv_t,
+                       unsigned long long seed, unsigned clip, unsigned attempt, hipStream_t st);
+// decode pool: launch_sample_step for the rows that are sampled (inv_t > 0), running and at a generation position
+// (pos[b] >= prompt_len - 1); advances pos[b] of those and writes ps.handled[b] for every row.  Runs ahead of
+// launch_logit_step(mode 2, handled = ps.handled), which does the probe, the prompt positions and the greedy rows.
+void launch_pool_sample_step(const float *logits, int V, DecodeState s, RuleTokens tk, int B, int ctx, int cap, int max_new,
+                             int prompt_len, PoolSampling ps, int32_t *pos, hipStream_t st);
 // t > 0: one SAMPLED token per sequence (model.rs:340-348) under the seeded contract of include/norma_hip.h;
 // sequence b draws with clip id clip0 + b, step = its current token count
 void launch_sample_step(const float *logits, int V, DecodeState s, RuleTokens tk, int B, int ctx, int cap, int max_new,

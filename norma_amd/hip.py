@@ -101,6 +101,7 @@ def load_library() -> C.CDLL:
     L.nh_pool_admit_from.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int32]
     L.nh_pool_step.argtypes = [vp, C.c_int, ip]
     L.nh_pool_collect.argtypes = [vp, ip, C.c_int, ip, C.POINTER(NhDecodeResult)]
+    L.nh_pool_retry.argtypes = [vp, C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_uint32]
     L.nh_logmel_samples.argtypes = [vp, vp, C.c_int, ip, C.c_int64, C.c_int]
     L.nh_sample_size.argtypes = [C.c_int]
     L.nh_encode.argtypes = [vp]
@@ -289,6 +290,11 @@ class HipWhisper:
         self._chk(self.L.nh_pool_collect(self._h, _ip(rows), len(rows), _ip(toks), res))
         return [dict(tokens=toks[i, :res[i].n_tokens].tolist(), avg_logprob=res[i].avg_logprob,
                      no_speech_prob=res[i].no_speech_prob, no_speech_exit=bool(res[i].no_speech_exit)) for i in range(len(rows))]
+
+    def pool_retry(self, row: int, temperature: float, seed: int, clip: int, attempt: int):
+        """the clip that row `row` last decoded (collected, not refilled since) decodes again, sampled at `temperature` under
+        the seeded contract of decode_sampled with this clip id and attempt; the row is busy again"""
+        self._chk(self.L.nh_pool_retry(self._h, int(row), float(temperature), int(seed), int(clip), int(attempt)))
 
     def get_mel(self, b: int, frames: int = N_FRAMES) -> np.ndarray:
         out = np.zeros((self.cfg.num_mel_bins, frames), dtype=np.float32)

@@ -4,21 +4,61 @@ The reference's decode loop ends per sequence at eot (src/models/whisper/model.r
 (src/lib.rs:462-464); a batch decoded in lockstep makes the short sequences wait for the longest one.  The pool keeps a fixed
 number of decode rows busy instead: the encoder is still fed `staging` clips at a time, every encoded clip is admitted to
 whichever row is free, finished rows are collected every `check_every` steps.  The policy is engine-agnostic (it only calls
-the five methods below), so the CPU tests drive it with a counting stand-in and the GPU tests with HipWhisper.
+the methods below), so the CPU tests drive it with a counting stand-in and the GPU tests with HipWhisper.
 
 engine methods used: pool_begin(rows, max_new, per_clip_language), pool_admit(src_row, dst_row, lang),
 pool_step(n) -> flags per row (0 running, 1 / 2 finished, 3 empty), pool_collect(rows) -> [result],
+pool_retry(row, temperature, seed, clip, attempt) (only with fallback=True),
 and the caller's encode(first_clip, n_clips, row0, must) which must leave clips first .. first + n - 1 encoded in rows
 row0 ... -- or, when `must` is false, may return False to say "the encoder is busy, ask again" (several pools share one GPU:
 the pool then goes on decoding what it has instead of waiting for the encoder with its rows idle).
+
+fallback=True adds decode_with_fallback (src/models/whisper/model.rs:164-191) per clip: an admitted clip is the t = 0 attempt;
+a collected result that fails the test of model.rs:177-179 sends its row through pool_retry(row, temperature, seed, clip,
+attempt) -- the same clip again, sampled at the next of `temperatures`, on the cross K/V the row still holds -- until a result
+is accepted or the temperatures are used up (the reference returns None there: the clip is dropped, accepted=False).  The row
+stays the clip's own meanwhile; the other rows go on being refilled.
 """
 from typing import Callable, List, Optional, Sequence
 
+TEMPERATURES = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0)   # m::TEMPERATURES of model.rs:175 (LOGPROB_THRESHOLD -1, NO_SPEECH_THRESHOLD 0.6)
 
-class DecodePool:
+
+class _Fallback:
+    """what both pools do with a collected result"""
+
+    def _init_fallback(self, fallback, seed, clip0, temperatures, logprob_threshold, no_speech_threshold):
+        self.fallback, self.seed, self.clip0 = bool(fallback), int(seed), int(clip0)
+        self.temperatures = tuple(float(t) for t in temperatures)
+        assert len(self.temperatures) >= 1 and self.temperatures[0] == 0.0 and all(t > 0.0 for t in self.temperatures[1:]), \
+            "temperatures: 0 first (an admitted row is greedy), then the sampled retries"
+        self.logprob_threshold, self.no_speech_threshold = float(logprob_threshold), float(no_speech_threshold)
+        self.retries = 0        # pool_retry calls
+
+    def _settle(self, row: int, clip: int, res: dict, attempt: int) -> bool:
+        """True: `res` is the clip's result (accepted, or dropped after the last temperature) and the row is free.
+        False: the row decodes the clip again at the next temperature."""
+        res["attempt"], res["temperature"], res["accepted"] = attempt, self.temperatures[attempt], True
+        if not self.fallback:
+            return True
+        # model.rs:177-179; compression_ratio is NaN there (:383), so `compression_ratio > threshold` never holds
+        needs = res["avg_logprob"] < self.logprob_threshold
+        if not needs or res["no_speech_prob"] > self.no_speech_threshold:
+            return True
+        if attempt + 1 >= len(self.temperatures):
+            res["accepted"] = False     # model.rs:190: None -- the numbers are the last attempt's
+            return True
+        self.e.pool_retry(row, self.temperatures[attempt + 1], self.seed, self.clip0 + clip, attempt + 1)
+        self.retries += 1
+        return False
+
+
+class DecodePool(_Fallback):
     def __init__(self, engine, rows: int = 64, staging: int = 32, max_new_tokens: int = 0, check_every: int = 16,
-                 per_clip_language: bool = False):
+                 per_clip_language: bool = False, fallback: bool = False, seed: int = 0, clip0: int = 0,
+                 temperatures: Sequence[float] = TEMPERATURES, logprob_threshold: float = -1.0, no_speech_threshold: float = 0.6):
         assert rows >= 1 and staging >= 1 and check_every >= 1
+        self._init_fallback(fallback, seed, clip0, temperatures, logprob_threshold, no_speech_threshold)
         self.e, self.rows, self.staging, self.check_every = engine, rows, staging, check_every
         self.max_new, self.per_clip_language = max_new_tokens, per_clip_language
         self.steps = 0          # decode steps launched
@@ -32,6 +72,7 @@ class DecodePool:
         e.pool_begin(R, self.max_new, self.per_clip_language)
         results: List[Optional[dict]] = [None] * n_clips
         owner = [-1] * R                  # clip decoding in each row
+        attempt = [0] * R                 # index into temperatures of the decode that row is on
         staged: List[int] = []            # clips encoded and waiting for a row, in order; clip c sits in staging row R + (c - staged_first)
         staged_first = 0
         next_clip = 0
@@ -50,7 +91,7 @@ class DecodePool:
                 if owner[r] < 0:
                     c = staged.pop(0)
                     e.pool_admit(R + (c - staged_first), r, -1 if langs is None else int(langs[c]))
-                    owner[r] = c
+                    owner[r], attempt[r] = c, 0
                     busy += 1
             flags = e.pool_step(self.check_every)
             self.steps += self.check_every
@@ -58,6 +99,9 @@ class DecodePool:
             fin = [r for r in range(R) if owner[r] >= 0 and flags[r] in (1, 2)]
             if fin:
                 for r, res in zip(fin, e.pool_collect(fin)):
+                    if not self._settle(r, owner[r], res, attempt[r]):
+                        attempt[r] += 1   # the row is busy again with the same clip
+                        continue
                     results[owner[r]] = res
                     if on_result:
                         on_result(owner[r], res)
@@ -66,7 +110,7 @@ class DecodePool:
         return results  # type: ignore[return-value]
 
 
-class FedDecodePool:
+class FedDecodePool(_Fallback):
     """One decoding context fed by encoder contexts of the same weight set (nh_pool_admit_from): the pool never stalls for an
     encoder submission -- its stream only ever runs decode steps and the device-to-device moves of admitted clips -- while an
     encoder thread keeps the encoder contexts busy one after the other.  `encode(e, first_clip, n)` must leave clips first ..
@@ -74,8 +118,10 @@ class FedDecodePool:
     out again only when every clip of its previous submission has been admitted)."""
 
     def __init__(self, engine, encoders: Sequence, rows: int = 64, batch: int = 32, max_new_tokens: int = 0, check_every: int = 16,
-                 per_clip_language: bool = False):
+                 per_clip_language: bool = False, fallback: bool = False, seed: int = 0, clip0: int = 0,
+                 temperatures: Sequence[float] = TEMPERATURES, logprob_threshold: float = -1.0, no_speech_threshold: float = 0.6):
         assert rows >= 1 and batch >= 1 and check_every >= 1 and len(encoders) >= 1
+        self._init_fallback(fallback, seed, clip0, temperatures, logprob_threshold, no_speech_threshold)
         self.e, self.encoders, self.rows, self.batch, self.check_every = engine, list(encoders), rows, batch, check_every
         self.max_new, self.per_clip_language = max_new_tokens, per_clip_language
         self.steps = self.row_steps = self.encodes = 0
@@ -106,6 +152,7 @@ class FedDecodePool:
         th.start()
         results: List[Optional[dict]] = [None] * n_clips
         owner = [-1] * R
+        attempt = [0] * R
         cur = None          # submission being admitted: [encoder index, first clip, n, next index in it]
         fed_all, busy, done_clips = False, 0, 0
         try:
@@ -128,7 +175,7 @@ class FedDecodePool:
                     i, first, n, j = cur
                     c = first + j
                     e.pool_admit_from(self.encoders[i], j, r, -1 if langs is None else int(langs[c]))
-                    owner[r] = c
+                    owner[r], attempt[r] = c, 0
                     busy += 1
                     cur[3] += 1
                     if cur[3] == n:
@@ -142,6 +189,9 @@ class FedDecodePool:
                 fin = [r for r in range(R) if owner[r] >= 0 and flags[r] in (1, 2)]
                 if fin:
                     for r, res in zip(fin, e.pool_collect(fin)):
+                        if not self._settle(r, owner[r], res, attempt[r]):
+                            attempt[r] += 1
+                            continue
                         results[owner[r]] = res
                         owner[r] = -1
                         busy -= 1

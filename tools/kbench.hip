@@ -106,5 +106,15 @@ int main(int argc, char **argv) {
     bench("dec_attn cross Tk=1500", 9, [&] { size_t o = (size_t)(kvr++ % 3) * B * S * d; launch_dec_attention(q, kc + o, vc + o, att, B, 1, H, d, S, S, nullptr, st); }, 2.0 * B * S * d * 2);
     bench("dec_attn cross Tk=1500, head-major K/V", 9, [&] { size_t o = (size_t)(kvr++ % 3) * B * S * d; launch_dec_attention(q, kc + o, vc + o, att, B, 1, H, d, S, S, nullptr, st, 1); }, 2.0 * B * S * d * 2);
     bench("logit_step mode 1", R, [&] { launch_logit_step(logits, V, ds, tk, B, 4096, 1 << 30, 0, 3, 1, lpart, ltick, nullptr, st); }, (double)B * V * 4);
+    {   // the sampled rows of a decode pool: every row at t = 0.2 and at a generation position (eot suppressed, so no row ends)
+        PoolSampling ps{};
+        ps.inv_t = dmalloc<float>(B); ps.seed = dmalloc<unsigned long long>(B); ps.clip = dmalloc<unsigned>(B);
+        ps.attempt = dmalloc<unsigned>(B); ps.handled = dmalloc<int32_t>(B);
+        std::vector<float> it(B, 5.0f); CK(hipMemcpy(ps.inv_t, it.data(), B * 4, hipMemcpyHostToDevice));
+        CK(hipMemset(const_cast<uint8_t *>(ds.suppress) + tk.eot, 1, 1));
+        int32_t *spos = dmalloc<int32_t>(B);
+        bench("pool_sample_step (all rows sampled)", R, [&] { launch_pool_sample_step(logits, V, ds, tk, B, 4096, 1 << 30, 0, 1, ps, spos, st); }, (double)B * V * 4);
+        bench("logit_step mode 2 behind it (all handled)", R, [&] { launch_logit_step(logits, V, ds, tk, B, 4096, 1 << 30, 0, 1, 2, lpart, ltick, spos, st, ps.handled); }, (double)B * V * 4);
+    }
     return 0;
 }
