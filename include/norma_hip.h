@@ -29,6 +29,8 @@
  *                                 Type::decoder_forward / decoder_final_linear (model.rs:466-483)
  *   nh_decode_sampled             Model::decode at t > 0 (model.rs:340-348) under the seeded sampling contract below
  *   nh_detect_language            Model::detect_language (model.rs:194-210)
+ *   nh_pool_detect_languages, nh_pool_languages
+ *                                 the same for the clips of a decode pool, each in its own first decode step
  *   nh_reset                      Type::reset_kv_cache (model.rs:485-490)
  */
 #ifndef NORMA_HIP_H
@@ -172,7 +174,12 @@ int nh_decode_greedy(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *results
  * result (:373-381) are those of nh_decode_greedy, and so are its bits: the same step kernels run, only the position is read
  * per row.  All clips of a pool must produce the same number of mel frames.  nh_logmel* with row0 = 0 ends the pool.
  * per_clip_language != 0: the prompt carries a language token given per clip at nh_pool_admit (LanguageState::Detect);
- * otherwise nh_tokens.lang decides, as in nh_decode_greedy, and `lang` must be -1. */
+ * otherwise nh_tokens.lang decides, as in nh_decode_greedy, and `lang` must be -1.
+ * lang == NH_LANG_DETECT (per_clip_language pools with a language table, nh_pool_detect_languages): the row detects its
+ * language itself.  Its prompt is [sot, <detected>, task]; slot 1 holds sot until the row's first step has written the
+ * language there, and nothing reads the slot before.  Refused: NH_ERR_INVALID in a pool begun without per-clip languages,
+ * NH_ERR_STATE while the pool has no table. */
+#define NH_LANG_DETECT (-2)
 int nh_pool_begin(nh_ctx *ctx, int rows, int max_new_tokens, int per_clip_language);
 /* The clip encoded at staging row src_row (>= rows) starts decoding in the free row dst_row (< rows): its cross K/V move
  * (device-to-device, 4 * S * d_model bytes per decoder layer), its decode state starts over.  Asynchronous. */
@@ -197,6 +204,24 @@ int nh_pool_collect(nh_ctx *ctx, const int32_t *rows, int n, int32_t *out_tokens
  * clip - clip0, whatever the other rows of the pool do meanwhile.  Refused (NH_ERR_INVALID / NH_ERR_STATE, nothing is
  * launched): no pool, row out of range, row busy, row never admitted since nh_pool_begin, temperature <= 0 or not finite. */
 int nh_pool_retry(nh_ctx *ctx, int row, float temperature, uint64_t seed, uint32_t clip, uint32_t attempt);
+/* Language detection inside the pool.  Model::detect_language (model.rs:194-210) is one decoder forward on [sot] and a softmax
+ * over the language-token logits; the first step of a pooled row is that forward (position 0 consumes sot against the clip's
+ * cross K/V), and the language token is first consumed one step later.  So a row admitted with lang = NH_LANG_DETECT detects
+ * in its first step and writes the token into its own prompt: no extra decoder step, no second context, no host round trip.
+ * Token and probabilities are, bit for bit, those of nh_detect_language on a batch that holds the clip (the same device
+ * function on the same logits).  A row that the no-speech probe ends in that step has a language too (the reference detects
+ * before it decodes); nh_pool_retry keeps the detected token, it is part of the prompt by then.
+ * nh_pool_detect_languages sets the pool's table: lang_tokens in `Language::iter()` order, 1 <= n <= 256, as for
+ * nh_detect_language.  Call it after nh_pool_begin, which clears the table.  Refused, nothing launched: no pool
+ * (NH_ERR_STATE); pool begun without per-clip languages, n out of range, a token id outside the vocabulary (NH_ERR_INVALID);
+ * any row busy (NH_ERR_STATE: the captured step graphs carry the table's size, and whether they detect at all).  A new table
+ * forgets what was detected under the one before (nh_pool_languages refuses those rows). */
+int nh_pool_detect_languages(nh_ctx *ctx, const int32_t *lang_tokens, int n);
+/* Detected token (out_lang: host i32 [n_rows]) and probabilities over the table (out_probs: host f32 [n_rows][n] or NULL) of
+ * rows[]: rows admitted with NH_LANG_DETECT that have taken at least one nh_pool_step step since and have not been refilled --
+ * while they run, and after nh_pool_collect (the lifetime nh_pool_retry relies on).  The token is also tokens[1] of the
+ * row's nh_pool_collect result.  Refused: NH_ERR_INVALID for a row outside the pool, NH_ERR_STATE for any other row. */
+int nh_pool_languages(nh_ctx *ctx, const int32_t *rows, int n_rows, int32_t *out_lang, float *out_probs);
 /* Model::decode at t > 0 (model.rs:340-348): every token is SAMPLED from softmax(q / t), q = the rule-masked
  * probabilities.  The reference draws with rand::WeightedIndex from an entropy-seeded StdRng (model.rs:30), so only its
  * distribution can be reproduced; this build fixes a seeded SAMPLING CONTRACT (the C oracle implements the same, bit for bit):

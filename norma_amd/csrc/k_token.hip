@@ -501,39 +501,44 @@ void launch_logit_step(const float *logits, int V, DecodeState s, RuleTokens tk,
                        prompt_len, mode, partials, tickets, pos_ptr, handled);
 }
 
-// decode pool: sequence `row` starts over with the prompt [t0, t1, (t2)] (model.rs:285-289) at position 0
-__global__ void pool_admit_kernel(DecodeState s, int32_t *pos, unsigned *tickets, int row, int ctx, int t0, int t1, int t2, int P) {
+// decode pool: sequence `row` starts over with the prompt [t0, t1, (t2)] (model.rs:285-289) at position 0.  detect_flag
+// (i32 [B] or null): whether the row detects its language in its first step (t1 is a placeholder until then).
+__global__ void pool_admit_kernel(DecodeState s, int32_t *pos, unsigned *tickets, int row, int ctx, int t0, int t1, int t2, int P,
+                                  int32_t *detect_flag, int detect) {
     int32_t *t = s.tokens + (long)row * ctx;
     t[0] = t0; t[1] = t1; if (P == 3) t[2] = t2;
     s.n_tokens[row] = P; s.done[row] = 0; s.have_last[row] = 0; s.last_ts[row] = 0;
     s.sum_logprob[row] = 0.0; s.no_speech[row] = 0.0;
     pos[row] = 0; tickets[row] = 0u;
+    if (detect_flag) detect_flag[row] = detect;
 }
-void launch_pool_admit(DecodeState s, int32_t *pos, unsigned *tickets, int row, int ctx, int t0, int t1, int t2, int P, hipStream_t st) {
-    hipLaunchKernelGGL(pool_admit_kernel, dim3(1), dim3(1), 0, st, s, pos, tickets, row, ctx, t0, t1, t2, P);
+void launch_pool_admit(DecodeState s, int32_t *pos, unsigned *tickets, int row, int ctx, int t0, int t1, int t2, int P, hipStream_t st,
+                       int32_t *detect_flag, int detect) {
+    hipLaunchKernelGGL(pool_admit_kernel, dim3(1), dim3(1), 0, st, s, pos, tickets, row, ctx, t0, t1, t2, P, detect_flag, detect);
 }
 
 // decode pool: sequence `row` decodes the clip it holds once more, sampled.  The prompt tokens [0, P) are still in place
 // (generation writes from P on; the trimming of finish_sequence works on the host copy), so is the clip's cross K/V.
+// A language the row detected in its t = 0 attempt is one of those prompt tokens: the retry does not detect again.
 __global__ void pool_retry_kernel(DecodeState s, int32_t *pos, unsigned *tickets, PoolSampling ps, int row, int P, float inv_t,
-                                  unsigned long long seed, unsigned clip, unsigned attempt) {
+                                  unsigned long long seed, unsigned clip, unsigned attempt, int32_t *detect_flag) {
     s.n_tokens[row] = P; s.done[row] = 0; s.have_last[row] = 0; s.last_ts[row] = 0;
     s.sum_logprob[row] = 0.0; s.no_speech[row] = 0.0;
     pos[row] = 0; tickets[row] = 0u;
     ps.inv_t[row] = inv_t; ps.seed[row] = seed; ps.clip[row] = clip; ps.attempt[row] = attempt;
+    if (detect_flag) detect_flag[row] = 0;
 }
 void launch_pool_retry(DecodeState s, int32_t *pos, unsigned *tickets, PoolSampling ps, int row, int P, float inv_t,
-                       unsigned long long seed, unsigned clip, unsigned attempt, hipStream_t st) {
-    hipLaunchKernelGGL(pool_retry_kernel, dim3(1), dim3(1), 0, st, s, pos, tickets, ps, row, P, inv_t, seed, clip, attempt);
+                       unsigned long long seed, unsigned clip, unsigned attempt, hipStream_t st, int32_t *detect_flag) {
+    hipLaunchKernelGGL(pool_retry_kernel, dim3(1), dim3(1), 0, st, s, pos, tickets, ps, row, P, inv_t, seed, clip, attempt, detect_flag);
 }
 
 // Model::detect_language (model.rs:194-210) on the position-0 logits of a [sot] prompt: softmax over the language
-// tokens and the FIRST maximum (the reference sorts descending with a stable sort).  One wave per sequence.
-__global__ __launch_bounds__(64) void lang_detect_kernel(const float *__restrict__ logits, int ldl,
-                                                         const int32_t *__restrict__ lang_tokens, int n,
-                                                         float *__restrict__ probs_out, int32_t *__restrict__ lang_out) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const float *lg = logits + (long)b * ldl;
+// tokens and the FIRST maximum (the reference sorts descending with a stable sort).  One whole wave per sequence; every
+// lane returns the winner's index in lang_tokens.  probs_row: f32 [n] or nullptr.  The one place this arithmetic lives:
+// lang_detect_kernel (nh_detect_language) and pool_lang_detect_kernel (the decode pool) both call it.
+__device__ __forceinline__ int lang_softmax_wave(const float *__restrict__ lg, const int32_t *__restrict__ lang_tokens, int n,
+                                                 float *__restrict__ probs_row, int lane) {
     float v[4]; int idx[4];
     float mx = -INFINITY;
 #pragma unroll
@@ -552,7 +557,7 @@ __global__ __launch_bounds__(64) void lang_detect_kernel(const float *__restrict
     for (int u = 0; u < 4; u++) {
         if (idx[u] < n) {
             float p = e[u] / se;
-            if (probs_out) probs_out[(long)b * n + idx[u]] = p;
+            if (probs_row) probs_row[idx[u]] = p;
             int key = total_key(p);
             if (key > bk || (key == bk && idx[u] < bi)) { bk = key; bi = idx[u]; }
         }
@@ -561,6 +566,14 @@ __global__ __launch_bounds__(64) void lang_detect_kernel(const float *__restrict
         int k2 = __shfl_xor(bk, o), i2 = __shfl_xor(bi, o);
         if (k2 > bk || (k2 == bk && i2 < bi)) { bk = k2; bi = i2; }
     }
+    return bi;
+}
+
+__global__ __launch_bounds__(64) void lang_detect_kernel(const float *__restrict__ logits, int ldl,
+                                                         const int32_t *__restrict__ lang_tokens, int n,
+                                                         float *__restrict__ probs_out, int32_t *__restrict__ lang_out) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int bi = lang_softmax_wave(logits + (long)b * ldl, lang_tokens, n, probs_out ? probs_out + (long)b * n : nullptr, lane);
     if (lane == 0) lang_out[b] = lang_tokens[bi];
 }
 
@@ -568,6 +581,29 @@ void launch_lang_detect(const float *logits, int V, const int32_t *lang_tokens, 
                         int B, hipStream_t st) {
     int ldl = (V + 63) & ~63;
     hipLaunchKernelGGL(lang_detect_kernel, dim3(B), dim3(64), 0, st, logits, ldl, lang_tokens, n, probs_out, lang_out);
+}
+
+// decode pool: a row admitted with NH_LANG_DETECT detects its language in the step it takes at position 0 -- that step IS
+// Model::detect_language's forward on [sot].  One wave per row, launched after the step's logits and ahead of
+// logit_step_kernel (which moves pos[b]); only the step graphs of a pool that has a language table carry it.  Lane 0 writes
+// the token into the row's own prompt; the embedding of position 1, a later kernel on the same stream, is the first to read
+// it.  A row that the no-speech probe ends in this very step is detected too: the reference detects before it decodes.
+__global__ __launch_bounds__(64) void pool_lang_detect_kernel(const float *__restrict__ logits, int ldl, DecodeState s, int ctx,
+                                                              const int32_t *__restrict__ pos, PoolDetect det) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (!det.flag[b] || s.done[b] || pos[b] != 0) return;
+    const int bi = lang_softmax_wave(logits + (long)b * ldl, det.lang_tokens, det.n, det.probs + (long)b * 256, lane);
+    if (lane == 0) {
+        const int32_t lt = det.lang_tokens[bi];
+        s.tokens[(long)b * ctx + 1] = lt;
+        det.lang_out[b] = lt;
+    }
+}
+
+void launch_pool_lang_detect(const float *logits, int V, DecodeState s, int B, int ctx, const int32_t *pos, PoolDetect det,
+                             hipStream_t st) {
+    const int ldl = (V + 63) & ~63;
+    hipLaunchKernelGGL(pool_lang_detect_kernel, dim3(B), dim3(64), 0, st, logits, ldl, s, ctx, pos, det);
 }
 
 __global__ __launch_bounds__(1024) void rules_only_kernel(const float *__restrict__ probs_in, float *masked_out,

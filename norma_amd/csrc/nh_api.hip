@@ -116,13 +116,18 @@ struct nh_ctx {
     std::vector<char> pool_sampled;  // the row is busy on a sampled retry (nh_pool_retry); cleared by nh_pool_collect and by an admit
     std::vector<char> pool_inv_t;    // the row's device-side inv_t is > 0 (its last decode was a retry): the next admit zeroes it
     PoolSampling psamp{};            // [max_batch] each: per-row temperature, seed, clip, attempt, and the step's handled flags
+    // language detection inside the pool (nh_pool_detect_languages): a row admitted with NH_LANG_DETECT detects in its first step
+    int pool_lang_n = 0;             // entries of the pool's language table in d_lang_tokens; 0: none (part of the graph key)
+    std::vector<char> pool_detect;   // the row's clip was admitted with NH_LANG_DETECT; an admit sets or clears it
+    std::vector<char> pool_detected; // ... and has taken a step since: d_lang_out / d_lang_probs hold its language
+    int32_t *d_lang_flag = nullptr;  // [max_batch] device side of pool_detect, cleared by a retry (the token is in the prompt by then)
     hipGraphExec_t step_graph = nullptr;   // one decode step
     hipGraphExec_t multi_graph = nullptr;  // NH_GRAPH_STEPS consecutive steps (one launch gap instead of NH_GRAPH_STEPS)
-    int graph_key[6] = {-1, -1, -1, -1, -1, -1};
+    int graph_key[7] = {-1, -1, -1, -1, -1, -1, -1};
     // the same pair for pool steps with at least one sampled row busy: pool_sample_step_kernel ahead of logit_step_kernel.
     // Kept beside the greedy pair, so a pool that goes back and forth between the two states captures each once.
     hipGraphExec_t step_graph_s = nullptr, multi_graph_s = nullptr;
-    int graph_key_s[6] = {-1, -1, -1, -1, -1, -1};
+    int graph_key_s[7] = {-1, -1, -1, -1, -1, -1, -1};
     int token_gen = 0;  // bumped by nh_set_tokens; part of the graph key
     bool opt_graphs = true, opt_fuse_ln = true;  // nh_set_option
     int opt_absorbed = 0;        // NH_OPT_ABSORBED_XATTN: 1 = numerics prototype, 2 = one-pass kernels
@@ -152,7 +157,7 @@ struct nh_ctx {
 };
 
 // the captured decode-step graphs bake in everything the step kernels take by value (batch, encoder length, the rule
-// token ids, the max_new_tokens knob): whoever changes one of those drops the graphs, the next greedy decode re-captures
+// token ids, the max_new_tokens knob, the size of a pool's language table): whoever changes one of those drops the graphs, the next greedy decode re-captures
 static void drop_sampled_graphs(nh_ctx *ctx) {
     if (ctx->step_graph_s) { hipGraphExecDestroy(ctx->step_graph_s); ctx->step_graph_s = nullptr; }
     if (ctx->multi_graph_s) { hipGraphExecDestroy(ctx->multi_graph_s); ctx->multi_graph_s = nullptr; }
@@ -380,7 +385,7 @@ static int build_context(std::shared_ptr<nh_model> mdl, int max_batch, nh_ctx **
     DA(ds.have_last, int32_t, B); DA(ds.last_ts, int32_t, B); DA(ds.sum_logprob, double, B); DA(ds.no_speech, double, B);
     DA(ds.n_active, int32_t, 1); DA(suppress, uint8_t, V); DA(lpart, float, (long)B * 64); DA(ltick, unsigned, B); DA(d_pos, int32_t, B);
     DA(psamp.inv_t, float, B); DA(psamp.seed, unsigned long long, B); DA(psamp.clip, unsigned, B); DA(psamp.attempt, unsigned, B); DA(psamp.handled, int32_t, B);
-    DA(d_lang_tokens, int32_t, 256); DA(d_lang_out, int32_t, B); DA(d_lang_probs, float, (long)B * 256);
+    DA(d_lang_tokens, int32_t, 256); DA(d_lang_out, int32_t, B); DA(d_lang_flag, int32_t, B); DA(d_lang_probs, float, (long)B * 256);
 #undef DA
     if (!ok) { ctx->err = "hipMalloc failed while sizing the context (out of device memory?)"; return bail(NH_ERR_NOMEM); }
     ctx->ds.suppress = ctx->suppress;
@@ -1043,7 +1048,7 @@ static int decode_impl(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *resul
     // pos + 2 >= cap, so pos never exceeds cap - 2.  The ~20-launch step is captured (once, and 8 steps back to back) into hipGraphs that
     // reads the position from device memory (the eager loop is host-launch-bound at ~5 us per tiny kernel).
     const bool no_graph = !ctx->opt_graphs || inv_t > 0.f;
-    const int key[6] = {B, ctx->S, max_new_tokens, P, ctx->token_gen, 0};
+    const int key[7] = {B, ctx->S, max_new_tokens, P, ctx->token_gen, 0, 0};
     if (!no_graph && memcmp(key, ctx->graph_key, sizeof(key)) != 0) {
         drop_graphs(ctx);
         if (int rc = capture_step_graphs(ctx, B, max_new_tokens, P, 1)) return rc;
@@ -1120,6 +1125,7 @@ extern "C" int nh_pool_begin(nh_ctx *ctx, int rows, int max_new_tokens, int per_
     ctx->pool_per_clip_language = per_clip_language != 0;
     const bool was_sampled = std::find(ctx->pool_inv_t.begin(), ctx->pool_inv_t.end(), 1) != ctx->pool_inv_t.end();
     ctx->pool_busy.assign(rows, 0); ctx->pool_held.assign(rows, 0); ctx->pool_sampled.assign(rows, 0); ctx->pool_inv_t.assign(rows, 0);
+    ctx->pool_lang_n = 0; ctx->pool_detect.assign(rows, 0); ctx->pool_detected.assign(rows, 0);
     ctx->cur_batch = rows; ctx->frames = -1; ctx->S = 0; ctx->have_mel = false; ctx->have_enc = false;
     ctx->seq_lang.clear();
     for (int b = 0; b < rows; b++) ctx->h_done[128 + b] = 3;  // 3: empty row (skipped like a finished one)
@@ -1134,8 +1140,11 @@ extern "C" int nh_pool_begin(nh_ctx *ctx, int rows, int max_new_tokens, int per_
 static int pool_admit_impl(nh_ctx *ctx, nh_ctx *src, int src_row, int dst_row, int32_t lang) {
     if (dst_row < 0 || dst_row >= ctx->pool_rows || ctx->pool_busy[dst_row]) return ctx->fail(NH_ERR_INVALID, "nh_pool_admit: dst_row is not a free row of the pool");
     const int P = ctx->pool_prompt;
-    if (!ctx->pool_per_clip_language && lang >= 0) return ctx->fail(NH_ERR_INVALID, "nh_pool_admit: the pool was begun without per-clip languages");
-    int32_t lg = lang >= 0 ? lang : ctx->tk.lang;
+    const bool detect = lang == NH_LANG_DETECT;
+    if (!ctx->pool_per_clip_language && (lang >= 0 || detect)) return ctx->fail(NH_ERR_INVALID, "nh_pool_admit: the pool was begun without per-clip languages");
+    if (detect && ctx->pool_lang_n < 1) return ctx->fail(NH_ERR_STATE, "nh_pool_admit: NH_LANG_DETECT needs the pool's language table (nh_pool_detect_languages)");
+    // a detecting row holds sot in slot 1 until its first step has written the language there; nothing reads the slot before
+    int32_t lg = detect ? ctx->tk.sot : lang >= 0 ? lang : ctx->tk.lang;
     if (P == 3 && (lg < 0 || lg >= ctx->c.vocab_size)) return ctx->fail(NH_ERR_INVALID, "nh_pool_admit: language token outside the vocabulary");
     hipSetDevice(ctx->dev);
     const size_t per = (size_t)ctx->S * ctx->c.d_model;  // cross K / V of one clip and layer, head-major [h][S][64]
@@ -1152,8 +1161,9 @@ static int pool_admit_impl(nh_ctx *ctx, nh_ctx *src, int src_row, int dst_row, i
     }
     // model.rs:285-289: prompt = [sot, lang?, task]
     launch_pool_admit(ctx->ds, ctx->d_pos, ctx->ltick, dst_row, ctx->c.max_target_positions, ctx->tk.sot, P == 3 ? lg : ctx->tk.task,
-                      ctx->tk.task, P, ctx->sd);
+                      ctx->tk.task, P, ctx->sd, ctx->d_lang_flag, detect ? 1 : 0);
     HIPCHK(hipGetLastError());
+    ctx->pool_detect[dst_row] = detect ? 1 : 0; ctx->pool_detected[dst_row] = 0;
     if (ctx->pool_inv_t[dst_row]) {  // an admitted row is greedy (a pool that never retried launches nothing here)
         HIPCHK(hipMemsetAsync(ctx->psamp.inv_t + dst_row, 0, sizeof(float), ctx->sd));
         ctx->pool_inv_t[dst_row] = 0;
@@ -1173,7 +1183,8 @@ extern "C" int nh_pool_retry(nh_ctx *ctx, int row, float temperature, uint64_t s
     if (!ctx->pool_held[row]) return ctx->fail(NH_ERR_STATE, "nh_pool_retry: no clip was admitted into that row since nh_pool_begin");
     if (!(temperature > 0.f && temperature < INFINITY)) return ctx->fail(NH_ERR_INVALID, "nh_pool_retry: temperature must be > 0 and finite (an admitted row decodes at t = 0)");
     hipSetDevice(ctx->dev);
-    launch_pool_retry(ctx->ds, ctx->d_pos, ctx->ltick, ctx->psamp, row, ctx->pool_prompt, 1.0f / temperature, seed, clip, attempt, ctx->sd);
+    launch_pool_retry(ctx->ds, ctx->d_pos, ctx->ltick, ctx->psamp, row, ctx->pool_prompt, 1.0f / temperature, seed, clip, attempt, ctx->sd,
+                      ctx->d_lang_flag);
     HIPCHK(hipGetLastError());
     ctx->pool_busy[row] = 1; ctx->pool_sampled[row] = 1; ctx->pool_inv_t[row] = 1;
     return NH_OK;
@@ -1198,6 +1209,10 @@ extern "C" int nh_pool_admit_from(nh_ctx *ctx, nh_ctx *enc, int src_row, int dst
     return pool_admit_impl(ctx, enc, src_row, dst_row, lang);
 }
 
+static PoolDetect pool_detect_args(nh_ctx *ctx) {
+    return PoolDetect{ctx->d_lang_flag, ctx->d_lang_tokens, ctx->pool_lang_n, ctx->d_lang_out, ctx->d_lang_probs};
+}
+
 static int capture_step_graphs(nh_ctx *ctx, int B, int max_new_tokens, int P, int mode, bool sampled) {
     const int C = ctx->c.max_target_positions, cap = C - 1, V = ctx->c.vocab_size;
     hipGraphExec_t &one = sampled ? ctx->step_graph_s : ctx->step_graph, &multi = sampled ? ctx->multi_graph_s : ctx->multi_graph;
@@ -1208,6 +1223,7 @@ static int capture_step_graphs(nh_ctx *ctx, int B, int max_new_tokens, int P, in
         for (int i = 0; i < (which ? NH_GRAPH_STEPS : 1); i++) {  // every step reads and advances the device-side positions
             decoder_step(ctx, 0, ctx->d_pos, false, true);
             logits_from_dx(ctx, B);
+            if (mode == 2 && ctx->pool_lang_n > 0) launch_pool_lang_detect(ctx->logits, V, ctx->ds, B, C, ctx->d_pos, pool_detect_args(ctx), ctx->sd);
             if (sampled) launch_pool_sample_step(ctx->logits, V, ctx->ds, ctx->tk, B, C, cap, max_new_tokens, P, ctx->psamp, ctx->d_pos, ctx->sd);
             launch_logit_step(ctx->logits, V, ctx->ds, ctx->tk, B, C, cap, max_new_tokens, P, mode, ctx->lpart, ctx->ltick, ctx->d_pos, ctx->sd,
                               sampled ? ctx->psamp.handled : nullptr);
@@ -1240,7 +1256,7 @@ extern "C" int nh_pool_step(nh_ctx *ctx, int n_steps, int32_t *done_out) {
     if (any && n_steps > 0) {
         if (ctx->S < 1) return ctx->fail(NH_ERR_STATE, "nh_pool_step: rows are busy but nothing was ever encoded");
         if (ctx->opt_graphs) {
-            const int key[6] = {B, ctx->S, ctx->pool_max_new, P, ctx->token_gen, 1};
+            const int key[7] = {B, ctx->S, ctx->pool_max_new, P, ctx->token_gen, 1, ctx->pool_lang_n};
             if (memcmp(key, ctx->graph_key, sizeof(key)) != 0) {
                 drop_graphs(ctx);
                 if (int rc = capture_step_graphs(ctx, B, ctx->pool_max_new, P, 2)) return rc;
@@ -1256,6 +1272,7 @@ extern "C" int nh_pool_step(nh_ctx *ctx, int n_steps, int32_t *done_out) {
             if (!ctx->opt_graphs) {
                 decoder_step(ctx, 0, ctx->d_pos, false, true);
                 logits_from_dx(ctx, B);
+                if (ctx->pool_lang_n > 0) launch_pool_lang_detect(ctx->logits, V, ctx->ds, B, C, ctx->d_pos, pool_detect_args(ctx), ctx->sd);
                 if (sampled) launch_pool_sample_step(ctx->logits, V, ctx->ds, ctx->tk, B, C, cap, ctx->pool_max_new, P, ctx->psamp, ctx->d_pos, ctx->sd);
                 launch_logit_step(ctx->logits, V, ctx->ds, ctx->tk, B, C, cap, ctx->pool_max_new, P, 2, ctx->lpart, ctx->ltick, ctx->d_pos, ctx->sd,
                                   sampled ? ctx->psamp.handled : nullptr);
@@ -1264,6 +1281,7 @@ extern "C" int nh_pool_step(nh_ctx *ctx, int n_steps, int32_t *done_out) {
             else { HIPCHK(hipGraphLaunch(sampled ? ctx->step_graph_s : ctx->step_graph, ctx->sd)); left--; }
         }
         ctx->tm.decode_steps += n_steps;
+        for (int b = 0; b < B; b++) if (ctx->pool_busy[b] && ctx->pool_detect[b]) ctx->pool_detected[b] = 1;  // its first step is behind it
     }
     HIPCHK(hipMemcpyAsync(ctx->h_done, ctx->ds.done, B * 4, hipMemcpyDeviceToHost, ctx->sd));
     HIPCHK(hipStreamSynchronize(ctx->sd));
@@ -1295,6 +1313,47 @@ extern "C" int nh_pool_collect(nh_ctx *ctx, const int32_t *rows, int n, int32_t 
         finish_sequence(ctx, toks.data() + (size_t)i * C, nt[b], done[b], slp[b], nsp[b], out_tokens + (size_t)i * C, results[i]);
         ctx->pool_busy[b] = 0; ctx->pool_sampled[b] = 0;
     }
+    return NH_OK;
+}
+
+// The pool's language table.  The step graphs bake the table's size in (PoolDetect::n goes by value) and whether the
+// detection kernel is part of a step at all, so the table changes only while no row is busy, and its size is in the graph key.
+extern "C" int nh_pool_detect_languages(nh_ctx *ctx, const int32_t *lang_tokens, int n) {
+    if (!ctx) return NH_ERR_INVALID;
+    if (ctx->pool_rows < 1) return ctx->fail(NH_ERR_STATE, "nh_pool_detect_languages: no decode pool (nh_pool_begin)");
+    if (!ctx->pool_per_clip_language) return ctx->fail(NH_ERR_INVALID, "nh_pool_detect_languages: the pool was begun without per-clip languages");
+    if (!lang_tokens || n < 1 || n > 256) return ctx->fail(NH_ERR_INVALID, "nh_pool_detect_languages: bad arguments (1 <= n <= 256)");
+    for (int i = 0; i < n; i++)
+        if (lang_tokens[i] < 0 || lang_tokens[i] >= ctx->c.vocab_size) return ctx->fail(NH_ERR_INVALID, "nh_pool_detect_languages: token id outside the vocabulary");
+    for (int b = 0; b < ctx->pool_rows; b++)
+        if (ctx->pool_busy[b]) return ctx->fail(NH_ERR_STATE, "nh_pool_detect_languages: rows are busy (the table is part of the captured steps)");
+    hipSetDevice(ctx->dev);
+    HIPCHK(hipMemcpyAsync(ctx->d_lang_tokens, lang_tokens, n * 4, hipMemcpyHostToDevice, ctx->sd));
+    HIPCHK(hipStreamSynchronize(ctx->sd));  // lang_tokens is the caller's
+    ctx->pool_lang_n = n;
+    // languages detected under another table are no longer answered for (nh_pool_languages)
+    std::fill(ctx->pool_detect.begin(), ctx->pool_detect.end(), 0);
+    std::fill(ctx->pool_detected.begin(), ctx->pool_detected.end(), 0);
+    return NH_OK;
+}
+
+extern "C" int nh_pool_languages(nh_ctx *ctx, const int32_t *rows, int n_rows, int32_t *out_lang, float *out_probs) {
+    if (!ctx || !rows || !out_lang || n_rows < 1) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_pool_languages: bad arguments") : NH_ERR_INVALID;
+    if (ctx->pool_rows < 1) return ctx->fail(NH_ERR_STATE, "nh_pool_languages: no decode pool (nh_pool_begin)");
+    for (int i = 0; i < n_rows; i++) {
+        if (rows[i] < 0 || rows[i] >= ctx->pool_rows) return ctx->fail(NH_ERR_INVALID, "nh_pool_languages: row outside the pool");
+        if (!ctx->pool_detect[rows[i]]) return ctx->fail(NH_ERR_STATE, "nh_pool_languages: that row's clip was not admitted with NH_LANG_DETECT");
+        if (!ctx->pool_detected[rows[i]]) return ctx->fail(NH_ERR_STATE, "nh_pool_languages: that row has not taken a step since it was admitted (nh_pool_step)");
+    }
+    hipSetDevice(ctx->dev);
+    const int n = ctx->pool_lang_n;
+    std::vector<int32_t> lang(ctx->pool_rows);
+    HIPCHK(hipMemcpyAsync(lang.data(), ctx->d_lang_out, sizeof(int32_t) * ctx->pool_rows, hipMemcpyDeviceToHost, ctx->sd));
+    if (out_probs)
+        for (int i = 0; i < n_rows; i++)
+            HIPCHK(hipMemcpyAsync(out_probs + (size_t)i * n, ctx->d_lang_probs + (size_t)rows[i] * 256, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->sd));
+    HIPCHK(hipStreamSynchronize(ctx->sd));
+    for (int i = 0; i < n_rows; i++) out_lang[i] = lang[rows[i]];
     return NH_OK;
 }
 

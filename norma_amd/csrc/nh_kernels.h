@@ -279,8 +279,10 @@ struct RuleTokens { int sot, eot, lang, task, no_speech, no_timestamps, zero_sec
 void launch_logit_step(const float *logits, int V, DecodeState s, RuleTokens tk, int B, int ctx, int cap,
                        int max_new, int prompt_len, int mode, float *partials, unsigned *tickets, int32_t *pos_ptr,
                        hipStream_t st, const int32_t *handled = nullptr);
-// decode pool: sequence `row` restarts at position 0 with the prompt [t0, t1] (P = 2) or [t0, t1, t2] (P = 3)
-void launch_pool_admit(DecodeState s, int32_t *pos, unsigned *tickets, int row, int ctx, int t0, int t1, int t2, int P, hipStream_t st);
+// decode pool: sequence `row` restarts at position 0 with the prompt [t0, t1] (P = 2) or [t0, t1, t2] (P = 3);
+// detect_flag != nullptr: detect_flag[row] = detect (see PoolDetect)
+void launch_pool_admit(DecodeState s, int32_t *pos, unsigned *tickets, int row, int ctx, int t0, int t1, int t2, int P, hipStream_t st,
+                       int32_t *detect_flag = nullptr, int detect = 0);
 // decode pool, sampled rows: how each row draws its tokens.  All device pointers, [B]; inv_t == 0: the row is greedy.
 struct PoolSampling {
     float *inv_t;
@@ -289,8 +291,9 @@ struct PoolSampling {
     int32_t *handled;       // written every step by pool_sample_step_kernel: 1 = it generated this row's token
 };
 // decode pool: sequence `row` decodes its clip again from position 0, sampled at 1 / inv_t; its prompt tokens [0, P) stay
+// (a detected language among them: detect_flag[row], when given, is cleared)
 void launch_pool_retry(DecodeState s, int32_t *pos, unsigned *tickets, PoolSampling ps, int row, int P, float inv_t,
-                       unsigned long long seed, unsigned clip, unsigned attempt, hipStream_t st);
+                       unsigned long long seed, unsigned clip, unsigned attempt, hipStream_t st, int32_t *detect_flag = nullptr);
 // decode pool: launch_sample_step for the rows that are sampled (inv_t > 0), running and at a generation position
 // (pos[b] >= prompt_len - 1); advances pos[b] of those and writes ps.handled[b] for every row.  Runs ahead of
 // launch_logit_step(mode 2, handled = ps.handled), which does the probe, the prompt positions and the greedy rows.
@@ -307,6 +310,18 @@ void launch_sample_rules(const float *probs_in, int32_t *token_out, const int32_
 // detect_language: logits [B][ldl] at prompt position 0 -> per-sequence language token (first maximum), optional probs [B][n]
 void launch_lang_detect(const float *logits, int V, const int32_t *lang_tokens, int n, float *probs_out, int32_t *lang_out,
                         int B, hipStream_t st);
+// decode pool with a language table (nh_pool_detect_languages): a row whose flag is set detects its language in the step it
+// takes at position 0 -- launch_lang_detect's arithmetic on that step's logits -- and writes the token into tokens[b][1].
+// Goes between the step's logits and launch_logit_step(mode 2), which advances pos.
+struct PoolDetect {
+    const int32_t *flag;         // i32 [B]: the row was admitted with NH_LANG_DETECT (launch_pool_admit sets, launch_pool_retry clears)
+    const int32_t *lang_tokens;  // i32 [n], Language::iter() order
+    int n;                       // 1 .. 256; taken by value, so part of the key of the captured step graphs
+    int32_t *lang_out;           // i32 [B]
+    float *probs;                // f32 [B][256]
+};
+void launch_pool_lang_detect(const float *logits, int V, DecodeState s, int B, int ctx, const int32_t *pos, PoolDetect det,
+                             hipStream_t st);
 // parity helper: apply rules to one already soft-maxed probability vector
 void launch_rules_only(const float *probs_in, float *masked_out, int32_t *argmax_out, const int32_t *tokens,
                        int n_tokens, int last_ts, const uint8_t *suppress, RuleTokens tk, int V, hipStream_t st);

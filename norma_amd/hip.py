@@ -23,6 +23,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "norma_hip.h")
 N_SAMPLES = 480000
 N_FRAMES = 3000
 NH_DTYPE_F32, NH_DTYPE_F16 = 0, 1
+NH_LANG_DETECT = -2   # `lang` of pool_admit*: the row detects its language in its first step (pool_detect_languages)
 NH_OPT_DECODE_GRAPHS, NH_OPT_FUSE_DECODE_LAYERNORM, NH_OPT_DECODER_LAYER_LIMIT, NH_OPT_ABSORBED_XATTN = 0, 1, 2, 3
 # NH_SAMPLE_* of include/norma_hip.h (the types of src/dtype.rs)
 SAMPLE_DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.int8): 2, np.dtype(np.int16): 3,
@@ -102,6 +103,8 @@ def load_library() -> C.CDLL:
     L.nh_pool_step.argtypes = [vp, C.c_int, ip]
     L.nh_pool_collect.argtypes = [vp, ip, C.c_int, ip, C.POINTER(NhDecodeResult)]
     L.nh_pool_retry.argtypes = [vp, C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_uint32]
+    L.nh_pool_detect_languages.argtypes = [vp, ip, C.c_int]
+    L.nh_pool_languages.argtypes = [vp, ip, C.c_int, ip, fp]
     L.nh_logmel_samples.argtypes = [vp, vp, C.c_int, ip, C.c_int64, C.c_int]
     L.nh_sample_size.argtypes = [C.c_int]
     L.nh_encode.argtypes = [vp]
@@ -295,6 +298,21 @@ class HipWhisper:
         """the clip that row `row` last decoded (collected, not refilled since) decodes again, sampled at `temperature` under
         the seeded contract of decode_sampled with this clip id and attempt; the row is busy again"""
         self._chk(self.L.nh_pool_retry(self._h, int(row), float(temperature), int(seed), int(clip), int(attempt)))
+
+    def pool_detect_languages(self, lang_tokens: Sequence[int]):
+        """the pool's language table (Language::iter() order), after pool_begin(per_clip_language=True) and while no row is
+        busy: clips admitted with lang = NH_LANG_DETECT detect their language in their own first decode step"""
+        lt = np.ascontiguousarray(lang_tokens, dtype=np.int32)
+        self._chk(self.L.nh_pool_detect_languages(self._h, _ip(lt), len(lt)))
+        self.pool_lang_n = len(lt)
+
+    def pool_languages(self, rows: Sequence[int], want_probs: bool = True):
+        """(tokens, probs [len(rows)][n] or None) of rows admitted with NH_LANG_DETECT that have stepped since"""
+        rows = np.asarray(rows, dtype=np.int32)
+        out = np.zeros(len(rows), dtype=np.int32)
+        probs = np.zeros((len(rows), getattr(self, "pool_lang_n", 0)), dtype=np.float32) if want_probs else None
+        self._chk(self.L.nh_pool_languages(self._h, _ip(rows), len(rows), _ip(out), _fp(probs) if want_probs else None))
+        return out.tolist(), probs
 
     def get_mel(self, b: int, frames: int = N_FRAMES) -> np.ndarray:
         out = np.zeros((self.cfg.num_mel_bins, frames), dtype=np.float32)

@@ -9,6 +9,7 @@ the methods below), so the CPU tests drive it with a counting stand-in and the G
 engine methods used: pool_begin(rows, max_new, per_clip_language), pool_admit(src_row, dst_row, lang),
 pool_step(n) -> flags per row (0 running, 1 / 2 finished, 3 empty), pool_collect(rows) -> [result],
 pool_retry(row, temperature, seed, clip, attempt) (only with fallback=True),
+pool_detect_languages(lang_tokens) and pool_languages(rows) -> (tokens, probs) (only with detect_languages=...),
 and the caller's encode(first_clip, n_clips, row0, must) which must leave clips first .. first + n - 1 encoded in rows
 row0 ... -- or, when `must` is false, may return False to say "the encoder is busy, ask again" (several pools share one GPU:
 the pool then goes on decoding what it has instead of waiting for the encoder with its rows idle).
@@ -18,8 +19,17 @@ a collected result that fails the test of model.rs:177-179 sends its row through
 attempt) -- the same clip again, sampled at the next of `temperatures`, on the cross K/V the row still holds -- until a result
 is accepted or the temperatures are used up (the reference returns None there: the clip is dropped, accepted=False).  The row
 stays the clip's own meanwhile; the other rows go on being refilled.
+
+detect_languages=<language tokens in Language::iter() order> adds the language step of decode_with_fallback (model.rs:170-173)
+per clip: the table goes to pool_detect_languages(tokens) once after pool_begin (per-clip languages are implied), a clip
+without an entry in `langs` is admitted with NH_LANG_DETECT and detects its language in its own first decode step, and
+pool_languages(rows) -> (tokens, probs) is read when its t = 0 attempt is collected.  Every result then carries "language",
+detected clips also "language_probs"; a retried clip keeps what its t = 0 attempt detected.  Without the keyword neither
+engine method is called.
 """
 from typing import Callable, List, Optional, Sequence
+
+from .hip import NH_LANG_DETECT
 
 TEMPERATURES = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0)   # m::TEMPERATURES of model.rs:175 (LOGPROB_THRESHOLD -1, NO_SPEECH_THRESHOLD 0.6)
 
@@ -34,6 +44,41 @@ class _Fallback:
             "temperatures: 0 first (an admitted row is greedy), then the sampled retries"
         self.logprob_threshold, self.no_speech_threshold = float(logprob_threshold), float(no_speech_threshold)
         self.retries = 0        # pool_retry calls
+
+    def _init_detect(self, detect_languages):
+        self.detect_languages = None if detect_languages is None else [int(t) for t in detect_languages]
+        if self.detect_languages is not None:
+            self.per_clip_language = True
+
+    def _begin(self):
+        self.e.pool_begin(self.rows, self.max_new, self.per_clip_language)
+        if self.detect_languages is not None:
+            self.e.pool_detect_languages(self.detect_languages)
+        self._lang = [None] * self.rows     # per row: (language token, probabilities or None) of the clip it holds
+
+    def _admit_lang(self, row: int, clip: int, langs) -> int:
+        """the `lang` a clip is admitted with"""
+        given = None if langs is None else langs[clip]
+        if self.detect_languages is None:
+            return -1 if given is None else int(given)
+        self._lang[row] = None if given is None else (int(given), None)
+        return NH_LANG_DETECT if given is None else int(given)
+
+    def _collect(self, fin: List[int], attempt: List[int]) -> List[dict]:
+        """pool_collect, plus the languages: detected ones are read once, with the t = 0 attempt (those rows have stepped)"""
+        out = self.e.pool_collect(fin)
+        if self.detect_languages is not None:
+            det = [r for r in fin if self._lang[r] is None]
+            if det:
+                assert all(attempt[r] == 0 for r in det)
+                toks, probs = self.e.pool_languages(det)
+                for i, r in enumerate(det):
+                    self._lang[r] = (int(toks[i]), probs[i])
+            for r, res in zip(fin, out):
+                res["language"] = self._lang[r][0]
+                if self._lang[r][1] is not None:
+                    res["language_probs"] = self._lang[r][1]
+        return out
 
     def _settle(self, row: int, clip: int, res: dict, attempt: int) -> bool:
         """True: `res` is the clip's result (accepted, or dropped after the last temperature) and the row is free.
@@ -56,20 +101,22 @@ class _Fallback:
 class DecodePool(_Fallback):
     def __init__(self, engine, rows: int = 64, staging: int = 32, max_new_tokens: int = 0, check_every: int = 16,
                  per_clip_language: bool = False, fallback: bool = False, seed: int = 0, clip0: int = 0,
-                 temperatures: Sequence[float] = TEMPERATURES, logprob_threshold: float = -1.0, no_speech_threshold: float = 0.6):
+                 temperatures: Sequence[float] = TEMPERATURES, logprob_threshold: float = -1.0, no_speech_threshold: float = 0.6,
+                 detect_languages: Optional[Sequence[int]] = None):
         assert rows >= 1 and staging >= 1 and check_every >= 1
         self._init_fallback(fallback, seed, clip0, temperatures, logprob_threshold, no_speech_threshold)
         self.e, self.rows, self.staging, self.check_every = engine, rows, staging, check_every
         self.max_new, self.per_clip_language = max_new_tokens, per_clip_language
+        self._init_detect(detect_languages)
         self.steps = 0          # decode steps launched
         self.row_steps = 0      # sum over steps of the rows that were busy (what the step kernels' per-row work scales with)
         self.encodes = 0
 
-    def run(self, n_clips: int, encode: Callable[[int, int, int, bool], Optional[bool]], langs: Optional[Sequence[int]] = None,
+    def run(self, n_clips: int, encode: Callable[[int, int, int, bool], Optional[bool]], langs: Optional[Sequence[Optional[int]]] = None,
             on_result: Optional[Callable[[int, dict], None]] = None) -> List[dict]:
         """Decode clips 0 .. n_clips - 1; returns their results in clip order."""
         e, R = self.e, self.rows
-        e.pool_begin(R, self.max_new, self.per_clip_language)
+        self._begin()
         results: List[Optional[dict]] = [None] * n_clips
         owner = [-1] * R                  # clip decoding in each row
         attempt = [0] * R                 # index into temperatures of the decode that row is on
@@ -90,7 +137,7 @@ class DecodePool(_Fallback):
                     break
                 if owner[r] < 0:
                     c = staged.pop(0)
-                    e.pool_admit(R + (c - staged_first), r, -1 if langs is None else int(langs[c]))
+                    e.pool_admit(R + (c - staged_first), r, self._admit_lang(r, c, langs))
                     owner[r], attempt[r] = c, 0
                     busy += 1
             flags = e.pool_step(self.check_every)
@@ -98,7 +145,7 @@ class DecodePool(_Fallback):
             self.row_steps += busy * self.check_every
             fin = [r for r in range(R) if owner[r] >= 0 and flags[r] in (1, 2)]
             if fin:
-                for r, res in zip(fin, e.pool_collect(fin)):
+                for r, res in zip(fin, self._collect(fin, attempt)):
                     if not self._settle(r, owner[r], res, attempt[r]):
                         attempt[r] += 1   # the row is busy again with the same clip
                         continue
@@ -119,18 +166,20 @@ class FedDecodePool(_Fallback):
 
     def __init__(self, engine, encoders: Sequence, rows: int = 64, batch: int = 32, max_new_tokens: int = 0, check_every: int = 16,
                  per_clip_language: bool = False, fallback: bool = False, seed: int = 0, clip0: int = 0,
-                 temperatures: Sequence[float] = TEMPERATURES, logprob_threshold: float = -1.0, no_speech_threshold: float = 0.6):
+                 temperatures: Sequence[float] = TEMPERATURES, logprob_threshold: float = -1.0, no_speech_threshold: float = 0.6,
+                 detect_languages: Optional[Sequence[int]] = None):
         assert rows >= 1 and batch >= 1 and check_every >= 1 and len(encoders) >= 1
         self._init_fallback(fallback, seed, clip0, temperatures, logprob_threshold, no_speech_threshold)
         self.e, self.encoders, self.rows, self.batch, self.check_every = engine, list(encoders), rows, batch, check_every
         self.max_new, self.per_clip_language = max_new_tokens, per_clip_language
+        self._init_detect(detect_languages)
         self.steps = self.row_steps = self.encodes = 0
 
-    def run(self, n_clips: int, encode: Callable[[int, int, int], None], langs: Optional[Sequence[int]] = None) -> List[dict]:
+    def run(self, n_clips: int, encode: Callable[[int, int, int], None], langs: Optional[Sequence[Optional[int]]] = None) -> List[dict]:
         import queue
         import threading
         e, R, NE = self.e, self.rows, len(self.encoders)
-        e.pool_begin(R, self.max_new, self.per_clip_language)
+        self._begin()
         ready: "queue.Queue" = queue.Queue()                 # (encoder index, first clip, n) in submission order
         free = [threading.Semaphore(1) for _ in range(NE)]   # encoder context not holding un-admitted clips
         errs: List[BaseException] = []
@@ -174,7 +223,7 @@ class FedDecodePool(_Fallback):
                         break
                     i, first, n, j = cur
                     c = first + j
-                    e.pool_admit_from(self.encoders[i], j, r, -1 if langs is None else int(langs[c]))
+                    e.pool_admit_from(self.encoders[i], j, r, self._admit_lang(r, c, langs))
                     owner[r], attempt[r] = c, 0
                     busy += 1
                     cur[3] += 1
@@ -188,7 +237,7 @@ class FedDecodePool(_Fallback):
                 self.row_steps += busy * self.check_every
                 fin = [r for r in range(R) if owner[r] >= 0 and flags[r] in (1, 2)]
                 if fin:
-                    for r, res in zip(fin, e.pool_collect(fin)):
+                    for r, res in zip(fin, self._collect(fin, attempt)):
                         if not self._settle(r, owner[r], res, attempt[r]):
                             attempt[r] += 1
                             continue
