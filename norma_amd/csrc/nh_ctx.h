@@ -1,0 +1,180 @@
+// nh_ctx.h -- the state behind the C ABI of include/norma_hip.h, shared by the three files that implement it: nh_model.hip
+// (create / destroy, weights, tokens, options, timings), nh_encode.hip (log-mel, encoder), nh_decode.hip (decoder step,
+// lockstep decode, decode pool, parity views).  No torch, no candle, no CPU fallback: an entry point runs the HIP path or fails.
+#pragma once
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <memory>
+#include <algorithm>
+#include <mutex>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "../../include/norma_hip.h"
+#include "nh_kernels.h"
+
+#define HIPCHK(expr)                                                                          \
+    do {                                                                                      \
+        hipError_t e_ = (expr);                                                               \
+        if (e_ != hipSuccess) {                                                               \
+            return ctx->fail(NH_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+        }                                                                                     \
+    } while (0)
+
+struct LinW { half_t *w = nullptr; float *b = nullptr; half_t *wt = nullptr; /* tile-major repack (decoder GEMVs) */ };
+struct LnW { float *w = nullptr, *b = nullptr; };
+struct EncLayer { LnW ln1, ln2; LinW qkv, o, fc1, fc2; };
+struct DecLayer { LnW ln1, ln2, ln3; LinW qkv, o, cq, ckv, co, fc1, fc2; };
+// one decoder layer's caches of one context: cross K/V of the current batch, self-attention K/V
+struct KvCache { half_t *ck = nullptr, *cv = nullptr, *sk = nullptr, *sv = nullptr; };
+
+// The read-only half of a context: everything nh_load_tensor / nh_set_mel_filters fill in.  Owned through a shared_ptr, so
+// that several contexts on one device (nh_create_shared) run on ONE copy of the weights: bench.py keeps three batches in
+// flight per GPU, and three private copies meant 3 x 1.5 GB of HBM and three different address ranges for the 225 MB of
+// decoder weights + embedding every in-flight decode streams per token.  The contexts read these tables in place: no
+// pointer in here moves once it is set (see ensure_decoder_repack).
+struct nh_model {
+    int dev = 0;
+    nh_config c{};
+    std::vector<void *> allocs;
+    LinW conv1, conv2;
+    float *enc_pos = nullptr;
+    std::vector<EncLayer> enc;
+    LnW ln_post, dec_ln;
+    half_t *tok_emb = nullptr, *dec_pos = nullptr;
+    half_t *tok_emb_t = nullptr;     // tile-major repack of the tied embedding (logits GEMV)
+    std::vector<DecLayer> dec;
+    bool dec_tiled_valid = false;    // the repacks mirror the row-major decoder weights loaded so far
+    std::set<std::string> expected, loaded;
+    MelTables mt{};
+    int32_t *mel_grp = nullptr;
+    bool have_filters = false;
+    std::mutex mu;                   // guards loaded / dec_tiled_valid and the lazy repack
+    // hipStreamWaitEvent fails ("dependency created on uncaptured work in another stream") on an event whose stream is capturing
+    // at that moment, even one recorded before: a step capture and the encoders' waits on kv_readers exclude each other
+    std::mutex capture_mu;
+    ~nh_model() {
+        hipSetDevice(dev);
+        for (void *p : allocs) hipFree(p);
+    }
+};
+
+struct PoolRow {   // one row of a decode pool, as the host knows it
+    bool busy = false;
+    bool held = false;       // the row holds a clip: admitted since nh_pool_begin (nh_pool_retry decodes that clip again)
+    bool sampled = false;    // the row is busy on a sampled retry (nh_pool_retry); cleared by nh_pool_collect and by an admit
+    bool inv_t_set = false;  // the row's device-side inv_t is > 0 (its last decode was a retry): the next admit zeroes it
+    bool detect = false;     // the row's clip was admitted with NH_LANG_DETECT; an admit sets or clears it
+    bool detected = false;   // ... and has taken a step since: d_lang_out / d_lang_probs hold its language
+};
+// Decode pool (nh_pool_*): rows [0, rows) decode, each at its own position; rows above are encoder staging.  rows == 0: no pool.
+struct Pool {
+    int rows = 0, max_new = 0, prompt = 0;
+    int lang_n = 0;          // entries of the pool's language table in d_lang_tokens (nh_pool_detect_languages); 0: none
+    bool per_clip_language = false;
+    std::vector<PoolRow> row;
+};
+
+// Everything a captured decode step takes by value (batch, encoder length, max_new_tokens, prompt length, the rule token ids,
+// the size of a pool's language table) and which kernels it holds.  A step under another key captures again.
+struct StepKey {
+    int B = -1, S = -1, max_new = -1, P = -1, token_gen = -1, lang_n = -1;
+    bool pool = false, sampled = false;
+    bool operator==(const StepKey &o) const {
+        return B == o.B && S == o.S && max_new == o.max_new && P == o.P && token_gen == o.token_gen && lang_n == o.lang_n &&
+               pool == o.pool && sampled == o.sampled;
+    }
+};
+struct StepGraphs {
+    StepKey key;                    // B == -1: nothing captured
+    hipGraphExec_t one = nullptr;   // one decode step
+    hipGraphExec_t multi = nullptr; // NH_GRAPH_STEPS consecutive steps (one launch gap instead of NH_GRAPH_STEPS)
+};
+
+struct nh_ctx {
+    int dev = 0;
+    std::shared_ptr<nh_model> mdl;
+    hipStream_t st = nullptr;   // the context's one stream: log-mel, encoder, cross K/V, decode loop (see build_context)
+    hipEvent_t enc_done = nullptr;
+    // nh_pool_admit_from: decode pools of OTHER contexts copy cross K/V out of this context's rows on THEIR streams; the next
+    // encoder submission here must not overwrite those rows before the copies have run
+    struct EventBox { hipEvent_t e = nullptr; ~EventBox() { if (e) hipEventDestroy(e); } };
+    std::shared_ptr<EventBox> kv_copied;       // recorded on this context's stream after it copied K/V out of another context
+    std::mutex readers_mu;
+    std::vector<std::shared_ptr<EventBox>> kv_readers;   // kv_copied of the pools that read this context's K/V since its last encode (kept alive here)
+    nh_config c{};
+    int B = 1;
+    std::string err;
+    std::vector<void *> allocs;
+    std::vector<KvCache> kv;    // [decoder_layers]; the weights are read from mdl
+    // mel
+    float *pcm = nullptr;
+    void *raw = nullptr; size_t raw_bytes = 0;   // native-sample staging of nh_logmel_samples
+    int32_t *nsamp = nullptr;
+    float *mel32 = nullptr;
+    unsigned *chunk_max = nullptr;
+    half_t *mel_img = nullptr;
+    // encoder workspaces
+    half_t *h1 = nullptr, *xn = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *att = nullptr, *hid = nullptr,
+           *xa16 = nullptr;
+    float *x = nullptr, *xa32 = nullptr;
+    // decoder workspaces
+    float *dx = nullptr, *dy32 = nullptr, *logits = nullptr;
+    half_t *dxn = nullptr, *dq = nullptr, *datt = nullptr, *dhid = nullptr;
+    DecodeState ds{};
+    uint8_t *suppress = nullptr;
+    float *lpart = nullptr;
+    unsigned *ltick = nullptr;
+    int32_t *d_pos = nullptr;  // [max_batch] device-side decode position of every sequence (hipGraph replays read and advance it)
+    Pool pool;                       // decode pool (nh_pool_*)
+    PoolSampling psamp{};            // [max_batch] each: per-row temperature, seed, clip, attempt, and the step's handled flags
+    int32_t *d_lang_flag = nullptr;  // [max_batch] device side of PoolRow::detect, cleared by a retry (the token is in the prompt by then)
+    // [0]: greedy steps, lockstep or pool; [1]: pool steps with at least one sampled row busy (pool_sample_step_kernel ahead of
+    // logit_step_kernel).  Kept side by side, so a pool that goes back and forth between the two states captures each once.
+    StepGraphs graphs[2];
+    int token_gen = 0;  // bumped by nh_set_tokens; part of the graph key
+    bool opt_graphs = true, opt_fuse_ln = true;  // nh_set_option
+    int opt_absorbed = 0;        // NH_OPT_ABSORBED_XATTN: 1 = numerics prototype, 2 = one-pass kernels
+    half_t *xabs_u = nullptr;    // [max_batch][32][d] scratch (heads padded to 32, pad rows zero)
+    float *xabs_z = nullptr, *xabs_ml = nullptr;   // key-range partials of the one-pass form
+    int dec_layer_limit = 0;    // parity view (NH_OPT_DECODER_LAYER_LIMIT): run only the first n decoder blocks; 0 = all
+    std::vector<int32_t> seq_lang;  // per-sequence language tokens (LanguageState::Detect), empty = tk.lang for all
+    int32_t *d_lang_tokens = nullptr, *d_lang_out = nullptr;
+    float *d_lang_probs = nullptr;
+    RuleTokens tk{};
+    bool have_tokens = false;
+    int VP = 0;
+    // pinned host staging
+    int32_t *h_done = nullptr;
+    // state
+    int cur_batch = 0, frames = 0, S = 0, last_frames = -1;
+    bool have_mel = false, have_enc = false;
+    // timings
+    hipEvent_t ev[7]{};
+    nh_timings tm{};
+    bool profile_gemm = false;
+    std::vector<hipEvent_t> gemm_ev;
+    size_t gemm_ev_used = 0;
+    double gemm_flops_acc = 0.0;
+
+    int fail(int code, const std::string &msg) { err = msg; return code; }
+};
+
+template <typename T>
+static T *dalloc_into(std::vector<void *> &allocs, size_t n, bool zero = true) {
+    void *p = nullptr;
+    if (n == 0) n = 1;
+    if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) return nullptr;
+    if (zero) hipMemset(p, 0, n * sizeof(T));
+    allocs.push_back(p);
+    return reinterpret_cast<T *>(p);
+}
+template <typename T>
+static T *dalloc(nh_ctx *ctx, size_t n, bool zero = true) { return dalloc_into<T>(ctx->allocs, n, zero); }
+
+void drop_graphs(nh_ctx *ctx, int first = 0);   // nh_decode.hip
+int ensure_decoder_repack(nh_ctx *ctx);         // nh_model.hip

@@ -1,4 +1,4 @@
-// nh_kernels.h -- internal launch interface between the C-ABI layer (nh_api.hip) and the gfx950
+// nh_kernels.h -- internal launch interface between the C-ABI layer (nh_*.hip) and the gfx950
 // kernels.  Not part of the public ABI (that is include/norma_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
