@@ -269,6 +269,47 @@ int nh_apply_rules(nh_ctx *ctx, const float *probs, const int32_t *tokens, int n
 int nh_sample_rules(nh_ctx *ctx, const float *probs, const int32_t *tokens, int n_tokens, int last_timestamp,
                     float temperature, uint64_t seed, uint32_t clip, uint32_t attempt, int32_t *token_out);
 
+/* ---- token-level timestamps ------------------------------------------------------------------------ */
+/* The decoder yields one timestamp token per segment boundary; nh_align gives every token a time, the way Whisper runtimes
+ * do: cross-attention weights of a few "alignment heads" over a teacher-forced pass, normalised, median-filtered, averaged,
+ * and a dynamic-time-warping (DTW) path through the result.  All of it runs on the device (DESIGN.md 9 has the stages and
+ * their exact arithmetic).  It aligns the sequence as decoded -- timestamp tokens included --: what the caller holds. */
+#define NH_ALIGN_MAX_HEADS 32
+typedef struct nh_align_head { int32_t layer, head; } nh_align_head;   /* decoder layer, head in that layer */
+/* For every clip of the current lockstep batch (after nh_encode / nh_encode_rows; a decode may or may not have run):
+ * tokens      host i32 [batch][max_target_positions], the sequences as nh_decode_* returned them (prompt .. eot)
+ * n_tokens    host i32 [batch], prompt_len < n_tokens[b] <= max_target_positions
+ * prompt_len  tokens [0, prompt_len) are the prompt ([sot, lang?, task]); they get no time.  >= 1
+ * n_keys      host i32 [batch] or NULL (= S): encoder frames that hold audio, 1 <= n_keys[b] <= S
+ * out_first / out_last  host i32 [batch][max_target_positions]: first and last encoder frame (20 ms each) on the
+ *                       DTW path of token i; -1 for i < prompt_len and i >= n_tokens[b]
+ * Stages, for clip b with n = n_tokens[b], nk = n_keys[b], P = prompt_len:
+ *   1 positions p = 0 .. n - 2 consume tokens[b][p] through the decoder step of nh_decoder_forward (no logits, no host
+ *     round trip between positions)
+ *   2 W[a][p][s] = softmax over s < nk of q . k_s / 8 for head a = (l, h): q the fp16 cross-attention query of layer l at
+ *     position p, k_s the fp16 cross K cache row; f32 accumulation, f32 result.  Row p belongs to token p + 1.
+ *   3 per (a, s): z = (W - mean) / std over the n - 1 rows (population std); std == 0 gives z = 0
+ *   4 median of 7 along s inside [0, nk), reflect padding without repeating the edge; nk <= 3 is left unfiltered
+ *   5 M[r][s] = mean over the heads, in list order, of the filtered z at row P - 1 + r, r = 0 .. n - P - 1 (token P + r)
+ *   6 DTW on x = -M in f32: cost[0][0] = 0, the other border cells +inf, cost[i][j] = x[i-1][j-1] + c with c the least of
+ *     c0 = cost[i-1][j-1], c1 = cost[i-1][j], c2 = cost[i][j-1]: c0 (trace 0) if c0 < c1 and c0 < c2, else c1 (trace 1) if
+ *     c1 < c0 and c1 < c2, else c2 (trace 2); backtrace from (R, nk): trace 0 i--, j--; 1 i--; 2 j--.  out_first[P + r]
+ *     and out_last[P + r] are the least and greatest j - 1 visited with i - 1 == r.
+ * Refused, nothing launched (NH_ERR_STATE): no encoder output, a decode pool, NH_OPT_ABSORBED_XATTN != 0 (no K cache);
+ * (NH_ERR_INVALID): n_heads outside 1 .. NH_ALIGN_MAX_HEADS, a layer or head out of range (or at or beyond
+ * NH_OPT_DECODER_LAYER_LIMIT), a token id outside the vocabulary, n_tokens, prompt_len or n_keys out of range.
+ * Afterwards the context is in the state nh_decoder_forward leaves: self K/V and the device-side tokens are overwritten,
+ * cross K/V and the encoder output untouched.  A clip's outputs are bit-identical whatever the batch around it. */
+int nh_align(nh_ctx *ctx, const int32_t *tokens, const int32_t *n_tokens, int prompt_len,
+             const nh_align_head *heads, int n_heads, const int32_t *n_keys,
+             int32_t *out_first, int32_t *out_last);
+/* parity views of the LAST nh_align, valid only under NH_OPT_ALIGN_KEEP = 1 (otherwise NH_ERR_STATE) */
+int nh_align_weights(nh_ctx *ctx, int b, int a, float *out);   /* f32 [n_tokens[b]-1][n_keys[b]] probabilities of heads[a] */
+int nh_align_matrix(nh_ctx *ctx, int b, float *out);           /* f32 [n_tokens[b]-prompt_len][n_keys[b]] the DTW input */
+/* the DTW alone on a host matrix f32 [R][nk] (cost = -matrix): parity view, R <= max_target_positions, nk <= S
+ * (S = max_source_positions when nothing is encoded yet); out_first / out_last host i32 [R] */
+int nh_align_path(nh_ctx *ctx, const float *matrix, int R, int nk, int32_t *out_first, int32_t *out_last);
+
 /* ---- instrumentation --------------------------------------------------------------------------- */
 /* Milliseconds (HIP events on the context's stream) spent in the phases of the last
  * nh_transcribe_batch / nh_logmel+nh_encode+nh_decode_greedy sequence. */
@@ -296,6 +337,10 @@ int nh_set_profile_gemm(nh_ctx *ctx, int enable);
  * 2: the one-pass kernels (xa streamed once per decoder layer; d_model 512 / 768 / 1024 / 1280, other widths fall back to 1).
  * 0 (default): K and V as the reference computes them. */
 #define NH_OPT_ABSORBED_XATTN 3
+/* nh_align's workspace.  1: keep every clip's weights and matrix for the views nh_align_weights / nh_align_matrix (the whole
+ * batch is held: NH_ERR_NOMEM when that does not fit); 0 (default): clips are processed in groups that keep the workspace at
+ * or under 256 MiB, and the views refuse. */
+#define NH_OPT_ALIGN_KEEP 4
 int nh_set_option(nh_ctx *ctx, int option, int value);
 
 #ifdef __cplusplus

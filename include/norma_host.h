@@ -103,6 +103,15 @@ void nm_model_free(nm_model *m);
  * written; *buffered = samples the model keeps for the next call.  Returns 0, or 1 on a backend error. */
 int nm_model_transcribe(nm_model *m, const float *data, size_t n, int final_chunk, int32_t *out_tokens, int cap,
                         int *n_out, size_t *buffered, char *err, int err_len);
+/* Token-level timestamps (nh_align of norma_hip.h).  heads: n [layer, head] pairs, n = 0 switches them off (the default).
+ * When on, every slice's accepted decode is aligned over the frames that hold audio.  Returns 0, or 1 when n is out of range. */
+int nm_model_set_alignment_heads(nm_model *m, const int32_t *layer_head_pairs, int n);
+/* alignment_heads of the checkpoint's generation_config.json (nm_definition_blocking_try_to_model_from_dir): writes up to cap
+ * pairs, returns how many the checkpoint lists (0 without that file).  Not enabled by itself. */
+int nm_model_checkpoint_alignment_heads(const nm_model *m, int32_t *layer_head_pairs, int cap);
+/* (start, end) in seconds from the start of its slice for every token the last nm_model_transcribe wrote to out_tokens, in that
+ * order (the -1 separators have no entry).  Writes up to cap pairs, returns how many there are: 0 with alignment off. */
+int nm_model_last_token_times(const nm_model *m, float *start, float *end, int cap);
 /* DecodingResult of the last decoded slice + whether the reference would have entered its sampled fallback */
 void nm_model_last_result(const nm_model *m, double *avg_logprob, double *no_speech_prob, int *needed_fallback,
                           int *n_tokens);

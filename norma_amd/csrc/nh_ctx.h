@@ -95,6 +95,23 @@ struct StepGraphs {
     hipGraphExec_t multi = nullptr; // NH_GRAPH_STEPS consecutive steps (one launch gap instead of NH_GRAPH_STEPS)
 };
 
+// nh_align's device state: allocated by the first nh_align (contexts that never align pay nothing), freed by nh_destroy.
+// The last call's shape is kept for the views (nh_align_weights / nh_align_matrix).
+struct AlignState {
+    std::vector<void *> allocs;      // everything below; released and re-made when a call needs more
+    size_t bytes = 0;                // what the workspace holds
+    half_t *qsave = nullptr;         // fp16 [heads][C - 1][max_batch][64]
+    int32_t *n_rows = nullptr, *n_keys = nullptr;   // [max_batch]
+    int32_t *first = nullptr, *last = nullptr;      // [max_batch][C + 1]
+    float *W = nullptr, *stats = nullptr, *M = nullptr;   // per clip of a group: [heads][C - 1][S], [heads][2][S], [C][S]
+    uint8_t *trace = nullptr;        // [C][S] per clip of a group
+    int heads = 0, group = 0, S = 0; // the shape the workspace was made for
+    // the last nh_align, for the views
+    bool kept = false;
+    int P = 0, A = 0;
+    std::vector<int32_t> n_tokens, keys;
+};
+
 struct nh_ctx {
     int dev = 0;
     std::shared_ptr<nh_model> mdl;
@@ -141,6 +158,8 @@ struct nh_ctx {
     int opt_absorbed = 0;        // NH_OPT_ABSORBED_XATTN: 1 = numerics prototype, 2 = one-pass kernels
     half_t *xabs_u = nullptr;    // [max_batch][32][d] scratch (heads padded to 32, pad rows zero)
     float *xabs_z = nullptr, *xabs_ml = nullptr;   // key-range partials of the one-pass form
+    bool opt_align_keep = false; // NH_OPT_ALIGN_KEEP
+    AlignState al;               // nh_align
     int dec_layer_limit = 0;    // parity view (NH_OPT_DECODER_LAYER_LIMIT): run only the first n decoder blocks; 0 = all
     std::vector<int32_t> seq_lang;  // per-sequence language tokens (LanguageState::Detect), empty = tk.lang for all
     int32_t *d_lang_tokens = nullptr, *d_lang_out = nullptr;

@@ -53,7 +53,11 @@ static void ln_skinny(nh_ctx *ctx, const LnW &ln, const LinW &W, int R, int N, i
 // final_ln: also LN(dx) -> dxn (fp16) / dy32 (f32) (the teacher-forced view; the step path fuses it into the logits).
 // pos_ptr != nullptr: the position comes from device memory (the step is being captured into a hipGraph).
 // skip_done: finished sequences skip their attention (only inside decode_impl, where ds.done is live).
-static void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr = nullptr, bool final_ln = true, bool skip_done = false) {
+// cap (nh_align only): the layers that hold alignment heads copy those heads' cross-attention query of every row to
+// cap->qsave[head][pos][row][64] right after the projection; nullptr (every other caller): nothing is added to the step.
+struct AlignCapture { half_t *qsave; int npos; std::vector<AlignLayerHeads> layer; };   // layer: [decoder_layers], n == 0: no head there
+static void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr = nullptr, bool final_ln = true, bool skip_done = false,
+                         const AlignCapture *cap = nullptr) {
     const int32_t *done = skip_done ? ctx->ds.done : nullptr;
     const nh_model &m = *ctx->mdl;
     const int d = ctx->c.d_model, B = ctx->pool.rows > 0 ? ctx->pool.rows : ctx->cur_batch, H = ctx->c.decoder_attention_heads, C = ctx->c.max_target_positions;
@@ -66,6 +70,7 @@ static void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr = nullptr,
         launch_dec_attention(ctx->dq, kv.sk, kv.sv, ctx->datt, B, 1, H, d, C, pos + 1, pos_ptr, ctx->st, 1, done);  // head-major cache
         skinny(ctx, ctx->datt, d, L.o, B, d, d, SK_RESID_F32, ctx->dx, nullptr, nullptr, d, 0, C);
         ln_skinny(ctx, L.ln2, L.cq, B, d, d, SK_F16, ctx->dq, nullptr, nullptr, d, 0, C, nullptr);
+        if (cap && cap->layer[l].n) launch_align_qsave(ctx->dq, cap->qsave, cap->layer[l], B, d, pos, cap->npos, ctx->st);
         if (ctx->opt_absorbed == 2) launch_xabs_attention_fast(ctx->dq, L.ckv.wt, L.ckv.w, L.ckv.b, ctx->xa16, ctx->xabs_u, ctx->xabs_z, ctx->xabs_ml, ctx->datt, B, H, d, ctx->S, done, ctx->st);
         else if (ctx->opt_absorbed) launch_xabs_attention(ctx->dq, L.ckv.w, L.ckv.b, ctx->xa16, ctx->xabs_u, ctx->datt, B, H, d, ctx->S, done, ctx->st);
         else launch_dec_attention(ctx->dq, kv.ck, kv.cv, ctx->datt, B, 1, H, d, ctx->S, ctx->S, nullptr, ctx->st, 1, done);  // head-major cross K/V
@@ -593,4 +598,171 @@ extern "C" int nh_apply_rules(nh_ctx *ctx, const float *probs, const int32_t *to
     if (tmp_out) hipFree(tmp_out);
     HIPCHK(hipGetLastError());
     return NH_OK;
+}
+
+// ---- token-level timestamps (contract: include/norma_hip.h, nh_align; kernels: k_align.hip) ----------------------------------
+static_assert(NH_ALIGN_HEADS == NH_ALIGN_MAX_HEADS, "nh_kernels.h and norma_hip.h disagree");
+#define NH_ALIGN_BUDGET ((size_t)256 << 20)   // workspace of a call under NH_OPT_ALIGN_KEEP = 0
+
+// The workspace for A heads and groups of `group` clips, made again when the shape differs from what is held.
+static int align_workspace(nh_ctx *ctx, int A, int group) {
+    AlignState &al = ctx->al;
+    const int S = ctx->S;
+    if (al.heads == A && al.group == group && al.S == S) return NH_OK;
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    for (void *p : al.allocs) hipFree(p);
+    al = AlignState{};
+    const size_t C = ctx->c.max_target_positions, NP = C - 1, B = ctx->B;
+    al.qsave = dalloc_into<half_t>(al.allocs, (size_t)A * NP * B * NH_DH, false);
+    al.n_rows = dalloc_into<int32_t>(al.allocs, B);
+    al.n_keys = dalloc_into<int32_t>(al.allocs, B);
+    al.first = dalloc_into<int32_t>(al.allocs, B * (C + 1));
+    al.last = dalloc_into<int32_t>(al.allocs, B * (C + 1));
+    al.W = dalloc_into<float>(al.allocs, (size_t)group * A * NP * S, false);
+    al.stats = dalloc_into<float>(al.allocs, (size_t)group * A * 2 * S, false);
+    al.M = dalloc_into<float>(al.allocs, (size_t)group * C * S, false);
+    al.trace = dalloc_into<uint8_t>(al.allocs, (size_t)group * C * S, false);
+    if (!al.qsave || !al.n_rows || !al.n_keys || !al.first || !al.last || !al.W || !al.stats || !al.M || !al.trace) {
+        for (void *p : al.allocs) hipFree(p);
+        al = AlignState{};
+        (void)hipGetLastError();
+        return ctx->fail(NH_ERR_NOMEM, "nh_align: the workspace for " + std::to_string(group) + " clips x " + std::to_string(A) +
+                                           " heads does not fit (NH_OPT_ALIGN_KEEP = 1 holds the whole batch)");
+    }
+    al.heads = A; al.group = group; al.S = S;
+    return NH_OK;
+}
+
+extern "C" int nh_align(nh_ctx *ctx, const int32_t *tokens, const int32_t *n_tokens, int prompt_len, const nh_align_head *heads,
+                        int n_heads, const int32_t *n_keys, int32_t *out_first, int32_t *out_last) {
+    if (!ctx || !tokens || !n_tokens || !heads || !out_first || !out_last) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_align: bad arguments") : NH_ERR_INVALID;
+    if (ctx->pool.rows > 0) return ctx->fail(NH_ERR_STATE, "nh_align: the context runs a decode pool (nh_pool_begin)");
+    if (!ctx->have_enc) return ctx->fail(NH_ERR_STATE, "nh_align: call nh_encode first");
+    if (ctx->opt_absorbed) return ctx->fail(NH_ERR_STATE, "nh_align: NH_OPT_ABSORBED_XATTN keeps no cross K cache to align against");
+    const int B = ctx->cur_batch, C = ctx->c.max_target_positions, V = ctx->c.vocab_size, S = ctx->S;
+    const int H = ctx->c.decoder_attention_heads, NL = ctx->dec_layer_limit > 0 ? ctx->dec_layer_limit : ctx->c.decoder_layers;
+    const int A = n_heads, P = prompt_len, NP = C - 1;
+    if (A < 1 || A > NH_ALIGN_MAX_HEADS) return ctx->fail(NH_ERR_INVALID, "nh_align: n_heads outside 1 .. NH_ALIGN_MAX_HEADS");
+    for (int a = 0; a < A; a++)
+        if (heads[a].layer < 0 || heads[a].layer >= NL || heads[a].head < 0 || heads[a].head >= H)
+            return ctx->fail(NH_ERR_INVALID, "nh_align: alignment head " + std::to_string(a) + " names a layer or head the decoder does not run");
+    if (P < 1 || P >= C) return ctx->fail(NH_ERR_INVALID, "nh_align: prompt_len out of range");
+    int maxn = 0;
+    std::vector<int32_t> toks((size_t)B * C, 0), rows(B), keys(B);
+    for (int b = 0; b < B; b++) {
+        const int n = n_tokens[b], nk = n_keys ? n_keys[b] : S;
+        if (n <= P || n > C) return ctx->fail(NH_ERR_INVALID, "nh_align: n_tokens must lie in (prompt_len, max_target_positions]");
+        if (nk < 1 || nk > S) return ctx->fail(NH_ERR_INVALID, "nh_align: n_keys must lie in [1, S]");
+        for (int i = 0; i < n; i++) {
+            const int t = tokens[(size_t)b * C + i];
+            if (t < 0 || t >= V) return ctx->fail(NH_ERR_INVALID, "nh_align: token id outside the vocabulary");
+            toks[(size_t)b * C + i] = t;
+        }
+        rows[b] = n - 1; keys[b] = nk;
+        maxn = std::max(maxn, n);
+    }
+    hipSetDevice(ctx->dev);
+    if (int rc = ensure_decoder_repack(ctx)) return rc;
+    // the clips of a group share the workspace; a group's size is the same for every batch of the same heads, and no
+    // kernel mixes clips, so grouping never shows in the results
+    const size_t fixed = (size_t)A * NP * ctx->B * NH_DH * sizeof(half_t) + (size_t)ctx->B * (2 * (C + 1) + 2) * sizeof(int32_t);
+    const size_t per_clip = ((size_t)A * NP + 2 * A + C) * S * sizeof(float) + (size_t)C * S;
+    int group = B;
+    if (!ctx->opt_align_keep) {
+        const size_t room = NH_ALIGN_BUDGET > fixed ? NH_ALIGN_BUDGET - fixed : 0;
+        group = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, room / per_clip));
+    }
+    if (int rc = align_workspace(ctx, A, group)) return rc;
+    AlignState &al = ctx->al;
+    al.kept = false;
+    AlignCapture cap{al.qsave, NP, std::vector<AlignLayerHeads>(ctx->c.decoder_layers)};
+    AlignHeadPtrs hp{};
+    for (int a = 0; a < A; a++) {
+        AlignLayerHeads &lh = cap.layer[heads[a].layer];
+        lh.slot[lh.n] = a; lh.head[lh.n] = heads[a].head; lh.n++;
+        hp.q[a] = al.qsave + (size_t)a * NP * B * NH_DH;
+        hp.k[a] = ctx->kv[heads[a].layer].ck + (size_t)heads[a].head * S * NH_DH;
+    }
+    HIPCHK(hipStreamWaitEvent(ctx->st, ctx->enc_done, 0));
+    HIPCHK(hipMemcpyAsync(ctx->ds.tokens, toks.data(), toks.size() * 4, hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipMemcpyAsync(al.n_rows, rows.data(), B * 4, hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipMemcpyAsync(al.n_keys, keys.data(), B * 4, hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));   // host buffers of this frame
+    // stage 1: the teacher-forced pass, every position enqueued back to back
+    for (int pos = 0; pos <= maxn - 2; pos++) decoder_step(ctx, pos, nullptr, false, false, &cap);
+    // stages 2 - 6, a group of clips at a time
+    const long wcs = (long)A * NP * S, whs = (long)NP * S, mcs = (long)C * S;
+    for (int c0 = 0; c0 < B; c0 += group) {
+        const int nc = std::min(group, B - c0);
+        bool ok = launch_align_weights(hp, A, (long)B * NH_DH, NH_DH, (long)H * S * NH_DH, al.n_rows, al.n_keys, NP, S, nc, c0, al.W, wcs, whs, S, ctx->st);
+        ok = ok && launch_align_reduce(al.W, wcs, whs, S, al.n_rows, al.n_keys, NP, S, nc, c0, A, P, al.stats, al.M, mcs, S, ctx->st);
+        ok = ok && launch_align_dtw(al.M, mcs, S, al.n_rows, al.n_keys, P, NP, S, nc, c0, al.trace, mcs, al.first, al.last, C + 1, ctx->st);
+        if (!ok) return ctx->fail(NH_ERR_INVALID, "nh_align: the alignment kernels do not cover this model's shape (S <= 1536, max_target_positions <= 512)");
+    }
+    std::vector<int32_t> fl((size_t)2 * B * (C + 1));
+    HIPCHK(hipMemcpyAsync(fl.data(), al.first, (size_t)B * (C + 1) * 4, hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipMemcpyAsync(fl.data() + (size_t)B * (C + 1), al.last, (size_t)B * (C + 1) * 4, hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    HIPCHK(hipGetLastError());
+    for (int b = 0; b < B; b++) {
+        memcpy(out_first + (size_t)b * C, fl.data() + (size_t)b * (C + 1), sizeof(int32_t) * C);
+        memcpy(out_last + (size_t)b * C, fl.data() + (size_t)(B + b) * (C + 1), sizeof(int32_t) * C);
+    }
+    al.kept = ctx->opt_align_keep; al.P = P; al.A = A;
+    al.n_tokens.assign(n_tokens, n_tokens + B); al.keys = keys;
+    return NH_OK;
+}
+
+// rows x nk floats out of a workspace image with row stride S
+static int align_view(nh_ctx *ctx, const float *src, int nrows, int nk, float *out) {
+    hipSetDevice(ctx->dev);
+    HIPCHK(hipMemcpy2DAsync(out, (size_t)nk * 4, src, (size_t)ctx->al.S * 4, (size_t)nk * 4, nrows, hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    return NH_OK;
+}
+
+extern "C" int nh_align_weights(nh_ctx *ctx, int b, int a, float *out) {
+    if (!ctx || !out) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_align_weights: bad arguments") : NH_ERR_INVALID;
+    const AlignState &al = ctx->al;
+    if (!al.kept) return ctx->fail(NH_ERR_STATE, "nh_align_weights: no nh_align under NH_OPT_ALIGN_KEEP = 1 to look at");
+    if (b < 0 || b >= (int)al.n_tokens.size() || a < 0 || a >= al.A) return ctx->fail(NH_ERR_INVALID, "nh_align_weights: clip or head out of range");
+    const size_t NP = ctx->c.max_target_positions - 1;
+    return align_view(ctx, al.W + ((size_t)b * al.A + a) * NP * al.S, al.n_tokens[b] - 1, al.keys[b], out);
+}
+
+extern "C" int nh_align_matrix(nh_ctx *ctx, int b, float *out) {
+    if (!ctx || !out) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_align_matrix: bad arguments") : NH_ERR_INVALID;
+    const AlignState &al = ctx->al;
+    if (!al.kept) return ctx->fail(NH_ERR_STATE, "nh_align_matrix: no nh_align under NH_OPT_ALIGN_KEEP = 1 to look at");
+    if (b < 0 || b >= (int)al.n_tokens.size()) return ctx->fail(NH_ERR_INVALID, "nh_align_matrix: clip out of range");
+    return align_view(ctx, al.M + (size_t)b * ctx->c.max_target_positions * al.S, al.n_tokens[b] - al.P, al.keys[b], out);
+}
+
+extern "C" int nh_align_path(nh_ctx *ctx, const float *matrix, int R, int nk, int32_t *out_first, int32_t *out_last) {
+    if (!ctx || !matrix || !out_first || !out_last) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_align_path: bad arguments") : NH_ERR_INVALID;
+    const int Smax = ctx->S > 0 ? ctx->S : ctx->c.max_source_positions;
+    if (R < 1 || R > ctx->c.max_target_positions || nk < 1 || nk > Smax) return ctx->fail(NH_ERR_INVALID, "nh_align_path: R or nk out of range");
+    hipSetDevice(ctx->dev);
+    // a parity view with buffers of its own: the workspace of the last nh_align (and its views) stays as it is
+    std::vector<void *> tmp;
+    float *M = dalloc_into<float>(tmp, (size_t)R * nk, false);
+    uint8_t *trace = dalloc_into<uint8_t>(tmp, (size_t)R * nk, false);
+    int32_t *meta = dalloc_into<int32_t>(tmp, 2 + 2 * (size_t)(R + 1));   // n_rows, n_keys, first [R + 1], last [R + 1]
+    auto done = [&](int rc) { for (void *p : tmp) hipFree(p); return rc; };
+    if (!M || !trace || !meta) return done(ctx->fail(NH_ERR_NOMEM, "nh_align_path: hipMalloc failed"));
+    const int32_t rk[2] = {R, nk};
+    std::vector<int32_t> fl(2 * (size_t)(R + 1));
+    hipError_t e = hipMemcpyAsync(M, matrix, (size_t)R * nk * 4, hipMemcpyHostToDevice, ctx->st);
+    if (e == hipSuccess) e = hipMemcpyAsync(meta, rk, 8, hipMemcpyHostToDevice, ctx->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->st);
+    // prompt_len 1 and n - 1 = R rows: row r of the matrix is token 1 + r
+    if (e == hipSuccess && !launch_align_dtw(M, (long)R * nk, nk, meta, meta + 1, 1, R, nk, 1, 0, trace, (long)R * nk, meta + 2, meta + 2 + (R + 1), R + 1, ctx->st))
+        return done(ctx->fail(NH_ERR_INVALID, "nh_align_path: the DTW kernel covers R <= 512"));
+    if (e == hipSuccess) e = hipMemcpyAsync(fl.data(), meta + 2, fl.size() * 4, hipMemcpyDeviceToHost, ctx->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->st);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return done(ctx->fail(NH_ERR_HIP, std::string("nh_align_path: ") + hipGetErrorString(e)));
+    memcpy(out_first, fl.data() + 1, sizeof(int32_t) * R);
+    memcpy(out_last, fl.data() + (R + 1) + 1, sizeof(int32_t) * R);
+    return done(NH_OK);
 }

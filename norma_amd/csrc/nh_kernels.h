@@ -325,3 +325,32 @@ void launch_pool_lang_detect(const float *logits, int V, DecodeState s, int B, i
 // parity helper: apply rules to one already soft-maxed probability vector
 void launch_rules_only(const float *probs_in, float *masked_out, int32_t *argmax_out, const int32_t *tokens,
                        int n_tokens, int last_ts, const uint8_t *suppress, RuleTokens tk, int V, hipStream_t st);
+
+// ---- token-level timestamps (k_align.hip; contract: nh_align in include/norma_hip.h) ----------------------------------------
+#define NH_ALIGN_HEADS 32   // == NH_ALIGN_MAX_HEADS of the public header
+// q capture: the heads of ONE decoder layer among the alignment heads; slot = the head's index in the caller's list
+struct AlignLayerHeads { int32_t slot[NH_ALIGN_HEADS], head[NH_ALIGN_HEADS]; int n; };
+// dq fp16 [B][d] (cross-attention query of that layer at position pos) -> qsave fp16 [slot][npos][B][64]
+void launch_align_qsave(const half_t *dq, half_t *qsave, const AlignLayerHeads &lh, int B, int d, int pos, int npos, hipStream_t st);
+// Per alignment head a: q[a] + p * q_pos_stride + b * q_clip_stride = the 64 halfs of the query of clip b at position p;
+// k[a] + b * k_clip_stride + s * 64 = key s of clip b (the head's slab of the head-major cross K cache).  16-byte aligned.
+struct AlignHeadPtrs { const half_t *q[NH_ALIGN_HEADS]; const half_t *k[NH_ALIGN_HEADS]; };
+// All three launchers work on clips clip0 .. clip0 + nclips - 1 of the batch: n_rows / n_keys (device i32, indexed by the
+// clip's index in the BATCH) give the clip's rows n - 1 (clamped to max_rows) and keys (clamped to S); workspaces (W, stats,
+// M, trace) are indexed by the clip's index in the GROUP, the outputs first / last by its index in the batch.  They return
+// false, and launch nothing, on a shape they do not cover.
+// W[g][a][p][s] = softmax_s(q . k_s / 8) over s < nk, f32, for p < n_rows; nothing else of W is written.  S <= 1536.
+bool launch_align_weights(const AlignHeadPtrs &hp, int A, long q_pos_stride, long q_clip_stride, long k_clip_stride, const int32_t *n_rows,
+                          const int32_t *n_keys, int max_rows, int S, int nclips, int clip0, float *W, long w_clip_stride, long w_head_stride,
+                          long ldw, hipStream_t st);
+// stats f32 [nclips][A][2][S] scratch (column mean and population std over the clip's rows); M[g][r][s], r < n_rows + 1 - P:
+// mean over the heads (in order) of the median of 7 along s (reflect padding, nk <= 3 unfiltered) of (W - mean) / std at
+// row P - 1 + r; std == 0 gives 0.  1 <= P <= max_rows.
+bool launch_align_reduce(const float *W, long w_clip_stride, long w_head_stride, long ldw, const int32_t *n_rows, const int32_t *n_keys,
+                         int max_rows, int S, int nclips, int clip0, int A, int P, float *stats, float *M, long m_clip_stride, long ldm,
+                         hipStream_t st);
+// DTW on -M (R = n_rows + 1 - P rows, nk keys; tie rule and trace as nh_align states them): first / last i32 [batch][ldo],
+// entries P + r get the first and last key on the path of row r, every other entry -1.  trace: u8 scratch, t_clip_stride
+// >= (max_rows + 1 - P) * S per clip.  max_rows + 1 - P <= 512, ldo >= max_rows + 1.
+bool launch_align_dtw(const float *M, long m_clip_stride, long ldm, const int32_t *n_rows, const int32_t *n_keys, int P, int max_rows, int S,
+                      int nclips, int clip0, uint8_t *trace, long t_clip_stride, int32_t *first, int32_t *last, int ldo, hipStream_t st);

@@ -45,6 +45,7 @@ extern "C" void nh_destroy(nh_ctx *ctx) {
     hipSetDevice(ctx->dev);
     if (ctx->st) hipStreamSynchronize(ctx->st);
     for (void *p : ctx->allocs) hipFree(p);
+    for (void *p : ctx->al.allocs) hipFree(p);
     drop_graphs(ctx);
     if (ctx->h_done) hipHostFree(ctx->h_done);
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);
@@ -489,6 +490,7 @@ extern "C" int nh_set_option(nh_ctx *ctx, int option, int value) {
         }
         ctx->opt_absorbed = value; drop_graphs(ctx);
     }
+    else if (option == NH_OPT_ALIGN_KEEP) ctx->opt_align_keep = value != 0;
     else return ctx->fail(NH_ERR_INVALID, "nh_set_option: unknown option " + std::to_string(option));
     return NH_OK;
 }

@@ -9,7 +9,7 @@ using namespace norma;
 using namespace norma::whisper;
 
 struct nm_definition { Definition def; };
-struct nm_model { Model *m; std::string last_text; };
+struct nm_model { Model *m; std::string last_text; std::vector<float> tok_start, tok_end; };
 struct nm_tensors { std::vector<TensorView> v; };
 
 static void put_err(char *err, int n, const std::string &s) {
@@ -54,7 +54,7 @@ nm_model *nm_definition_blocking_try_to_model(const nm_definition *d, const nh_c
     std::vector<int32_t> sup(suppress, suppress + (n_suppress > 0 ? n_suppress : 0));
     Error e = d->def.blocking_try_to_model(*cfg, *tk, sup, mel_filters, n_mel, tensors->v, &m);
     if (e) { put_err(err, err_len, e.message); return nullptr; }
-    return new nm_model{m, std::string()};
+    return new nm_model{m, std::string(), {}, {}};
     NM_CATCH({ put_err(err, err_len, "blocking_try_to_model: " + what_); return nullptr; })
 }
 
@@ -66,7 +66,7 @@ nm_model *nm_definition_blocking_try_to_model_from_dir(const nm_definition *d, c
     const bool detect = language == nullptr || language[0] == 0;  // multilingual::Definition: infer the language
     Error e = d->def.blocking_try_to_model_from_dir(dir, mel_filters, n_mel, &m, detect ? "" : language, translate != 0, detect);
     if (e) { put_err(err, err_len, e.message); return nullptr; }
-    return new nm_model{m, std::string()};
+    return new nm_model{m, std::string(), {}, {}};
     NM_CATCH({ put_err(err, err_len, "blocking_try_to_model_from_dir: " + what_); return nullptr; })
 }
 
@@ -89,6 +89,7 @@ int nm_model_transcribe(nm_model *m, const float *data, size_t n, int final_chun
     std::vector<float> v(data, data + n);
     std::vector<Segment> segs;
     m->last_text.clear();
+    m->tok_start.clear(); m->tok_end.clear();
     Error e = m->m->transcribe(v, final_chunk != 0, segs, &m->last_text);
     if (buffered) *buffered = m->m->buffered_samples();
     if (e) { put_err(err, err_len, e.message); return 1; }
@@ -96,6 +97,8 @@ int nm_model_transcribe(nm_model *m, const float *data, size_t n, int final_chun
     for (const auto &s : segs) {
         if (w + (int)s.tokens.size() + 1 > cap) { put_err(err, err_len, "output buffer too small"); return 1; }
         for (uint32_t t : s.tokens) out_tokens[w++] = (int32_t)t;
+        m->tok_start.insert(m->tok_start.end(), s.token_start.begin(), s.token_start.end());
+        m->tok_end.insert(m->tok_end.end(), s.token_end.begin(), s.token_end.end());
         out_tokens[w++] = -1;
     }
     if (n_out) *n_out = w;
@@ -169,6 +172,25 @@ int nm_safetensors_list(const char *path, char *buf, int cap) {
 
 void nm_model_set_temperature_fallback(nm_model *m, int enable, uint64_t seed) {
     if (m && m->m) m->m->set_temperature_fallback(enable != 0, seed);
+}
+
+int nm_model_set_alignment_heads(nm_model *m, const int32_t *layer_head_pairs, int n) {
+    if (!m || !m->m || n < 0 || n > NH_ALIGN_MAX_HEADS || (n > 0 && !layer_head_pairs)) return 1;
+    std::vector<nh_align_head> heads;
+    for (int i = 0; i < n; i++) heads.push_back(nh_align_head{layer_head_pairs[2 * i], layer_head_pairs[2 * i + 1]});
+    m->m->set_alignment_heads(std::move(heads));
+    return 0;
+}
+
+int nm_model_checkpoint_alignment_heads(const nm_model *m, int32_t *layer_head_pairs, int cap) {
+    const std::vector<nh_align_head> &h = m->m->checkpoint_alignment_heads();
+    for (int i = 0; i < (int)h.size() && i < cap && layer_head_pairs; i++) { layer_head_pairs[2 * i] = h[i].layer; layer_head_pairs[2 * i + 1] = h[i].head; }
+    return (int)h.size();
+}
+
+int nm_model_last_token_times(const nm_model *m, float *start, float *end, int cap) {
+    for (int i = 0; i < (int)m->tok_start.size() && i < cap && start && end; i++) { start[i] = m->tok_start[i]; end[i] = m->tok_end[i]; }
+    return (int)m->tok_start.size();
 }
 
 void nm_model_last_result(const nm_model *m, double *avg_logprob, double *no_speech_prob, int *needed_fallback,

@@ -139,16 +139,22 @@ enum class Task { Transcribe, Translate };  // multilingual.rs:19-25
 struct DecodingResult {  // model.rs:494-499
     std::vector<uint32_t> tokens;
     double avg_logprob = 0, no_speech_prob = 0, compression_ratio = 0;
+    // with alignment heads set (Model::set_alignment_heads): first and last 20 ms encoder frame of every token, -1 for the
+    // prompt; empty otherwise (no counterpart in the reference, whose timing stops at the segment)
+    std::vector<int32_t> first_frame, last_frame;
 };
 
-struct Segment { std::vector<uint32_t> tokens; std::string text; };  // one `<ts> text <ts|eot>` span, model.rs:100-149
+// one `<ts> text <ts|eot>` span, model.rs:100-149.  token_start / token_end: seconds from the start of the slice the segment was
+// decoded from, one pair per entry of `tokens`, when alignment heads are set; empty otherwise
+struct Segment { std::vector<uint32_t> tokens; std::string text; std::vector<float> token_start, token_end; };
 
 // The loaded model: owns one nh_ctx (batch 1, like the reference) and the carried-over PCM buffer.
 class Model {
   public:
     typedef float Data;                               // Model::Data = f32 (model.rs:49)
     Model(nh_ctx *ctx, nh_config cfg, nh_tokens tk) : ctx_(ctx), cfg_(cfg), tk_(tk) {}
-    Model(Model &&o) noexcept : ctx_(o.ctx_), cfg_(o.cfg_), tk_(o.tk_), buf_(std::move(o.buf_)), detok_(std::move(o.detok_)) { o.ctx_ = nullptr; }
+    Model(Model &&o) noexcept : ctx_(o.ctx_), cfg_(o.cfg_), tk_(o.tk_), buf_(std::move(o.buf_)), detok_(std::move(o.detok_)),
+                                align_heads_(std::move(o.align_heads_)), checkpoint_heads_(std::move(o.checkpoint_heads_)) { o.ctx_ = nullptr; }
     Model(const Model &) = delete;
     ~Model() { if (ctx_) nh_destroy(ctx_); }
 
@@ -158,6 +164,14 @@ class Model {
     void enable_language_detection(std::vector<int32_t> language_tokens) { detect_ = true; lang_tokens_ = std::move(language_tokens); lang_token_ = -1; }
     int32_t language_token() const { return detect_ ? lang_token_ : tk_.lang; }
     size_t buffered_samples() const { return buf_.size(); }
+    // Token-level timestamps: with a non-empty list, decode_with_fallback aligns the attempt it accepts (nh_align over the
+    // audio-bearing frames of the slice) and transcribe fills Segment::token_start / token_end.  Empty (the default): off,
+    // nothing runs and nothing changes.
+    void set_alignment_heads(std::vector<nh_align_head> heads) { align_heads_ = std::move(heads); }
+    // what the checkpoint's generation_config.json lists as alignment_heads ([layer, head] pairs; empty without one).
+    // Remembered, not enabled: hand it to set_alignment_heads to turn the timestamps on.
+    const std::vector<nh_align_head> &checkpoint_alignment_heads() const { return checkpoint_heads_; }
+    void set_checkpoint_alignment_heads(std::vector<nh_align_head> heads) { checkpoint_heads_ = std::move(heads); }
 
     // Model::transcribe (model.rs:55-159).  `data` is consumed (swapped/appended into the model's buffer).
     // Returns an Error with kind != None on a backend failure (the reference's TranscriberError, which
@@ -194,6 +208,11 @@ class Model {
                 }
                 Segment sg;
                 sg.tokens.assign(tok + 1, tok + n - 1);                                                   // tokens[1..len-1], :147
+                if (!dr.first_frame.empty())
+                    for (size_t i = seg.first + 1; i + 1 < seg.second; i++) {   // 20 ms per encoder frame
+                        sg.token_start.push_back(0.02f * (float)dr.first_frame[i]);
+                        sg.token_end.push_back(0.02f * (float)(dr.last_frame[i] + 1));
+                    }
                 if (detok_) { sg.text = detok_(sg.tokens.data(), sg.tokens.size()); if (text) *text += sg.text; }
                 out.push_back(std::move(sg));
             }
@@ -241,6 +260,16 @@ class Model {
             const bool needs_fallback = dr.avg_logprob < LOGPROB_THRESHOLD;
             if (a == 0) needs_fallback_ = needs_fallback && !(dr.no_speech_prob > NO_SPEECH_THRESHOLD);
             if (!needs_fallback || dr.no_speech_prob > NO_SPEECH_THRESHOLD || !fallback_) have = true;
+            dr.first_frame.clear(); dr.last_frame.clear();
+            const int P = (detect_ || tk_.lang >= 0) ? 3 : 2;                    // [sot, lang?, task], model.rs:285-289
+            if (have && !align_heads_.empty() && r.n_tokens > P) {               // the accepted attempt; a no-speech exit holds the prompt alone
+                const int32_t nt = r.n_tokens;
+                const int32_t nk = (int32_t)std::min<size_t>((size_t)cfg_.max_source_positions, (n + 319) / 320);   // frames that hold audio
+                std::vector<int32_t> first(cfg_.max_target_positions), last(cfg_.max_target_positions);
+                if (nh_align(ctx_, toks.data(), &nt, P, align_heads_.data(), (int)align_heads_.size(), &nk, first.data(), last.data())) return backend_error();
+                dr.first_frame.assign(first.begin(), first.begin() + nt);
+                dr.last_frame.assign(last.begin(), last.begin() + nt);
+            }
         }
         last_ = dr;
         return Error{};                                                          // have == false: Ok(None), :189-190
@@ -264,6 +293,7 @@ class Model {
     uint64_t seed_ = entropy_seed();
     uint32_t slices_ = 0;
     bool detect_ = false;
+    std::vector<nh_align_head> align_heads_, checkpoint_heads_;
     std::vector<int32_t> lang_tokens_;
     int32_t lang_token_ = -1;
 };
@@ -372,6 +402,21 @@ class Definition {
         if (e) return e;
         (*out)->set_detokenizer([tok](const uint32_t *ids, size_t n) { return tok->decode(ids, n); });  // model.rs:147
         if (detect_language) (*out)->enable_language_detection(std::move(lang_tokens));
+        // generation_config.json, when the checkpoint has one: alignment_heads = [[layer, head], ...] (remembered, not enabled)
+        {
+            assets::MappedFile gf;
+            std::string gerr;
+            if (gf.open(dir + "/generation_config" + sfx + ".json", gerr)) {
+                assets::Json gj; assets::JsonParser gp(gf.data(), gf.size());
+                std::vector<nh_align_head> heads;
+                if (gp.parse(gj) && gj.type == assets::Json::Obj)
+                    if (const assets::Json *ah = gj.get("alignment_heads"))
+                        for (const auto &pr : ah->arr)
+                            if (pr.type == assets::Json::Arr && pr.arr.size() == 2 && pr.arr[0].type == assets::Json::Num && pr.arr[1].type == assets::Json::Num)
+                                heads.push_back(nh_align_head{(int32_t)pr.arr[0].num, (int32_t)pr.arr[1].num});
+                (*out)->set_checkpoint_alignment_heads(std::move(heads));
+            }
+        }
         return Error{};
     }
 

@@ -25,6 +25,8 @@ N_FRAMES = 3000
 NH_DTYPE_F32, NH_DTYPE_F16 = 0, 1
 NH_LANG_DETECT = -2   # `lang` of pool_admit*: the row detects its language in its first step (pool_detect_languages)
 NH_OPT_DECODE_GRAPHS, NH_OPT_FUSE_DECODE_LAYERNORM, NH_OPT_DECODER_LAYER_LIMIT, NH_OPT_ABSORBED_XATTN = 0, 1, 2, 3
+NH_OPT_ALIGN_KEEP = 4      # 1: align() keeps every clip's weights and matrix for align_weights / align_matrix
+NH_ALIGN_MAX_HEADS = 32
 # NH_SAMPLE_* of include/norma_hip.h (the types of src/dtype.rs)
 SAMPLE_DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.int8): 2, np.dtype(np.int16): 3,
                  np.dtype(np.int32): 4, np.dtype(np.int64): 5, np.dtype(np.uint8): 6, np.dtype(np.uint16): 7,
@@ -53,6 +55,10 @@ class NhTokens(C.Structure):
 class NhDecodeResult(C.Structure):
     _fields_ = [("n_tokens", C.c_int32), ("no_speech_exit", C.c_int32), ("avg_logprob", C.c_double),
                 ("no_speech_prob", C.c_double)]
+
+
+class NhAlignHead(C.Structure):
+    _fields_ = [("layer", C.c_int32), ("head", C.c_int32)]
 
 
 class NhTimings(C.Structure):
@@ -122,6 +128,10 @@ def load_library() -> C.CDLL:
     L.nh_decoder_forward.argtypes = [vp, ip, C.c_int, fp]
     L.nh_final_linear.argtypes = [vp, fp, C.c_int, fp]
     L.nh_apply_rules.argtypes = [vp, fp, ip, C.c_int, C.c_int, fp, ip]
+    L.nh_align.argtypes = [vp, ip, ip, C.c_int, C.POINTER(NhAlignHead), C.c_int, ip, ip, ip]
+    L.nh_align_weights.argtypes = [vp, C.c_int, C.c_int, fp]
+    L.nh_align_matrix.argtypes = [vp, C.c_int, fp]
+    L.nh_align_path.argtypes = [vp, fp, C.c_int, C.c_int, ip, ip]
     L.nh_get_timings.argtypes = [vp, C.POINTER(NhTimings)]
     L.nh_set_profile_gemm.argtypes = [vp, C.c_int]
     L.nh_set_option.argtypes = [vp, C.c_int, C.c_int]
@@ -423,6 +433,55 @@ class HipWhisper:
         self._chk(self.L.nh_sample_rules(self._h, _fp(p), _ip(t), len(t), last_timestamp, float(temperature), int(seed),
                                          int(clip), int(attempt), C.byref(tok)))
         return int(tok.value)
+
+    # -- token-level timestamps -------------------------------------------------------------------
+    def align(self, tokens: Sequence[Sequence[int]], n_tokens: Optional[Sequence[int]] = None, prompt_len: int = 3,
+              heads: Sequence[Tuple[int, int]] = (), n_keys: Optional[Sequence[int]] = None):
+        """nh_align for every clip of the batch: tokens = the sequences as decode_* returned them (lists, or an i32 array
+        [batch][max_target_positions] with n_tokens), heads = [(decoder layer, head)], n_keys = encoder frames that hold audio
+        (None: all).  Returns (first, last): i32 [batch][max_target_positions], the first and last 20 ms encoder frame of every
+        token, -1 for the prompt and past the end."""
+        B, Cn = self.batch, self.cfg.max_target_positions
+        if n_tokens is None:
+            n_tokens = [len(t) for t in tokens]
+        nt = np.ascontiguousarray(n_tokens, dtype=np.int32)
+        toks = np.zeros((B, Cn), dtype=np.int32)
+        assert len(nt) == B and len(tokens) == B
+        for b in range(B):
+            n = max(0, min(int(nt[b]), Cn))
+            toks[b, :n] = np.asarray(tokens[b], dtype=np.int32)[:n]
+        hs = (NhAlignHead * max(1, len(heads)))(*[NhAlignHead(int(l), int(h)) for l, h in heads])
+        nk = None if n_keys is None else np.ascontiguousarray(n_keys, dtype=np.int32)
+        assert nk is None or len(nk) == B
+        first = np.full((B, Cn), -2, dtype=np.int32)
+        last = np.full((B, Cn), -2, dtype=np.int32)
+        self._align_out = (first, last)   # a refused call leaves them as they are (the tests look)
+        self._chk(self.L.nh_align(self._h, _ip(toks), _ip(nt), int(prompt_len), hs, len(heads), None if nk is None else _ip(nk),
+                                  _ip(first), _ip(last)))
+        self._align_shape = (nt.copy(), int(prompt_len), np.full(B, self.cfg.max_source_positions, np.int32) if nk is None else nk.copy())
+        return first, last
+
+    def align_weights(self, b: int, a: int) -> np.ndarray:
+        """f32 [n_tokens[b] - 1][n_keys[b]]: the softmax of heads[a] of the last align (NH_OPT_ALIGN_KEEP = 1)"""
+        nt, _, nk = self._align_shape
+        out = np.zeros((int(nt[b]) - 1, int(nk[b])), dtype=np.float32)
+        self._chk(self.L.nh_align_weights(self._h, int(b), int(a), _fp(out)))
+        return out
+
+    def align_matrix(self, b: int) -> np.ndarray:
+        """f32 [n_tokens[b] - prompt_len][n_keys[b]]: the DTW input of the last align (NH_OPT_ALIGN_KEEP = 1)"""
+        nt, P, nk = self._align_shape
+        out = np.zeros((int(nt[b]) - P, int(nk[b])), dtype=np.float32)
+        self._chk(self.L.nh_align_matrix(self._h, int(b), _fp(out)))
+        return out
+
+    def align_path(self, matrix: np.ndarray):
+        """the DTW alone on a host matrix f32 [R][nk] (cost = -matrix): (first, last) i32 [R]"""
+        m = np.ascontiguousarray(matrix, dtype=np.float32)
+        R, nk = m.shape
+        first, last = np.full(R, -2, np.int32), np.full(R, -2, np.int32)
+        self._chk(self.L.nh_align_path(self._h, _fp(m), R, nk, _ip(first), _ip(last)))
+        return first, last
 
     # -- instrumentation ---------------------------------------------------------------------------
     def set_profile_gemm(self, enable: bool):

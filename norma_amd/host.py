@@ -107,6 +107,9 @@ def _lib():
         L.nm_model_free.argtypes = [vp]
         L.nm_model_transcribe.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                           C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.c_char_p, C.c_int]
+        L.nm_model_set_alignment_heads.argtypes = [vp, C.POINTER(C.c_int32), C.c_int]
+        L.nm_model_checkpoint_alignment_heads.argtypes = [vp, C.POINTER(C.c_int32), C.c_int]
+        L.nm_model_last_token_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]
         L.nm_model_last_result.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),
                                            C.POINTER(C.c_int)]
         _bound = True
@@ -153,6 +156,7 @@ class Model:
                 cur = []
             else:
                 cur.append(t)
+        self._last_segments = segs
         return segs
 
     def enable_language_detection(self, lang_tokens: Sequence[int]):
@@ -163,6 +167,34 @@ class Model:
     def set_temperature_fallback(self, enable: bool, seed: int = 0):
         """decode_with_fallback's sampled attempts (model.rs:175-188) on/off; draws follow the seeded sampling contract."""
         _lib().nm_model_set_temperature_fallback(self._h, int(enable), int(seed))
+
+    def set_alignment_heads(self, heads: Sequence[Tuple[int, int]]):
+        """Token-level timestamps: [(decoder layer, head)] switches them on for every slice transcribe decodes, an empty
+        list (the default) off.  last_token_times() then holds one (start, end) per token transcribe returned."""
+        a = np.ascontiguousarray(heads, dtype=np.int32).reshape(-1, 2)
+        if _lib().nm_model_set_alignment_heads(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), len(a)):
+            raise WhisperError(f"set_alignment_heads: 0 .. {hip.NH_ALIGN_MAX_HEADS} heads")
+
+    def checkpoint_alignment_heads(self) -> List[Tuple[int, int]]:
+        """alignment_heads of the checkpoint's generation_config.json ([] without one); not enabled by itself"""
+        a = np.zeros((hip.NH_ALIGN_MAX_HEADS * 8, 2), dtype=np.int32)
+        n = _lib().nm_model_checkpoint_alignment_heads(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), len(a))
+        return [(int(l), int(h)) for l, h in a[:min(n, len(a))]]
+
+    def last_token_times(self) -> List[List[Tuple[float, float]]]:
+        """(start, end) in seconds from the start of its slice for every token of the last transcribe call, grouped like
+        its segments; [] with alignment off"""
+        cap = 64 * (self._ctx_len + 2)
+        s, e = np.zeros(cap, dtype=np.float32), np.zeros(cap, dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        n = _lib().nm_model_last_token_times(self._h, s.ctypes.data_as(fp), e.ctypes.data_as(fp), cap)
+        if n == 0:
+            return []
+        out, i = [], 0
+        for seg in self._last_segments:
+            out.append([(float(s[i + k]), float(e[i + k])) for k in range(len(seg))])
+            i += len(seg)
+        return out
 
     @property
     def language_token(self) -> int:

@@ -348,3 +348,69 @@ int kref_lang_detect(const float *logits, int V, int B, const int32_t *lang_toke
 }
 
 }  // extern "C"
+
+// ---- token-level timestamps (k_align.hip) ---------------------------------------------------------------------------------
+extern "C" {
+
+// launch_align_weights: q fp16 [A][max_rows][B][64] (the capture layout), K fp16 [B][H][S][64] (head-major cross K cache),
+// heads i32 [A] = the head of K each list entry reads, n_rows / n_keys i32 [B]; W f32 [B][A][max_rows][S], copied in and back
+int kref_align_weights(const void *q, const void *K, const int32_t *heads, int A, int H, int S, int B, const int32_t *n_rows,
+                       const int32_t *n_keys, int max_rows, float *W) {
+    if (A < 1 || A > NH_ALIGN_HEADS || B < 1 || max_rows < 1 || S < 1) return -1;
+    for (int a = 0; a < A; a++) if (heads[a] < 0 || heads[a] >= H) return -1;
+    for (int b = 0; b < B; b++) if (n_rows[b] < 0 || n_rows[b] > max_rows || n_keys[b] < 0 || n_keys[b] > S) return -1;
+    Bufs b;
+    Stream st;
+    const half_t *dq = b.in<half_t>(q, (size_t)A * max_rows * B * NH_DH * 2), *dk = b.in<half_t>(K, (size_t)B * H * S * NH_DH * 2);
+    const int32_t *dr = b.in<int32_t>(n_rows, (size_t)B * 4), *dn = b.in<int32_t>(n_keys, (size_t)B * 4);
+    const size_t wbytes = (size_t)B * A * max_rows * S * 4;
+    float *dW = b.in<float>(W, wbytes);
+    KREF_CHECK(b);
+    AlignHeadPtrs hp{};
+    for (int a = 0; a < A; a++) { hp.q[a] = dq + (size_t)a * max_rows * B * NH_DH; hp.k[a] = dk + (size_t)heads[a] * S * NH_DH; }
+    const bool launched = launch_align_weights(hp, A, (long)B * NH_DH, NH_DH, (long)H * S * NH_DH, dr, dn, max_rows, S, B, 0, dW,
+                                               (long)A * max_rows * S, (long)max_rows * S, S, st.s);
+    if (hipError_t e = st.finish()) return (int)e;
+    b.out(W, dW, wbytes);
+    return launched ? (int)b.err : -1;
+}
+
+// launch_align_reduce: W f32 [B][A][max_rows][S] -> M f32 [B][max_rows][S] (rows r < n_rows + 1 - P; copied in and back)
+int kref_align_reduce(const float *W, int A, int B, int S, int max_rows, const int32_t *n_rows, const int32_t *n_keys, int P, float *M) {
+    if (B < 1 || max_rows < 1 || S < 1 || A < 1) return -1;
+    for (int b = 0; b < B; b++) if (n_rows[b] < 0 || n_rows[b] > max_rows || n_keys[b] < 0 || n_keys[b] > S) return -1;
+    Bufs b;
+    Stream st;
+    const float *dW = b.in<float>(W, (size_t)B * A * max_rows * S * 4);
+    const int32_t *dr = b.in<int32_t>(n_rows, (size_t)B * 4), *dn = b.in<int32_t>(n_keys, (size_t)B * 4);
+    const size_t mbytes = (size_t)B * max_rows * S * 4;
+    float *dM = b.in<float>(M, mbytes);
+    float *stats = b.zeros<float>((size_t)B * A * 2 * S * 4);
+    KREF_CHECK(b);
+    const bool launched = launch_align_reduce(dW, (long)A * max_rows * S, (long)max_rows * S, S, dr, dn, max_rows, S, B, 0, A, P, stats, dM,
+                                              (long)max_rows * S, S, st.s);
+    if (hipError_t e = st.finish()) return (int)e;
+    b.out(M, dM, mbytes);
+    return launched ? (int)b.err : -1;
+}
+
+// launch_align_dtw: M f32 [B][max_rows][S] -> first, last i32 [B][ldo] (copied in and back), ldo >= max_rows + 1
+int kref_align_dtw(const float *M, int B, int S, int max_rows, const int32_t *n_rows, const int32_t *n_keys, int P, int32_t *first,
+                   int32_t *last, int ldo) {
+    if (B < 1 || max_rows < 1 || S < 1) return -1;
+    for (int b = 0; b < B; b++) if (n_rows[b] < 0 || n_rows[b] > max_rows || n_keys[b] < 0 || n_keys[b] > S) return -1;
+    Bufs b;
+    Stream st;
+    const float *dM = b.in<float>(M, (size_t)B * max_rows * S * 4);
+    const int32_t *dr = b.in<int32_t>(n_rows, (size_t)B * 4), *dn = b.in<int32_t>(n_keys, (size_t)B * 4);
+    int32_t *df = b.in<int32_t>(first, (size_t)B * ldo * 4), *dl = b.in<int32_t>(last, (size_t)B * ldo * 4);
+    uint8_t *trace = b.zeros<uint8_t>((size_t)B * max_rows * S);
+    KREF_CHECK(b);
+    const bool launched = launch_align_dtw(dM, (long)max_rows * S, S, dr, dn, P, max_rows, S, B, 0, trace, (long)max_rows * S, df, dl, ldo, st.s);
+    if (hipError_t e = st.finish()) return (int)e;
+    b.out(first, df, (size_t)B * ldo * 4);
+    b.out(last, dl, (size_t)B * ldo * 4);
+    return launched ? (int)b.err : -1;
+}
+
+}  // extern "C"
