@@ -1,10 +1,12 @@
-// k_token.hip -- token selection of a decode step (gfx950).
-//
-// Replaces, per decode step of Model::decode (src/models/whisper/model.rs:317-371):
-//   logit_step_kernel    softmax over V, the suppression rules on PROBABILITIES (model.rs:212-277,
-//                        :331-338), greedy argmax with Iterator::max_by(total_cmp) semantics
-//                        (:350-356, last maximum wins), log-prob bookkeeping (:359-370) -- replacing
-//                        a 207 KB D2H + a fresh [V] mask H2D + three sync scalar reads per token.
+// k_token.hip -- token selection of a decode step (gfx950): the rules of Model::decode (src/models/whisper/model.rs:212-277,
+// :293-370) on the device, replacing a 207 KB D2H + a fresh [V] mask H2D + three sync scalar reads per token.
+//   logit_step_kernel        t = 0: softmax over V, the suppression rules on PROBABILITIES (:212-277, :331-338), greedy argmax
+//                            with Iterator::max_by(total_cmp) semantics (:350-356, last maximum wins); the no-speech probe
+//                            (:293-315); in a decode pool also the prompt positions
+//   sample_step_kernel, pool_sample_step_kernel    t > 0: the same rules, then one seeded draw (:340-348)
+//   pool_admit_kernel, pool_retry_kernel           a pool row starts a clip / decodes its clip again, sampled
+//   lang_detect_kernel, pool_lang_detect_kernel    Model::detect_language (:194-210), batched / inside a pool step
+//   rules_only_kernel, sample_rules_kernel         parity views: the rules (and one draw) on a given probability vector
 #include "nh_kernels.h"
 
 // ---------------------------------------------------------------------------------------------------
@@ -90,21 +92,18 @@ __device__ __forceinline__ int rules_decide(ProbFn probs, int V, const int32_t *
     return (sum_ts >= max_text) ? RULE_NON_TS : RULE_PAST;
 }
 
-// shared by the parity helper and the sampled step: rules, then the greedy arg max
-template <typename ProbFn>
-__device__ __forceinline__ void rules_argmax(ProbFn probs, int V, const int32_t *tokens, int n, int have_last,
-                                             int last_ts, const uint8_t *sup, const RuleTokens &tk, BlockRed &sm,
-                                             int &rule_out, int &next_out) {
-    const int rule = rules_decide(probs, V, tokens, n, have_last, sup, tk, sm);
-    int bk = INT_MIN, bi = -1;
-    for (int i = threadIdx.x; i < V; i += blockDim.x) {
-        float v = masked_value(probs(i), i, rule, sup, tk, last_ts);
-        int k = total_key(v);
-        if (k > bk || (k == bk && i > bi)) { bk = k; bi = i; }
-    }
-    int ok, oi;
-    block_argmax(bk, bi, sm, ok, oi);
-    rule_out = rule; next_out = oi;
+// thread 0: the books of model.rs:359-370 for `next`, chosen at token count n; the log-prob of :364-365 stays with the caller.
+// logit_step_kernel's tail.  The two sampled kernels keep theirs written out, with the all-masked exit of :343-346 in it.
+__device__ __forceinline__ void append_token(const DecodeState &s, int b, int32_t *toks, int n, int next, const RuleTokens &tk,
+                                             int cap, int max_new, int prompt_len) {
+    int nn = n, fin = 0;
+    if (next > tk.no_timestamps) { s.last_ts[b] = next; s.have_last[b] = 1; }  // :359-361
+    toks[nn++] = next;
+    if (nn >= cap) { toks[nn++] = tk.eot; fin = 1; }  // :367-370
+    else if (next == tk.eot) fin = 1;                 // :317
+    else if (max_new > 0 && nn - prompt_len >= max_new) { toks[nn++] = tk.eot; fin = 1; }  // bench knob
+    s.n_tokens[b] = nn;
+    if (fin) s.done[b] = 1;
 }
 
 // ---- sampled decoding, t > 0 (model.rs:340-348) ------------------------------------------------------------
@@ -224,8 +223,7 @@ __global__ __launch_bounds__(1024) void sample_step_kernel(const float *__restri
 
 void launch_sample_step(const float *logits, int V, DecodeState s, RuleTokens tk, int B, int ctx, int cap, int max_new,
                         int prompt_len, float inv_t, unsigned long long seed, unsigned clip0, unsigned attempt, hipStream_t st) {
-    const int ldl = (V + 63) & ~63;
-    hipLaunchKernelGGL(sample_step_kernel, dim3(B), dim3(1024), 0, st, logits, V, ldl, s, tk, ctx, cap, max_new, prompt_len,
+    hipLaunchKernelGGL(sample_step_kernel, dim3(B), dim3(1024), 0, st, logits, V, nh_logits_ld(V), s, tk, ctx, cap, max_new, prompt_len,
                        inv_t, seed, clip0, attempt);
 }
 
@@ -276,8 +274,7 @@ __global__ __launch_bounds__(1024) void pool_sample_step_kernel(const float *__r
 
 void launch_pool_sample_step(const float *logits, int V, DecodeState s, RuleTokens tk, int B, int ctx, int cap, int max_new,
                              int prompt_len, PoolSampling ps, int32_t *pos, hipStream_t st) {
-    const int ldl = (V + 63) & ~63;
-    hipLaunchKernelGGL(pool_sample_step_kernel, dim3(B), dim3(1024), 0, st, logits, V, ldl, s, tk, ctx, cap, max_new, prompt_len,
+    hipLaunchKernelGGL(pool_sample_step_kernel, dim3(B), dim3(1024), 0, st, logits, V, nh_logits_ld(V), s, tk, ctx, cap, max_new, prompt_len,
                        ps, pos);
 }
 
@@ -312,6 +309,11 @@ void launch_sample_rules(const float *probs_in, int32_t *token_out, const int32_
 #define LSPLIT 8
 constexpr int LMAX = 32;  // logits per thread: ceil(51866 / 8 / 256) = 26 for the largest Whisper vocabulary
 static_assert(NH_MAX_VOCAB == LSPLIT * 256 * LMAX, "logit_step_kernel holds exactly NH_MAX_VOCAB logits in registers");
+
+// what logit_step_kernel knows about a sequence BEFORE its sweep.  The first three are the RULE_* of the same name;
+// STEP_TEXT (the last token is text) becomes RULE_NON_TS or RULE_PAST only when the last workgroup compares sum_ts with
+// max_text, so RULE_PAST has no counterpart here; STEP_PROBE is mode 0, which selects no token.
+enum { STEP_FIRST = RULE_FIRST, STEP_SUP_TS = RULE_SUP_TS, STEP_NON_TS = RULE_NON_TS, STEP_TEXT = 3, STEP_PROBE = 4 };
 
 __device__ __forceinline__ void merge_ms(float &m, float &s, float &ts, float m2, float s2, float ts2) {
     float mn = fmaxf(m, m2);
@@ -367,11 +369,11 @@ __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict
     }
     const int NT = tk.no_timestamps;
     // candidate sets: A = allowed non-timestamp tokens (or the first-token window), B = allowed timestamps
-    int kind;  // 0 FIRST, 1 SUP_TS, 2 NON_TS, 3 TEXT (NON_TS vs PAST decided at the end), 4 no-speech probe
-    if (mode == 0) kind = 4;
-    else if (!have_last) kind = 0;
-    else if (l1 > NT) kind = (n >= 2 && l2 >= tk.eot) ? 1 : 2;
-    else kind = 3;
+    int kind;
+    if (mode == 0) kind = STEP_PROBE;
+    else if (!have_last) kind = STEP_FIRST;
+    else if (l1 > NT) kind = (n >= 2 && l2 >= tk.eot) ? STEP_SUP_TS : STEP_NON_TS;
+    else kind = STEP_TEXT;
     float m = -INFINITY, se = 0.f, ts = 0.f, tsinf = 0.f, av = -INFINITY, bv = -INFINITY;
     int ai = -1, bi = -1;
     // slice maximum first, then one exp per element against it (the slice lives in registers)
@@ -387,10 +389,10 @@ __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict
         const float e = __expf(l - m);   // softmax mass, and the timestamp mass of model.rs:263-266
         se += e;
         if (is_ts) { ts += e; if (sup) tsinf = 1.f; }  // p + (-inf) inside the summed slice -> the sum is -inf
-        if (kind == 0) { if (i >= tk.zero_sec && i <= tk.one_sec) better(av, ai, l, i); }
-        else if (kind == 1) { if (!is_ts && !sup) better(av, ai, l, i); }
-        else if (kind == 2) { if (is_ts && i > last_ts && !sup) better(bv, bi, l, i); }
-        else if (kind == 3) {  // max_text of model.rs:267-270 runs over i < no_timestamps
+        if (kind == STEP_FIRST) { if (i >= tk.zero_sec && i <= tk.one_sec) better(av, ai, l, i); }
+        else if (kind == STEP_SUP_TS) { if (!is_ts && !sup) better(av, ai, l, i); }
+        else if (kind == STEP_NON_TS) { if (is_ts && i > last_ts && !sup) better(bv, bi, l, i); }
+        else if (kind == STEP_TEXT) {  // max_text of model.rs:267-270 runs over i < no_timestamps
             if (i < NT && !sup) better(av, ai, l, i);
             else if (is_ts && i > last_ts && !sup) better(bv, bi, l, i);
         }
@@ -466,8 +468,8 @@ __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict
     }
     if (pos_ptr) pos_ptr[b] = my_pos + 1;  // every workgroup of this sequence read it before taking its ticket
     int next = -1; float lnext = 0.f;
-    if (kind == 0 || kind == 1) { next = ai; lnext = av; }
-    else if (kind == 2) { next = bi; lnext = bv; }
+    if (kind == STEP_FIRST || kind == STEP_SUP_TS) { next = ai; lnext = av; }
+    else if (kind == STEP_NON_TS) { next = bi; lnext = bv; }
     else {
         float sum_ts = tsinf > 0.f ? -INFINITY : ts / se;          // probabilities, as the reference compares them
         float max_text = ai >= 0 ? expf(av - m) / se : -INFINITY;
@@ -480,25 +482,22 @@ __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict
     float pv;
     if (next < 0) { next = V - 1; pv = -INFINITY; }  // every candidate masked: all -inf, last index wins (H3)
     else pv = expf(lnext - m) / se;
-    int32_t *wt = s.tokens + (long)b * ctx;
-    int nn = n;
-    if (next > NT) { s.last_ts[b] = next; s.have_last[b] = 1; }  // :359-361
-    wt[nn++] = next;
     s.sum_logprob[b] = sum_lp_in + log((double)pv);               // :364-365
-    int fin = 0;
-    if (nn >= cap) { wt[nn++] = tk.eot; fin = 1; }                // :367-370
-    else if (next == tk.eot) fin = 1;                             // :317
-    else if (max_new > 0 && nn - prompt_len >= max_new) { wt[nn++] = tk.eot; fin = 1; }  // bench knob
-    s.n_tokens[b] = nn;
-    if (fin) s.done[b] = 1;
+    append_token(s, b, s.tokens + (long)b * ctx, n, next, tk, cap, max_new, prompt_len);
 }
 
 void launch_logit_step(const float *logits, int V, DecodeState s, RuleTokens tk, int B, int ctx, int cap,
                        int max_new, int prompt_len, int mode, float *partials, unsigned *tickets, int32_t *pos_ptr,
                        hipStream_t st, const int32_t *handled) {
-    int ldl = (V + 63) & ~63;
-    hipLaunchKernelGGL(logit_step_kernel, dim3(LSPLIT, B), dim3(256), 0, st, logits, V, ldl, s, tk, ctx, cap, max_new,
+    hipLaunchKernelGGL(logit_step_kernel, dim3(LSPLIT, B), dim3(256), 0, st, logits, V, nh_logits_ld(V), s, tk, ctx, cap, max_new,
                        prompt_len, mode, partials, tickets, pos_ptr, handled);
+}
+
+// decode pool: what admission and retry both clear -- row `row` stands at position 0 with its P prompt tokens and no history
+__device__ __forceinline__ void pool_row_reset(const DecodeState &s, int32_t *pos, unsigned *tickets, int row, int P) {
+    s.n_tokens[row] = P; s.done[row] = 0; s.have_last[row] = 0; s.last_ts[row] = 0;
+    s.sum_logprob[row] = 0.0; s.no_speech[row] = 0.0;
+    pos[row] = 0; tickets[row] = 0u;
 }
 
 // decode pool: sequence `row` starts over with the prompt [t0, t1, (t2)] (model.rs:285-289) at position 0.  detect_flag
@@ -507,9 +506,7 @@ __global__ void pool_admit_kernel(DecodeState s, int32_t *pos, unsigned *tickets
                                   int32_t *detect_flag, int detect) {
     int32_t *t = s.tokens + (long)row * ctx;
     t[0] = t0; t[1] = t1; if (P == 3) t[2] = t2;
-    s.n_tokens[row] = P; s.done[row] = 0; s.have_last[row] = 0; s.last_ts[row] = 0;
-    s.sum_logprob[row] = 0.0; s.no_speech[row] = 0.0;
-    pos[row] = 0; tickets[row] = 0u;
+    pool_row_reset(s, pos, tickets, row, P);
     if (detect_flag) detect_flag[row] = detect;
 }
 void launch_pool_admit(DecodeState s, int32_t *pos, unsigned *tickets, int row, int ctx, int t0, int t1, int t2, int P, hipStream_t st,
@@ -522,9 +519,7 @@ void launch_pool_admit(DecodeState s, int32_t *pos, unsigned *tickets, int row, 
 // A language the row detected in its t = 0 attempt is one of those prompt tokens: the retry does not detect again.
 __global__ void pool_retry_kernel(DecodeState s, int32_t *pos, unsigned *tickets, PoolSampling ps, int row, int P, float inv_t,
                                   unsigned long long seed, unsigned clip, unsigned attempt, int32_t *detect_flag) {
-    s.n_tokens[row] = P; s.done[row] = 0; s.have_last[row] = 0; s.last_ts[row] = 0;
-    s.sum_logprob[row] = 0.0; s.no_speech[row] = 0.0;
-    pos[row] = 0; tickets[row] = 0u;
+    pool_row_reset(s, pos, tickets, row, P);
     ps.inv_t[row] = inv_t; ps.seed[row] = seed; ps.clip[row] = clip; ps.attempt[row] = attempt;
     if (detect_flag) detect_flag[row] = 0;
 }
@@ -579,8 +574,7 @@ __global__ __launch_bounds__(64) void lang_detect_kernel(const float *__restrict
 
 void launch_lang_detect(const float *logits, int V, const int32_t *lang_tokens, int n, float *probs_out, int32_t *lang_out,
                         int B, hipStream_t st) {
-    int ldl = (V + 63) & ~63;
-    hipLaunchKernelGGL(lang_detect_kernel, dim3(B), dim3(64), 0, st, logits, ldl, lang_tokens, n, probs_out, lang_out);
+    hipLaunchKernelGGL(lang_detect_kernel, dim3(B), dim3(64), 0, st, logits, nh_logits_ld(V), lang_tokens, n, probs_out, lang_out);
 }
 
 // decode pool: a row admitted with NH_LANG_DETECT detects its language in the step it takes at position 0 -- that step IS
@@ -602,8 +596,7 @@ __global__ __launch_bounds__(64) void pool_lang_detect_kernel(const float *__res
 
 void launch_pool_lang_detect(const float *logits, int V, DecodeState s, int B, int ctx, const int32_t *pos, PoolDetect det,
                              hipStream_t st) {
-    const int ldl = (V + 63) & ~63;
-    hipLaunchKernelGGL(pool_lang_detect_kernel, dim3(B), dim3(64), 0, st, logits, ldl, s, ctx, pos, det);
+    hipLaunchKernelGGL(pool_lang_detect_kernel, dim3(B), dim3(64), 0, st, logits, nh_logits_ld(V), s, ctx, pos, det);
 }
 
 __global__ __launch_bounds__(1024) void rules_only_kernel(const float *__restrict__ probs_in, float *masked_out,
@@ -611,9 +604,16 @@ __global__ __launch_bounds__(1024) void rules_only_kernel(const float *__restric
                                                           int last_ts, const uint8_t *sup, RuleTokens tk, int V) {
     __shared__ BlockRed sm;
     auto probs = [&](int i) { return probs_in[i]; };
-    int rule, next;
-    rules_argmax(probs, V, tokens, n, last_ts >= 0, last_ts, sup, tk, sm, rule, next);
-    for (int i = threadIdx.x; i < V; i += blockDim.x) masked_out[i] = masked_value(probs_in[i], i, rule, sup, tk, last_ts);
+    const int rule = rules_decide(probs, V, tokens, n, last_ts >= 0, sup, tk, sm);
+    int bk = INT_MIN, bi = -1;  // the greedy arg max of model.rs:350-356
+    for (int i = threadIdx.x; i < V; i += blockDim.x) {
+        const float v = masked_value(probs_in[i], i, rule, sup, tk, last_ts);
+        masked_out[i] = v;
+        const int k = total_key(v);
+        if (k > bk || (k == bk && i > bi)) { bk = k; bi = i; }
+    }
+    int ok, next;
+    block_argmax(bk, bi, sm, ok, next);
     if (threadIdx.x == 0) *argmax_out = next;
 }
 

@@ -148,10 +148,14 @@ static void emit_token_step(nh_ctx *ctx, const StepSpec &s) {
     logits_from_dx(ctx, s.B);
     if (pool && ctx->pool.lang_n > 0)
         launch_pool_lang_detect(ctx->logits, V, ctx->ds, s.B, C, s.pos_ptr, PoolDetect{ctx->d_lang_flag, ctx->d_lang_tokens, ctx->pool.lang_n, ctx->d_lang_out, ctx->d_lang_probs}, ctx->st);
-    if (pool && s.sampled) launch_pool_sample_step(ctx->logits, V, ctx->ds, ctx->tk, s.B, C, cap, s.max_new, s.P, ctx->psamp, s.pos_ptr, ctx->st);
-    if (!pool && s.sampled) launch_sample_step(ctx->logits, V, ctx->ds, ctx->tk, s.B, C, cap, s.max_new, s.P, s.inv_t, s.seed, s.clip0, s.attempt, ctx->st);
-    else launch_logit_step(ctx->logits, V, ctx->ds, ctx->tk, s.B, C, cap, s.max_new, s.P, s.mode, ctx->lpart, ctx->ltick, s.pos_ptr, ctx->st,
-                           pool && s.sampled ? ctx->psamp.handled : nullptr);
+    if (s.sampled && !pool) {  // lockstep sampled: every sequence draws its token
+        launch_sample_step(ctx->logits, V, ctx->ds, ctx->tk, s.B, C, cap, s.max_new, s.P, s.inv_t, s.seed, s.clip0, s.attempt, ctx->st);
+        return;
+    }
+    // greedy.  In a pool with a row on a sampled retry, the kernel of those rows goes first and tells the greedy one which it took.
+    if (s.sampled) launch_pool_sample_step(ctx->logits, V, ctx->ds, ctx->tk, s.B, C, cap, s.max_new, s.P, ctx->psamp, s.pos_ptr, ctx->st);
+    launch_logit_step(ctx->logits, V, ctx->ds, ctx->tk, s.B, C, cap, s.max_new, s.P, s.mode, ctx->lpart, ctx->ltick, s.pos_ptr, ctx->st,
+                      s.sampled ? ctx->psamp.handled : nullptr);
 }
 
 // The graphs of `key`, captured unless the slot holds them already.  A key that the greedy slot does not hold drops both

@@ -269,6 +269,8 @@ struct DecodeState {        // all device pointers
     const uint8_t *suppress;  // [V] 1 = suppressed (suppress_tokens U {no_timestamps})
 };
 struct RuleTokens { int sot, eot, lang, task, no_speech, no_timestamps, zero_sec, one_sec; };
+// row stride of every logits buffer [B][ld]: V rounded up to 64 floats.  The pad columns are never read.
+inline int nh_logits_ld(int V) { return (V + 63) & ~63; }
 // mode 0: no-speech probe at prompt position 0; mode 1: generate a token from logits [B][V]; mode 2 (decode pool): every
 // sequence is in the phase its own position pos_ptr[b] says -- 0: no-speech probe, < prompt_len - 1: nothing (the next prompt
 // token is given), otherwise generate

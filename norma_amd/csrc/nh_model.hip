@@ -161,7 +161,7 @@ static int build_context(std::shared_ptr<nh_model> mdl, int max_batch, nh_ctx **
     for (auto &e : ctx->ev) hipEventCreate(&e);
     const int B = max_batch, V = cfg->vocab_size, nm = cfg->num_mel_bins, ctxlen = cfg->max_target_positions;
     const long M = (long)B * 1500;
-    ctx->VP = (V + 63) & ~63;
+    ctx->VP = nh_logits_ld(V);
     bool ok = true;
 #define DA(field, T, n) ok = ok && ((ctx->field = dalloc<T>(ctx, (size_t)(n))) != nullptr)
     // this context's K/V caches: cross K/V of the current batch, self-attention cache

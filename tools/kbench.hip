@@ -29,7 +29,7 @@ static double bench(const char *name, int reps, std::function<void()> f, double 
     return us;
 }
 int main(int argc, char **argv) {
-    const int B = argc > 1 ? atoi(argv[1]) : 32, d = 1280, V = 51866, VP = (V + 63) & ~63, C = 448, S = 1500, H = 20;
+    const int B = argc > 1 ? atoi(argv[1]) : 32, d = 1280, V = 51866, VP = nh_logits_ld(V), C = 448, S = 1500, H = 20;
     // KBENCH_CUS=n: run everything on a stream confined to the first n CUs (n / 8 per XCD) -- how the decode kernels scale
     // down; the stream is not destroyed (hipStreamDestroy of a masked stream hangs on ROCm 7.2)
     if (getenv("KBENCH_CUS") && atoi(getenv("KBENCH_CUS")) > 0) {

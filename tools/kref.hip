@@ -283,7 +283,7 @@ int kref_logit_step(const float *logits, int K, int V, int B, int ctx, int cap, 
     for (int r = 0; r < B; r++) if (!done[r] && (n_tokens[r] < 1 || n_tokens[r] >= cap)) return -1;
     Bufs b;
     Stream st;
-    const long ldl = (V + 63) & ~63;
+    const long ldl = nh_logits_ld(V);
     const float *dl = b.in<float>(logits, (size_t)K * B * ldl * 4);
     KrefState ks(b, B, ctx, V, suppress, tokens, n_tokens, done, have_last, last_ts, sum_logprob, no_speech);
     int32_t *dpos = b.in<int32_t>(pos, (size_t)B * 4);
@@ -317,7 +317,7 @@ int kref_sample_step(const float *logits, int K, int V, int B, int ctx, int cap,
     for (int r = 0; r < B; r++) if (!done[r] && (n_tokens[r] < 1 || n_tokens[r] >= cap)) return -1;
     Bufs b;
     Stream st;
-    const long ldl = (V + 63) & ~63;
+    const long ldl = nh_logits_ld(V);
     const float *dl = b.in<float>(logits, (size_t)K * B * ldl * 4);
     KrefState ks(b, B, ctx, V, suppress, tokens, n_tokens, done, have_last, last_ts, sum_logprob, no_speech);
     KREF_CHECK(b);
@@ -334,7 +334,7 @@ int kref_lang_detect(const float *logits, int V, int B, const int32_t *lang_toke
     Bufs b;
     Stream st;
     if (n < 1 || n > 256) return -1;
-    const long ldl = (V + 63) & ~63;
+    const long ldl = nh_logits_ld(V);
     const float *dl = b.in<float>(logits, (size_t)B * ldl * 4);
     const int32_t *dlt = b.in<int32_t>(lang_tokens, (size_t)n * 4);
     float *dp = b.in<float>(probs, (size_t)B * n * 4);
