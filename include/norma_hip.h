@@ -303,7 +303,36 @@ typedef struct nh_align_head { int32_t layer, head; } nh_align_head;   /* decode
 int nh_align(nh_ctx *ctx, const int32_t *tokens, const int32_t *n_tokens, int prompt_len,
              const nh_align_head *heads, int n_heads, const int32_t *n_keys,
              int32_t *out_first, int32_t *out_last);
-/* parity views of the LAST nh_align, valid only under NH_OPT_ALIGN_KEEP = 1 (otherwise NH_ERR_STATE) */
+/* Alignment from the decode itself.  The only thing nh_align's teacher-forced pass produces that the decode did not already
+ * hold is the 64 fp16 query values per alignment head and position; a context told the heads beforehand keeps them while it
+ * decodes, and stages 2 - 6 then run on what is kept: no second decoder pass, and the rows of a decode pool can be aligned.
+ *
+ * nh_align_capture: the alignment heads whose cross-attention queries every following decode of this context keeps
+ * (nh_decode_greedy, nh_decode_sampled, every step of a pool row): one 64-thread-per-(row, head) launch per decoder layer
+ * that holds a head, writing the running rows at their own positions.  n_heads == 0: off (the default; the decode step is
+ * launched as without this function).  Tokens, log-probs and no-speech probabilities are the same bits either way.
+ * Refused, nothing changed: n_heads outside 0 .. NH_ALIGN_MAX_HEADS, a layer or head out of range or at or beyond
+ * NH_OPT_DECODER_LAYER_LIMIT (NH_ERR_INVALID); NH_OPT_ABSORBED_XATTN != 0, any pool row busy -- the captured step graphs
+ * carry the list -- (NH_ERR_STATE).  A new list forgets what was kept under the one before. */
+int nh_align_capture(nh_ctx *ctx, const nh_align_head *heads, int n_heads);
+/* Token times of sequences this context has just decoded, from the kept queries: stages 2 - 6 of nh_align, no decoder pass.
+ * rows == NULL: the n == batch clips of the last lockstep decode.  rows != NULL: n pool rows that nh_pool_collect has
+ * handed back and that no admit / retry has touched since (the lifetime nh_pool_retry and nh_pool_languages rely on); a
+ * retried row is aligned on its retry, once that has been collected.
+ * The sequence aligned is the one the decode / collect returned (n_tokens after the trailing-timestamp trim; the context
+ * remembers it -- the trim only drops trailing timestamp tokens and moves eot up, so query rows 0 .. n - 2 consumed exactly
+ * the returned tokens 0 .. n - 2), prompt_len is the decode's own.  n_keys: host i32 [n] or NULL (= S).
+ * out_first / out_last: host i32 [n][max_target_positions], as for nh_align, and equal to nh_align's on the returned tokens.
+ * A sequence ended by the no-speech exit has nothing to align: all -1.
+ * A lockstep context's sequences stay valid until nh_logmel* / nh_encode* / another decode / nh_align / nh_decoder_forward /
+ * nh_detect_language; a pool row's until an admit or retry of that row.
+ * Refused, nothing launched, outputs untouched.  NH_ERR_STATE: no heads set; no valid captured sequence (lockstep); a pool
+ * row that is busy, was never admitted, was decoded before the current head list was set, or was refilled or retried and not
+ * collected since.  NH_ERR_INVALID: a row outside the pool; rows == NULL on a pool context, or rows on a lockstep one; n
+ * that does not match the batch (pool: outside [1, rows of the pool]); n_keys outside [1, S]. */
+int nh_align_decoded(nh_ctx *ctx, const int32_t *rows, int n, const int32_t *n_keys, int32_t *out_first, int32_t *out_last);
+/* parity views of the LAST alignment (nh_align or nh_align_decoded; b = the index within that call), valid only under
+ * NH_OPT_ALIGN_KEEP = 1 (otherwise NH_ERR_STATE) */
 int nh_align_weights(nh_ctx *ctx, int b, int a, float *out);   /* f32 [n_tokens[b]-1][n_keys[b]] probabilities of heads[a] */
 int nh_align_matrix(nh_ctx *ctx, int b, float *out);           /* f32 [n_tokens[b]-prompt_len][n_keys[b]] the DTW input */
 /* the DTW alone on a host matrix f32 [R][nk] (cost = -matrix): parity view, R <= max_target_positions, nk <= S
@@ -337,7 +366,8 @@ int nh_set_profile_gemm(nh_ctx *ctx, int enable);
  * 2: the one-pass kernels (xa streamed once per decoder layer; d_model 512 / 768 / 1024 / 1280, other widths fall back to 1).
  * 0 (default): K and V as the reference computes them. */
 #define NH_OPT_ABSORBED_XATTN 3
-/* nh_align's workspace.  1: keep every clip's weights and matrix for the views nh_align_weights / nh_align_matrix (the whole
+/* The workspace of nh_align / nh_align_decoded.
+ * 1: keep every clip's weights and matrix for the views nh_align_weights / nh_align_matrix (the whole
  * batch is held: NH_ERR_NOMEM when that does not fit); 0 (default): clips are processed in groups that keep the workspace at
  * or under 256 MiB, and the views refuse. */
 #define NH_OPT_ALIGN_KEEP 4

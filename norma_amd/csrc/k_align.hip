@@ -20,28 +20,49 @@ void launch_align_qsave(const half_t *dq, half_t *qsave, const AlignLayerHeads &
     hipLaunchKernelGGL(align_qsave_kernel, dim3(B, lh.n), dim3(64), 0, st, dq, qsave, lh, B, d, pos, npos);
 }
 
+// The capture of a running decode (nh_align_capture): row b at its own position, read from device memory when the step is a
+// captured graph or a pool step, so the launch bakes in no host position.  qlive[a][pos][b][64] with ldb rows per position.
+// Rows that are not running (done != 0: finished, no-speech exit, empty) and positions outside [0, npos) write nothing.
+__global__ __launch_bounds__(64) void align_qsave_rows_kernel(const half_t *dq, half_t *qlive, AlignLayerHeads lh, int ldb, int d, int pos,
+                                                              const int32_t *pos_ptr, const int32_t *done, int npos) {
+    const int b = blockIdx.x, i = blockIdx.y;
+    if (done && done[b] != 0) return;   // uniform over the workgroup
+    const int p = pos_ptr ? pos_ptr[b] : pos;
+    if (p < 0 || p >= npos) return;
+    const int a = lh.slot[i], h = lh.head[i];
+    qlive[(((long)a * npos + p) * ldb + b) * NH_DH + threadIdx.x] = dq[(long)b * d + h * NH_DH + threadIdx.x];
+}
+
+void launch_align_qsave_rows(const half_t *dq, half_t *qlive, const AlignLayerHeads &lh, int B, int ldb, int d, int pos, const int32_t *pos_ptr,
+                             const int32_t *done, int npos, hipStream_t st) {
+    if (lh.n < 1 || B < 1 || B > ldb || npos < 1) return;
+    hipLaunchKernelGGL(align_qsave_rows_kernel, dim3(B, lh.n), dim3(64), 0, st, dq, qlive, lh, ldb, d, pos, pos_ptr, done, npos);
+}
+
 // ---- weights: W[p][s] = softmax_s(q_p . k_s / 8), s < nk ---------------------------------------------------------------------
 // One workgroup (4 waves) per (16 query rows, head, clip).  Both MFMA operands come from registers, loaded straight from
 // global memory in fragment order (lane l: row / key l & 15, dims 8 (l >> 4) .. + 7 of each 32-deep k-step), so no LDS feeds
 // the matrix pipe ("A neighbour on the CU").  Wave w owns the 16-key tiles w, w + 4, ...; the scores of all its
 // tiles (<= 24: nk <= 1536) stay in registers between the maximum, the sum and the division, so the head's K is read once per
-// 16 rows (from L2 after the first row block) and W is written once.
+// 16 rows (from L2 after the first row block) and W is written once.  row_map moves the two base pointers (query and K) of
+// the workgroup to another context row; the fragment loads, the MFMAs and every index of W are the same with and without it.
 #define AW_TILES 24
 #define AW_MAX_KEYS (AW_TILES * 4 * 16)
 
 __global__ __launch_bounds__(256) void align_weights_kernel(AlignHeadPtrs hp, long q_pos_stride, long q_clip_stride, long k_clip_stride,
                                                             const int32_t *n_rows, const int32_t *n_keys, int max_rows, int S, int clip0,
-                                                            float *W, long w_clip_stride, long w_head_stride, long ldw) {
+                                                            float *W, long w_clip_stride, long w_head_stride, long ldw, const int32_t *row_map) {
     __shared__ float red[2][4][16];
     const int g = blockIdx.z, a = blockIdx.y, rb = blockIdx.x * 16, b = clip0 + g;
     const int nr = min(n_rows[b], max_rows), nk = min(n_keys[b], S);
     if (rb >= nr || nk < 1) return;   // uniform over the workgroup
+    const int crow = row_map ? row_map[b] : b;   // the context row that holds the clip's queries and cross K
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
     // the query fragment; rows past the clip's last are clamped (computed, never stored)
     const int qrow = min(rb + fr, nr - 1);
-    const half_t *qp = hp.q[a] + (long)qrow * q_pos_stride + (long)b * q_clip_stride + 8 * fq;
+    const half_t *qp = hp.q[a] + (long)qrow * q_pos_stride + (long)crow * q_clip_stride + 8 * fq;
     const half8 qa0 = *reinterpret_cast<const half8 *>(qp), qa1 = *reinterpret_cast<const half8 *>(qp + 32);
-    const half_t *kb = hp.k[a] + (long)b * k_clip_stride + 8 * fq;
+    const half_t *kb = hp.k[a] + (long)crow * k_clip_stride + 8 * fq;
     const int ntiles = (nk + 15) >> 4;
     const float ninf = -INFINITY;
     f32x4 sc[AW_TILES];
@@ -121,10 +142,10 @@ __global__ __launch_bounds__(256) void align_weights_kernel(AlignHeadPtrs hp, lo
 
 bool launch_align_weights(const AlignHeadPtrs &hp, int A, long q_pos_stride, long q_clip_stride, long k_clip_stride, const int32_t *n_rows,
                           const int32_t *n_keys, int max_rows, int S, int nclips, int clip0, float *W, long w_clip_stride, long w_head_stride,
-                          long ldw, hipStream_t st) {
+                          long ldw, const int32_t *row_map, hipStream_t st) {
     if (A < 1 || A > NH_ALIGN_HEADS || S < 1 || S > AW_MAX_KEYS || ldw < S || max_rows < 1 || nclips < 1) return false;
     hipLaunchKernelGGL(align_weights_kernel, dim3((max_rows + 15) / 16, A, nclips), dim3(256), 0, st, hp, q_pos_stride, q_clip_stride,
-                       k_clip_stride, n_rows, n_keys, max_rows, S, clip0, W, w_clip_stride, w_head_stride, ldw);
+                       k_clip_stride, n_rows, n_keys, max_rows, S, clip0, W, w_clip_stride, w_head_stride, ldw, row_map);
     return true;
 }
 
@@ -191,7 +212,8 @@ __global__ __launch_bounds__(256) void align_reduce_kernel(const float *W, long 
 
 bool launch_align_reduce(const float *W, long w_clip_stride, long w_head_stride, long ldw, const int32_t *n_rows, const int32_t *n_keys,
                          int max_rows, int S, int nclips, int clip0, int A, int P, float *stats, float *M, long m_clip_stride, long ldm,
-                         hipStream_t st) {
+                         const int32_t *row_map, hipStream_t st) {
+    (void)row_map;   // W, stats and M are the call's own: nothing here is read from a context row
     if (A < 1 || A > NH_ALIGN_HEADS || P < 1 || P > max_rows || S < 1 || ldw < S || ldm < S || nclips < 1) return false;
     hipLaunchKernelGGL(align_stats_kernel, dim3((S + 255) / 256, A, nclips), dim3(256), 0, st, W, w_clip_stride, w_head_stride, ldw, n_rows,
                        n_keys, max_rows, S, clip0, stats, A);
@@ -271,7 +293,9 @@ __global__ __launch_bounds__(DTW_THREADS) void align_dtw_kernel(const float *M, 
 }
 
 bool launch_align_dtw(const float *M, long m_clip_stride, long ldm, const int32_t *n_rows, const int32_t *n_keys, int P, int max_rows, int S,
-                      int nclips, int clip0, uint8_t *trace, long t_clip_stride, int32_t *first, int32_t *last, int ldo, hipStream_t st) {
+                      int nclips, int clip0, uint8_t *trace, long t_clip_stride, int32_t *first, int32_t *last, int ldo, const int32_t *row_map,
+                      hipStream_t st) {
+    (void)row_map;   // M, trace, first and last are the call's own
     if (P < 1 || max_rows < 1 || max_rows + 1 - P > DTW_THREADS || S < 1 || ldm < S || t_clip_stride < (long)(max_rows + 1 - P) * S || nclips < 1 ||
         ldo < max_rows + 1)
         return false;

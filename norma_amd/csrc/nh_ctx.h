@@ -70,6 +70,9 @@ struct PoolRow {   // one row of a decode pool, as the host knows it
     bool inv_t_set = false;  // the row's device-side inv_t is > 0 (its last decode was a retry): the next admit zeroes it
     bool detect = false;     // the row's clip was admitted with NH_LANG_DETECT; an admit sets or clears it
     bool detected = false;   // ... and has taken a step since: d_lang_out / d_lang_probs hold its language
+    // what nh_pool_collect last read off the row (nh_align_decoded): tokens after finish_sequence's trim, the done flag, and
+    // the alignment generation its queries were kept under (-1: none; an admit or a retry clears it)
+    int n = 0, done = 0, align_gen = -1;
 };
 // Decode pool (nh_pool_*): rows [0, rows) decode, each at its own position; rows above are encoder staging.  rows == 0: no pool.
 struct Pool {
@@ -84,9 +87,10 @@ struct Pool {
 struct StepKey {
     int B = -1, S = -1, max_new = -1, P = -1, token_gen = -1, lang_n = -1;
     bool pool = false, sampled = false;
+    int align_gen = 0;   // the alignment heads whose queries the steps keep go by value too (nh_align_capture)
     bool operator==(const StepKey &o) const {
         return B == o.B && S == o.S && max_new == o.max_new && P == o.P && token_gen == o.token_gen && lang_n == o.lang_n &&
-               pool == o.pool && sampled == o.sampled;
+               pool == o.pool && sampled == o.sampled && align_gen == o.align_gen;
     }
 };
 struct StepGraphs {
@@ -100,16 +104,33 @@ struct StepGraphs {
 struct AlignState {
     std::vector<void *> allocs;      // everything below; released and re-made when a call needs more
     size_t bytes = 0;                // what the workspace holds
-    half_t *qsave = nullptr;         // fp16 [heads][C - 1][max_batch][64]
+    half_t *qsave = nullptr;         // fp16 [heads][C - 1][max_batch][64]; only once nh_align itself has run
     int32_t *n_rows = nullptr, *n_keys = nullptr;   // [max_batch]
+    int32_t *row_map = nullptr;                     // [max_batch] context row of every clip of a call (nh_align_decoded on a pool)
     int32_t *first = nullptr, *last = nullptr;      // [max_batch][C + 1]
     float *W = nullptr, *stats = nullptr, *M = nullptr;   // per clip of a group: [heads][C - 1][S], [heads][2][S], [C][S]
     uint8_t *trace = nullptr;        // [C][S] per clip of a group
     int heads = 0, group = 0, S = 0; // the shape the workspace was made for
-    // the last nh_align, for the views
+    // the last nh_align / nh_align_decoded, for the views (n_tokens 0: that clip had nothing to align)
     bool kept = false;
     int P = 0, A = 0;
     std::vector<int32_t> n_tokens, keys;
+};
+
+// nh_align_capture: the alignment heads whose cross-attention queries every decode of the context keeps, and what the
+// context remembers of the last lockstep decode for nh_align_decoded.  A == 0 (the default): the decode step launches nothing
+// for it.  The buffer is allocated by the first call with heads, grown by a call with more, freed by nh_destroy.
+struct AlignLive {
+    half_t *q = nullptr;             // fp16 [cap_heads][C - 1][max_batch][64]
+    int cap_heads = 0;
+    int A = 0;
+    nh_align_head heads[NH_ALIGN_HEADS];
+    std::vector<AlignLayerHeads> layer;   // [decoder_layers] while A > 0; n == 0: no head there
+    int gen = 0;                     // bumped by nh_align_capture (and by options that change what a step computes); in StepKey
+    // the last lockstep decode, while nothing has overwritten what it left: per clip the tokens after the trim and the done flag
+    bool lock_valid = false;
+    int P = 0;
+    std::vector<int32_t> n, done;
 };
 
 struct nh_ctx {
@@ -159,7 +180,8 @@ struct nh_ctx {
     half_t *xabs_u = nullptr;    // [max_batch][32][d] scratch (heads padded to 32, pad rows zero)
     float *xabs_z = nullptr, *xabs_ml = nullptr;   // key-range partials of the one-pass form
     bool opt_align_keep = false; // NH_OPT_ALIGN_KEEP
-    AlignState al;               // nh_align
+    AlignState al;               // nh_align, nh_align_decoded
+    AlignLive live;              // nh_align_capture
     int dec_layer_limit = 0;    // parity view (NH_OPT_DECODER_LAYER_LIMIT): run only the first n decoder blocks; 0 = all
     std::vector<int32_t> seq_lang;  // per-sequence language tokens (LanguageState::Detect), empty = tk.lang for all
     int32_t *d_lang_tokens = nullptr, *d_lang_out = nullptr;

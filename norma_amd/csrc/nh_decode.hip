@@ -55,6 +55,8 @@ static void ln_skinny(nh_ctx *ctx, const LnW &ln, const LinW &W, int R, int N, i
 // skip_done: finished sequences skip their attention (only inside decode_impl, where ds.done is live).
 // cap (nh_align only): the layers that hold alignment heads copy those heads' cross-attention query of every row to
 // cap->qsave[head][pos][row][64] right after the projection; nullptr (every other caller): nothing is added to the step.
+// ctx->live (nh_align_capture), inside a decode only (skip_done): the same copy for the running rows, each at its own position,
+// into ctx->live.q; no heads set (the default): nothing is added to the step either.
 struct AlignCapture { half_t *qsave; int npos; std::vector<AlignLayerHeads> layer; };   // layer: [decoder_layers], n == 0: no head there
 static void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr = nullptr, bool final_ln = true, bool skip_done = false,
                          const AlignCapture *cap = nullptr) {
@@ -71,6 +73,8 @@ static void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr = nullptr,
         skinny(ctx, ctx->datt, d, L.o, B, d, d, SK_RESID_F32, ctx->dx, nullptr, nullptr, d, 0, C);
         ln_skinny(ctx, L.ln2, L.cq, B, d, d, SK_F16, ctx->dq, nullptr, nullptr, d, 0, C, nullptr);
         if (cap && cap->layer[l].n) launch_align_qsave(ctx->dq, cap->qsave, cap->layer[l], B, d, pos, cap->npos, ctx->st);
+        if (skip_done && ctx->live.A > 0 && ctx->live.layer[l].n)
+            launch_align_qsave_rows(ctx->dq, ctx->live.q, ctx->live.layer[l], B, ctx->B, d, pos, pos_ptr, done, C - 1, ctx->st);
         if (ctx->opt_absorbed == 2) launch_xabs_attention_fast(ctx->dq, L.ckv.wt, L.ckv.w, L.ckv.b, ctx->xa16, ctx->xabs_u, ctx->xabs_z, ctx->xabs_ml, ctx->datt, B, H, d, ctx->S, done, ctx->st);
         else if (ctx->opt_absorbed) launch_xabs_attention(ctx->dq, L.ckv.w, L.ckv.b, ctx->xa16, ctx->xabs_u, ctx->datt, B, H, d, ctx->S, done, ctx->st);
         else launch_dec_attention(ctx->dq, kv.ck, kv.cv, ctx->datt, B, 1, H, d, ctx->S, ctx->S, nullptr, ctx->st, 1, done);  // head-major cross K/V
@@ -124,9 +128,13 @@ static int read_results(nh_ctx *ctx, const int32_t *rows, int n, int32_t *out_to
     HIPCHK(hipStreamSynchronize(ctx->st));
     for (int i = 0; i < n; i++)
         if (rows && done[rows[i]] != 1 && done[rows[i]] != 2) return ctx->fail(NH_ERR_STATE, "nh_pool_collect: that row has not finished (see nh_pool_step's done flags)");
+    if (!rows) { ctx->live.n.assign(n, 0); ctx->live.done.assign(n, 0); }
     for (int i = 0; i < n; i++) {
         const int b = rows ? rows[i] : i;
         finish_sequence(ctx, toks.data() + (size_t)i * C, nt[b], done[b], slp[b], nsp[b], out_tokens + (size_t)i * C, results[i]);
+        // what nh_align_decoded aligns: the sequence as returned
+        if (rows) { PoolRow &r = ctx->pool.row[b]; r.n = results[i].n_tokens; r.done = done[b]; }
+        else { ctx->live.n[i] = results[i].n_tokens; ctx->live.done[i] = done[b]; }
     }
     return NH_OK;
 }
@@ -199,6 +207,7 @@ static int decode_impl(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *resul
     if (ctx->pool.rows > 0) return ctx->fail(NH_ERR_STATE, "nh_decode: the context runs a decode pool (nh_pool_begin); a batch submitted with row0 = 0 ends it");
     hipSetDevice(ctx->dev);
     if (int rc = ensure_decoder_repack(ctx)) return rc;
+    ctx->live.lock_valid = false;
     const int B = ctx->cur_batch, C = ctx->c.max_target_positions, cap = C - 1, V = ctx->c.vocab_size;
     // model.rs:285-289: prompt = [sot, lang?, task]
     const bool per_seq = (int)ctx->seq_lang.size() == B;
@@ -240,7 +249,7 @@ static int decode_impl(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *resul
     // reads the position from device memory (the eager loop is host-launch-bound at ~5 us per tiny kernel).
     const bool no_graph = !ctx->opt_graphs || inv_t > 0.f;
     if (!no_graph)
-        if (int rc = ensure_step_graphs(ctx, StepKey{B, ctx->S, max_new_tokens, P, ctx->token_gen, 0, false, false})) return rc;
+        if (int rc = ensure_step_graphs(ctx, StepKey{B, ctx->S, max_new_tokens, P, ctx->token_gen, 0, false, false, ctx->live.gen})) return rc;
     const int32_t first_pos = P - 1;
     for (int b = 0; b < B; b++) ctx->h_done[128 + b] = first_pos;  // every sequence of a batch starts generating at the same position
     HIPCHK(hipMemcpyAsync(ctx->d_pos, ctx->h_done + 128, sizeof(int32_t) * B, hipMemcpyHostToDevice, ctx->st));
@@ -270,6 +279,7 @@ static int decode_impl(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *resul
     HIPCHK(hipGetLastError());
     if (int rc = read_results(ctx, nullptr, B, out_tokens, results)) return rc;
     ctx->tm.decode_steps = steps;
+    ctx->live.lock_valid = ctx->live.A > 0; ctx->live.P = P;
     return NH_OK;
 }
 
@@ -300,6 +310,7 @@ extern "C" int nh_pool_begin(nh_ctx *ctx, int rows, int max_new_tokens, int per_
     const int prompt = (per_clip_language || ctx->tk.lang >= 0) ? 3 : 2;
     ctx->pool = Pool{rows, max_new_tokens, prompt, 0, per_clip_language != 0, std::vector<PoolRow>(rows)};   // no language table, fresh rows
     ctx->cur_batch = rows; ctx->frames = -1; ctx->S = 0; ctx->have_mel = false; ctx->have_enc = false;
+    ctx->live.lock_valid = false;
     ctx->seq_lang.clear();
     for (int b = 0; b < rows; b++) ctx->h_done[128 + b] = 3;  // 3: empty row (skipped like a finished one)
     HIPCHK(hipMemcpyAsync(ctx->ds.done, ctx->h_done + 128, sizeof(int32_t) * rows, hipMemcpyHostToDevice, ctx->st));
@@ -342,7 +353,7 @@ static int pool_admit_impl(nh_ctx *ctx, nh_ctx *src, int src_row, int dst_row, i
         HIPCHK(hipMemsetAsync(ctx->psamp.inv_t + dst_row, 0, sizeof(float), ctx->st));
         row.inv_t_set = false;
     }
-    row.busy = true; row.held = true; row.sampled = false;
+    row.busy = true; row.held = true; row.sampled = false; row.align_gen = -1;
     return NH_OK;
 }
 
@@ -361,7 +372,7 @@ extern "C" int nh_pool_retry(nh_ctx *ctx, int row, float temperature, uint64_t s
     launch_pool_retry(ctx->ds, ctx->d_pos, ctx->ltick, ctx->psamp, row, ctx->pool.prompt, 1.0f / temperature, seed, clip, attempt, ctx->st,
                       ctx->d_lang_flag);
     HIPCHK(hipGetLastError());
-    r.busy = true; r.sampled = true; r.inv_t_set = true;
+    r.busy = true; r.sampled = true; r.inv_t_set = true; r.align_gen = -1;
     return NH_OK;
 }
 
@@ -397,7 +408,7 @@ extern "C" int nh_pool_step(nh_ctx *ctx, int n_steps, int32_t *done_out) {
         if (ctx->S < 1) return ctx->fail(NH_ERR_STATE, "nh_pool_step: rows are busy but nothing was ever encoded");
         const StepGraphs &g = ctx->graphs[sampled];
         for (int s = 0; ctx->opt_graphs && s <= (int)sampled; s++)   // the greedy pair also when this call replays the sampled one
-            if (int rc = ensure_step_graphs(ctx, StepKey{B, ctx->S, pl.max_new, pl.prompt, ctx->token_gen, pl.lang_n, true, s == 1})) return rc;
+            if (int rc = ensure_step_graphs(ctx, StepKey{B, ctx->S, pl.max_new, pl.prompt, ctx->token_gen, pl.lang_n, true, s == 1, ctx->live.gen})) return rc;
         for (int left = n_steps; left > 0;) {
             if (!ctx->opt_graphs) {
                 emit_token_step(ctx, StepSpec{B, pl.max_new, pl.prompt, 2, sampled, 0, ctx->d_pos, 0.f, 0, 0, 0});
@@ -422,7 +433,8 @@ extern "C" int nh_pool_collect(nh_ctx *ctx, const int32_t *rows, int n, int32_t 
         if (rows[i] < 0 || rows[i] >= ctx->pool.rows || !ctx->pool.row[rows[i]].busy) return ctx->fail(NH_ERR_INVALID, "nh_pool_collect: not a busy row of the pool");
     hipSetDevice(ctx->dev);
     if (int rc = read_results(ctx, rows, n, out_tokens, results)) return rc;
-    for (int i = 0; i < n; i++) { PoolRow &r = ctx->pool.row[rows[i]]; r.busy = false; r.sampled = false; }
+    // heads cannot change while a row is busy (nh_align_capture refuses), so the whole decode ran under the current list
+    for (int i = 0; i < n; i++) { PoolRow &r = ctx->pool.row[rows[i]]; r.busy = false; r.sampled = false; r.align_gen = ctx->live.A > 0 ? ctx->live.gen : -1; }
     return NH_OK;
 }
 
@@ -505,6 +517,7 @@ extern "C" int nh_detect_language(nh_ctx *ctx, const int32_t *lang_tokens, int n
     hipSetDevice(ctx->dev);
     if (int rc = ensure_decoder_repack(ctx)) return rc;
     const int B = ctx->cur_batch, C = ctx->c.max_target_positions, V = ctx->c.vocab_size;
+    ctx->live.lock_valid = false;
     for (int i = 0; i < n; i++) if (lang_tokens[i] < 0 || lang_tokens[i] >= V) return ctx->fail(NH_ERR_INVALID, "nh_detect_language: token id outside the vocabulary");
     std::vector<int32_t> toks((size_t)B * C, 0);
     for (int b = 0; b < B; b++) toks[(size_t)b * C] = ctx->tk.sot;  // tokens = [[sot]], model.rs:195
@@ -540,6 +553,7 @@ extern "C" int nh_decoder_forward(nh_ctx *ctx, const int32_t *tokens, int T, flo
     hipSetDevice(ctx->dev);
     if (int rc = ensure_decoder_repack(ctx)) return rc;
     HIPCHK(hipStreamWaitEvent(ctx->st, ctx->enc_done, 0));
+    ctx->live.lock_valid = false;
     std::vector<int32_t> toks((size_t)B * C, 0);
     for (int b = 0; b < B; b++)
         for (int i = 0; i < T; i++) {
@@ -609,24 +623,30 @@ static_assert(NH_ALIGN_HEADS == NH_ALIGN_MAX_HEADS, "nh_kernels.h and norma_hip.
 #define NH_ALIGN_BUDGET ((size_t)256 << 20)   // workspace of a call under NH_OPT_ALIGN_KEEP = 0
 
 // The workspace for A heads and groups of `group` clips, made again when the shape differs from what is held.
-static int align_workspace(nh_ctx *ctx, int A, int group) {
+// want_q: the caller is nh_align, whose teacher-forced pass needs qsave; nh_align_decoded reads the context's live buffer, and a
+// context that only ever aligns what it decoded never holds a second query buffer.
+static int align_workspace(nh_ctx *ctx, int A, int group, bool want_q) {
     AlignState &al = ctx->al;
     const int S = ctx->S;
-    if (al.heads == A && al.group == group && al.S == S) return NH_OK;
+    // kept whenever it is large enough: the rows a pool hands back differ from collect to collect, and making it again costs a
+    // stream synchronise and device-wide hipFree / hipMalloc pairs on the path the pool exists for
+    if (al.heads == A && al.group >= group && al.S == S && (al.qsave || !want_q)) return NH_OK;
+    want_q = want_q || al.qsave;
     HIPCHK(hipStreamSynchronize(ctx->st));
     for (void *p : al.allocs) hipFree(p);
     al = AlignState{};
     const size_t C = ctx->c.max_target_positions, NP = C - 1, B = ctx->B;
-    al.qsave = dalloc_into<half_t>(al.allocs, (size_t)A * NP * B * NH_DH, false);
+    if (want_q) al.qsave = dalloc_into<half_t>(al.allocs, (size_t)A * NP * B * NH_DH, false);
     al.n_rows = dalloc_into<int32_t>(al.allocs, B);
     al.n_keys = dalloc_into<int32_t>(al.allocs, B);
+    al.row_map = dalloc_into<int32_t>(al.allocs, B);
     al.first = dalloc_into<int32_t>(al.allocs, B * (C + 1));
     al.last = dalloc_into<int32_t>(al.allocs, B * (C + 1));
     al.W = dalloc_into<float>(al.allocs, (size_t)group * A * NP * S, false);
     al.stats = dalloc_into<float>(al.allocs, (size_t)group * A * 2 * S, false);
     al.M = dalloc_into<float>(al.allocs, (size_t)group * C * S, false);
     al.trace = dalloc_into<uint8_t>(al.allocs, (size_t)group * C * S, false);
-    if (!al.qsave || !al.n_rows || !al.n_keys || !al.first || !al.last || !al.W || !al.stats || !al.M || !al.trace) {
+    if ((want_q && !al.qsave) || !al.n_rows || !al.n_keys || !al.row_map || !al.first || !al.last || !al.W || !al.stats || !al.M || !al.trace) {
         for (void *p : al.allocs) hipFree(p);
         al = AlignState{};
         (void)hipGetLastError();
@@ -634,6 +654,47 @@ static int align_workspace(nh_ctx *ctx, int A, int group) {
                                            " heads does not fit (NH_OPT_ALIGN_KEEP = 1 holds the whole batch)");
     }
     al.heads = A; al.group = group; al.S = S;
+    return NH_OK;
+}
+
+// The workspace of a call over n clips: the clips of a group share it; a group's size is the same for every call of the same
+// heads, and no kernel mixes clips, so grouping never shows in the results.
+static int align_prepare(nh_ctx *ctx, int A, int n, bool want_q) {
+    const size_t C = ctx->c.max_target_positions, NP = C - 1, S = ctx->S;
+    const size_t fixed = (size_t)A * NP * ctx->B * NH_DH * sizeof(half_t) + (size_t)ctx->B * (2 * (C + 1) + 2) * sizeof(int32_t);
+    const size_t per_clip = ((size_t)A * NP + 2 * A + C) * S * sizeof(float) + (size_t)C * S;
+    if (ctx->pool.rows > 0) n = ctx->pool.rows;   // a pool's calls name 1 .. rows rows: sized once for all of them
+    int group = n;
+    if (!ctx->opt_align_keep) {
+        const size_t room = NH_ALIGN_BUDGET > fixed ? NH_ALIGN_BUDGET - fixed : 0;
+        group = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, room / per_clip));
+    }
+    return align_workspace(ctx, A, group, want_q);
+}
+
+// Stages 2 - 6 for the n clips whose rows and keys al.n_rows / al.n_keys hold, a group at a time, and the paths back to the
+// host.  hp / q_pos_stride: where the queries are (nh_align's qsave or the live buffer); row_map: device i32 [n] or nullptr.
+static int align_stages(nh_ctx *ctx, const char *who, const AlignHeadPtrs &hp, int A, int P, long q_pos_stride, int n, const int32_t *row_map,
+                        int32_t *out_first, int32_t *out_last) {
+    AlignState &al = ctx->al;
+    const int C = ctx->c.max_target_positions, S = ctx->S, H = ctx->c.decoder_attention_heads, NP = C - 1, group = al.group;
+    const long wcs = (long)A * NP * S, whs = (long)NP * S, mcs = (long)C * S;
+    for (int c0 = 0; c0 < n; c0 += group) {
+        const int nc = std::min(group, n - c0);
+        bool ok = launch_align_weights(hp, A, q_pos_stride, NH_DH, (long)H * S * NH_DH, al.n_rows, al.n_keys, NP, S, nc, c0, al.W, wcs, whs, S, row_map, ctx->st);
+        ok = ok && launch_align_reduce(al.W, wcs, whs, S, al.n_rows, al.n_keys, NP, S, nc, c0, A, P, al.stats, al.M, mcs, S, row_map, ctx->st);
+        ok = ok && launch_align_dtw(al.M, mcs, S, al.n_rows, al.n_keys, P, NP, S, nc, c0, al.trace, mcs, al.first, al.last, C + 1, row_map, ctx->st);
+        if (!ok) return ctx->fail(NH_ERR_INVALID, std::string(who) + ": the alignment kernels do not cover this model's shape (S <= 1536, max_target_positions <= 512)");
+    }
+    std::vector<int32_t> fl((size_t)2 * n * (C + 1));
+    HIPCHK(hipMemcpyAsync(fl.data(), al.first, (size_t)n * (C + 1) * 4, hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipMemcpyAsync(fl.data() + (size_t)n * (C + 1), al.last, (size_t)n * (C + 1) * 4, hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    HIPCHK(hipGetLastError());
+    for (int b = 0; b < n; b++) {
+        memcpy(out_first + (size_t)b * C, fl.data() + (size_t)b * (C + 1), sizeof(int32_t) * C);
+        memcpy(out_last + (size_t)b * C, fl.data() + (size_t)(n + b) * (C + 1), sizeof(int32_t) * C);
+    }
     return NH_OK;
 }
 
@@ -667,18 +728,10 @@ extern "C" int nh_align(nh_ctx *ctx, const int32_t *tokens, const int32_t *n_tok
     }
     hipSetDevice(ctx->dev);
     if (int rc = ensure_decoder_repack(ctx)) return rc;
-    // the clips of a group share the workspace; a group's size is the same for every batch of the same heads, and no
-    // kernel mixes clips, so grouping never shows in the results
-    const size_t fixed = (size_t)A * NP * ctx->B * NH_DH * sizeof(half_t) + (size_t)ctx->B * (2 * (C + 1) + 2) * sizeof(int32_t);
-    const size_t per_clip = ((size_t)A * NP + 2 * A + C) * S * sizeof(float) + (size_t)C * S;
-    int group = B;
-    if (!ctx->opt_align_keep) {
-        const size_t room = NH_ALIGN_BUDGET > fixed ? NH_ALIGN_BUDGET - fixed : 0;
-        group = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, room / per_clip));
-    }
-    if (int rc = align_workspace(ctx, A, group)) return rc;
+    if (int rc = align_prepare(ctx, A, B, true)) return rc;
     AlignState &al = ctx->al;
     al.kept = false;
+    ctx->live.lock_valid = false;   // the pass below overwrites the tokens and self K/V the last decode left
     AlignCapture cap{al.qsave, NP, std::vector<AlignLayerHeads>(ctx->c.decoder_layers)};
     AlignHeadPtrs hp{};
     for (int a = 0; a < A; a++) {
@@ -695,25 +748,98 @@ extern "C" int nh_align(nh_ctx *ctx, const int32_t *tokens, const int32_t *n_tok
     // stage 1: the teacher-forced pass, every position enqueued back to back
     for (int pos = 0; pos <= maxn - 2; pos++) decoder_step(ctx, pos, nullptr, false, false, &cap);
     // stages 2 - 6, a group of clips at a time
-    const long wcs = (long)A * NP * S, whs = (long)NP * S, mcs = (long)C * S;
-    for (int c0 = 0; c0 < B; c0 += group) {
-        const int nc = std::min(group, B - c0);
-        bool ok = launch_align_weights(hp, A, (long)B * NH_DH, NH_DH, (long)H * S * NH_DH, al.n_rows, al.n_keys, NP, S, nc, c0, al.W, wcs, whs, S, ctx->st);
-        ok = ok && launch_align_reduce(al.W, wcs, whs, S, al.n_rows, al.n_keys, NP, S, nc, c0, A, P, al.stats, al.M, mcs, S, ctx->st);
-        ok = ok && launch_align_dtw(al.M, mcs, S, al.n_rows, al.n_keys, P, NP, S, nc, c0, al.trace, mcs, al.first, al.last, C + 1, ctx->st);
-        if (!ok) return ctx->fail(NH_ERR_INVALID, "nh_align: the alignment kernels do not cover this model's shape (S <= 1536, max_target_positions <= 512)");
-    }
-    std::vector<int32_t> fl((size_t)2 * B * (C + 1));
-    HIPCHK(hipMemcpyAsync(fl.data(), al.first, (size_t)B * (C + 1) * 4, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipMemcpyAsync(fl.data() + (size_t)B * (C + 1), al.last, (size_t)B * (C + 1) * 4, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    HIPCHK(hipGetLastError());
-    for (int b = 0; b < B; b++) {
-        memcpy(out_first + (size_t)b * C, fl.data() + (size_t)b * (C + 1), sizeof(int32_t) * C);
-        memcpy(out_last + (size_t)b * C, fl.data() + (size_t)(B + b) * (C + 1), sizeof(int32_t) * C);
-    }
+    if (int rc = align_stages(ctx, "nh_align", hp, A, P, (long)B * NH_DH, B, nullptr, out_first, out_last)) return rc;
     al.kept = ctx->opt_align_keep; al.P = P; al.A = A;
     al.n_tokens.assign(n_tokens, n_tokens + B); al.keys = keys;
+    return NH_OK;
+}
+
+// ---- alignment from the decode itself (contract: include/norma_hip.h, nh_align_capture / nh_align_decoded) -------------------
+extern "C" int nh_align_capture(nh_ctx *ctx, const nh_align_head *heads, int n_heads) {
+    if (!ctx || (n_heads > 0 && !heads)) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_align_capture: bad arguments") : NH_ERR_INVALID;
+    const int A = n_heads, H = ctx->c.decoder_attention_heads, NL = ctx->dec_layer_limit > 0 ? ctx->dec_layer_limit : ctx->c.decoder_layers;
+    if (A < 0 || A > NH_ALIGN_MAX_HEADS) return ctx->fail(NH_ERR_INVALID, "nh_align_capture: n_heads outside 0 .. NH_ALIGN_MAX_HEADS");
+    for (int a = 0; a < A; a++)
+        if (heads[a].layer < 0 || heads[a].layer >= NL || heads[a].head < 0 || heads[a].head >= H)
+            return ctx->fail(NH_ERR_INVALID, "nh_align_capture: alignment head " + std::to_string(a) + " names a layer or head the decoder does not run");
+    if (A > 0 && ctx->opt_absorbed) return ctx->fail(NH_ERR_STATE, "nh_align_capture: NH_OPT_ABSORBED_XATTN keeps no cross K cache to align against");
+    for (const PoolRow &r : ctx->pool.row)
+        if (ctx->pool.rows > 0 && r.busy) return ctx->fail(NH_ERR_STATE, "nh_align_capture: rows are busy (the head list is part of the captured steps)");
+    AlignLive &lv = ctx->live;
+    hipSetDevice(ctx->dev);
+    if (A > lv.cap_heads) {
+        HIPCHK(hipStreamSynchronize(ctx->st));   // a finished decode may still be copying into the buffer that goes
+        half_t *q = nullptr;
+        if (hipMalloc(reinterpret_cast<void **>(&q), (size_t)A * (ctx->c.max_target_positions - 1) * ctx->B * NH_DH * sizeof(half_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            return ctx->fail(NH_ERR_NOMEM, "nh_align_capture: hipMalloc failed");
+        }
+        if (lv.q) hipFree(lv.q);
+        lv.q = q; lv.cap_heads = A;
+    }
+    lv.A = A;
+    lv.layer.assign(A > 0 ? ctx->c.decoder_layers : 0, AlignLayerHeads{});
+    for (int a = 0; a < A; a++) {
+        lv.heads[a] = heads[a];
+        AlignLayerHeads &lh = lv.layer[heads[a].layer];
+        lh.slot[lh.n] = a; lh.head[lh.n] = heads[a].head; lh.n++;
+    }
+    // what was kept under the list before is no longer answered for; the step graphs of that list are stale (StepKey)
+    lv.gen++; lv.lock_valid = false;
+    return NH_OK;
+}
+
+extern "C" int nh_align_decoded(nh_ctx *ctx, const int32_t *rows, int n, const int32_t *n_keys, int32_t *out_first, int32_t *out_last) {
+    if (!ctx || !out_first || !out_last) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_align_decoded: bad arguments") : NH_ERR_INVALID;
+    AlignLive &lv = ctx->live;
+    const bool pool = ctx->pool.rows > 0;
+    const int C = ctx->c.max_target_positions, S = ctx->S, NP = C - 1, A = lv.A;
+    const int NL = ctx->dec_layer_limit > 0 ? ctx->dec_layer_limit : ctx->c.decoder_layers;
+    if (pool && !rows) return ctx->fail(NH_ERR_INVALID, "nh_align_decoded: the context runs a decode pool: name the rows");
+    if (!pool && rows) return ctx->fail(NH_ERR_INVALID, "nh_align_decoded: rows are a decode pool's; a lockstep context aligns its whole batch (rows = NULL)");
+    if (pool) {
+        if (n < 1 || n > ctx->pool.rows) return ctx->fail(NH_ERR_INVALID, "nh_align_decoded: n must lie in [1, rows of the pool]");
+        for (int i = 0; i < n; i++)
+            if (rows[i] < 0 || rows[i] >= ctx->pool.rows) return ctx->fail(NH_ERR_INVALID, "nh_align_decoded: row outside the pool");
+    } else if (lv.lock_valid && n != (int)lv.n.size()) return ctx->fail(NH_ERR_INVALID, "nh_align_decoded: n is not the batch of the last decode");
+    if (A < 1) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: no alignment heads are set (nh_align_capture)");
+    if (ctx->opt_absorbed) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: NH_OPT_ABSORBED_XATTN keeps no cross K cache to align against");
+    for (int a = 0; a < A; a++)
+        if (lv.heads[a].layer >= NL) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: NH_OPT_DECODER_LAYER_LIMIT cut an alignment head's layer off");
+    if (!pool && !lv.lock_valid) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: no decode under these alignment heads whose state is still in place");
+    std::vector<int32_t> nrows(n), keys(n), ntok(n);
+    for (int i = 0; i < n; i++) {
+        int nt, done;
+        if (pool) {
+            const PoolRow &r = ctx->pool.row[rows[i]];
+            if (r.busy) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: that row is busy (nh_pool_collect hands it back first)");
+            if (!r.held) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: no clip was admitted into that row since nh_pool_begin");
+            if (r.align_gen != lv.gen) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: that row has not been collected since it was admitted or retried under the current alignment heads");
+            nt = r.n; done = r.done;
+        } else { nt = lv.n[i]; done = lv.done[i]; }
+        const int nk = n_keys ? n_keys[i] : S;
+        if (nk < 1 || nk > S) return ctx->fail(NH_ERR_INVALID, "nh_align_decoded: n_keys must lie in [1, S]");
+        const int P = pool ? ctx->pool.prompt : lv.P;
+        const bool nothing = done == 2 || nt <= P || nt > C;   // the no-speech exit holds the prompt alone
+        ntok[i] = nothing ? 0 : nt; nrows[i] = nothing ? 0 : nt - 1; keys[i] = nk;
+    }
+    const int P = pool ? ctx->pool.prompt : lv.P;
+    hipSetDevice(ctx->dev);
+    if (int rc = align_prepare(ctx, A, n, false)) return rc;
+    AlignState &al = ctx->al;
+    al.kept = false;
+    AlignHeadPtrs hp{};
+    for (int a = 0; a < A; a++) {
+        hp.q[a] = lv.q + (size_t)a * NP * ctx->B * NH_DH;
+        hp.k[a] = ctx->kv[lv.heads[a].layer].ck + (size_t)lv.heads[a].head * S * NH_DH;
+    }
+    HIPCHK(hipMemcpyAsync(al.n_rows, nrows.data(), n * 4, hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipMemcpyAsync(al.n_keys, keys.data(), n * 4, hipMemcpyHostToDevice, ctx->st));
+    if (pool) HIPCHK(hipMemcpyAsync(al.row_map, rows, n * 4, hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));   // host buffers of this frame (and the caller's rows)
+    if (int rc = align_stages(ctx, "nh_align_decoded", hp, A, P, (long)ctx->B * NH_DH, n, pool ? al.row_map : nullptr, out_first, out_last)) return rc;
+    al.kept = ctx->opt_align_keep; al.P = P; al.A = A;
+    al.n_tokens = ntok; al.keys = keys;
     return NH_OK;
 }
 
@@ -728,8 +854,9 @@ static int align_view(nh_ctx *ctx, const float *src, int nrows, int nk, float *o
 extern "C" int nh_align_weights(nh_ctx *ctx, int b, int a, float *out) {
     if (!ctx || !out) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_align_weights: bad arguments") : NH_ERR_INVALID;
     const AlignState &al = ctx->al;
-    if (!al.kept) return ctx->fail(NH_ERR_STATE, "nh_align_weights: no nh_align under NH_OPT_ALIGN_KEEP = 1 to look at");
+    if (!al.kept) return ctx->fail(NH_ERR_STATE, "nh_align_weights: no alignment under NH_OPT_ALIGN_KEEP = 1 to look at");
     if (b < 0 || b >= (int)al.n_tokens.size() || a < 0 || a >= al.A) return ctx->fail(NH_ERR_INVALID, "nh_align_weights: clip or head out of range");
+    if (al.n_tokens[b] < 1) return ctx->fail(NH_ERR_STATE, "nh_align_weights: that sequence had nothing to align (no-speech exit)");
     const size_t NP = ctx->c.max_target_positions - 1;
     return align_view(ctx, al.W + ((size_t)b * al.A + a) * NP * al.S, al.n_tokens[b] - 1, al.keys[b], out);
 }
@@ -737,8 +864,9 @@ extern "C" int nh_align_weights(nh_ctx *ctx, int b, int a, float *out) {
 extern "C" int nh_align_matrix(nh_ctx *ctx, int b, float *out) {
     if (!ctx || !out) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_align_matrix: bad arguments") : NH_ERR_INVALID;
     const AlignState &al = ctx->al;
-    if (!al.kept) return ctx->fail(NH_ERR_STATE, "nh_align_matrix: no nh_align under NH_OPT_ALIGN_KEEP = 1 to look at");
+    if (!al.kept) return ctx->fail(NH_ERR_STATE, "nh_align_matrix: no alignment under NH_OPT_ALIGN_KEEP = 1 to look at");
     if (b < 0 || b >= (int)al.n_tokens.size()) return ctx->fail(NH_ERR_INVALID, "nh_align_matrix: clip out of range");
+    if (al.n_tokens[b] < 1) return ctx->fail(NH_ERR_STATE, "nh_align_matrix: that sequence had nothing to align (no-speech exit)");
     return align_view(ctx, al.M + (size_t)b * ctx->c.max_target_positions * al.S, al.n_tokens[b] - al.P, al.keys[b], out);
 }
 
@@ -760,7 +888,7 @@ extern "C" int nh_align_path(nh_ctx *ctx, const float *matrix, int R, int nk, in
     if (e == hipSuccess) e = hipMemcpyAsync(meta, rk, 8, hipMemcpyHostToDevice, ctx->st);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->st);
     // prompt_len 1 and n - 1 = R rows: row r of the matrix is token 1 + r
-    if (e == hipSuccess && !launch_align_dtw(M, (long)R * nk, nk, meta, meta + 1, 1, R, nk, 1, 0, trace, (long)R * nk, meta + 2, meta + 2 + (R + 1), R + 1, ctx->st))
+    if (e == hipSuccess && !launch_align_dtw(M, (long)R * nk, nk, meta, meta + 1, 1, R, nk, 1, 0, trace, (long)R * nk, meta + 2, meta + 2 + (R + 1), R + 1, nullptr, ctx->st))
         return done(ctx->fail(NH_ERR_INVALID, "nh_align_path: the DTW kernel covers R <= 512"));
     if (e == hipSuccess) e = hipMemcpyAsync(fl.data(), meta + 2, fl.size() * 4, hipMemcpyDeviceToHost, ctx->st);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->st);

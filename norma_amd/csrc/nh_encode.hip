@@ -29,6 +29,7 @@ static int prepare_batch(nh_ctx *ctx, const int32_t *n_samples, int batch, int r
         if (fr < 0) fr = f;
         else if (fr != f) return ctx->fail(NH_ERR_INVALID, "clips of one batch must produce the same number of mel frames");
     }
+    ctx->live.lock_valid = false;   // a lockstep decode's captured sequences (nh_align_decoded) end with the batch they belong to
     if (ctx->pool.rows > 0 && row0 >= ctx->pool.rows) {  // decode pool: encoder staging rows above the decoding ones
         if (ctx->frames < 0) {
             ctx->frames = (int)fr; ctx->S = (int)((fr + 2 - 3) / 2 + 1);
@@ -201,6 +202,7 @@ static int encode_rows(nh_ctx *ctx, int row0, int B) {
     if (nh_missing_tensors(ctx) != 0) return ctx->fail(NH_ERR_STATE, "nh_encode: " + std::to_string(nh_missing_tensors(ctx)) + " tensors not loaded");
     if (row0 < 0 || B < 1 || row0 + B > ctx->cur_batch) return ctx->fail(NH_ERR_INVALID, "nh_encode_rows: rows outside the clips given to nh_logmel");
     hipSetDevice(ctx->dev);
+    ctx->live.lock_valid = false;
     const nh_model &m = *ctx->mdl;
     const int d = ctx->c.d_model, F = ctx->frames, S = ctx->S, H = ctx->c.encoder_attention_heads;
     const int M = B * S;

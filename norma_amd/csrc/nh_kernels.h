@@ -334,6 +334,12 @@ void launch_rules_only(const float *probs_in, float *masked_out, int32_t *argmax
 struct AlignLayerHeads { int32_t slot[NH_ALIGN_HEADS], head[NH_ALIGN_HEADS]; int n; };
 // dq fp16 [B][d] (cross-attention query of that layer at position pos) -> qsave fp16 [slot][npos][B][64]
 void launch_align_qsave(const half_t *dq, half_t *qsave, const AlignLayerHeads &lh, int B, int d, int pos, int npos, hipStream_t st);
+// The same copy inside a decode (nh_align_capture): every row b < B at its OWN position -- pos_ptr[b] when pos_ptr != nullptr
+// (captured steps, pools: nothing of the launch depends on a host position), the host `pos` otherwise -- into
+// qlive fp16 [slot][npos][ldb][64], ldb >= B the buffer's rows.  Written only for rows with done[b] == 0 (running; done ==
+// nullptr: every row) at positions in [0, npos): finished and empty rows and positions past the buffer are left alone.
+void launch_align_qsave_rows(const half_t *dq, half_t *qlive, const AlignLayerHeads &lh, int B, int ldb, int d, int pos, const int32_t *pos_ptr,
+                             const int32_t *done, int npos, hipStream_t st);
 // Per alignment head a: q[a] + p * q_pos_stride + b * q_clip_stride = the 64 halfs of the query of clip b at position p;
 // k[a] + b * k_clip_stride + s * 64 = key s of clip b (the head's slab of the head-major cross K cache).  16-byte aligned.
 struct AlignHeadPtrs { const half_t *q[NH_ALIGN_HEADS]; const half_t *k[NH_ALIGN_HEADS]; };
@@ -341,18 +347,22 @@ struct AlignHeadPtrs { const half_t *q[NH_ALIGN_HEADS]; const half_t *k[NH_ALIGN
 // clip's index in the BATCH) give the clip's rows n - 1 (clamped to max_rows) and keys (clamped to S); workspaces (W, stats,
 // M, trace) are indexed by the clip's index in the GROUP, the outputs first / last by its index in the batch.  They return
 // false, and launch nothing, on a shape they do not cover.
+// row_map (device i32, indexed like n_rows; nullptr: the identity): the context row whose queries and cross K the clip reads
+// -- the `b` of q_clip_stride / k_clip_stride above -- so that a call can work on rows that are no contiguous range (the rows
+// of a decode pool).  Everything a launcher writes or sizes stays indexed as described; only the weights read through it.
 // W[g][a][p][s] = softmax_s(q . k_s / 8) over s < nk, f32, for p < n_rows; nothing else of W is written.  S <= 1536.
 bool launch_align_weights(const AlignHeadPtrs &hp, int A, long q_pos_stride, long q_clip_stride, long k_clip_stride, const int32_t *n_rows,
                           const int32_t *n_keys, int max_rows, int S, int nclips, int clip0, float *W, long w_clip_stride, long w_head_stride,
-                          long ldw, hipStream_t st);
+                          long ldw, const int32_t *row_map, hipStream_t st);
 // stats f32 [nclips][A][2][S] scratch (column mean and population std over the clip's rows); M[g][r][s], r < n_rows + 1 - P:
 // mean over the heads (in order) of the median of 7 along s (reflect padding, nk <= 3 unfiltered) of (W - mean) / std at
 // row P - 1 + r; std == 0 gives 0.  1 <= P <= max_rows.
 bool launch_align_reduce(const float *W, long w_clip_stride, long w_head_stride, long ldw, const int32_t *n_rows, const int32_t *n_keys,
                          int max_rows, int S, int nclips, int clip0, int A, int P, float *stats, float *M, long m_clip_stride, long ldm,
-                         hipStream_t st);
+                         const int32_t *row_map, hipStream_t st);
 // DTW on -M (R = n_rows + 1 - P rows, nk keys; tie rule and trace as nh_align states them): first / last i32 [batch][ldo],
 // entries P + r get the first and last key on the path of row r, every other entry -1.  trace: u8 scratch, t_clip_stride
 // >= (max_rows + 1 - P) * S per clip.  max_rows + 1 - P <= 512, ldo >= max_rows + 1.
 bool launch_align_dtw(const float *M, long m_clip_stride, long ldm, const int32_t *n_rows, const int32_t *n_keys, int P, int max_rows, int S,
-                      int nclips, int clip0, uint8_t *trace, long t_clip_stride, int32_t *first, int32_t *last, int ldo, hipStream_t st);
+                      int nclips, int clip0, uint8_t *trace, long t_clip_stride, int32_t *first, int32_t *last, int ldo, const int32_t *row_map,
+                      hipStream_t st);

@@ -46,6 +46,7 @@ extern "C" void nh_destroy(nh_ctx *ctx) {
     if (ctx->st) hipStreamSynchronize(ctx->st);
     for (void *p : ctx->allocs) hipFree(p);
     for (void *p : ctx->al.allocs) hipFree(p);
+    if (ctx->live.q) hipFree(ctx->live.q);
     drop_graphs(ctx);
     if (ctx->h_done) hipHostFree(ctx->h_done);
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);
@@ -472,6 +473,7 @@ extern "C" int nh_set_option(nh_ctx *ctx, int option, int value) {
     else if (option == NH_OPT_DECODER_LAYER_LIMIT) {
         if (value < 0 || value > ctx->c.decoder_layers) return ctx->fail(NH_ERR_INVALID, "nh_set_option: layer limit outside [0, decoder_layers]");
         ctx->dec_layer_limit = value; drop_graphs(ctx);
+        ctx->live.gen++; ctx->live.lock_valid = false;   // queries kept under another depth are not answered for (nh_align_decoded)
     }
     else if (option == NH_OPT_ABSORBED_XATTN) {
         if (value < 0 || value > 2) return ctx->fail(NH_ERR_INVALID, "nh_set_option: NH_OPT_ABSORBED_XATTN takes 0, 1 or 2");
@@ -489,6 +491,7 @@ extern "C" int nh_set_option(nh_ctx *ctx, int option, int value) {
             if (!ctx->xabs_z || !ctx->xabs_ml) return ctx->fail(NH_ERR_NOMEM, "nh_set_option: hipMalloc failed");
         }
         ctx->opt_absorbed = value; drop_graphs(ctx);
+        ctx->live.gen++; ctx->live.lock_valid = false;
     }
     else if (option == NH_OPT_ALIGN_KEEP) ctx->opt_align_keep = value != 0;
     else return ctx->fail(NH_ERR_INVALID, "nh_set_option: unknown option " + std::to_string(option));

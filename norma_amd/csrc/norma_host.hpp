@@ -154,7 +154,7 @@ class Model {
     typedef float Data;                               // Model::Data = f32 (model.rs:49)
     Model(nh_ctx *ctx, nh_config cfg, nh_tokens tk) : ctx_(ctx), cfg_(cfg), tk_(tk) {}
     Model(Model &&o) noexcept : ctx_(o.ctx_), cfg_(o.cfg_), tk_(o.tk_), buf_(std::move(o.buf_)), detok_(std::move(o.detok_)),
-                                align_heads_(std::move(o.align_heads_)), checkpoint_heads_(std::move(o.checkpoint_heads_)) { o.ctx_ = nullptr; }
+                                align_heads_(std::move(o.align_heads_)), checkpoint_heads_(std::move(o.checkpoint_heads_)), capture_stale_(o.capture_stale_) { o.ctx_ = nullptr; }
     Model(const Model &) = delete;
     ~Model() { if (ctx_) nh_destroy(ctx_); }
 
@@ -164,10 +164,11 @@ class Model {
     void enable_language_detection(std::vector<int32_t> language_tokens) { detect_ = true; lang_tokens_ = std::move(language_tokens); lang_token_ = -1; }
     int32_t language_token() const { return detect_ ? lang_token_ : tk_.lang; }
     size_t buffered_samples() const { return buf_.size(); }
-    // Token-level timestamps: with a non-empty list, decode_with_fallback aligns the attempt it accepts (nh_align over the
-    // audio-bearing frames of the slice) and transcribe fills Segment::token_start / token_end.  Empty (the default): off,
-    // nothing runs and nothing changes.
-    void set_alignment_heads(std::vector<nh_align_head> heads) { align_heads_ = std::move(heads); }
+    // Token-level timestamps: with a non-empty list, every decode keeps those heads' cross-attention queries
+    // (nh_align_capture) and decode_with_fallback aligns the attempt it accepts from them (nh_align_decoded over the
+    // audio-bearing frames of the slice: no second decoder pass); transcribe fills Segment::token_start / token_end.  Empty
+    // (the default): off, nothing runs and nothing changes.  The list reaches the context with the next slice.
+    void set_alignment_heads(std::vector<nh_align_head> heads) { align_heads_ = std::move(heads); capture_stale_ = true; }
     // what the checkpoint's generation_config.json lists as alignment_heads ([layer, head] pairs; empty without one).
     // Remembered, not enabled: hand it to set_alignment_heads to turn the timestamps on.
     const std::vector<nh_align_head> &checkpoint_alignment_heads() const { return checkpoint_heads_; }
@@ -246,6 +247,10 @@ class Model {
                 if (nh_detect_language(ctx_, lang_tokens_.data(), (int)lang_tokens_.size(), &lang_token_, nullptr)) return backend_error();
             } else if (nh_set_languages(ctx_, &lang_token_)) return backend_error();
         }
+        if (capture_stale_) {                                                   // the decodes below keep the heads' queries
+            if (nh_align_capture(ctx_, align_heads_.data(), (int)align_heads_.size())) return backend_error();
+            capture_stale_ = false;
+        }
         std::vector<int32_t> toks(cfg_.max_target_positions);
         have = false;
         const uint32_t clip = slices_++;
@@ -266,7 +271,7 @@ class Model {
                 const int32_t nt = r.n_tokens;
                 const int32_t nk = (int32_t)std::min<size_t>((size_t)cfg_.max_source_positions, (n + 319) / 320);   // frames that hold audio
                 std::vector<int32_t> first(cfg_.max_target_positions), last(cfg_.max_target_positions);
-                if (nh_align(ctx_, toks.data(), &nt, P, align_heads_.data(), (int)align_heads_.size(), &nk, first.data(), last.data())) return backend_error();
+                if (nh_align_decoded(ctx_, nullptr, 1, &nk, first.data(), last.data())) return backend_error();   // of the decode just above
                 dr.first_frame.assign(first.begin(), first.begin() + nt);
                 dr.last_frame.assign(last.begin(), last.begin() + nt);
             }
@@ -294,6 +299,7 @@ class Model {
     uint32_t slices_ = 0;
     bool detect_ = false;
     std::vector<nh_align_head> align_heads_, checkpoint_heads_;
+    bool capture_stale_ = false;   // align_heads_ changed since the context was last told (nh_align_capture)
     std::vector<int32_t> lang_tokens_;
     int32_t lang_token_ = -1;
 };

@@ -129,6 +129,8 @@ def load_library() -> C.CDLL:
     L.nh_final_linear.argtypes = [vp, fp, C.c_int, fp]
     L.nh_apply_rules.argtypes = [vp, fp, ip, C.c_int, C.c_int, fp, ip]
     L.nh_align.argtypes = [vp, ip, ip, C.c_int, C.POINTER(NhAlignHead), C.c_int, ip, ip, ip]
+    L.nh_align_capture.argtypes = [vp, C.POINTER(NhAlignHead), C.c_int]
+    L.nh_align_decoded.argtypes = [vp, ip, C.c_int, ip, ip, ip]
     L.nh_align_weights.argtypes = [vp, C.c_int, C.c_int, fp]
     L.nh_align_matrix.argtypes = [vp, C.c_int, fp]
     L.nh_align_path.argtypes = [vp, fp, C.c_int, C.c_int, ip, ip]
@@ -173,6 +175,7 @@ class HipWhisper:
             raise HipError(rc, self.L.nh_last_error(None).decode())
         self._h = h
         self.batch = 0
+        self._decoded, self._decoded_rows, self._task = [], {}, -1   # what the last decode / collects returned (align_decoded)
         self._experiment_switches()
 
     # -- lifetime ------------------------------------------------------------------------------
@@ -224,6 +227,7 @@ class HipWhisper:
                       tokens.zero_sec, tokens.one_sec)
         sup = np.asarray(self.cfg.suppress_tokens if suppress is None else suppress, dtype=np.int32)
         self._chk(self.L.nh_set_tokens(self._h, C.byref(tk), _ip(sup), len(sup)))
+        self._task = int(task)
 
     # -- hot path ------------------------------------------------------------------------------
     def logmel(self, clips: Sequence[np.ndarray]):
@@ -282,6 +286,7 @@ class HipWhisper:
     def pool_begin(self, rows: int, max_new_tokens: int = 0, per_clip_language: bool = False):
         self._chk(self.L.nh_pool_begin(self._h, rows, max_new_tokens, int(per_clip_language)))
         self.pool_rows = rows
+        self._decoded_rows = {}
 
     def pool_admit(self, src_row: int, dst_row: int, lang: int = -1):
         self._chk(self.L.nh_pool_admit(self._h, src_row, dst_row, lang))
@@ -301,6 +306,8 @@ class HipWhisper:
         toks = np.zeros((len(rows), self.cfg.max_target_positions), dtype=np.int32)
         res = (NhDecodeResult * len(rows))()
         self._chk(self.L.nh_pool_collect(self._h, _ip(rows), len(rows), _ip(toks), res))
+        for i, r in enumerate(rows):   # what align_decoded aligns for these rows
+            self._decoded_rows[int(r)] = (int(res[i].n_tokens), bool(res[i].no_speech_exit), int(toks[i, 1]))
         return [dict(tokens=toks[i, :res[i].n_tokens].tolist(), avg_logprob=res[i].avg_logprob,
                      no_speech_prob=res[i].no_speech_prob, no_speech_exit=bool(res[i].no_speech_exit)) for i in range(len(rows))]
 
@@ -345,6 +352,8 @@ class HipWhisper:
 
     def _results(self, toks: np.ndarray, res) -> List[dict]:
         out = []
+        # what align_decoded aligns after this decode: (n_tokens, no-speech exit, tokens[1]) per clip
+        self._decoded = [(int(res[b].n_tokens), bool(res[b].no_speech_exit), int(toks[b, 1])) for b in range(self.batch)]
         for b in range(self.batch):
             n = res[b].n_tokens
             out.append(dict(tokens=toks[b, :n].tolist(), avg_logprob=res[b].avg_logprob,
@@ -459,6 +468,32 @@ class HipWhisper:
         self._chk(self.L.nh_align(self._h, _ip(toks), _ip(nt), int(prompt_len), hs, len(heads), None if nk is None else _ip(nk),
                                   _ip(first), _ip(last)))
         self._align_shape = (nt.copy(), int(prompt_len), np.full(B, self.cfg.max_source_positions, np.int32) if nk is None else nk.copy())
+        return first, last
+
+    def align_capture(self, heads: Sequence[Tuple[int, int]]):
+        """nh_align_capture: every following decode of this context (decode_greedy, decode_sampled, the rows of a pool) keeps
+        the cross-attention queries of `heads` = [(decoder layer, head)] for align_decoded; [] turns it off (the default)."""
+        hs = (NhAlignHead * max(1, len(heads)))(*[NhAlignHead(int(l), int(h)) for l, h in heads])
+        self._chk(self.L.nh_align_capture(self._h, hs, len(heads)))
+
+    def align_decoded(self, rows: Optional[Sequence[int]] = None, n_keys: Optional[Sequence[int]] = None):
+        """nh_align_decoded: (first, last) i32 [n][max_target_positions] of the sequences this context has just decoded, from
+        the queries kept while decoding (align_capture) -- no decoder pass.  rows=None: the clips of the last lockstep decode;
+        rows=[...]: pool rows that pool_collect has handed back and nothing has refilled or retried since.  The sequences are
+        the ones the decode / collect returned; first / last are -1 for the prompt, past the end, and for a no-speech exit."""
+        Cn = self.cfg.max_target_positions
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+        n = self.batch if r is None else len(r)
+        nk = None if n_keys is None else np.ascontiguousarray(n_keys, dtype=np.int32)
+        assert nk is None or len(nk) == n
+        first = np.full((n, Cn), -1, dtype=np.int32)
+        last = np.full((n, Cn), -1, dtype=np.int32)
+        self._chk(self.L.nh_align_decoded(self._h, None if r is None else _ip(r), n, None if nk is None else _ip(nk), _ip(first), _ip(last)))
+        # the views' shape, from what the decode / collect returned: the prompt is [sot, task] or [sot, language, task]
+        seqs = self._decoded if r is None else [self._decoded_rows[int(x)] for x in r]
+        nt = np.array([0 if exit_ else n_ for n_, exit_, _ in seqs], dtype=np.int32)
+        P = 2 if seqs and seqs[0][2] == self._task else 3
+        self._align_shape = (nt, P, np.full(n, self.cfg.max_source_positions, np.int32) if nk is None else nk.copy())
         return first, last
 
     def align_weights(self, b: int, a: int) -> np.ndarray:

@@ -26,6 +26,14 @@ without an entry in `langs` is admitted with NH_LANG_DETECT and detects its lang
 pool_languages(rows) -> (tokens, probs) is read when its t = 0 attempt is collected.  Every result then carries "language",
 detected clips also "language_probs"; a retried clip keeps what its t = 0 attempt detected.  Without the keyword neither
 engine method is called.
+
+align_heads=[(decoder layer, head), ...] adds token-level timestamps ("Alignment from the decode"): the list goes
+to align_capture(heads) once after pool_begin, so every row keeps those heads' cross-attention queries while it decodes, and
+align_decoded(rows, n_keys) -> (first, last) is read right after the collect that yields a clip's accepted attempt -- under
+fallback=True after _settle accepts, never for a rejected or dropped attempt -- and before the row is offered for admission.
+The result gains "token_first" / "token_last": one encoder frame (20 ms) per entry of "tokens", -1 for the prompt.  A no-speech
+exit gets none.  run(.., n_keys=[frames that hold audio per clip]) bounds each clip's alignment (None: all frames).  Without
+the keyword neither engine method is called.
 """
 from typing import Callable, List, Optional, Sequence
 
@@ -50,8 +58,14 @@ class _Fallback:
         if self.detect_languages is not None:
             self.per_clip_language = True
 
+    def _init_align(self, align_heads):
+        self.align_heads = None if align_heads is None else [(int(l), int(h)) for l, h in align_heads]
+        self.aligned = 0        # clips aligned
+
     def _begin(self):
         self.e.pool_begin(self.rows, self.max_new, self.per_clip_language)
+        if self.align_heads is not None:
+            self.e.align_capture(self.align_heads)   # the fresh pool has no busy row: the steps are captured with the list
         if self.detect_languages is not None:
             self.e.pool_detect_languages(self.detect_languages)
         self._lang = [None] * self.rows     # per row: (language token, probabilities or None) of the clip it holds
@@ -97,23 +111,39 @@ class _Fallback:
         self.retries += 1
         return False
 
+    def _align(self, settled, n_keys):
+        """settled: [(row, clip, result)] of this collect whose rows are about to be freed; the accepted ones that produced
+        tokens are aligned in one call, on the state their rows still hold"""
+        if self.align_heads is None:
+            return
+        todo = [(r, c, res) for r, c, res in settled if res["accepted"] and not res["no_speech_exit"]]
+        if not todo:
+            return
+        nk = None if n_keys is None else [int(n_keys[c]) for _, c, _ in todo]
+        first, last = self.e.align_decoded([r for r, _, _ in todo], n_keys=nk)
+        for i, (_, _, res) in enumerate(todo):
+            n = len(res["tokens"])
+            res["token_first"], res["token_last"] = [int(v) for v in first[i][:n]], [int(v) for v in last[i][:n]]
+        self.aligned += len(todo)
+
 
 class DecodePool(_Fallback):
     def __init__(self, engine, rows: int = 64, staging: int = 32, max_new_tokens: int = 0, check_every: int = 16,
                  per_clip_language: bool = False, fallback: bool = False, seed: int = 0, clip0: int = 0,
                  temperatures: Sequence[float] = TEMPERATURES, logprob_threshold: float = -1.0, no_speech_threshold: float = 0.6,
-                 detect_languages: Optional[Sequence[int]] = None):
+                 detect_languages: Optional[Sequence[int]] = None, align_heads: Optional[Sequence] = None):
         assert rows >= 1 and staging >= 1 and check_every >= 1
         self._init_fallback(fallback, seed, clip0, temperatures, logprob_threshold, no_speech_threshold)
         self.e, self.rows, self.staging, self.check_every = engine, rows, staging, check_every
         self.max_new, self.per_clip_language = max_new_tokens, per_clip_language
         self._init_detect(detect_languages)
+        self._init_align(align_heads)
         self.steps = 0          # decode steps launched
         self.row_steps = 0      # sum over steps of the rows that were busy (what the step kernels' per-row work scales with)
         self.encodes = 0
 
     def run(self, n_clips: int, encode: Callable[[int, int, int, bool], Optional[bool]], langs: Optional[Sequence[Optional[int]]] = None,
-            on_result: Optional[Callable[[int, dict], None]] = None) -> List[dict]:
+            on_result: Optional[Callable[[int, dict], None]] = None, n_keys: Optional[Sequence[int]] = None) -> List[dict]:
         """Decode clips 0 .. n_clips - 1; returns their results in clip order."""
         e, R = self.e, self.rows
         self._begin()
@@ -145,13 +175,17 @@ class DecodePool(_Fallback):
             self.row_steps += busy * self.check_every
             fin = [r for r in range(R) if owner[r] >= 0 and flags[r] in (1, 2)]
             if fin:
+                settled = []
                 for r, res in zip(fin, self._collect(fin, attempt)):
                     if not self._settle(r, owner[r], res, attempt[r]):
                         attempt[r] += 1   # the row is busy again with the same clip
                         continue
-                    results[owner[r]] = res
+                    settled.append((r, owner[r], res))
+                self._align(settled, n_keys)   # while the rows still hold their clips
+                for r, c, res in settled:
+                    results[c] = res
                     if on_result:
-                        on_result(owner[r], res)
+                        on_result(c, res)
                     owner[r] = -1
                     busy -= 1
         return results  # type: ignore[return-value]
@@ -167,15 +201,17 @@ class FedDecodePool(_Fallback):
     def __init__(self, engine, encoders: Sequence, rows: int = 64, batch: int = 32, max_new_tokens: int = 0, check_every: int = 16,
                  per_clip_language: bool = False, fallback: bool = False, seed: int = 0, clip0: int = 0,
                  temperatures: Sequence[float] = TEMPERATURES, logprob_threshold: float = -1.0, no_speech_threshold: float = 0.6,
-                 detect_languages: Optional[Sequence[int]] = None):
+                 detect_languages: Optional[Sequence[int]] = None, align_heads: Optional[Sequence] = None):
         assert rows >= 1 and batch >= 1 and check_every >= 1 and len(encoders) >= 1
         self._init_fallback(fallback, seed, clip0, temperatures, logprob_threshold, no_speech_threshold)
         self.e, self.encoders, self.rows, self.batch, self.check_every = engine, list(encoders), rows, batch, check_every
         self.max_new, self.per_clip_language = max_new_tokens, per_clip_language
         self._init_detect(detect_languages)
+        self._init_align(align_heads)
         self.steps = self.row_steps = self.encodes = 0
 
-    def run(self, n_clips: int, encode: Callable[[int, int, int], None], langs: Optional[Sequence[Optional[int]]] = None) -> List[dict]:
+    def run(self, n_clips: int, encode: Callable[[int, int, int], None], langs: Optional[Sequence[Optional[int]]] = None,
+            n_keys: Optional[Sequence[int]] = None) -> List[dict]:
         import queue
         import threading
         e, R, NE = self.e, self.rows, len(self.encoders)
@@ -237,11 +273,15 @@ class FedDecodePool(_Fallback):
                 self.row_steps += busy * self.check_every
                 fin = [r for r in range(R) if owner[r] >= 0 and flags[r] in (1, 2)]
                 if fin:
+                    settled = []
                     for r, res in zip(fin, self._collect(fin, attempt)):
                         if not self._settle(r, owner[r], res, attempt[r]):
                             attempt[r] += 1
                             continue
-                        results[owner[r]] = res
+                        settled.append((r, owner[r], res))
+                    self._align(settled, n_keys)
+                    for r, c, res in settled:
+                        results[c] = res
                         owner[r] = -1
                         busy -= 1
                         done_clips += 1

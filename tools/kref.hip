@@ -369,7 +369,7 @@ int kref_align_weights(const void *q, const void *K, const int32_t *heads, int A
     AlignHeadPtrs hp{};
     for (int a = 0; a < A; a++) { hp.q[a] = dq + (size_t)a * max_rows * B * NH_DH; hp.k[a] = dk + (size_t)heads[a] * S * NH_DH; }
     const bool launched = launch_align_weights(hp, A, (long)B * NH_DH, NH_DH, (long)H * S * NH_DH, dr, dn, max_rows, S, B, 0, dW,
-                                               (long)A * max_rows * S, (long)max_rows * S, S, st.s);
+                                               (long)A * max_rows * S, (long)max_rows * S, S, nullptr, st.s);
     if (hipError_t e = st.finish()) return (int)e;
     b.out(W, dW, wbytes);
     return launched ? (int)b.err : -1;
@@ -388,7 +388,7 @@ int kref_align_reduce(const float *W, int A, int B, int S, int max_rows, const i
     float *stats = b.zeros<float>((size_t)B * A * 2 * S * 4);
     KREF_CHECK(b);
     const bool launched = launch_align_reduce(dW, (long)A * max_rows * S, (long)max_rows * S, S, dr, dn, max_rows, S, B, 0, A, P, stats, dM,
-                                              (long)max_rows * S, S, st.s);
+                                              (long)max_rows * S, S, nullptr, st.s);
     if (hipError_t e = st.finish()) return (int)e;
     b.out(M, dM, mbytes);
     return launched ? (int)b.err : -1;
@@ -406,10 +406,100 @@ int kref_align_dtw(const float *M, int B, int S, int max_rows, const int32_t *n_
     int32_t *df = b.in<int32_t>(first, (size_t)B * ldo * 4), *dl = b.in<int32_t>(last, (size_t)B * ldo * 4);
     uint8_t *trace = b.zeros<uint8_t>((size_t)B * max_rows * S);
     KREF_CHECK(b);
-    const bool launched = launch_align_dtw(dM, (long)max_rows * S, S, dr, dn, P, max_rows, S, B, 0, trace, (long)max_rows * S, df, dl, ldo, st.s);
+    const bool launched = launch_align_dtw(dM, (long)max_rows * S, S, dr, dn, P, max_rows, S, B, 0, trace, (long)max_rows * S, df, dl, ldo, nullptr, st.s);
     if (hipError_t e = st.finish()) return (int)e;
     b.out(first, df, (size_t)B * ldo * 4);
     b.out(last, dl, (size_t)B * ldo * 4);
+    return launched ? (int)b.err : -1;
+}
+
+}  // extern "C"
+
+// ---- alignment from the decode (k_align.hip: the capture kernel, the row map of the three stage launchers) -------------------
+extern "C" {
+
+// launch_align_qsave_rows for the heads `heads` (i32 [n], slots 0 .. n - 1) of one layer: dq fp16 [B][d], qlive fp16
+// [n][npos][ldb][64] copied in and back, pos_ptr i32 [B] or null (then `pos`), done i32 [B] or null
+int kref_align_qsave_rows(const void *dq, void *qlive, const int32_t *heads, int n, int B, int ldb, int d, int pos, const int32_t *pos_ptr,
+                          const int32_t *done, int npos) {
+    if (n < 1 || n > NH_ALIGN_HEADS || B < 1 || B > ldb || npos < 1 || d < NH_DH) return -1;
+    AlignLayerHeads lh{};
+    for (int i = 0; i < n; i++) {
+        if (heads[i] < 0 || (heads[i] + 1) * NH_DH > d) return -1;
+        lh.slot[i] = i; lh.head[i] = heads[i];
+    }
+    lh.n = n;
+    Bufs b;
+    Stream st;
+    const size_t qbytes = (size_t)n * npos * ldb * NH_DH * 2;
+    const half_t *ddq = b.in<half_t>(dq, (size_t)B * d * 2);
+    half_t *dql = b.in<half_t>(qlive, qbytes);
+    const int32_t *dp = b.in<int32_t>(pos_ptr, (size_t)B * 4), *dd = b.in<int32_t>(done, (size_t)B * 4);
+    KREF_CHECK(b);
+    launch_align_qsave_rows(ddq, dql, lh, B, ldb, d, pos, dp, dd, npos, st.s);
+    if (hipError_t e = st.finish()) return (int)e;
+    b.out(qlive, dql, qbytes);
+    return (int)b.err;
+}
+
+// The three stage launchers over n clips that read context rows row_map[0 .. n) (i32, every entry in [0, B); null: the
+// identity, n <= B).  Layouts as for kref_align_weights / _reduce / _dtw, the outputs [n]-major.
+int kref_align_weights_rows(const void *q, const void *K, const int32_t *heads, int A, int H, int S, int B, const int32_t *row_map, int n,
+                            const int32_t *n_rows, const int32_t *n_keys, int max_rows, float *W) {
+    if (A < 1 || A > NH_ALIGN_HEADS || B < 1 || n < 1 || max_rows < 1 || S < 1 || (!row_map && n > B)) return -1;
+    for (int a = 0; a < A; a++) if (heads[a] < 0 || heads[a] >= H) return -1;
+    for (int g = 0; g < n; g++)
+        if (n_rows[g] < 0 || n_rows[g] > max_rows || n_keys[g] < 0 || n_keys[g] > S || (row_map && (row_map[g] < 0 || row_map[g] >= B))) return -1;
+    Bufs b;
+    Stream st;
+    const half_t *dq = b.in<half_t>(q, (size_t)A * max_rows * B * NH_DH * 2), *dk = b.in<half_t>(K, (size_t)B * H * S * NH_DH * 2);
+    const int32_t *dr = b.in<int32_t>(n_rows, (size_t)n * 4), *dn = b.in<int32_t>(n_keys, (size_t)n * 4), *dm = b.in<int32_t>(row_map, (size_t)n * 4);
+    const size_t wbytes = (size_t)n * A * max_rows * S * 4;
+    float *dW = b.in<float>(W, wbytes);
+    KREF_CHECK(b);
+    AlignHeadPtrs hp{};
+    for (int a = 0; a < A; a++) { hp.q[a] = dq + (size_t)a * max_rows * B * NH_DH; hp.k[a] = dk + (size_t)heads[a] * S * NH_DH; }
+    const bool launched = launch_align_weights(hp, A, (long)B * NH_DH, NH_DH, (long)H * S * NH_DH, dr, dn, max_rows, S, n, 0, dW,
+                                               (long)A * max_rows * S, (long)max_rows * S, S, dm, st.s);
+    if (hipError_t e = st.finish()) return (int)e;
+    b.out(W, dW, wbytes);
+    return launched ? (int)b.err : -1;
+}
+
+int kref_align_reduce_rows(const float *W, int A, int n, int S, int max_rows, const int32_t *row_map, const int32_t *n_rows, const int32_t *n_keys,
+                           int P, float *M) {
+    if (n < 1 || max_rows < 1 || S < 1 || A < 1) return -1;
+    for (int g = 0; g < n; g++) if (n_rows[g] < 0 || n_rows[g] > max_rows || n_keys[g] < 0 || n_keys[g] > S) return -1;
+    Bufs b;
+    Stream st;
+    const float *dW = b.in<float>(W, (size_t)n * A * max_rows * S * 4);
+    const int32_t *dr = b.in<int32_t>(n_rows, (size_t)n * 4), *dn = b.in<int32_t>(n_keys, (size_t)n * 4), *dm = b.in<int32_t>(row_map, (size_t)n * 4);
+    const size_t mbytes = (size_t)n * max_rows * S * 4;
+    float *dM = b.in<float>(M, mbytes);
+    float *stats = b.zeros<float>((size_t)n * A * 2 * S * 4);
+    KREF_CHECK(b);
+    const bool launched = launch_align_reduce(dW, (long)A * max_rows * S, (long)max_rows * S, S, dr, dn, max_rows, S, n, 0, A, P, stats, dM,
+                                              (long)max_rows * S, S, dm, st.s);
+    if (hipError_t e = st.finish()) return (int)e;
+    b.out(M, dM, mbytes);
+    return launched ? (int)b.err : -1;
+}
+
+int kref_align_dtw_rows(const float *M, int n, int S, int max_rows, const int32_t *row_map, const int32_t *n_rows, const int32_t *n_keys, int P,
+                        int32_t *first, int32_t *last, int ldo) {
+    if (n < 1 || max_rows < 1 || S < 1) return -1;
+    for (int g = 0; g < n; g++) if (n_rows[g] < 0 || n_rows[g] > max_rows || n_keys[g] < 0 || n_keys[g] > S) return -1;
+    Bufs b;
+    Stream st;
+    const float *dM = b.in<float>(M, (size_t)n * max_rows * S * 4);
+    const int32_t *dr = b.in<int32_t>(n_rows, (size_t)n * 4), *dn = b.in<int32_t>(n_keys, (size_t)n * 4), *dm = b.in<int32_t>(row_map, (size_t)n * 4);
+    int32_t *df = b.in<int32_t>(first, (size_t)n * ldo * 4), *dl = b.in<int32_t>(last, (size_t)n * ldo * 4);
+    uint8_t *trace = b.zeros<uint8_t>((size_t)n * max_rows * S);
+    KREF_CHECK(b);
+    const bool launched = launch_align_dtw(dM, (long)max_rows * S, S, dr, dn, P, max_rows, S, n, 0, trace, (long)max_rows * S, df, dl, ldo, dm, st.s);
+    if (hipError_t e = st.finish()) return (int)e;
+    b.out(first, df, (size_t)n * ldo * 4);
+    b.out(last, dl, (size_t)n * ldo * 4);
     return launched ? (int)b.err : -1;
 }
 
