@@ -8,23 +8,12 @@
 #include "nh_kernels.h"
 
 // ---- q capture ------------------------------------------------------------------------------------------------------------
-// dq [B][d] (the cross-attention query of one layer at one position) -> qsave[a][pos][b][64] for the n heads of that layer
-__global__ __launch_bounds__(64) void align_qsave_kernel(const half_t *dq, half_t *qsave, AlignLayerHeads lh, int B, int d, int pos, int npos) {
-    const int b = blockIdx.x, i = blockIdx.y;
-    const int a = lh.slot[i], h = lh.head[i];
-    qsave[(((long)a * npos + pos) * B + b) * NH_DH + threadIdx.x] = dq[(long)b * d + h * NH_DH + threadIdx.x];
-}
-
-void launch_align_qsave(const half_t *dq, half_t *qsave, const AlignLayerHeads &lh, int B, int d, int pos, int npos, hipStream_t st) {
-    if (lh.n < 1 || B < 1) return;
-    hipLaunchKernelGGL(align_qsave_kernel, dim3(B, lh.n), dim3(64), 0, st, dq, qsave, lh, B, d, pos, npos);
-}
-
-// The capture of a running decode (nh_align_capture): row b at its own position, read from device memory when the step is a
-// captured graph or a pool step, so the launch bakes in no host position.  qlive[a][pos][b][64] with ldb rows per position.
+// dq [B][d] (the cross-attention query of one layer at one position) -> q[a][pos][b][64] for the n heads of that layer, with
+// ldb rows per position.  Row b goes to its own position, read from device memory when the step is a captured graph or a pool
+// step (the launch then bakes in no host position), to the host's `pos` otherwise (nh_align's pass, eager decode steps).
 // Rows that are not running (done != 0: finished, no-speech exit, empty) and positions outside [0, npos) write nothing.
-__global__ __launch_bounds__(64) void align_qsave_rows_kernel(const half_t *dq, half_t *qlive, AlignLayerHeads lh, int ldb, int d, int pos,
-                                                              const int32_t *pos_ptr, const int32_t *done, int npos) {
+__global__ __launch_bounds__(64) void align_qsave_kernel(const half_t *dq, half_t *qlive, AlignLayerHeads lh, int ldb, int d, int pos,
+                                                         const int32_t *pos_ptr, const int32_t *done, int npos) {
     const int b = blockIdx.x, i = blockIdx.y;
     if (done && done[b] != 0) return;   // uniform over the workgroup
     const int p = pos_ptr ? pos_ptr[b] : pos;
@@ -33,10 +22,10 @@ __global__ __launch_bounds__(64) void align_qsave_rows_kernel(const half_t *dq, 
     qlive[(((long)a * npos + p) * ldb + b) * NH_DH + threadIdx.x] = dq[(long)b * d + h * NH_DH + threadIdx.x];
 }
 
-void launch_align_qsave_rows(const half_t *dq, half_t *qlive, const AlignLayerHeads &lh, int B, int ldb, int d, int pos, const int32_t *pos_ptr,
-                             const int32_t *done, int npos, hipStream_t st) {
+void launch_align_qsave(const half_t *dq, half_t *qlive, const AlignLayerHeads &lh, int B, int ldb, int d, int pos, const int32_t *pos_ptr,
+                        const int32_t *done, int npos, hipStream_t st) {
     if (lh.n < 1 || B < 1 || B > ldb || npos < 1) return;
-    hipLaunchKernelGGL(align_qsave_rows_kernel, dim3(B, lh.n), dim3(64), 0, st, dq, qlive, lh, ldb, d, pos, pos_ptr, done, npos);
+    hipLaunchKernelGGL(align_qsave_kernel, dim3(B, lh.n), dim3(64), 0, st, dq, qlive, lh, ldb, d, pos, pos_ptr, done, npos);
 }
 
 // ---- weights: W[p][s] = softmax_s(q_p . k_s / 8), s < nk ---------------------------------------------------------------------

@@ -1,6 +1,7 @@
-// nh_ctx.h -- the state behind the C ABI of include/norma_hip.h, shared by the three files that implement it: nh_model.hip
+// nh_ctx.h -- the state behind the C ABI of include/norma_hip.h, shared by the four files that implement it: nh_model.hip
 // (create / destroy, weights, tokens, options, timings), nh_encode.hip (log-mel, encoder), nh_decode.hip (decoder step,
-// lockstep decode, decode pool, parity views).  No torch, no candle, no CPU fallback: an entry point runs the HIP path or fails.
+// lockstep decode, decode pool, parity views), nh_align.hip (token-level timestamps).  No torch, no candle, no CPU fallback:
+// an entry point runs the HIP path or fails.
 #pragma once
 #include <math.h>
 #include <stdio.h>
@@ -99,12 +100,10 @@ struct StepGraphs {
     hipGraphExec_t multi = nullptr; // NH_GRAPH_STEPS consecutive steps (one launch gap instead of NH_GRAPH_STEPS)
 };
 
-// nh_align's device state: allocated by the first nh_align (contexts that never align pay nothing), freed by nh_destroy.
-// The last call's shape is kept for the views (nh_align_weights / nh_align_matrix).
+// The workspace of stages 2 - 6 (nh_align, nh_align_decoded): allocated by the first alignment (contexts that never align pay
+// nothing), freed by nh_destroy.  The last call's shape is kept for the views (nh_align_weights / nh_align_matrix).
 struct AlignState {
     std::vector<void *> allocs;      // everything below; released and re-made when a call needs more
-    size_t bytes = 0;                // what the workspace holds
-    half_t *qsave = nullptr;         // fp16 [heads][C - 1][max_batch][64]; only once nh_align itself has run
     int32_t *n_rows = nullptr, *n_keys = nullptr;   // [max_batch]
     int32_t *row_map = nullptr;                     // [max_batch] context row of every clip of a call (nh_align_decoded on a pool)
     int32_t *first = nullptr, *last = nullptr;      // [max_batch][C + 1]
@@ -117,16 +116,19 @@ struct AlignState {
     std::vector<int32_t> n_tokens, keys;
 };
 
-// nh_align_capture: the alignment heads whose cross-attention queries every decode of the context keeps, and what the
-// context remembers of the last lockstep decode for nh_align_decoded.  A == 0 (the default): the decode step launches nothing
-// for it.  The buffer is allocated by the first call with heads, grown by a call with more, freed by nh_destroy.
-struct AlignLive {
-    half_t *q = nullptr;             // fp16 [cap_heads][C - 1][max_batch][64]
-    int cap_heads = 0;
+// A validated list of alignment heads and its per-layer table (align_head_set, nh_align.hip)
+struct AlignHeadSet {
     int A = 0;
     nh_align_head heads[NH_ALIGN_HEADS];
     std::vector<AlignLayerHeads> layer;   // [decoder_layers] while A > 0; n == 0: no head there
-    int gen = 0;                     // bumped by nh_align_capture (and by options that change what a step computes); in StepKey
+};
+
+// nh_align_capture: the alignment heads whose cross-attention queries every decode of the context keeps, and what the
+// context remembers of the last lockstep decode for nh_align_decoded.  hs.A == 0 (the default): the decode step launches
+// nothing for it.
+struct AlignLive {
+    AlignHeadSet hs;
+    int gen = 0;   // in StepKey; bumped by nh_align_capture, by options that change what a step computes, and when align_q moves
     // the last lockstep decode, while nothing has overwritten what it left: per clip the tokens after the trim and the done flag
     bool lock_valid = false;
     int P = 0;
@@ -182,6 +184,10 @@ struct nh_ctx {
     bool opt_align_keep = false; // NH_OPT_ALIGN_KEEP
     AlignState al;               // nh_align, nh_align_decoded
     AlignLive live;              // nh_align_capture
+    // The context's one query buffer, fp16 [align_q_heads][C - 1][max_batch][64]: nh_align's teacher-forced pass and the decodes
+    // under nh_align_capture both write it, stages 2 - 6 read it.  Grown by align_q_buffer alone, freed by nh_destroy.
+    half_t *align_q = nullptr;
+    int align_q_heads = 0;
     int dec_layer_limit = 0;    // parity view (NH_OPT_DECODER_LAYER_LIMIT): run only the first n decoder blocks; 0 = all
     std::vector<int32_t> seq_lang;  // per-sequence language tokens (LanguageState::Detect), empty = tk.lang for all
     int32_t *d_lang_tokens = nullptr, *d_lang_out = nullptr;
@@ -218,4 +224,6 @@ template <typename T>
 static T *dalloc(nh_ctx *ctx, size_t n, bool zero = true) { return dalloc_into<T>(ctx->allocs, n, zero); }
 
 void drop_graphs(nh_ctx *ctx, int first = 0);   // nh_decode.hip
+void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr = nullptr, bool final_ln = true, bool skip_done = false,
+                  const AlignHeadSet *keep = nullptr);   // nh_decode.hip
 int ensure_decoder_repack(nh_ctx *ctx);         // nh_model.hip

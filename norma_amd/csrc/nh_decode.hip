@@ -1,5 +1,5 @@
 // nh_decode.hip -- the C ABI of include/norma_hip.h, part 3: the decoder step and what sequences it -- the lockstep decode,
-// the decode pool, language detection and the parity views.
+// the decode pool, language detection and the parity views.  Token-level timestamps (nh_align.hip) come here for decoder_step.
 #include "nh_ctx.h"
 
 // ---- decoder ---------------------------------------------------------------------------------------------
@@ -53,13 +53,10 @@ static void ln_skinny(nh_ctx *ctx, const LnW &ln, const LinW &W, int R, int N, i
 // final_ln: also LN(dx) -> dxn (fp16) / dy32 (f32) (the teacher-forced view; the step path fuses it into the logits).
 // pos_ptr != nullptr: the position comes from device memory (the step is being captured into a hipGraph).
 // skip_done: finished sequences skip their attention (only inside decode_impl, where ds.done is live).
-// cap (nh_align only): the layers that hold alignment heads copy those heads' cross-attention query of every row to
-// cap->qsave[head][pos][row][64] right after the projection; nullptr (every other caller): nothing is added to the step.
-// ctx->live (nh_align_capture), inside a decode only (skip_done): the same copy for the running rows, each at its own position,
-// into ctx->live.q; no heads set (the default): nothing is added to the step either.
-struct AlignCapture { half_t *qsave; int npos; std::vector<AlignLayerHeads> layer; };   // layer: [decoder_layers], n == 0: no head there
-static void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr = nullptr, bool final_ln = true, bool skip_done = false,
-                         const AlignCapture *cap = nullptr) {
+// keep (nh_align's pass; a decode under nh_align_capture): the layers that hold alignment heads copy those heads' cross-attention
+// query to ctx->align_q[head][pos][row][64] right after the projection, every row at the position and under the done flag the
+// step itself goes by; nullptr (every other caller, and a decode with no heads set): nothing is added to the step.
+void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr, bool final_ln, bool skip_done, const AlignHeadSet *keep) {
     const int32_t *done = skip_done ? ctx->ds.done : nullptr;
     const nh_model &m = *ctx->mdl;
     const int d = ctx->c.d_model, B = ctx->pool.rows > 0 ? ctx->pool.rows : ctx->cur_batch, H = ctx->c.decoder_attention_heads, C = ctx->c.max_target_positions;
@@ -72,9 +69,7 @@ static void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr = nullptr,
         launch_dec_attention(ctx->dq, kv.sk, kv.sv, ctx->datt, B, 1, H, d, C, pos + 1, pos_ptr, ctx->st, 1, done);  // head-major cache
         skinny(ctx, ctx->datt, d, L.o, B, d, d, SK_RESID_F32, ctx->dx, nullptr, nullptr, d, 0, C);
         ln_skinny(ctx, L.ln2, L.cq, B, d, d, SK_F16, ctx->dq, nullptr, nullptr, d, 0, C, nullptr);
-        if (cap && cap->layer[l].n) launch_align_qsave(ctx->dq, cap->qsave, cap->layer[l], B, d, pos, cap->npos, ctx->st);
-        if (skip_done && ctx->live.A > 0 && ctx->live.layer[l].n)
-            launch_align_qsave_rows(ctx->dq, ctx->live.q, ctx->live.layer[l], B, ctx->B, d, pos, pos_ptr, done, C - 1, ctx->st);
+        if (keep && keep->layer[l].n) launch_align_qsave(ctx->dq, ctx->align_q, keep->layer[l], B, ctx->B, d, pos, pos_ptr, done, C - 1, ctx->st);
         if (ctx->opt_absorbed == 2) launch_xabs_attention_fast(ctx->dq, L.ckv.wt, L.ckv.w, L.ckv.b, ctx->xa16, ctx->xabs_u, ctx->xabs_z, ctx->xabs_ml, ctx->datt, B, H, d, ctx->S, done, ctx->st);
         else if (ctx->opt_absorbed) launch_xabs_attention(ctx->dq, L.ckv.w, L.ckv.b, ctx->xa16, ctx->xabs_u, ctx->datt, B, H, d, ctx->S, done, ctx->st);
         else launch_dec_attention(ctx->dq, kv.ck, kv.cv, ctx->datt, B, 1, H, d, ctx->S, ctx->S, nullptr, ctx->st, 1, done);  // head-major cross K/V
@@ -149,10 +144,13 @@ struct StepSpec {
     int32_t *pos_ptr;          // device-side positions, read and advanced by the step (pools, captured steps)
     float inv_t; unsigned long long seed; unsigned clip0, attempt;   // lockstep sampling (nh_decode_sampled)
 };
+// the heads whose queries the context's decodes keep (nh_align_capture); nullptr: none
+static const AlignHeadSet *kept_heads(const nh_ctx *ctx) { return ctx->live.hs.A > 0 ? &ctx->live.hs : nullptr; }
+
 static void emit_token_step(nh_ctx *ctx, const StepSpec &s) {
     const int C = ctx->c.max_target_positions, cap = C - 1, V = ctx->c.vocab_size;
     const bool pool = s.mode == 2;
-    decoder_step(ctx, s.pos, s.pos_ptr, false, true);
+    decoder_step(ctx, s.pos, s.pos_ptr, false, true, kept_heads(ctx));
     logits_from_dx(ctx, s.B);
     if (pool && ctx->pool.lang_n > 0)
         launch_pool_lang_detect(ctx->logits, V, ctx->ds, s.B, C, s.pos_ptr, PoolDetect{ctx->d_lang_flag, ctx->d_lang_tokens, ctx->pool.lang_n, ctx->d_lang_out, ctx->d_lang_probs}, ctx->st);
@@ -237,7 +235,7 @@ static int decode_impl(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *resul
     // Prompt phase (eager): position pos consumes tokens[pos]; pos 0 also yields no_speech_prob
     // (model.rs:293-305: logits at position 0 of the flush = true pass).
     for (int pos = 0; pos < P - 1; pos++) {
-        decoder_step(ctx, pos, nullptr, true, true);
+        decoder_step(ctx, pos, nullptr, true, true, kept_heads(ctx));
         steps++;
         if (pos == 0) {
             logits_from_dxn(ctx, B);
@@ -279,7 +277,7 @@ static int decode_impl(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *resul
     HIPCHK(hipGetLastError());
     if (int rc = read_results(ctx, nullptr, B, out_tokens, results)) return rc;
     ctx->tm.decode_steps = steps;
-    ctx->live.lock_valid = ctx->live.A > 0; ctx->live.P = P;
+    ctx->live.lock_valid = kept_heads(ctx) != nullptr; ctx->live.P = P;
     return NH_OK;
 }
 
@@ -434,7 +432,7 @@ extern "C" int nh_pool_collect(nh_ctx *ctx, const int32_t *rows, int n, int32_t 
     hipSetDevice(ctx->dev);
     if (int rc = read_results(ctx, rows, n, out_tokens, results)) return rc;
     // heads cannot change while a row is busy (nh_align_capture refuses), so the whole decode ran under the current list
-    for (int i = 0; i < n; i++) { PoolRow &r = ctx->pool.row[rows[i]]; r.busy = false; r.sampled = false; r.align_gen = ctx->live.A > 0 ? ctx->live.gen : -1; }
+    for (int i = 0; i < n; i++) { PoolRow &r = ctx->pool.row[rows[i]]; r.busy = false; r.sampled = false; r.align_gen = kept_heads(ctx) ? ctx->live.gen : -1; }
     return NH_OK;
 }
 
@@ -616,285 +614,4 @@ extern "C" int nh_apply_rules(nh_ctx *ctx, const float *probs, const int32_t *to
     if (tmp_out) hipFree(tmp_out);
     HIPCHK(hipGetLastError());
     return NH_OK;
-}
-
-// ---- token-level timestamps (contract: include/norma_hip.h, nh_align; kernels: k_align.hip) ----------------------------------
-static_assert(NH_ALIGN_HEADS == NH_ALIGN_MAX_HEADS, "nh_kernels.h and norma_hip.h disagree");
-#define NH_ALIGN_BUDGET ((size_t)256 << 20)   // workspace of a call under NH_OPT_ALIGN_KEEP = 0
-
-// The workspace for A heads and groups of `group` clips, made again when the shape differs from what is held.
-// want_q: the caller is nh_align, whose teacher-forced pass needs qsave; nh_align_decoded reads the context's live buffer, and a
-// context that only ever aligns what it decoded never holds a second query buffer.
-static int align_workspace(nh_ctx *ctx, int A, int group, bool want_q) {
-    AlignState &al = ctx->al;
-    const int S = ctx->S;
-    // kept whenever it is large enough: the rows a pool hands back differ from collect to collect, and making it again costs a
-    // stream synchronise and device-wide hipFree / hipMalloc pairs on the path the pool exists for
-    if (al.heads == A && al.group >= group && al.S == S && (al.qsave || !want_q)) return NH_OK;
-    want_q = want_q || al.qsave;
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    for (void *p : al.allocs) hipFree(p);
-    al = AlignState{};
-    const size_t C = ctx->c.max_target_positions, NP = C - 1, B = ctx->B;
-    if (want_q) al.qsave = dalloc_into<half_t>(al.allocs, (size_t)A * NP * B * NH_DH, false);
-    al.n_rows = dalloc_into<int32_t>(al.allocs, B);
-    al.n_keys = dalloc_into<int32_t>(al.allocs, B);
-    al.row_map = dalloc_into<int32_t>(al.allocs, B);
-    al.first = dalloc_into<int32_t>(al.allocs, B * (C + 1));
-    al.last = dalloc_into<int32_t>(al.allocs, B * (C + 1));
-    al.W = dalloc_into<float>(al.allocs, (size_t)group * A * NP * S, false);
-    al.stats = dalloc_into<float>(al.allocs, (size_t)group * A * 2 * S, false);
-    al.M = dalloc_into<float>(al.allocs, (size_t)group * C * S, false);
-    al.trace = dalloc_into<uint8_t>(al.allocs, (size_t)group * C * S, false);
-    if ((want_q && !al.qsave) || !al.n_rows || !al.n_keys || !al.row_map || !al.first || !al.last || !al.W || !al.stats || !al.M || !al.trace) {
-        for (void *p : al.allocs) hipFree(p);
-        al = AlignState{};
-        (void)hipGetLastError();
-        return ctx->fail(NH_ERR_NOMEM, "nh_align: the workspace for " + std::to_string(group) + " clips x " + std::to_string(A) +
-                                           " heads does not fit (NH_OPT_ALIGN_KEEP = 1 holds the whole batch)");
-    }
-    al.heads = A; al.group = group; al.S = S;
-    return NH_OK;
-}
-
-// The workspace of a call over n clips: the clips of a group share it; a group's size is the same for every call of the same
-// heads, and no kernel mixes clips, so grouping never shows in the results.
-static int align_prepare(nh_ctx *ctx, int A, int n, bool want_q) {
-    const size_t C = ctx->c.max_target_positions, NP = C - 1, S = ctx->S;
-    const size_t fixed = (size_t)A * NP * ctx->B * NH_DH * sizeof(half_t) + (size_t)ctx->B * (2 * (C + 1) + 2) * sizeof(int32_t);
-    const size_t per_clip = ((size_t)A * NP + 2 * A + C) * S * sizeof(float) + (size_t)C * S;
-    if (ctx->pool.rows > 0) n = ctx->pool.rows;   // a pool's calls name 1 .. rows rows: sized once for all of them
-    int group = n;
-    if (!ctx->opt_align_keep) {
-        const size_t room = NH_ALIGN_BUDGET > fixed ? NH_ALIGN_BUDGET - fixed : 0;
-        group = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, room / per_clip));
-    }
-    return align_workspace(ctx, A, group, want_q);
-}
-
-// Stages 2 - 6 for the n clips whose rows and keys al.n_rows / al.n_keys hold, a group at a time, and the paths back to the
-// host.  hp / q_pos_stride: where the queries are (nh_align's qsave or the live buffer); row_map: device i32 [n] or nullptr.
-static int align_stages(nh_ctx *ctx, const char *who, const AlignHeadPtrs &hp, int A, int P, long q_pos_stride, int n, const int32_t *row_map,
-                        int32_t *out_first, int32_t *out_last) {
-    AlignState &al = ctx->al;
-    const int C = ctx->c.max_target_positions, S = ctx->S, H = ctx->c.decoder_attention_heads, NP = C - 1, group = al.group;
-    const long wcs = (long)A * NP * S, whs = (long)NP * S, mcs = (long)C * S;
-    for (int c0 = 0; c0 < n; c0 += group) {
-        const int nc = std::min(group, n - c0);
-        bool ok = launch_align_weights(hp, A, q_pos_stride, NH_DH, (long)H * S * NH_DH, al.n_rows, al.n_keys, NP, S, nc, c0, al.W, wcs, whs, S, row_map, ctx->st);
-        ok = ok && launch_align_reduce(al.W, wcs, whs, S, al.n_rows, al.n_keys, NP, S, nc, c0, A, P, al.stats, al.M, mcs, S, row_map, ctx->st);
-        ok = ok && launch_align_dtw(al.M, mcs, S, al.n_rows, al.n_keys, P, NP, S, nc, c0, al.trace, mcs, al.first, al.last, C + 1, row_map, ctx->st);
-        if (!ok) return ctx->fail(NH_ERR_INVALID, std::string(who) + ": the alignment kernels do not cover this model's shape (S <= 1536, max_target_positions <= 512)");
-    }
-    std::vector<int32_t> fl((size_t)2 * n * (C + 1));
-    HIPCHK(hipMemcpyAsync(fl.data(), al.first, (size_t)n * (C + 1) * 4, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipMemcpyAsync(fl.data() + (size_t)n * (C + 1), al.last, (size_t)n * (C + 1) * 4, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    HIPCHK(hipGetLastError());
-    for (int b = 0; b < n; b++) {
-        memcpy(out_first + (size_t)b * C, fl.data() + (size_t)b * (C + 1), sizeof(int32_t) * C);
-        memcpy(out_last + (size_t)b * C, fl.data() + (size_t)(n + b) * (C + 1), sizeof(int32_t) * C);
-    }
-    return NH_OK;
-}
-
-extern "C" int nh_align(nh_ctx *ctx, const int32_t *tokens, const int32_t *n_tokens, int prompt_len, const nh_align_head *heads,
-                        int n_heads, const int32_t *n_keys, int32_t *out_first, int32_t *out_last) {
-    if (!ctx || !tokens || !n_tokens || !heads || !out_first || !out_last) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_align: bad arguments") : NH_ERR_INVALID;
-    if (ctx->pool.rows > 0) return ctx->fail(NH_ERR_STATE, "nh_align: the context runs a decode pool (nh_pool_begin)");
-    if (!ctx->have_enc) return ctx->fail(NH_ERR_STATE, "nh_align: call nh_encode first");
-    if (ctx->opt_absorbed) return ctx->fail(NH_ERR_STATE, "nh_align: NH_OPT_ABSORBED_XATTN keeps no cross K cache to align against");
-    const int B = ctx->cur_batch, C = ctx->c.max_target_positions, V = ctx->c.vocab_size, S = ctx->S;
-    const int H = ctx->c.decoder_attention_heads, NL = ctx->dec_layer_limit > 0 ? ctx->dec_layer_limit : ctx->c.decoder_layers;
-    const int A = n_heads, P = prompt_len, NP = C - 1;
-    if (A < 1 || A > NH_ALIGN_MAX_HEADS) return ctx->fail(NH_ERR_INVALID, "nh_align: n_heads outside 1 .. NH_ALIGN_MAX_HEADS");
-    for (int a = 0; a < A; a++)
-        if (heads[a].layer < 0 || heads[a].layer >= NL || heads[a].head < 0 || heads[a].head >= H)
-            return ctx->fail(NH_ERR_INVALID, "nh_align: alignment head " + std::to_string(a) + " names a layer or head the decoder does not run");
-    if (P < 1 || P >= C) return ctx->fail(NH_ERR_INVALID, "nh_align: prompt_len out of range");
-    int maxn = 0;
-    std::vector<int32_t> toks((size_t)B * C, 0), rows(B), keys(B);
-    for (int b = 0; b < B; b++) {
-        const int n = n_tokens[b], nk = n_keys ? n_keys[b] : S;
-        if (n <= P || n > C) return ctx->fail(NH_ERR_INVALID, "nh_align: n_tokens must lie in (prompt_len, max_target_positions]");
-        if (nk < 1 || nk > S) return ctx->fail(NH_ERR_INVALID, "nh_align: n_keys must lie in [1, S]");
-        for (int i = 0; i < n; i++) {
-            const int t = tokens[(size_t)b * C + i];
-            if (t < 0 || t >= V) return ctx->fail(NH_ERR_INVALID, "nh_align: token id outside the vocabulary");
-            toks[(size_t)b * C + i] = t;
-        }
-        rows[b] = n - 1; keys[b] = nk;
-        maxn = std::max(maxn, n);
-    }
-    hipSetDevice(ctx->dev);
-    if (int rc = ensure_decoder_repack(ctx)) return rc;
-    if (int rc = align_prepare(ctx, A, B, true)) return rc;
-    AlignState &al = ctx->al;
-    al.kept = false;
-    ctx->live.lock_valid = false;   // the pass below overwrites the tokens and self K/V the last decode left
-    AlignCapture cap{al.qsave, NP, std::vector<AlignLayerHeads>(ctx->c.decoder_layers)};
-    AlignHeadPtrs hp{};
-    for (int a = 0; a < A; a++) {
-        AlignLayerHeads &lh = cap.layer[heads[a].layer];
-        lh.slot[lh.n] = a; lh.head[lh.n] = heads[a].head; lh.n++;
-        hp.q[a] = al.qsave + (size_t)a * NP * B * NH_DH;
-        hp.k[a] = ctx->kv[heads[a].layer].ck + (size_t)heads[a].head * S * NH_DH;
-    }
-    HIPCHK(hipStreamWaitEvent(ctx->st, ctx->enc_done, 0));
-    HIPCHK(hipMemcpyAsync(ctx->ds.tokens, toks.data(), toks.size() * 4, hipMemcpyHostToDevice, ctx->st));
-    HIPCHK(hipMemcpyAsync(al.n_rows, rows.data(), B * 4, hipMemcpyHostToDevice, ctx->st));
-    HIPCHK(hipMemcpyAsync(al.n_keys, keys.data(), B * 4, hipMemcpyHostToDevice, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));   // host buffers of this frame
-    // stage 1: the teacher-forced pass, every position enqueued back to back
-    for (int pos = 0; pos <= maxn - 2; pos++) decoder_step(ctx, pos, nullptr, false, false, &cap);
-    // stages 2 - 6, a group of clips at a time
-    if (int rc = align_stages(ctx, "nh_align", hp, A, P, (long)B * NH_DH, B, nullptr, out_first, out_last)) return rc;
-    al.kept = ctx->opt_align_keep; al.P = P; al.A = A;
-    al.n_tokens.assign(n_tokens, n_tokens + B); al.keys = keys;
-    return NH_OK;
-}
-
-// ---- alignment from the decode itself (contract: include/norma_hip.h, nh_align_capture / nh_align_decoded) -------------------
-extern "C" int nh_align_capture(nh_ctx *ctx, const nh_align_head *heads, int n_heads) {
-    if (!ctx || (n_heads > 0 && !heads)) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_align_capture: bad arguments") : NH_ERR_INVALID;
-    const int A = n_heads, H = ctx->c.decoder_attention_heads, NL = ctx->dec_layer_limit > 0 ? ctx->dec_layer_limit : ctx->c.decoder_layers;
-    if (A < 0 || A > NH_ALIGN_MAX_HEADS) return ctx->fail(NH_ERR_INVALID, "nh_align_capture: n_heads outside 0 .. NH_ALIGN_MAX_HEADS");
-    for (int a = 0; a < A; a++)
-        if (heads[a].layer < 0 || heads[a].layer >= NL || heads[a].head < 0 || heads[a].head >= H)
-            return ctx->fail(NH_ERR_INVALID, "nh_align_capture: alignment head " + std::to_string(a) + " names a layer or head the decoder does not run");
-    if (A > 0 && ctx->opt_absorbed) return ctx->fail(NH_ERR_STATE, "nh_align_capture: NH_OPT_ABSORBED_XATTN keeps no cross K cache to align against");
-    for (const PoolRow &r : ctx->pool.row)
-        if (ctx->pool.rows > 0 && r.busy) return ctx->fail(NH_ERR_STATE, "nh_align_capture: rows are busy (the head list is part of the captured steps)");
-    AlignLive &lv = ctx->live;
-    hipSetDevice(ctx->dev);
-    if (A > lv.cap_heads) {
-        HIPCHK(hipStreamSynchronize(ctx->st));   // a finished decode may still be copying into the buffer that goes
-        half_t *q = nullptr;
-        if (hipMalloc(reinterpret_cast<void **>(&q), (size_t)A * (ctx->c.max_target_positions - 1) * ctx->B * NH_DH * sizeof(half_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            return ctx->fail(NH_ERR_NOMEM, "nh_align_capture: hipMalloc failed");
-        }
-        if (lv.q) hipFree(lv.q);
-        lv.q = q; lv.cap_heads = A;
-    }
-    lv.A = A;
-    lv.layer.assign(A > 0 ? ctx->c.decoder_layers : 0, AlignLayerHeads{});
-    for (int a = 0; a < A; a++) {
-        lv.heads[a] = heads[a];
-        AlignLayerHeads &lh = lv.layer[heads[a].layer];
-        lh.slot[lh.n] = a; lh.head[lh.n] = heads[a].head; lh.n++;
-    }
-    // what was kept under the list before is no longer answered for; the step graphs of that list are stale (StepKey)
-    lv.gen++; lv.lock_valid = false;
-    return NH_OK;
-}
-
-extern "C" int nh_align_decoded(nh_ctx *ctx, const int32_t *rows, int n, const int32_t *n_keys, int32_t *out_first, int32_t *out_last) {
-    if (!ctx || !out_first || !out_last) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_align_decoded: bad arguments") : NH_ERR_INVALID;
-    AlignLive &lv = ctx->live;
-    const bool pool = ctx->pool.rows > 0;
-    const int C = ctx->c.max_target_positions, S = ctx->S, NP = C - 1, A = lv.A;
-    const int NL = ctx->dec_layer_limit > 0 ? ctx->dec_layer_limit : ctx->c.decoder_layers;
-    if (pool && !rows) return ctx->fail(NH_ERR_INVALID, "nh_align_decoded: the context runs a decode pool: name the rows");
-    if (!pool && rows) return ctx->fail(NH_ERR_INVALID, "nh_align_decoded: rows are a decode pool's; a lockstep context aligns its whole batch (rows = NULL)");
-    if (pool) {
-        if (n < 1 || n > ctx->pool.rows) return ctx->fail(NH_ERR_INVALID, "nh_align_decoded: n must lie in [1, rows of the pool]");
-        for (int i = 0; i < n; i++)
-            if (rows[i] < 0 || rows[i] >= ctx->pool.rows) return ctx->fail(NH_ERR_INVALID, "nh_align_decoded: row outside the pool");
-    } else if (lv.lock_valid && n != (int)lv.n.size()) return ctx->fail(NH_ERR_INVALID, "nh_align_decoded: n is not the batch of the last decode");
-    if (A < 1) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: no alignment heads are set (nh_align_capture)");
-    if (ctx->opt_absorbed) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: NH_OPT_ABSORBED_XATTN keeps no cross K cache to align against");
-    for (int a = 0; a < A; a++)
-        if (lv.heads[a].layer >= NL) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: NH_OPT_DECODER_LAYER_LIMIT cut an alignment head's layer off");
-    if (!pool && !lv.lock_valid) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: no decode under these alignment heads whose state is still in place");
-    std::vector<int32_t> nrows(n), keys(n), ntok(n);
-    for (int i = 0; i < n; i++) {
-        int nt, done;
-        if (pool) {
-            const PoolRow &r = ctx->pool.row[rows[i]];
-            if (r.busy) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: that row is busy (nh_pool_collect hands it back first)");
-            if (!r.held) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: no clip was admitted into that row since nh_pool_begin");
-            if (r.align_gen != lv.gen) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: that row has not been collected since it was admitted or retried under the current alignment heads");
-            nt = r.n; done = r.done;
-        } else { nt = lv.n[i]; done = lv.done[i]; }
-        const int nk = n_keys ? n_keys[i] : S;
-        if (nk < 1 || nk > S) return ctx->fail(NH_ERR_INVALID, "nh_align_decoded: n_keys must lie in [1, S]");
-        const int P = pool ? ctx->pool.prompt : lv.P;
-        const bool nothing = done == 2 || nt <= P || nt > C;   // the no-speech exit holds the prompt alone
-        ntok[i] = nothing ? 0 : nt; nrows[i] = nothing ? 0 : nt - 1; keys[i] = nk;
-    }
-    const int P = pool ? ctx->pool.prompt : lv.P;
-    hipSetDevice(ctx->dev);
-    if (int rc = align_prepare(ctx, A, n, false)) return rc;
-    AlignState &al = ctx->al;
-    al.kept = false;
-    AlignHeadPtrs hp{};
-    for (int a = 0; a < A; a++) {
-        hp.q[a] = lv.q + (size_t)a * NP * ctx->B * NH_DH;
-        hp.k[a] = ctx->kv[lv.heads[a].layer].ck + (size_t)lv.heads[a].head * S * NH_DH;
-    }
-    HIPCHK(hipMemcpyAsync(al.n_rows, nrows.data(), n * 4, hipMemcpyHostToDevice, ctx->st));
-    HIPCHK(hipMemcpyAsync(al.n_keys, keys.data(), n * 4, hipMemcpyHostToDevice, ctx->st));
-    if (pool) HIPCHK(hipMemcpyAsync(al.row_map, rows, n * 4, hipMemcpyHostToDevice, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));   // host buffers of this frame (and the caller's rows)
-    if (int rc = align_stages(ctx, "nh_align_decoded", hp, A, P, (long)ctx->B * NH_DH, n, pool ? al.row_map : nullptr, out_first, out_last)) return rc;
-    al.kept = ctx->opt_align_keep; al.P = P; al.A = A;
-    al.n_tokens = ntok; al.keys = keys;
-    return NH_OK;
-}
-
-// rows x nk floats out of a workspace image with row stride S
-static int align_view(nh_ctx *ctx, const float *src, int nrows, int nk, float *out) {
-    hipSetDevice(ctx->dev);
-    HIPCHK(hipMemcpy2DAsync(out, (size_t)nk * 4, src, (size_t)ctx->al.S * 4, (size_t)nk * 4, nrows, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    return NH_OK;
-}
-
-extern "C" int nh_align_weights(nh_ctx *ctx, int b, int a, float *out) {
-    if (!ctx || !out) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_align_weights: bad arguments") : NH_ERR_INVALID;
-    const AlignState &al = ctx->al;
-    if (!al.kept) return ctx->fail(NH_ERR_STATE, "nh_align_weights: no alignment under NH_OPT_ALIGN_KEEP = 1 to look at");
-    if (b < 0 || b >= (int)al.n_tokens.size() || a < 0 || a >= al.A) return ctx->fail(NH_ERR_INVALID, "nh_align_weights: clip or head out of range");
-    if (al.n_tokens[b] < 1) return ctx->fail(NH_ERR_STATE, "nh_align_weights: that sequence had nothing to align (no-speech exit)");
-    const size_t NP = ctx->c.max_target_positions - 1;
-    return align_view(ctx, al.W + ((size_t)b * al.A + a) * NP * al.S, al.n_tokens[b] - 1, al.keys[b], out);
-}
-
-extern "C" int nh_align_matrix(nh_ctx *ctx, int b, float *out) {
-    if (!ctx || !out) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_align_matrix: bad arguments") : NH_ERR_INVALID;
-    const AlignState &al = ctx->al;
-    if (!al.kept) return ctx->fail(NH_ERR_STATE, "nh_align_matrix: no alignment under NH_OPT_ALIGN_KEEP = 1 to look at");
-    if (b < 0 || b >= (int)al.n_tokens.size()) return ctx->fail(NH_ERR_INVALID, "nh_align_matrix: clip out of range");
-    if (al.n_tokens[b] < 1) return ctx->fail(NH_ERR_STATE, "nh_align_matrix: that sequence had nothing to align (no-speech exit)");
-    return align_view(ctx, al.M + (size_t)b * ctx->c.max_target_positions * al.S, al.n_tokens[b] - al.P, al.keys[b], out);
-}
-
-extern "C" int nh_align_path(nh_ctx *ctx, const float *matrix, int R, int nk, int32_t *out_first, int32_t *out_last) {
-    if (!ctx || !matrix || !out_first || !out_last) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_align_path: bad arguments") : NH_ERR_INVALID;
-    const int Smax = ctx->S > 0 ? ctx->S : ctx->c.max_source_positions;
-    if (R < 1 || R > ctx->c.max_target_positions || nk < 1 || nk > Smax) return ctx->fail(NH_ERR_INVALID, "nh_align_path: R or nk out of range");
-    hipSetDevice(ctx->dev);
-    // a parity view with buffers of its own: the workspace of the last nh_align (and its views) stays as it is
-    std::vector<void *> tmp;
-    float *M = dalloc_into<float>(tmp, (size_t)R * nk, false);
-    uint8_t *trace = dalloc_into<uint8_t>(tmp, (size_t)R * nk, false);
-    int32_t *meta = dalloc_into<int32_t>(tmp, 2 + 2 * (size_t)(R + 1));   // n_rows, n_keys, first [R + 1], last [R + 1]
-    auto done = [&](int rc) { for (void *p : tmp) hipFree(p); return rc; };
-    if (!M || !trace || !meta) return done(ctx->fail(NH_ERR_NOMEM, "nh_align_path: hipMalloc failed"));
-    const int32_t rk[2] = {R, nk};
-    std::vector<int32_t> fl(2 * (size_t)(R + 1));
-    hipError_t e = hipMemcpyAsync(M, matrix, (size_t)R * nk * 4, hipMemcpyHostToDevice, ctx->st);
-    if (e == hipSuccess) e = hipMemcpyAsync(meta, rk, 8, hipMemcpyHostToDevice, ctx->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->st);
-    // prompt_len 1 and n - 1 = R rows: row r of the matrix is token 1 + r
-    if (e == hipSuccess && !launch_align_dtw(M, (long)R * nk, nk, meta, meta + 1, 1, R, nk, 1, 0, trace, (long)R * nk, meta + 2, meta + 2 + (R + 1), R + 1, nullptr, ctx->st))
-        return done(ctx->fail(NH_ERR_INVALID, "nh_align_path: the DTW kernel covers R <= 512"));
-    if (e == hipSuccess) e = hipMemcpyAsync(fl.data(), meta + 2, fl.size() * 4, hipMemcpyDeviceToHost, ctx->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->st);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return done(ctx->fail(NH_ERR_HIP, std::string("nh_align_path: ") + hipGetErrorString(e)));
-    memcpy(out_first, fl.data() + 1, sizeof(int32_t) * R);
-    memcpy(out_last, fl.data() + (R + 1) + 1, sizeof(int32_t) * R);
-    return done(NH_OK);
 }

@@ -332,14 +332,12 @@ void launch_rules_only(const float *probs_in, float *masked_out, int32_t *argmax
 #define NH_ALIGN_HEADS 32   // == NH_ALIGN_MAX_HEADS of the public header
 // q capture: the heads of ONE decoder layer among the alignment heads; slot = the head's index in the caller's list
 struct AlignLayerHeads { int32_t slot[NH_ALIGN_HEADS], head[NH_ALIGN_HEADS]; int n; };
-// dq fp16 [B][d] (cross-attention query of that layer at position pos) -> qsave fp16 [slot][npos][B][64]
-void launch_align_qsave(const half_t *dq, half_t *qsave, const AlignLayerHeads &lh, int B, int d, int pos, int npos, hipStream_t st);
-// The same copy inside a decode (nh_align_capture): every row b < B at its OWN position -- pos_ptr[b] when pos_ptr != nullptr
-// (captured steps, pools: nothing of the launch depends on a host position), the host `pos` otherwise -- into
-// qlive fp16 [slot][npos][ldb][64], ldb >= B the buffer's rows.  Written only for rows with done[b] == 0 (running; done ==
-// nullptr: every row) at positions in [0, npos): finished and empty rows and positions past the buffer are left alone.
-void launch_align_qsave_rows(const half_t *dq, half_t *qlive, const AlignLayerHeads &lh, int B, int ldb, int d, int pos, const int32_t *pos_ptr,
-                             const int32_t *done, int npos, hipStream_t st);
+// dq fp16 [B][d] (cross-attention query of that layer) -> q fp16 [slot][npos][ldb][64], ldb >= B the buffer's rows.  Every row
+// b < B at its OWN position: pos_ptr[b] when pos_ptr != nullptr (captured steps, pools: nothing of the launch depends on a host
+// position), the host `pos` otherwise.  Written only for rows with done[b] == 0 (running; done == nullptr: every row) at
+// positions in [0, npos): finished and empty rows and positions past the buffer are left alone.
+void launch_align_qsave(const half_t *dq, half_t *q, const AlignLayerHeads &lh, int B, int ldb, int d, int pos, const int32_t *pos_ptr,
+                        const int32_t *done, int npos, hipStream_t st);
 // Per alignment head a: q[a] + p * q_pos_stride + b * q_clip_stride = the 64 halfs of the query of clip b at position p;
 // k[a] + b * k_clip_stride + s * 64 = key s of clip b (the head's slab of the head-major cross K cache).  16-byte aligned.
 struct AlignHeadPtrs { const half_t *q[NH_ALIGN_HEADS]; const half_t *k[NH_ALIGN_HEADS]; };

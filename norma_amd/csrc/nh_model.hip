@@ -46,7 +46,7 @@ extern "C" void nh_destroy(nh_ctx *ctx) {
     if (ctx->st) hipStreamSynchronize(ctx->st);
     for (void *p : ctx->allocs) hipFree(p);
     for (void *p : ctx->al.allocs) hipFree(p);
-    if (ctx->live.q) hipFree(ctx->live.q);
+    if (ctx->align_q) hipFree(ctx->align_q);
     drop_graphs(ctx);
     if (ctx->h_done) hipHostFree(ctx->h_done);
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);

@@ -1,5 +1,5 @@
 """Alignment from the decode (nh_align_capture / nh_align_decoded): the ctypes signatures of the test-only entry points of
-tools/kref.hip for the capture kernel (launch_align_qsave_rows) and for the row-mapped stage launchers, and a numpy statement
+tools/kref.hip for the capture kernel (launch_align_qsave) and for the row-mapped stage launchers, and a numpy statement
 of what the capture kernel may write."""
 import ctypes as C
 

@@ -445,6 +445,64 @@ def test_refusals(fx):
     hm.align_capture([])
 
 
+def _fresh(fx):
+    """a lockstep context of the fixture's weights that has never aligned (no query buffer yet), the three clips encoded"""
+    h = fx.shared(3)
+    h.set_option(fx.hip.NH_OPT_ALIGN_KEEP, 1)
+    h.logmel_array(fx.clips)
+    h.encode()
+    return h
+
+
+def _align_equals_reference(fx, h, toks, heads):
+    """nh_align of the whole batch on h against the reference context, clip by clip; returns (first, last, views)"""
+    first, last = h.align(toks, prompt_len=P_LEN, heads=heads)
+    views = [[h.align_weights(b, a) for a in range(len(heads))] + [h.align_matrix(b)] for b in range(3)]
+    for b in range(3):
+        rf, rl, rW, rM = fx.reference(b, toks[b], heads)
+        assert first[b].tolist() == rf.tolist() and last[b].tolist() == rl.tolist(), b
+        assert all(same_bits(v, r) for v, r in zip(views[b], rW + [rM])), b
+    return first, last, views
+
+
+def test_nh_align_with_more_heads_moves_the_query_buffer_under_captured_step_graphs(fx):
+    """the context's one query buffer holds 2 heads and the captured steps hold its address when nh_align asks for 3: the
+    buffer moves, what the decode kept is gone (refused, not read), and the next decode captures its steps again and keeps its
+    queries in the new buffer -- same tokens, same log-probs, same times as before the move"""
+    h = _fresh(fx)
+    h.align_capture(HEADS)
+    res = h.decode_greedy(max_new_tokens=MAX_NEW)                       # the step graphs are captured here
+    toks = [r["tokens"] for r in res]
+    f0, l0 = h.align_decoded()
+    _align_equals_reference(fx, h, toks, HEADS_B)
+    _decoded_refused(h, STATE)
+    again = h.decode_greedy(max_new_tokens=MAX_NEW)
+    assert all(_same(a, b) for a, b in zip(res, again))
+    f1, l1 = h.align_decoded()
+    assert np.array_equal(f1, f0) and np.array_equal(l1, l0)
+    for b in range(3):
+        fx.check(h, b, b, toks[b], f1, l1, heads=HEADS)
+    h.close()
+
+
+def test_a_capture_of_fewer_heads_uses_the_buffer_nh_align_made(fx):
+    """the other order: nh_align allocates the buffer for 3 heads, nh_align_capture of 2 heads does not grow it, and the decode
+    keeps its queries there; nh_align over it again gives what it gave the first time"""
+    h = _fresh(fx)
+    toks = [r["tokens"] for r in h.decode_greedy(max_new_tokens=MAX_NEW)]   # no heads set: there is no buffer yet
+    fa, la, va = _align_equals_reference(fx, h, toks, HEADS_B)
+    h.align_capture(HEADS)
+    res = h.decode_greedy(max_new_tokens=MAX_NEW)
+    assert [r["tokens"] for r in res] == toks
+    first, last = h.align_decoded()
+    for b in range(3):
+        fx.check(h, b, b, toks[b], first, last, heads=HEADS)
+    fb, lb, vb = _align_equals_reference(fx, h, toks, HEADS_B)
+    assert np.array_equal(fa, fb) and np.array_equal(la, lb)
+    assert all(same_bits(x, y) for p, q in zip(va, vb) for x, y in zip(p, q))
+    h.close()
+
+
 def test_a_no_speech_exit_has_nothing_to_align():
     """model.rs:308-315: position-0 logits put their mass on the no-speech token -> bare prompt; lockstep and pooled: all -1"""
     from norma_amd import hip, synth

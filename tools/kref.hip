@@ -418,7 +418,7 @@ int kref_align_dtw(const float *M, int B, int S, int max_rows, const int32_t *n_
 // ---- alignment from the decode (k_align.hip: the capture kernel, the row map of the three stage launchers) -------------------
 extern "C" {
 
-// launch_align_qsave_rows for the heads `heads` (i32 [n], slots 0 .. n - 1) of one layer: dq fp16 [B][d], qlive fp16
+// launch_align_qsave for the heads `heads` (i32 [n], slots 0 .. n - 1) of one layer: dq fp16 [B][d], qlive fp16
 // [n][npos][ldb][64] copied in and back, pos_ptr i32 [B] or null (then `pos`), done i32 [B] or null
 int kref_align_qsave_rows(const void *dq, void *qlive, const int32_t *heads, int n, int B, int ldb, int d, int pos, const int32_t *pos_ptr,
                           const int32_t *done, int npos) {
@@ -436,7 +436,7 @@ int kref_align_qsave_rows(const void *dq, void *qlive, const int32_t *heads, int
     half_t *dql = b.in<half_t>(qlive, qbytes);
     const int32_t *dp = b.in<int32_t>(pos_ptr, (size_t)B * 4), *dd = b.in<int32_t>(done, (size_t)B * 4);
     KREF_CHECK(b);
-    launch_align_qsave_rows(ddq, dql, lh, B, ldb, d, pos, dp, dd, npos, st.s);
+    launch_align_qsave(ddq, dql, lh, B, ldb, d, pos, dp, dd, npos, st.s);
     if (hipError_t e = st.finish()) return (int)e;
     b.out(qlive, dql, qbytes);
     return (int)b.err;
