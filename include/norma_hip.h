@@ -21,6 +21,8 @@
  *   nh_set_tokens                 special-token ids + the four vocab masks (monolingual.rs:376-430)
  *   nh_logmel                     audio::pcm_to_mel + Tensor::from_vec + narrow
  *                                 (src/models/whisper/model.rs:74-88)
+ *   nh_resample, nh_logmel_resampled_rows
+ *                                 the capture side's channel mixdown and Sinc resampler (src/lib.rs:172-216)
  *   nh_encode                     Type::encoder_forward (model.rs:168, :455-464)
  *   nh_decode_greedy              Model::decode at t = 0 (model.rs:279-389) including the logit
  *                                 rules (model.rs:212-277), batched, on device
@@ -142,6 +144,47 @@ int nh_logmel(nh_ctx *ctx, const float *pcm, const int32_t *n_samples, int64_t s
 int nh_sample_size(int sample_dtype);
 /* Like nh_logmel, with `pcm` holding samples of type `sample_dtype` (host memory, `stride` SAMPLES between clips). */
 int nh_logmel_samples(nh_ctx *ctx, const void *pcm, int sample_dtype, const int32_t *n_samples, int64_t stride, int batch);
+/* ---- audio ingest: channel mixdown and resampling to 16 kHz on the device --------------------------------
+ * The capture side of the reference mixes the device's channels down to mono and, when the device's rate is not
+ * Model::SAMPLE_RATE, runs a sinc resampler before Model::transcribe sees a sample (src/lib.rs:172-216).  Here a clip is
+ * n_frames frames of `channels` interleaved samples of one NH_SAMPLE_* type at src_hz, and
+ *   1 every sample becomes f32 by the formulas above (nh_logmel_samples)
+ *   2 mono[j] = (s[j][0] + s[j][1] + ...) / (float)channels: f32 additions in channel order, one IEEE division (the
+ *     reference's `x.iter().sum() / channels`; integer input is summed in f32, not in the native type, and cannot overflow)
+ *   3 g = gcd(16000, src_hz), L = 16000 / g, M = src_hz / g.  Output n sits at source position (num0 + n M) / L frames
+ *     (num0: caller-supplied, in units of 1/L frame; 0 for a whole clip): i = floor of it, p = (num0 + n M) mod L, in 64-bit
+ *     integers, and
+ *       y[n] = sum over k = -Wc+1 .. Wc of coef[p][k] * mono[i + k]       one f32 accumulator, fmaf, k ascending
+ *       coef[p][k] = (float)h(p/L - k),  h(u) = c sinc(c u) I0(8.6 sqrt(1 - (u/W)^2)) / I0(8.6) for |u| < W, else 0
+ *       c = 0.92 min(1, L/M), W = 32 / c, Wc = ceil(W), T = 2 Wc taps;  sinc(x) = sin(pi x) / (pi x)
+ *     (a Kaiser-windowed sinc with 32 zero crossings whose cut-off follows the lower of the two rates: stop band at or
+ *     below -87 dB from the target Nyquist frequency on, -3 dB at 7.24 kHz when downsampling); evaluated on the host in
+ *     double, once per src_hz and weight set.  Frames outside [0, n_frames) contribute nothing.
+ *     src_hz == 16000: no filter, y[n] = mono[num0 + n] (T = 0), as the reference skips its resampler at equal rates.
+ * A whole clip yields ceil(n_frames L / M) samples.  A clip's outputs are bit-identical alone or in a batch and from host or
+ * device memory; outputs computed from a window of the clip's frames (num0 shifted accordingly) equal the whole clip's as
+ * long as the window holds every in-range frame within Wc of their positions.
+ * Refused with NH_ERR_INVALID, nothing launched, outputs untouched: unknown sample type; channels outside 1 .. 8; src_hz
+ * outside 8000 .. 192000; L * T > 2^20 (the standard rates need at most 44 800 entries); n_frames < 1; n_out outside
+ * 1 .. 480000; num0 < 0; batch or rows outside the context. */
+/* samples a whole clip of n_frames frames at src_hz yields, or -1 where nh_resample would refuse it */
+int nh_resample_len(int src_hz, int64_t n_frames);
+/* The filter of src_hz as the device holds it (a view for tests): *L, *M, *T and, unless coef == NULL (sizes only, no device
+ * work, ctx may be NULL), coef f32 [L][T] with coef[p][k + T/2 - 1] = (float)h(p/L - k).  src_hz == 16000: L = M = 1, T = 0. */
+int nh_resample_table(nh_ctx *ctx, int src_hz, float *coef, int32_t *L, int32_t *M, int32_t *T);
+/* frames: `batch` clips, clip b at frame b * stride_frames (host memory, or device memory when on_device != 0) with
+ * n_frames[b] frames.  num0: host i64 [batch] or NULL (0); n_out: host i32 [batch] or NULL (the whole clip).  The result
+ * lands in the context's PCM rows -- row b at b * 480000 floats, where nh_logmel puts host PCM -- and, when out_host is
+ * given, is copied there (clip b at b * out_stride floats) and the stream synchronised.  Host frames are staged in groups
+ * of clips that keep the native staging at or under 256 MiB (a clip that needs more on its own is staged alone); staging is
+ * allocated by the first call that needs it.  One launch per group; device frames: one launch. */
+int nh_resample(nh_ctx *ctx, const void *frames, int on_device, int sample_dtype, int channels, int src_hz,
+                const int32_t *n_frames, int64_t stride_frames, int batch, const int64_t *num0, const int32_t *n_out,
+                float *out_host, int64_t out_stride);
+/* Whole clips through nh_resample into the PCM rows row0 .., then exactly what nh_logmel_device_rows does on them (same row
+ * rules; row0 = 0 is the plain batch).  No copy back, no synchronisation. */
+int nh_logmel_resampled_rows(nh_ctx *ctx, const void *frames, int on_device, int sample_dtype, int channels, int src_hz,
+                             const int32_t *n_frames, int64_t stride_frames, int batch, int row0);
 /* Same, but pcm is a DEVICE pointer (already resident in HBM; no copy). */
 int nh_logmel_device(nh_ctx *ctx, const float *pcm_dev, const int32_t *n_samples, int64_t stride, int batch);
 /* Encoder forward over the mel of the last nh_logmel call (flush = true semantics: the cross

@@ -103,6 +103,35 @@ void nm_model_free(nm_model *m);
  * written; *buffered = samples the model keeps for the next call.  Returns 0, or 1 on a backend error. */
 int nm_model_transcribe(nm_model *m, const float *data, size_t n, int final_chunk, int32_t *out_tokens, int cap,
                         int *n_out, size_t *buffered, char *err, int err_len);
+/* ---- audio ingest (src/lib.rs:172-216: the capture callback's channel mixdown and resampler; nh_resample of norma_hip.h) --- */
+/* The format of the frames nm_model_transcribe_frames takes; the default is 16 000 Hz mono, what nm_model_transcribe takes.
+ * Set on a definition it applies to the models made from it afterwards. */
+void nm_definition_set_input_format(nm_definition *d, uint32_t src_hz, int channels);
+void nm_model_set_input_format(nm_model *m, uint32_t src_hz, int channels);
+/* Model::transcribe on native frames: n frames of `channels` interleaved samples of type sample_dtype (NH_SAMPLE_*) at the
+ * model's input rate go through the model's streaming resampler; the 16 kHz samples that became computable are appended to
+ * the buffer nm_model_transcribe uses and its loop runs unchanged.  final_chunk also flushes and resets the resampler.
+ * Outputs as for nm_model_transcribe. */
+int nm_model_transcribe_frames(nm_model *m, const void *frames, int sample_dtype, size_t n, int final_chunk, int32_t *out_tokens,
+                               int cap, int *n_out, size_t *buffered, char *err, int err_len);
+/* The streaming resampler's bookkeeping as a pure function (no GPU).  A stream has `received` frames and `emitted` outputs so
+ * far and keeps the frames from first_kept on.  With L, M, T of nh_resample_table and Wc = T / 2, output n is ready when
+ * floor(n M / L) + Wc <= received - 1; on the final push everything below ceil(received L / M) is (zeros beyond the end).
+ * *n_ready: outputs emitted .. emitted + n_ready - 1 are ready; *f0, *num0: first frame of the window and start position to
+ * give nh_resample for output `emitted`: f0 = max(first_kept, floor(emitted M / L) - Wc + 1), num0 = emitted M - f0 L;
+ * *drop_before: first frame still needed once they are out (= received on the final push).  Returns 0, or 1 for a rate
+ * nh_resample refuses or inconsistent counts. */
+int nm_resample_plan(int src_hz, int64_t received, int64_t emitted, int64_t first_kept, int final_push, int64_t *n_ready,
+                     int64_t *f0, int64_t *num0, int64_t *drop_before);
+/* norma::Resampler: the streaming form of nh_resample on the model's context.  push returns how many 16 kHz samples became
+ * computable (-1: refused, message in err; the stream is reset), read copies them out (returns how many there are); the
+ * total over a stream equals nh_resample on the whole of it, however it was cut.  final_push flushes and resets. */
+typedef struct nm_resampler nm_resampler;
+nm_resampler *nm_resampler_new(nm_model *m, int src_hz, int channels, int sample_dtype);
+void nm_resampler_free(nm_resampler *r);
+int64_t nm_resampler_push(nm_resampler *r, const void *frames, size_t n, int final_push, char *err, int err_len);
+int64_t nm_resampler_read(const nm_resampler *r, float *out, int64_t cap);
+void nm_resampler_state(const nm_resampler *r, int64_t *received, int64_t *emitted, int64_t *kept);
 /* Token-level timestamps (nh_align of norma_hip.h).  heads: n [layer, head] pairs, n = 0 switches them off (the default).
  * When on, every slice's accepted decode is aligned over the frames that hold audio.  Returns 0, or 1 when n is out of range. */
 int nm_model_set_alignment_heads(nm_model *m, const int32_t *layer_head_pairs, int n);

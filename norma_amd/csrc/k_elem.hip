@@ -105,18 +105,7 @@ void launch_embed(const int32_t *tokens, int tok_stride, const half_t *E, const 
 // (s - 2^(bits - 1)) / 2^(bits - 1), the subtraction in integers; f64: round to nearest.  Integer -> float conversions
 // round to nearest even (v_cvt_f32_i32, and the compiler's i64 sequence), like Rust's `as f32`; the divisions are by
 // powers of two, i.e. exact.
-template <typename T> __device__ __forceinline__ float sample_to_f32(T v);
-template <> __device__ __forceinline__ float sample_to_f32<float>(float v) { return v; }
-template <> __device__ __forceinline__ float sample_to_f32<double>(double v) { return (float)v; }
-template <> __device__ __forceinline__ float sample_to_f32<int8_t>(int8_t v) { return (float)v * (1.0f / 128.0f); }
-template <> __device__ __forceinline__ float sample_to_f32<int16_t>(int16_t v) { return (float)v * (1.0f / 32768.0f); }
-template <> __device__ __forceinline__ float sample_to_f32<int32_t>(int32_t v) { return (float)v * (1.0f / 2147483648.0f); }
-template <> __device__ __forceinline__ float sample_to_f32<int64_t>(int64_t v) { return (float)v * (1.0f / 9223372036854775808.0f); }
-template <> __device__ __forceinline__ float sample_to_f32<uint8_t>(uint8_t v) { return (float)((int)v - 128) * (1.0f / 128.0f); }
-template <> __device__ __forceinline__ float sample_to_f32<uint16_t>(uint16_t v) { return (float)((int)v - 32768) * (1.0f / 32768.0f); }
-template <> __device__ __forceinline__ float sample_to_f32<uint32_t>(uint32_t v) { return (float)(int32_t)(v ^ 0x80000000u) * (1.0f / 2147483648.0f); }
-template <> __device__ __forceinline__ float sample_to_f32<uint64_t>(uint64_t v) { return (float)(int64_t)(v ^ 0x8000000000000000ull) * (1.0f / 9223372036854775808.0f); }
-
+// (sample_to_f32<T>: nh_kernels.h, shared with k_resample.hip)
 template <typename T>
 __global__ __launch_bounds__(256) void convert_samples_kernel(const T *__restrict__ src, float *__restrict__ dst, long count) {
     for (long i = blockIdx.x * 256L + threadIdx.x; i < count; i += (long)gridDim.x * 256L) dst[i] = sample_to_f32<T>(src[i]);

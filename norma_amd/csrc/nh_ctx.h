@@ -1,6 +1,6 @@
-// nh_ctx.h -- the state behind the C ABI of include/norma_hip.h, shared by the four files that implement it: nh_model.hip
+// nh_ctx.h -- the state behind the C ABI of include/norma_hip.h, shared by the five files that implement it: nh_model.hip
 // (create / destroy, weights, tokens, options, timings), nh_encode.hip (log-mel, encoder), nh_decode.hip (decoder step,
-// lockstep decode, decode pool, parity views), nh_align.hip (token-level timestamps).  No torch, no candle, no CPU fallback:
+// lockstep decode, decode pool, parity views), nh_align.hip (token-level timestamps), nh_resample.hip (audio ingest).  No torch, no candle, no CPU fallback:
 // an entry point runs the HIP path or fails.
 #pragma once
 #include <math.h>
@@ -54,6 +54,9 @@ struct nh_model {
     MelTables mt{};
     int32_t *mel_grp = nullptr;
     bool have_filters = false;
+    // nh_resample's filters, one per source rate seen so far (coef: device f32 [L][T], in allocs); built under mu on first use
+    struct ResampleTable { int src_hz, L, M, T; float *coef; };
+    std::vector<ResampleTable> rs_tables;
     std::mutex mu;                   // guards loaded / dec_tiled_valid and the lazy repack
     // hipStreamWaitEvent fails ("dependency created on uncaptured work in another stream") on an event whose stream is capturing
     // at that moment, even one recorded before: a step capture and the encoders' waits on kv_readers exclude each other
@@ -154,6 +157,10 @@ struct nh_ctx {
     // mel
     float *pcm = nullptr;
     void *raw = nullptr; size_t raw_bytes = 0;   // native-sample staging of nh_logmel_samples
+    // nh_resample: native staging of host frames and the per-clip records of a call; allocated by the first call that needs
+    // them (contexts that never resample hold nothing), freed by nh_destroy
+    void *rs_stage = nullptr; size_t rs_stage_bytes = 0;
+    ResampleClip *rs_clips = nullptr;
     int32_t *nsamp = nullptr;
     float *mel32 = nullptr;
     unsigned *chunk_max = nullptr;
@@ -227,3 +234,5 @@ void drop_graphs(nh_ctx *ctx, int first = 0);   // nh_decode.hip
 void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr = nullptr, bool final_ln = true, bool skip_done = false,
                   const AlignHeadSet *keep = nullptr);   // nh_decode.hip
 int ensure_decoder_repack(nh_ctx *ctx);         // nh_model.hip
+// nh_encode.hip: log-mel of `batch` clips of device PCM into rows row0 .. (what nh_logmel_device_rows does after its checks)
+int run_logmel(nh_ctx *ctx, const float *pcm_dev, const int32_t *n_samples, int64_t stride, int batch, int row0 = 0);

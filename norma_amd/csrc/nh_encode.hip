@@ -53,7 +53,7 @@ static int prepare_batch(nh_ctx *ctx, const int32_t *n_samples, int batch, int r
     return reframe(ctx);
 }
 
-static int run_logmel(nh_ctx *ctx, const float *pcm_dev, const int32_t *n_samples, int64_t stride, int batch, int row0 = 0) {
+int run_logmel(nh_ctx *ctx, const float *pcm_dev, const int32_t *n_samples, int64_t stride, int batch, int row0) {
     if (!ctx->mdl->have_filters) return ctx->fail(NH_ERR_STATE, "nh_logmel: mel filters not set");
     int rc = prepare_batch(ctx, n_samples, batch, row0);
     if (rc) return rc;

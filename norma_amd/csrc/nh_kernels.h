@@ -207,6 +207,43 @@ void launch_embed(const int32_t *tokens, int tok_stride, const half_t *E, const 
 // ---- sample conversion (src/dtype.rs / dasp_sample): native capture samples -> f32 PCM -------------------------------
 // src: `count` samples of NH_SAMPLE_* type `dtype` (device memory); dst: f32
 void launch_convert_samples(const void *src, float *dst, long count, int dtype, hipStream_t st);
+#ifdef __HIPCC__
+// the conversions themselves (k_elem.hip has their derivation), shared by convert_samples_kernel and resample_kernel
+template <typename T> __device__ __forceinline__ float sample_to_f32(T v);
+template <> __device__ __forceinline__ float sample_to_f32<float>(float v) { return v; }
+template <> __device__ __forceinline__ float sample_to_f32<double>(double v) { return (float)v; }
+template <> __device__ __forceinline__ float sample_to_f32<int8_t>(int8_t v) { return (float)v * (1.0f / 128.0f); }
+template <> __device__ __forceinline__ float sample_to_f32<int16_t>(int16_t v) { return (float)v * (1.0f / 32768.0f); }
+template <> __device__ __forceinline__ float sample_to_f32<int32_t>(int32_t v) { return (float)v * (1.0f / 2147483648.0f); }
+template <> __device__ __forceinline__ float sample_to_f32<int64_t>(int64_t v) { return (float)v * (1.0f / 9223372036854775808.0f); }
+template <> __device__ __forceinline__ float sample_to_f32<uint8_t>(uint8_t v) { return (float)((int)v - 128) * (1.0f / 128.0f); }
+template <> __device__ __forceinline__ float sample_to_f32<uint16_t>(uint16_t v) { return (float)((int)v - 32768) * (1.0f / 32768.0f); }
+template <> __device__ __forceinline__ float sample_to_f32<uint32_t>(uint32_t v) { return (float)(int32_t)(v ^ 0x80000000u) * (1.0f / 2147483648.0f); }
+template <> __device__ __forceinline__ float sample_to_f32<uint64_t>(uint64_t v) { return (float)(int64_t)(v ^ 0x8000000000000000ull) * (1.0f / 9223372036854775808.0f); }
+#endif
+
+// ---- audio ingest: channel mixdown + polyphase resampling to 16 kHz (k_resample.hip; the contract is DESIGN.md 10) --------
+struct ResampleClip {   // one clip of a launch (device memory)
+    long long off;      // first frame of the clip's window inside `frames`, in frames
+    long long num0;     // source position of output 0 in units of 1/L frame, >= 0
+    int n_frames;       // frames the window holds; frames outside [0, n_frames) contribute nothing
+    int n_out;          // outputs to write, <= 480000
+};
+struct ResampleParams {
+    const void *frames; // interleaved native samples (device memory)
+    int dtype, channels;            // NH_SAMPLE_*, 1 .. 8
+    const ResampleClip *clips; int batch;
+    const float *coef;  // [L][T]: row p holds f32(h(p/L - k)), k = -T/2 + 1 .. T/2; unused when T == 0
+    int L, M, T;        // T == 0 (L == M == 1): the source is at 16 kHz already, y[n] = mono[num0 + n]
+    float *out; long out_stride;    // clip b writes out[b * out_stride + n]
+    int max_out;        // largest n_out of the launch (sizes the grid)
+};
+#define NH_RS_TILE 2048   // outputs per workgroup: its window of mono frames is ((TILE - 1) M / L + T + 2) floats of LDS
+static inline size_t resample_lds_bytes(int L, int M, int T) {
+    return sizeof(float) * (size_t)(((long long)(NH_RS_TILE - 1) * M + L - 1) / L + T + 2);
+}
+// false (nothing launched): the window does not fit the LDS of a CU, or an unknown sample type
+[[nodiscard]] bool launch_resample(const ResampleParams &p, hipStream_t st);
 
 // ---- log-mel -------------------------------------------------------------------------------------------
 struct MelTables {      // device pointers, built once on the host with libm (bit-identical twiddles)

@@ -47,6 +47,8 @@ extern "C" void nh_destroy(nh_ctx *ctx) {
     for (void *p : ctx->allocs) hipFree(p);
     for (void *p : ctx->al.allocs) hipFree(p);
     if (ctx->align_q) hipFree(ctx->align_q);
+    if (ctx->rs_stage) hipFree(ctx->rs_stage);
+    if (ctx->rs_clips) hipFree(ctx->rs_clips);
     drop_graphs(ctx);
     if (ctx->h_done) hipHostFree(ctx->h_done);
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);

@@ -83,14 +83,9 @@ int nm_model_last_text(const nm_model *m, char *buf, int cap) {
 }
 void nm_model_free(nm_model *m) { if (m) { delete m->m; delete m; } }
 
-int nm_model_transcribe(nm_model *m, const float *data, size_t n, int final_chunk, int32_t *out_tokens, int cap,
-                        int *n_out, size_t *buffered, char *err, int err_len) {
-    NM_TRY
-    std::vector<float> v(data, data + n);
-    std::vector<Segment> segs;
-    m->last_text.clear();
-    m->tok_start.clear(); m->tok_end.clear();
-    Error e = m->m->transcribe(v, final_chunk != 0, segs, &m->last_text);
+// what nm_model_transcribe and nm_model_transcribe_frames hand back of one transcribe call
+static int put_segments(nm_model *m, const Error &e, const std::vector<Segment> &segs, int32_t *out_tokens, int cap, int *n_out,
+                        size_t *buffered, char *err, int err_len) {
     if (buffered) *buffered = m->m->buffered_samples();
     if (e) { put_err(err, err_len, e.message); return 1; }
     int w = 0;
@@ -103,7 +98,68 @@ int nm_model_transcribe(nm_model *m, const float *data, size_t n, int final_chun
     }
     if (n_out) *n_out = w;
     return 0;
+}
+
+int nm_model_transcribe(nm_model *m, const float *data, size_t n, int final_chunk, int32_t *out_tokens, int cap,
+                        int *n_out, size_t *buffered, char *err, int err_len) {
+    NM_TRY
+    std::vector<float> v(data, data + n);
+    std::vector<Segment> segs;
+    m->last_text.clear();
+    m->tok_start.clear(); m->tok_end.clear();
+    Error e = m->m->transcribe(v, final_chunk != 0, segs, &m->last_text);
+    return put_segments(m, e, segs, out_tokens, cap, n_out, buffered, err, err_len);
     NM_CATCH({ put_err(err, err_len, "transcribe: " + what_); return 1; })
+}
+
+// ---- audio ingest ---------------------------------------------------------------------------------------------------
+void nm_definition_set_input_format(nm_definition *d, uint32_t src_hz, int channels) { d->def.set_input_format(src_hz, channels); }
+void nm_model_set_input_format(nm_model *m, uint32_t src_hz, int channels) { m->m->set_input_format(src_hz, channels); }
+
+int nm_model_transcribe_frames(nm_model *m, const void *frames, int sample_dtype, size_t n, int final_chunk, int32_t *out_tokens,
+                               int cap, int *n_out, size_t *buffered, char *err, int err_len) {
+    NM_TRY
+    std::vector<Segment> segs;
+    m->last_text.clear();
+    m->tok_start.clear(); m->tok_end.clear();
+    Error e = m->m->transcribe_frames(frames, sample_dtype, n, final_chunk != 0, segs, &m->last_text);
+    return put_segments(m, e, segs, out_tokens, cap, n_out, buffered, err, err_len);
+    NM_CATCH({ put_err(err, err_len, "transcribe_frames: " + what_); return 1; })
+}
+
+int nm_resample_plan(int src_hz, int64_t received, int64_t emitted, int64_t first_kept, int final_push, int64_t *n_ready,
+                     int64_t *f0, int64_t *num0, int64_t *drop_before) {
+    ResamplePlan pl;
+    if (!resample_plan(src_hz, received, emitted, first_kept, final_push != 0, pl)) return 1;
+    if (n_ready) *n_ready = pl.n_ready;
+    if (f0) *f0 = pl.f0;
+    if (num0) *num0 = pl.num0;
+    if (drop_before) *drop_before = pl.drop_before;
+    return 0;
+}
+
+struct nm_resampler { Resampler r; std::vector<float> out; };
+nm_resampler *nm_resampler_new(nm_model *m, int src_hz, int channels, int sample_dtype) {
+    if (!m || !m->m) return nullptr;
+    return new nm_resampler{Resampler(m->m->context(), src_hz, channels, sample_dtype), {}};
+}
+void nm_resampler_free(nm_resampler *r) { delete r; }
+int64_t nm_resampler_push(nm_resampler *r, const void *frames, size_t n, int final_push, char *err, int err_len) {
+    NM_TRY
+    r->out.clear();
+    if (!r->r.push(frames, n, final_push != 0, r->out)) { r->out.clear(); put_err(err, err_len, r->r.last_error()); return -1; }
+    return (int64_t)r->out.size();
+    NM_CATCH({ put_err(err, err_len, "resampler_push: " + what_); return -1; })
+}
+int64_t nm_resampler_read(const nm_resampler *r, float *out, int64_t cap) {
+    const int64_t n = std::min<int64_t>(cap, (int64_t)r->out.size());
+    if (out && n > 0) memcpy(out, r->out.data(), sizeof(float) * (size_t)n);
+    return (int64_t)r->out.size();
+}
+void nm_resampler_state(const nm_resampler *r, int64_t *received, int64_t *emitted, int64_t *kept) {
+    if (received) *received = r->r.received();
+    if (emitted) *emitted = r->r.emitted();
+    if (kept) *kept = (int64_t)r->r.kept_frames();
 }
 
 int nm_gguf_list(const char *path, char *buf, int cap) {

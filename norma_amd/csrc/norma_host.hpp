@@ -13,6 +13,7 @@
 //   whisper::Model::transcribe          model.rs:55-159           Model::transcribe
 //   Model::decode_with_fallback (t=0)   model.rs:164-191          Model::decode_with_fallback
 //   SliceExt::inclusive_boxed_by        src/utils.rs:22-76        norma::inclusive_boxed_by
+//   capture callback: mixdown + Sinc    src/lib.rs:172-216        norma::Resampler, Model::transcribe_frames
 //
 // Text decoding needs a tokenizer (`tokenizers` crate in the reference, model.rs:147); none is
 // available offline, so transcribe() returns the token ids of each segment and, when a detokenizer
@@ -22,6 +23,7 @@
 
 #include <algorithm>
 #include <functional>
+#include <memory>
 #include <random>
 #include <string>
 #include <utility>
@@ -134,6 +136,89 @@ NORMA_DTYPE(int32_t, NH_SAMPLE_I32, false); NORMA_DTYPE(int64_t, NH_SAMPLE_I64, 
 NORMA_DTYPE(uint16_t, NH_SAMPLE_U16, false); NORMA_DTYPE(uint64_t, NH_SAMPLE_U64, false);
 #undef NORMA_DTYPE
 
+
+// ---- audio ingest (src/lib.rs:172-216): native frames at the device's rate -> Model::Data at SAMPLE_RATE ------------------
+// The streaming bookkeeping of Resampler as a pure function (nm_resample_plan of norma_host.h; no GPU): a stream has
+// `received` frames so far, `emitted` outputs so far, and still keeps the frames from `first_kept` on.  With L, M, Wc of
+// nh_resample (Wc = T / 2): output n is ready when floor(n M / L) + Wc <= received - 1, or, on the final push, when
+// n < ceil(received L / M) (frames past the end are zeros).  n_ready: outputs emitted .. emitted + n_ready - 1 are ready now;
+// f0, num0: the window [f0, ..) and start position nh_resample takes for output `emitted`; drop_before: the first frame
+// still needed once they are out (everything received, on the final push).
+struct ResamplePlan { long long n_ready = 0, f0 = 0, num0 = 0, drop_before = 0; };
+inline bool resample_plan(int src_hz, long long received, long long emitted, long long first_kept, bool final_push, ResamplePlan &pl) {
+    int32_t L = 0, M = 0, T = 0;
+    if (nh_resample_table(nullptr, src_hz, nullptr, &L, &M, &T) || received < 0 || emitted < 0 || first_kept < 0 || first_kept > received) return false;
+    const long long Wc = T / 2, lo = Wc > 0 ? Wc - 1 : 0;
+    const long long usable = final_push ? received : received - Wc;              // outputs below ceil(usable L / M) are ready
+    const long long total = usable > 0 ? (usable * L + M - 1) / M : 0;
+    pl.n_ready = std::max(0LL, total - emitted);
+    pl.f0 = std::max(first_kept, emitted * M / L - lo);
+    pl.num0 = emitted * M - pl.f0 * L;
+    pl.drop_before = final_push ? received : std::min(received, std::max(first_kept, (emitted + pl.n_ready) * M / L - lo));
+    return true;
+}
+
+// The streaming form of nh_resample: push(frames, n, final) returns the 16 kHz samples that have become computable.  It keeps
+// the frames it still needs and the counts of frames received and outputs emitted; every push calls nh_resample on the kept
+// window, in pieces of at most 480000 outputs.  The samples are those of nh_resample on the whole stream, whatever the pieces.
+// (The reference's ring buffer restarts at every capture callback, src/lib.rs:198-202; this one does not.)
+class Resampler {
+  public:
+    Resampler(nh_ctx *ctx, int src_hz, int channels, int sample_dtype)
+        : ctx_(ctx), src_hz_(src_hz), channels_(channels), dtype_(sample_dtype), frame_bytes_((size_t)nh_sample_size(sample_dtype) * (size_t)std::max(channels, 0)) {}
+    int src_hz() const { return src_hz_; }
+    int channels() const { return channels_; }
+    int sample_dtype() const { return dtype_; }
+    long long received() const { return received_; }
+    long long emitted() const { return emitted_; }
+    size_t kept_frames() const { return frame_bytes_ ? kept_.size() / frame_bytes_ : 0; }
+    const char *last_error() const { return nh_last_error(ctx_); }
+    // frames: n frames of `channels` interleaved samples of the resampler's type.  Appends to `out`.  false: the backend
+    // refused (nh_last_error has the message); the stream is reset.
+    bool push(const void *frames, size_t n, bool final_push, std::vector<float> &out) {
+        int32_t L = 0, M = 0, T = 0;
+        if (!frame_bytes_ || nh_resample_table(ctx_, src_hz_, nullptr, &L, &M, &T)) { reset(); return refuse(); }
+        const long long Wc = T / 2;
+        const char *src = static_cast<const char *>(frames);
+        kept_.insert(kept_.end(), src, src + n * frame_bytes_);
+        received_ += (long long)n;
+        ResamplePlan pl;
+        if (!resample_plan(src_hz_, received_, emitted_, first_kept_, final_push, pl)) { reset(); return refuse(); }
+        const long long drop_before = pl.drop_before;
+        for (long long left = pl.n_ready; left > 0;) {
+            const int32_t piece = (int32_t)std::min<long long>(left, NH_N_SAMPLES);
+            resample_plan(src_hz_, received_, emitted_, first_kept_, final_push, pl);   // f0, num0 of this piece
+            const long long hi = std::min(received_, (emitted_ + piece - 1) * M / L + Wc + 1);
+            const int32_t nf = (int32_t)(hi - pl.f0);
+            const int64_t num0 = pl.num0;
+            const size_t at = out.size();
+            out.resize(at + (size_t)piece);
+            if (nh_resample(ctx_, kept_.data() + (size_t)(pl.f0 - first_kept_) * frame_bytes_, 0, dtype_, channels_, src_hz_, &nf, nf, 1,
+                            &num0, &piece, out.data() + at, piece)) { out.resize(at); reset(); return false; }
+            emitted_ += piece; left -= piece;
+        }
+        if (final_push) reset();
+        else {
+            kept_.erase(kept_.begin(), kept_.begin() + (long)((size_t)(drop_before - first_kept_) * frame_bytes_));
+            first_kept_ = drop_before;
+        }
+        return true;
+    }
+    void reset() { kept_.clear(); received_ = emitted_ = first_kept_ = 0; }
+
+  private:
+    bool refuse() {   // leaves the refusal's message in the context: a whole-clip call with the same format is refused the same way
+        const int32_t one = 1; const float z = 0.f;
+        nh_resample(ctx_, &z, 0, dtype_, channels_, src_hz_, &one, 1, 1, nullptr, nullptr, nullptr, 0);
+        return false;
+    }
+    nh_ctx *ctx_;
+    int src_hz_, channels_, dtype_;
+    size_t frame_bytes_;
+    std::vector<char> kept_;
+    long long received_ = 0, emitted_ = 0, first_kept_ = 0;
+};
+
 enum class Task { Transcribe, Translate };  // multilingual.rs:19-25
 
 struct DecodingResult {  // model.rs:494-499
@@ -154,7 +239,8 @@ class Model {
     typedef float Data;                               // Model::Data = f32 (model.rs:49)
     Model(nh_ctx *ctx, nh_config cfg, nh_tokens tk) : ctx_(ctx), cfg_(cfg), tk_(tk) {}
     Model(Model &&o) noexcept : ctx_(o.ctx_), cfg_(o.cfg_), tk_(o.tk_), buf_(std::move(o.buf_)), detok_(std::move(o.detok_)),
-                                align_heads_(std::move(o.align_heads_)), checkpoint_heads_(std::move(o.checkpoint_heads_)), capture_stale_(o.capture_stale_) { o.ctx_ = nullptr; }
+                                align_heads_(std::move(o.align_heads_)), checkpoint_heads_(std::move(o.checkpoint_heads_)), capture_stale_(o.capture_stale_),
+                                src_hz_(o.src_hz_), channels_(o.channels_), resampler_(std::move(o.resampler_)) { o.ctx_ = nullptr; }
     Model(const Model &) = delete;
     ~Model() { if (ctx_) nh_destroy(ctx_); }
 
@@ -173,6 +259,28 @@ class Model {
     // Remembered, not enabled: hand it to set_alignment_heads to turn the timestamps on.
     const std::vector<nh_align_head> &checkpoint_alignment_heads() const { return checkpoint_heads_; }
     void set_checkpoint_alignment_heads(std::vector<nh_align_head> heads) { checkpoint_heads_ = std::move(heads); }
+
+    // The format of the frames transcribe_frames takes: the capture device's rate and channel count (src/lib.rs:172-216 reads
+    // them from the stream's config).  The default, 16 000 Hz mono, is what transcribe takes.  A new format starts a new stream.
+    void set_input_format(uint32_t src_hz, int channels) { src_hz_ = src_hz; channels_ = channels; resampler_.reset(); }
+    uint32_t input_rate() const { return src_hz_; }
+    int input_channels() const { return channels_; }
+    nh_ctx *context() const { return ctx_; }
+    // Native frames in, as the capture callback hands them over (n frames of input_channels() interleaved samples of one
+    // NH_SAMPLE_* type): they go through the model's Resampler (mixdown and resampling on the device), the 16 kHz samples that
+    // became computable are appended to the buffer transcribe uses, and transcribe's loop runs on it unchanged.  final_chunk
+    // also flushes the resampler (the tail of the stream, zeros beyond its end) and resets it.
+    Error transcribe_frames(const void *frames, int sample_dtype, size_t n, bool final_chunk, std::vector<Segment> &out, std::string *text = nullptr) {
+        if (!resampler_ || resampler_->sample_dtype() != sample_dtype)
+            resampler_.reset(new Resampler(ctx_, (int)src_hz_, channels_, sample_dtype));
+        std::vector<float> pcm;
+        if (!resampler_->push(frames, n, final_chunk, pcm)) return backend_error();
+        return transcribe(pcm, final_chunk, out, text);
+    }
+    template <typename T>
+    Error transcribe_frames(const T *frames, size_t n, bool final_chunk, std::vector<Segment> &out, std::string *text = nullptr) {
+        return transcribe_frames(static_cast<const void *>(frames), DType<T>::sample, n, final_chunk, out, text);
+    }
 
     // Model::transcribe (model.rs:55-159).  `data` is consumed (swapped/appended into the model's buffer).
     // Returns an Error with kind != None on a backend failure (the reference's TranscriberError, which
@@ -302,6 +410,9 @@ class Model {
     bool capture_stale_ = false;   // align_heads_ changed since the context was last told (nh_align_capture)
     std::vector<int32_t> lang_tokens_;
     int32_t lang_token_ = -1;
+    uint32_t src_hz_ = SAMPLE_RATE;
+    int channels_ = 1;
+    std::unique_ptr<Resampler> resampler_;   // made by the first transcribe_frames
 };
 
 // One tensor handed to the loader (HF name, f32 or f16 data) -- stands in for the safetensors mmap of
@@ -322,6 +433,8 @@ class Definition {
     void set_data_buffer_size(size_t n) { common_params_.set_data_buffer_size(n); }
     void set_string_buffer_size(size_t n) { common_params_.set_string_buffer_size(n); }
     ModelType model() const { return model_; }
+    // what the capture device delivers (Model::transcribe_frames); the default is Model::SAMPLE_RATE, mono
+    void set_input_format(uint32_t src_hz, int channels) { src_hz_ = src_hz; channels_ = channels; }
 
     // blocking_try_to_model (monolingual.rs:320-451) for SelectedDevice::Rocm.
     Error blocking_try_to_model(const nh_config &cfg, const nh_tokens &tk, const std::vector<int32_t> &suppress,
@@ -340,6 +453,7 @@ class Definition {
         if (nh_set_mel_filters(ctx, mel_filters, n_mel)) return fail();
         if (nh_set_tokens(ctx, &tk, suppress.data(), (int)suppress.size())) return fail();
         *out = new Model(ctx, cfg, tk);
+        (*out)->set_input_format(src_hz_, channels_);
         return Error{};
     }
 
@@ -430,6 +544,8 @@ class Definition {
     ModelType model_;
     SelectedDevice device_;
     CommonModelParams common_params_;
+    uint32_t src_hz_ = SAMPLE_RATE;
+    int channels_ = 1;
 };
 
 }  // namespace whisper

@@ -23,6 +23,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "norma_hip.h")
 N_SAMPLES = 480000
 N_FRAMES = 3000
 NH_DTYPE_F32, NH_DTYPE_F16 = 0, 1
+NH_ERR_NOMEM = 4
 NH_LANG_DETECT = -2   # `lang` of pool_admit*: the row detects its language in its first step (pool_detect_languages)
 NH_OPT_DECODE_GRAPHS, NH_OPT_FUSE_DECODE_LAYERNORM, NH_OPT_DECODER_LAYER_LIMIT, NH_OPT_ABSORBED_XATTN = 0, 1, 2, 3
 NH_OPT_ALIGN_KEEP = 4      # 1: align() keeps every clip's weights and matrix for align_weights / align_matrix
@@ -113,6 +114,11 @@ def load_library() -> C.CDLL:
     L.nh_pool_languages.argtypes = [vp, ip, C.c_int, ip, fp]
     L.nh_logmel_samples.argtypes = [vp, vp, C.c_int, ip, C.c_int64, C.c_int]
     L.nh_sample_size.argtypes = [C.c_int]
+    i64p = C.POINTER(C.c_int64)
+    L.nh_resample_len.argtypes = [C.c_int, C.c_int64]
+    L.nh_resample_table.argtypes = [vp, C.c_int, fp, ip, ip, ip]
+    L.nh_resample.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int64, C.c_int, i64p, ip, fp, C.c_int64]
+    L.nh_logmel_resampled_rows.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int64, C.c_int, C.c_int]
     L.nh_encode.argtypes = [vp]
     L.nh_decode_greedy.argtypes = [vp, ip, C.POINTER(NhDecodeResult), C.c_int]
     L.nh_decode_sampled.argtypes = [vp, ip, C.POINTER(NhDecodeResult), C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_uint32]
@@ -143,6 +149,53 @@ def load_library() -> C.CDLL:
 
 def device_count() -> int:
     return int(load_library().nh_device_count())
+
+
+class DeviceBuffer:
+    """The bytes of a numpy array in HBM, for the entry points that take a device pointer (logmel_device, resample, ...):
+    hipMalloc + hipMemcpy of the HIP runtime libnorma_hip.so itself is linked to.  `.ptr` is the device address; free() or the
+    garbage collector releases it."""
+
+    _rt = None
+
+    @classmethod
+    def runtime(cls) -> C.CDLL:
+        if cls._rt is None:
+            load_library()
+            path = "libamdhip64.so"
+            with open("/proc/self/maps") as f:   # the copy already in this process, not whichever the search path finds
+                for line in f:
+                    if "libamdhip64" in line:
+                        path = line.split()[-1]
+                        break
+            rt = C.CDLL(path)
+            rt.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+            rt.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+            rt.hipFree.argtypes = [C.c_void_p]
+            cls._rt = rt
+        return cls._rt
+
+    def __init__(self, arr: np.ndarray):
+        rt = self.runtime()
+        a = np.ascontiguousarray(arr)
+        p = C.c_void_p()
+        if rt.hipMalloc(C.byref(p), max(1, a.nbytes)) != 0:
+            raise HipError(NH_ERR_NOMEM, f"hipMalloc({a.nbytes})")
+        self.ptr, self.nbytes = int(p.value), a.nbytes
+        if rt.hipMemcpy(C.c_void_p(self.ptr), a.ctypes.data_as(C.c_void_p), a.nbytes, 1) != 0:   # hipMemcpyHostToDevice
+            self.free()
+            raise HipError(2, "hipMemcpy to the device failed")
+
+    def free(self):
+        if getattr(self, "ptr", 0):
+            self._rt.hipFree(C.c_void_p(self.ptr))
+            self.ptr = 0
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def _fp(a):
@@ -257,6 +310,57 @@ class HipWhisper:
         ns = np.full(B, stride, dtype=np.int32) if n_samples is None else np.asarray(n_samples, dtype=np.int32)
         self._chk(self.L.nh_logmel_samples(self._h, pcm.ctypes.data_as(C.c_void_p), SAMPLE_DTYPES[pcm.dtype], _ip(ns), stride, B))
         self.batch = B
+
+    # -- audio ingest (include/norma_hip.h: nh_resample*): native interleaved frames at any rate -> 16 kHz mono on the device
+    def _frames(self, frames, n_frames, stride_frames, dtype, channels):
+        """(pointer, on_device, NH_SAMPLE_*, channels, n_frames i32 [B], stride in frames, keep-alive) of either a numpy
+        array [B][frames][channels] / [B][frames] (mono), or a device pointer with dtype, channels, n_frames and stride given"""
+        if isinstance(frames, np.ndarray):
+            assert frames.ndim in (2, 3) and frames.dtype in SAMPLE_DTYPES
+            a = np.ascontiguousarray(frames)
+            ch = 1 if a.ndim == 2 else a.shape[2]
+            nf = np.full(a.shape[0], a.shape[1], dtype=np.int32) if n_frames is None else np.ascontiguousarray(n_frames, dtype=np.int32)
+            assert len(nf) == a.shape[0]
+            return a.ctypes.data_as(C.c_void_p), 0, SAMPLE_DTYPES[a.dtype], ch, nf, a.shape[1], a
+        nf = np.ascontiguousarray(n_frames, dtype=np.int32)
+        return C.c_void_p(int(frames)), 1, SAMPLE_DTYPES[np.dtype(dtype)], int(channels), nf, int(stride_frames), None
+
+    def resample_table(self, src_hz: int):
+        """(coef f32 [L][T], L, M, T): the filter of src_hz as the device holds it (nh_resample_table)"""
+        L_, M_, T_ = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._chk(self.L.nh_resample_table(self._h, int(src_hz), None, C.byref(L_), C.byref(M_), C.byref(T_)))
+        coef = np.zeros((L_.value, T_.value), dtype=np.float32)
+        if coef.size:
+            self._chk(self.L.nh_resample_table(self._h, int(src_hz), _fp(coef), C.byref(L_), C.byref(M_), C.byref(T_)))
+        return coef, L_.value, M_.value, T_.value
+
+    def resample(self, frames, src_hz: int, n_frames: Optional[Sequence[int]] = None, num0: Optional[Sequence[int]] = None,
+                 n_out: Optional[Sequence[int]] = None, stride_frames: int = 0, dtype=None, channels: int = 1) -> List[np.ndarray]:
+        """nh_resample: the clips of `frames` (see _frames) mixed down and resampled to 16 kHz; returns one f32 array per clip.
+        num0 / n_out: per-clip start position (units of 1/L frame) and output count, None = whole clips."""
+        ptr, dev, dt, ch, nf, stride, keep = self._frames(frames, n_frames, stride_frames, dtype, channels)
+        B = len(nf)
+        z = None if num0 is None else np.ascontiguousarray(num0, dtype=np.int64)
+        no = None if n_out is None else np.ascontiguousarray(n_out, dtype=np.int32)
+        lens = [int(x) if 1 <= int(x) <= N_SAMPLES else 0 for x in no] if no is not None else \
+               [max(0, self.L.nh_resample_len(int(src_hz), int(x))) for x in nf]
+        out = np.zeros((B, max(1, max(lens, default=1))), dtype=np.float32)
+        self._chk(self.L.nh_resample(self._h, ptr, dev, dt, ch, int(src_hz), _ip(nf), stride, B,
+                                     None if z is None else z.ctypes.data_as(C.POINTER(C.c_int64)), None if no is None else _ip(no),
+                                     _fp(out), out.shape[1]))
+        return [out[b, :lens[b]].copy() for b in range(B)]
+
+    def logmel_resampled_rows(self, frames, src_hz: int, row0: int, n_frames: Optional[Sequence[int]] = None,
+                              stride_frames: int = 0, dtype=None, channels: int = 1):
+        """nh_logmel_resampled_rows: whole clips of native frames -> 16 kHz mono -> log-mel of rows [row0, row0 + B)"""
+        ptr, dev, dt, ch, nf, stride, keep = self._frames(frames, n_frames, stride_frames, dtype, channels)
+        self._chk(self.L.nh_logmel_resampled_rows(self._h, ptr, dev, dt, ch, int(src_hz), _ip(nf), stride, len(nf), int(row0)))
+        self.batch = row0 + len(nf) if row0 > 0 else len(nf)
+
+    def logmel_resampled(self, frames, src_hz: int, n_frames: Optional[Sequence[int]] = None, stride_frames: int = 0,
+                         dtype=None, channels: int = 1):
+        """the plain batch: logmel_resampled_rows with row0 = 0"""
+        self.logmel_resampled_rows(frames, src_hz, 0, n_frames, stride_frames, dtype, channels)
 
     def logmel_device(self, pcm_dev_ptr: int, n_samples: Sequence[int], stride: int):
         """PCM already resident in HBM (device pointer, f32 [batch][stride])."""

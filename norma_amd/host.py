@@ -112,8 +112,43 @@ def _lib():
         L.nm_model_last_token_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]
         L.nm_model_last_result.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),
                                            C.POINTER(C.c_int)]
+        i64, i64p = C.c_int64, C.POINTER(C.c_int64)
+        L.nm_definition_set_input_format.argtypes = [vp, C.c_uint32, C.c_int]
+        L.nm_definition_set_input_format.restype = None
+        L.nm_model_set_input_format.argtypes = [vp, C.c_uint32, C.c_int]
+        L.nm_model_set_input_format.restype = None
+        L.nm_model_transcribe_frames.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                                 C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.c_char_p, C.c_int]
+        L.nm_resample_plan.argtypes = [C.c_int, i64, i64, i64, C.c_int, i64p, i64p, i64p, i64p]
+        L.nm_resampler_new.restype = vp
+        L.nm_resampler_new.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+        L.nm_resampler_free.argtypes = [vp]
+        L.nm_resampler_free.restype = None
+        L.nm_resampler_push.restype = i64
+        L.nm_resampler_push.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_char_p, C.c_int]
+        L.nm_resampler_read.restype = i64
+        L.nm_resampler_read.argtypes = [vp, C.POINTER(C.c_float), i64]
+        L.nm_resampler_state.argtypes = [vp, i64p, i64p, i64p]
+        L.nm_resampler_state.restype = None
         _bound = True
     return L
+
+
+def resample_plan(src_hz: int, received: int, emitted: int, first_kept: int, final: bool):
+    """nm_resample_plan, the streaming resampler's bookkeeping (pure, no GPU): (n_ready, f0, num0, drop_before), or None
+    where it refuses."""
+    v = [C.c_int64(0) for _ in range(4)]
+    if _lib().nm_resample_plan(int(src_hz), int(received), int(emitted), int(first_kept), int(final), *[C.byref(x) for x in v]):
+        return None
+    return tuple(int(x.value) for x in v)
+
+
+def _native_frames(frames: np.ndarray, channels: int) -> np.ndarray:
+    """[frames][channels] (or [frames] for mono) of a native capture type, contiguous"""
+    a = np.ascontiguousarray(frames)
+    assert a.dtype in hip.SAMPLE_DTYPES and a.ndim in (1, 2) and (a.shape[1] if a.ndim == 2 else 1) == channels, \
+        f"expected [frames][{channels}] of a capture sample type"
+    return a
 
 
 class Model:
@@ -149,8 +184,11 @@ class Model:
         self.buffered_samples = int(buffered.value)
         if rc:
             raise WhisperError(err.value.decode())
+        return self._segments(out, n_out.value)
+
+    def _segments(self, out, n_out):
         segs, cur = [], []
-        for t in out[:n_out.value].tolist():
+        for t in out[:n_out].tolist():
             if t == -1:
                 segs.append(cur)
                 cur = []
@@ -158,6 +196,28 @@ class Model:
                 cur.append(t)
         self._last_segments = segs
         return segs
+
+    def set_input_format(self, src_hz: int, channels: int):
+        """The capture device's rate and channel count, for transcribe_frames (default: 16 000 Hz mono)."""
+        _lib().nm_model_set_input_format(self._h, int(src_hz), int(channels))
+        self._channels = int(channels)
+
+    def transcribe_frames(self, frames: np.ndarray, final_chunk: bool) -> List[List[int]]:
+        """Model::transcribe on native frames ([frames][channels], or [frames] for mono, of a capture sample type at the
+        rate given to set_input_format): mixed down and resampled on the device by the model's streaming Resampler, then
+        transcribe's own loop.  final_chunk also flushes and resets the resampler."""
+        a = _native_frames(frames, getattr(self, "_channels", 1))
+        cap = 64 * (self._ctx_len + 2)
+        out = np.zeros(cap, dtype=np.int32)
+        n_out, buffered = C.c_int(0), C.c_size_t(0)
+        err = C.create_string_buffer(512)
+        rc = _lib().nm_model_transcribe_frames(self._h, a.ctypes.data_as(C.c_void_p), hip.SAMPLE_DTYPES[a.dtype], a.shape[0],
+                                               int(final_chunk), out.ctypes.data_as(C.POINTER(C.c_int32)), cap, C.byref(n_out),
+                                               C.byref(buffered), err, 512)
+        self.buffered_samples = int(buffered.value)
+        if rc:
+            raise WhisperError(err.value.decode())
+        return self._segments(out, n_out.value)
 
     def enable_language_detection(self, lang_tokens: Sequence[int]):
         """multilingual LanguageState::Detect: tokens of `Language::iter()` (languages.rs:7-107) in order."""
@@ -213,6 +273,44 @@ class Model:
         return dict(avg_logprob=a.value, no_speech_prob=n.value, needed_fallback=bool(f.value), n_tokens=k.value)
 
 
+class Resampler:
+    """norma::Resampler on a model's context: the streaming form of HipWhisper.resample.  push(frames, final) returns the
+    16 kHz samples that have become computable; over a stream they are those of one resample of the whole of it."""
+
+    def __init__(self, model: Model, src_hz: int, channels: int, dtype):
+        self._channels, self._dtype = int(channels), np.dtype(dtype)
+        self._model = model   # the resampler runs on the model's context: keep it alive
+        self._h = _lib().nm_resampler_new(model._h, int(src_hz), int(channels), hip.SAMPLE_DTYPES[self._dtype])
+        if not self._h:
+            raise WhisperError("nm_resampler_new failed")
+
+    def close(self):
+        if self._h:
+            _lib().nm_resampler_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def push(self, frames: np.ndarray, final: bool = False) -> np.ndarray:
+        a = _native_frames(np.asarray(frames, dtype=self._dtype), self._channels)
+        err = C.create_string_buffer(512)
+        n = _lib().nm_resampler_push(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0], int(final), err, 512)
+        if n < 0:
+            raise WhisperError(err.value.decode())
+        out = np.zeros(n, dtype=np.float32)
+        _lib().nm_resampler_read(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), n)
+        return out
+
+    def state(self) -> dict:
+        v = [C.c_int64(0) for _ in range(3)]
+        _lib().nm_resampler_state(self._h, *[C.byref(x) for x in v])
+        return dict(received=int(v[0].value), emitted=int(v[1].value), kept=int(v[2].value))
+
+
 def gguf_list(path: str):
     """Tensors of a GGUF file as the C++ reader sees them: [(name, ggml_type, shape, sum of dequantised values)]."""
     _lib()
@@ -242,12 +340,23 @@ class Definition:
         except Exception:
             pass
 
+    def _model(self, h, ctx_len: int) -> Model:
+        m = Model(C.c_void_p(h), ctx_len)
+        m._channels = getattr(self, "_channels", 1)
+        return m
+
     def set_responsiveness(self, period_ms: int):
         if _lib().nm_definition_set_responsiveness(self._h, period_ms):
             raise WhisperError("The respnsivness must be over 1 second and under 30")
 
     def set_data_buffer_size(self, n: int):
         _lib().nm_definition_set_data_buffer_size(self._h, n)
+
+    def set_input_format(self, src_hz: int, channels: int):
+        """what the capture device delivers to Model.transcribe_frames (default 16 000 Hz mono); applies to the models made
+        from this definition afterwards"""
+        _lib().nm_definition_set_input_format(self._h, int(src_hz), int(channels))
+        self._channels = int(channels)
 
     @property
     def max_chunk_len(self) -> int:
@@ -273,7 +382,7 @@ class Definition:
                                                                 filt.shape[0], (language or "").encode(), int(translate), err, 512)
         if not h:
             raise WhisperError(err.value.decode())
-        return Model(C.c_void_p(h), ctx_len)
+        return self._model(h, ctx_len)
 
     def blocking_try_to_model(self, cfg: Config, tokens, lang: int, task: int,
                               weights: Iterable[Tuple[str, np.ndarray]], mel_filters: Optional[np.ndarray] = None) -> Model:
@@ -304,6 +413,6 @@ class Definition:
                                                       filt.ctypes.data_as(C.POINTER(C.c_float)), filt.shape[0], tl, err, 512)
             if not h:
                 raise WhisperError(err.value.decode())
-            return Model(C.c_void_p(h), cfg.max_target_positions)
+            return self._model(h, cfg.max_target_positions)
         finally:
             L.nm_tensors_free(tl)
