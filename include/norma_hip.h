@@ -23,6 +23,9 @@
  *                                 (src/models/whisper/model.rs:74-88)
  *   nh_resample, nh_logmel_resampled_rows
  *                                 the capture side's channel mixdown and Sinc resampler (src/lib.rs:172-216)
+ *   nh_cut_plan, nh_logmel_chunks_rows
+ *                                 (no counterpart: the reference re-seeks sequentially, model.rs:100-146) the clips of a long
+ *                                 recording for the batched path, cut in pauses
  *   nh_encode                     Type::encoder_forward (model.rs:168, :455-464)
  *   nh_decode_greedy              Model::decode at t = 0 (model.rs:279-389) including the logit
  *                                 rules (model.rs:212-277), batched, on device
@@ -185,6 +188,45 @@ int nh_resample(nh_ctx *ctx, const void *frames, int on_device, int sample_dtype
  * rules; row0 = 0 is the plain batch).  No copy back, no synchronisation. */
 int nh_logmel_resampled_rows(nh_ctx *ctx, const void *frames, int on_device, int sample_dtype, int channels, int src_hz,
                              const int32_t *n_frames, int64_t stride_frames, int batch, int row0);
+/* ---- long recordings: cut chunks at the quietest frame, on the device --------------------------------------
+ * The reference walks a recording sequentially and re-seeks to its last timestamp (model.rs:100-146); the batched path
+ * decodes independent clips of at most 30 s.  nh_cut_plan chooses their boundaries in pauses instead of every 480 000
+ * samples.  A recording is N >= 1 f32 mono samples at 16 kHz, in host or device memory; F = ceil(N / 160) analysis frames
+ * (160 samples: the log-mel hop, half a timestamp unit), W = half_window.  All arithmetic is IEEE f32, unfused:
+ *   1 e[f]: acc = 0; for j = 0 .. 159 ascending: x = pcm[160 f + j] (0 at or past N), p = x * x, acc = acc + p.  One
+ *     accumulator in that order: a frame's bits do not depend on tiling, on N or on where the samples live.
+ *   2 E[f]: acc = 0; for k = -W .. W ascending: acc = acc + e[f + k], a frame outside [0, F) adding 0.0f.
+ *   3 s_0 = 0; while F - s_k > max_frames: best = +inf, c* = s_k + max_frames; for c = s_k + min_frames .. s_k + max_frames
+ *     ascending: if E[c] <= best then best = E[c], c* = c; s_{k+1} = c*.  So a cut is the LATEST minimum of its range, a
+ *     NaN is never chosen, and an all-NaN range cuts at s_k + max_frames.  Chunk k starts at starts[k] = 160 s_k and is
+ *     lens[k] = min(160 (s_{k+1} - s_k), N - starts[k]) samples long; the last chunk runs to N.
+ *   4 stages 1 - 3 run on the context's stream without returning to the host between cuts; only starts, lens and the count
+ *     come back, and the call returns when they are on the host.
+ * Refused with NH_ERR_INVALID, nothing launched, starts / lens and the view of nh_cut_energy untouched: n_samples < 1 or
+ * > 2^31 - 1; max_frames outside 1 .. 3000; min_frames outside 1 .. max_frames; half_window outside 0 .. 100.  cap smaller
+ * than the number of chunks is refused the same way as far as the caller can see -- starts, lens and the view of the plan
+ * before stay as they were -- but *n_chunks is set to the number needed, so the caller can retry (the number is known only
+ * once the search has run: it runs in a second workspace that becomes the view when the call succeeds).
+ * Host PCM is staged in groups of whole frames that keep the staging at or under 256 MiB.  Staging and workspaces are
+ * allocated by the first call that needs them and grow on demand.  The call touches nothing else in the context and is
+ * legal in any state (before the tensors are loaded, beside a running decode pool).
+ * Results for samples whose squares are subnormal are unspecified up to a flush to zero. */
+#define NH_CUT_HOP 160                       /* samples per analysis frame: the log-mel hop, half a timestamp unit */
+typedef struct nh_cut_params { int32_t max_frames, min_frames, half_window; } nh_cut_params;
+/* p == NULL: the defaults {3000, 2000, 15}: chunks of at most 30 s, the cut searched in their last 10 s, a 0.31 s window.
+ * starts: host i64 [cap], lens: host i32 [cap], n_chunks: host i32 [1]. */
+int nh_cut_plan(nh_ctx *ctx, const float *pcm, int on_device, int64_t n_samples, const nh_cut_params *p,
+                int64_t *starts, int32_t *lens, int cap, int32_t *n_chunks);
+/* Parity view of the LAST successful plan: e and E, F floats each (host; either may be NULL).  NH_ERR_STATE before any
+ * plan, NH_ERR_INVALID if cap_frames < F. */
+int nh_cut_energy(nh_ctx *ctx, float *e, float *E, int64_t cap_frames);
+/* Clip b = pcm[starts[b] .. starts[b] + n_samples[b]) of a recording in host or device (on_device != 0) memory goes to the
+ * context's PCM row row0 + b; then exactly what nh_logmel_device_rows does on those rows (same row rules, the bits of a
+ * log-mel of a copy of those samples).  No copy back, no synchronisation.  starts[b] >= 0, 1 <= n_samples[b] <= 480000.
+ * A clip of fewer than 160 samples produces 1500 mel frames, not 3000, and is refused beside longer clips like in every
+ * nh_logmel*; of a plan only the final chunk can be that short. */
+int nh_logmel_chunks_rows(nh_ctx *ctx, const float *pcm, int on_device, const int64_t *starts,
+                          const int32_t *n_samples, int batch, int row0);
 /* Same, but pcm is a DEVICE pointer (already resident in HBM; no copy). */
 int nh_logmel_device(nh_ctx *ctx, const float *pcm_dev, const int32_t *n_samples, int64_t stride, int batch);
 /* Encoder forward over the mel of the last nh_logmel call (flush = true semantics: the cross

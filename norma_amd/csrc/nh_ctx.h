@@ -1,6 +1,7 @@
-// nh_ctx.h -- the state behind the C ABI of include/norma_hip.h, shared by the five files that implement it: nh_model.hip
+// nh_ctx.h -- the state behind the C ABI of include/norma_hip.h, shared by the six files that implement it: nh_model.hip
 // (create / destroy, weights, tokens, options, timings), nh_encode.hip (log-mel, encoder), nh_decode.hip (decoder step,
-// lockstep decode, decode pool, parity views), nh_align.hip (token-level timestamps), nh_resample.hip (audio ingest).  No torch, no candle, no CPU fallback:
+// lockstep decode, decode pool, parity views), nh_align.hip (token-level timestamps), nh_resample.hip (audio ingest),
+// nh_cut.hip (cutting long recordings).  No torch, no candle, no CPU fallback:
 // an entry point runs the HIP path or fails.
 #pragma once
 #include <math.h>
@@ -138,6 +139,19 @@ struct AlignLive {
     std::vector<int32_t> n, done;
 };
 
+// nh_cut_plan: everything it owns, allocated by the first call that needs it and grown on demand (a context that never plans
+// holds nothing), freed by nh_destroy.  Two (e, E) workspaces: a plan computes into the one that is not the view of
+// nh_cut_energy and becomes the view only when it succeeds, so a refused call -- cap too small is known only after the
+// search -- leaves the view of the plan before as it was.
+struct CutState {
+    struct Ws { float *e = nullptr, *E = nullptr; long long frames = 0; } ws[2];
+    int view = -1;               // the workspace of the last successful plan; -1: none yet
+    long long F = 0;             // its frames
+    float *stage = nullptr; size_t stage_bytes = 0;   // staging of host PCM, at most 256 MiB
+    long long *starts = nullptr; int32_t *lens = nullptr; int32_t *count = nullptr;   // the search's outputs, [out_cap], [out_cap], [1]
+    long long out_cap = 0;
+};
+
 struct nh_ctx {
     int dev = 0;
     std::shared_ptr<nh_model> mdl;
@@ -161,6 +175,7 @@ struct nh_ctx {
     // them (contexts that never resample hold nothing), freed by nh_destroy
     void *rs_stage = nullptr; size_t rs_stage_bytes = 0;
     ResampleClip *rs_clips = nullptr;
+    CutState cut;               // nh_cut_plan, nh_cut_energy
     int32_t *nsamp = nullptr;
     float *mel32 = nullptr;
     unsigned *chunk_max = nullptr;

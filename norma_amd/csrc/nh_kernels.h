@@ -245,8 +245,29 @@ static inline size_t resample_lds_bytes(int L, int M, int T) {
 // false (nothing launched): the window does not fit the LDS of a CU, or an unknown sample type
 [[nodiscard]] bool launch_resample(const ResampleParams &p, hipStream_t st);
 
+// ---- long recordings: frame energies, window energies and the cut search (k_cut.hip; the contract is DESIGN.md 11) -------
+#define NH_CUT_FRAME 160      // == NH_CUT_HOP of the public header
+#define NH_CUT_TILE 128       // frames per workgroup of the energy kernel
+#define NH_CUT_ROW 161        // LDS row stride in floats: 160 would put the 32 lanes that read one column onto one bank
+static inline size_t cut_lds_bytes() { return sizeof(float) * (size_t)NH_CUT_TILE * NH_CUT_ROW; }
+// e[f] for f < n_frames: the ordered sum of squares of pcm[160 f .. 160 f + 159] (device memory), samples at or past
+// n_valid taken as 0.  1 <= n_valid, n_frames >= 1; pcm[0] must be readable.
+void launch_cut_energy(const float *pcm, long long n_valid, float *e, long long n_frames, hipStream_t st);
+// E[f] = e[f - W] + .. + e[f + W] in that order, frames outside [0, F) adding 0.0f
+void launch_cut_window(const float *e, float *E, long long F, int W, hipStream_t st);
+struct CutSearch {
+    const float *E; long long F;        // window energies of the F frames
+    int min_frames, max_frames;         // 1 <= min_frames <= max_frames
+    long long n_samples;                // of the recording: the last chunk runs up to it
+    long long *starts; int32_t *lens;   // [cap]: chunk k, for k < cap
+    int32_t *count;                     // [1]: the number of chunks, written last, whatever cap is
+    long long cap;
+};
+// one workgroup walks the chunks (the sequential loop of the contract, each search a parallel arg-min)
+void launch_cut_search(const CutSearch &p, hipStream_t st);
+
 // ---- log-mel -------------------------------------------------------------------------------------------
-struct MelTables {      // device pointers, built once on the host with libm (bit-identical twiddles)
+struct MelTables {     // device pointers, built once on the host with libm (bit-identical twiddles)
     const float *hann;      // [400]
     const float *dft_cos;   // [25][25]  cos(2pi*k*j/25) evaluated as candle's dft() does in f32
     const float *dft_sin;   // [25][25]

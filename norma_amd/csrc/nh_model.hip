@@ -49,6 +49,9 @@ extern "C" void nh_destroy(nh_ctx *ctx) {
     if (ctx->align_q) hipFree(ctx->align_q);
     if (ctx->rs_stage) hipFree(ctx->rs_stage);
     if (ctx->rs_clips) hipFree(ctx->rs_clips);
+    for (auto &w : ctx->cut.ws) { if (w.e) hipFree(w.e); if (w.E) hipFree(w.E); }
+    for (void *p : {(void *)ctx->cut.stage, (void *)ctx->cut.starts, (void *)ctx->cut.lens, (void *)ctx->cut.count})
+        if (p) hipFree(p);
     drop_graphs(ctx);
     if (ctx->h_done) hipHostFree(ctx->h_done);
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);

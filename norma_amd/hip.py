@@ -22,6 +22,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "norma_hip.h")
 
 N_SAMPLES = 480000
 N_FRAMES = 3000
+NH_CUT_HOP = 160     # samples per analysis frame of cut_plan
 NH_DTYPE_F32, NH_DTYPE_F16 = 0, 1
 NH_ERR_NOMEM = 4
 NH_LANG_DETECT = -2   # `lang` of pool_admit*: the row detects its language in its first step (pool_detect_languages)
@@ -60,6 +61,11 @@ class NhDecodeResult(C.Structure):
 
 class NhAlignHead(C.Structure):
     _fields_ = [("layer", C.c_int32), ("head", C.c_int32)]
+
+
+class NhCutParams(C.Structure):
+    """nh_cut_params: analysis frames of 160 samples (nh_cut_plan); the defaults are {3000, 2000, 15}"""
+    _fields_ = [("max_frames", C.c_int32), ("min_frames", C.c_int32), ("half_window", C.c_int32)]
 
 
 class NhTimings(C.Structure):
@@ -119,6 +125,9 @@ def load_library() -> C.CDLL:
     L.nh_resample_table.argtypes = [vp, C.c_int, fp, ip, ip, ip]
     L.nh_resample.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int64, C.c_int, i64p, ip, fp, C.c_int64]
     L.nh_logmel_resampled_rows.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int64, C.c_int, C.c_int]
+    L.nh_cut_plan.argtypes = [vp, vp, C.c_int, C.c_int64, C.POINTER(NhCutParams), i64p, ip, C.c_int, ip]
+    L.nh_cut_energy.argtypes = [vp, fp, fp, C.c_int64]
+    L.nh_logmel_chunks_rows.argtypes = [vp, vp, C.c_int, i64p, ip, C.c_int, C.c_int]
     L.nh_encode.argtypes = [vp]
     L.nh_decode_greedy.argtypes = [vp, ip, C.POINTER(NhDecodeResult), C.c_int]
     L.nh_decode_sampled.argtypes = [vp, ip, C.POINTER(NhDecodeResult), C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_uint32]
@@ -361,6 +370,52 @@ class HipWhisper:
                          dtype=None, channels: int = 1):
         """the plain batch: logmel_resampled_rows with row0 = 0"""
         self.logmel_resampled_rows(frames, src_hz, 0, n_frames, stride_frames, dtype, channels)
+
+    # -- long recordings (include/norma_hip.h: nh_cut_plan, nh_logmel_chunks_rows): cut at the quietest frame, on the device
+    @staticmethod
+    def _recording(pcm, n_samples):
+        """(pointer, on_device, samples, keep-alive) of a host f32 array or of a device pointer with n_samples given"""
+        if isinstance(pcm, np.ndarray):
+            a = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+            return a.ctypes.data_as(C.c_void_p), 0, len(a) if n_samples is None else int(n_samples), a
+        return C.c_void_p(int(pcm)), 1, int(n_samples), None
+
+    def cut_plan(self, pcm, n_samples: Optional[int] = None, params=None):
+        """nh_cut_plan: (starts i64 [n], lens i32 [n]) of the chunks of a 16 kHz mono recording -- a host f32 array, or a
+        device pointer with n_samples.  params: None (the defaults {3000, 2000, 15}), an NhCutParams, or a tuple
+        (max_frames, min_frames, half_window)."""
+        ptr, dev, n, keep = self._recording(pcm, n_samples)
+        q = None if params is None else params if isinstance(params, NhCutParams) else NhCutParams(*[int(v) for v in params])
+        cap = max(4, 2 * (n // (NH_CUT_HOP * (q.max_frames if q is not None and q.max_frames > 0 else N_FRAMES))) + 2)
+        while True:
+            starts, lens, cnt = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int32), C.c_int32(0)
+            rc = self.L.nh_cut_plan(self._h, ptr, dev, n, None if q is None else C.byref(q),
+                                    starts.ctypes.data_as(C.POINTER(C.c_int64)), _ip(lens), cap, C.byref(cnt))
+            if rc != 0 and cnt.value > cap:   # refused for cap alone: the call says how many there are
+                cap = int(cnt.value)
+                continue
+            self._chk(rc)
+            self._cut_frames = -(-n // NH_CUT_HOP)
+            return starts[:cnt.value].copy(), lens[:cnt.value].copy()
+
+    def cut_energy(self):
+        """(e, E) f32 [F] of the last cut_plan: frame and window energies (nh_cut_energy)"""
+        F = getattr(self, "_cut_frames", 0)
+        e, E = np.zeros(F, dtype=np.float32), np.zeros(F, dtype=np.float32)
+        self._chk(self.L.nh_cut_energy(self._h, _fp(e), _fp(E), F))
+        return e, E
+
+    def logmel_chunks_rows(self, pcm, starts: Sequence[int], lens: Sequence[int], row0: int = 0):
+        """nh_logmel_chunks_rows: clips pcm[starts[b] : starts[b] + lens[b]] of a recording (host f32 array or device
+        pointer) -> log-mel of rows [row0, row0 + len(starts))"""
+        ptr, dev, _, keep = self._recording(pcm, 0)
+        st = np.ascontiguousarray(starts, dtype=np.int64)
+        ns = np.ascontiguousarray(lens, dtype=np.int32)
+        assert len(st) == len(ns)
+        if keep is not None and len(st):
+            assert int(st.min()) >= 0 and int((st + ns).max()) <= len(keep), "a clip leaves the recording"
+        self._chk(self.L.nh_logmel_chunks_rows(self._h, ptr, dev, st.ctypes.data_as(C.POINTER(C.c_int64)), _ip(ns), len(ns), int(row0)))
+        self.batch = row0 + len(ns) if row0 > 0 else len(ns)
 
     def logmel_device(self, pcm_dev_ptr: int, n_samples: Sequence[int], stride: int):
         """PCM already resident in HBM (device pointer, f32 [batch][stride])."""

@@ -1,0 +1,88 @@
+"""One call for a whole recording: plan the cuts on the device (HipWhisper.cut_plan: the quietest frame near the end of every
+clip of at most 30 s), run the chunks through log-mel, encoder and greedy decode in groups, and join the chunks' segments on
+one time axis.  The contract of the cuts is in include/norma_hip.h and DESIGN.md 11.
+
+The reference walks a recording sequentially and re-seeks to its last timestamp (`model.rs:100-146`); here the chunks are
+independent, which is what lets them be batched.  `stitch` delimits segments the way `model.rs:100-105` does.
+"""
+from typing import List, Sequence, Tuple
+
+import numpy as np
+
+SAMPLE_RATE = 16000
+KEY_SAMPLES = 320      # samples per encoder frame (20 ms): one timestamp unit
+MIN_MEL_SAMPLES = 160  # a shorter clip produces 1500 mel frames, not 3000, and cannot share a batch with longer ones
+
+
+def _groups(lens: Sequence[int], max_batch: int) -> List[Tuple[int, int]]:
+    """[first, last) of consecutive chunks submitted together: at most max_batch, and a chunk of fewer than 160 samples
+    (only the final one can be) alone"""
+    out, a, n = [], 0, len(lens)
+    while a < n:
+        b = a + 1
+        if lens[a] >= MIN_MEL_SAMPLES:
+            while b < n and b - a < max_batch and lens[b] >= MIN_MEL_SAMPLES:
+                b += 1
+        out.append((a, b))
+        a = b
+    return out
+
+
+def transcribe_recording(hm, pcm, params=None, max_new_tokens: int = 0, align: bool = False) -> List[dict]:
+    """hm: a HipWhisper with weights, filters and tokens set.  pcm: a host f32 array (16 kHz mono), or (device pointer,
+    n_samples).  params: the cut parameters (HipWhisper.cut_plan).  Returns one dict per chunk: the fields of decode_greedy
+    plus start_sample, n_samples and n_keys = ceil(n_samples / 320), the encoder frames that hold audio.  align=True (the
+    caller has set hm.align_capture): token_first / token_last of align_decoded(n_keys=...) as well."""
+    if isinstance(pcm, np.ndarray):
+        rec, n = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1), None
+    else:
+        rec, n = int(pcm[0]), int(pcm[1])
+    starts, lens = hm.cut_plan(rec, n, params)
+    out = []
+    for a, b in _groups(lens, hm.max_batch):
+        hm.logmel_chunks_rows(rec, starts[a:b], lens[a:b], 0)
+        hm.encode()
+        res = hm.decode_greedy(max_new_tokens)
+        keys = [-(-int(v) // KEY_SAMPLES) for v in lens[a:b]]
+        if align:
+            first, last = hm.align_decoded(n_keys=keys)
+        for i, r in enumerate(res):
+            r.update(start_sample=int(starts[a + i]), n_samples=int(lens[a + i]), n_keys=keys[i])
+            if align:
+                r.update(token_first=first[i].copy(), token_last=last[i].copy())
+            out.append(r)
+    return out
+
+
+def stitch(results: Sequence[dict], tokens) -> List[Tuple[float, float, List[int]]]:
+    """results: what transcribe_recording returned; tokens: the vocabulary's special tokens (eot, no_timestamps).
+    Returns (start_s, end_s, token_ids) per segment, in order, on the recording's own time axis: a chunk's tokens are split
+    at its timestamp tokens the way model.rs:100-105 delimits segments (a boundary token is a timestamp or eot; a segment
+    runs from one boundary token to the next, both excluded from token_ids), and a timestamp token `t` of a chunk stands for
+    start_sample / 16000 + 0.02 * (t - no_timestamps - 1) seconds.  A segment the decode left open (closed by eot instead of
+    a timestamp) ends with its chunk.  Segments without text and chunks ended by the no-speech exit contribute nothing."""
+    def boundary(t):
+        return t > tokens.no_timestamps or t == tokens.eot
+
+    out = []
+    for r in results:
+        if r.get("no_speech_exit"):
+            continue
+        t0 = r["start_sample"] / SAMPLE_RATE
+        v = list(r["tokens"])
+        i = 0
+        while True:
+            s = next((j for j in range(i, len(v)) if boundary(v[j])), None)
+            if s is None or v[s] == tokens.eot:
+                break
+            e = next((j for j in range(s + 1, len(v)) if boundary(v[j])), None)
+            if e is None:
+                break
+            start = t0 + 0.02 * (v[s] - tokens.no_timestamps - 1)
+            end = (r["start_sample"] + r["n_samples"]) / SAMPLE_RATE if v[e] == tokens.eot else t0 + 0.02 * (v[e] - tokens.no_timestamps - 1)
+            if e > s + 1:
+                out.append((start, end, v[s + 1:e]))
+            if v[e] == tokens.eot:
+                break
+            i = e + 1
+    return out
