@@ -145,7 +145,8 @@ int nh_logmel(nh_ctx *ctx, const float *pcm, const int32_t *n_samples, int64_t s
 #define NH_SAMPLE_U64 9
 /* Bytes per sample of an NH_SAMPLE_* type (0: unknown). */
 int nh_sample_size(int sample_dtype);
-/* Like nh_logmel, with `pcm` holding samples of type `sample_dtype` (host memory, `stride` SAMPLES between clips). */
+/* Like nh_logmel, with `pcm` holding samples of type `sample_dtype` (host memory, `stride` SAMPLES between clips).  The
+ * samples are staged and converted as nh_resample's host frames are, at 16 kHz and one channel (f32 goes to nh_logmel). */
 int nh_logmel_samples(nh_ctx *ctx, const void *pcm, int sample_dtype, const int32_t *n_samples, int64_t stride, int batch);
 /* ---- audio ingest: channel mixdown and resampling to 16 kHz on the device --------------------------------
  * The capture side of the reference mixes the device's channels down to mono and, when the device's rate is not
@@ -179,8 +180,9 @@ int nh_resample_table(nh_ctx *ctx, int src_hz, float *coef, int32_t *L, int32_t 
  * n_frames[b] frames.  num0: host i64 [batch] or NULL (0); n_out: host i32 [batch] or NULL (the whole clip).  The result
  * lands in the context's PCM rows -- row b at b * 480000 floats, where nh_logmel puts host PCM -- and, when out_host is
  * given, is copied there (clip b at b * out_stride floats) and the stream synchronised.  Host frames are staged in groups
- * of clips that keep the native staging at or under 256 MiB (a clip that needs more on its own is staged alone); staging is
- * allocated by the first call that needs it.  One launch per group; device frames: one launch. */
+ * of clips that keep the native staging at or under 256 MiB (a clip that needs more on its own is staged alone).  The
+ * context has ONE staging, shared by nh_resample*, nh_logmel_samples and nh_cut_plan, allocated by the first call that
+ * needs it and grown on demand.  One launch per group; device frames: one launch. */
 int nh_resample(nh_ctx *ctx, const void *frames, int on_device, int sample_dtype, int channels, int src_hz,
                 const int32_t *n_frames, int64_t stride_frames, int batch, const int64_t *num0, const int32_t *n_out,
                 float *out_host, int64_t out_stride);
@@ -207,8 +209,8 @@ int nh_logmel_resampled_rows(nh_ctx *ctx, const void *frames, int on_device, int
  * than the number of chunks is refused the same way as far as the caller can see -- starts, lens and the view of the plan
  * before stay as they were -- but *n_chunks is set to the number needed, so the caller can retry (the number is known only
  * once the search has run: it runs in a second workspace that becomes the view when the call succeeds).
- * Host PCM is staged in groups of whole frames that keep the staging at or under 256 MiB.  Staging and workspaces are
- * allocated by the first call that needs them and grow on demand.  The call touches nothing else in the context and is
+ * Host PCM is staged in groups of whole frames that keep the staging at or under 256 MiB (the context's one staging, see
+ * nh_resample).  Staging and workspaces are allocated by the first call that needs them and grow on demand.  The call touches nothing else in the context and is
  * legal in any state (before the tensors are loaded, beside a running decode pool).
  * Results for samples whose squares are subnormal are unspecified up to a flush to zero. */
 #define NH_CUT_HOP 160                       /* samples per analysis frame: the log-mel hop, half a timestamp unit */

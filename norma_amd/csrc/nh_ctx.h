@@ -1,8 +1,10 @@
 // nh_ctx.h -- the state behind the C ABI of include/norma_hip.h, shared by the six files that implement it: nh_model.hip
 // (create / destroy, weights, tokens, options, timings), nh_encode.hip (log-mel, encoder), nh_decode.hip (decoder step,
 // lockstep decode, decode pool, parity views), nh_align.hip (token-level timestamps), nh_resample.hip (audio ingest),
-// nh_cut.hip (cutting long recordings).  No torch, no candle, no CPU fallback:
-// an entry point runs the HIP path or fails.
+// nh_cut.hip (cutting long recordings).  It also holds the two things every audio route into the PCM rows shares: the
+// grow-on-demand device buffer (DevBuf: the one staging of host audio, the cut workspaces) and the batch check
+// (check_batch) that runs before anything is queued.  No torch, no candle, no CPU fallback: an entry point runs the HIP
+// path or fails.
 #pragma once
 #include <math.h>
 #include <stdio.h>
@@ -139,17 +141,29 @@ struct AlignLive {
     std::vector<int32_t> n, done;
 };
 
-// nh_cut_plan: everything it owns, allocated by the first call that needs it and grown on demand (a context that never plans
-// holds nothing), freed by nh_destroy.  Two (e, E) workspaces: a plan computes into the one that is not the view of
-// nh_cut_energy and becomes the view only when it succeeds, so a refused call -- cap too small is known only after the
-// search -- leaves the view of the plan before as it was.
+// A device scratch buffer that grows on demand: empty until the first call that needs it (a context that never stages or
+// plans holds nothing), released with the context it is a member of -- nh_destroy names none of them.
+struct nh_ctx;
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) hipFree(p); }   // nh_destroy has made the device current and drained the stream
+    // room for `need` bytes (contents are not kept); on failure the buffer is empty and NH_ERR_NOMEM names `what`
+    int reserve(nh_ctx *ctx, size_t need, const char *what);
+};
+
+// nh_cut_plan: everything it owns.  Two (e, E) workspaces: a plan computes into the one that is not the view of nh_cut_energy
+// and becomes the view only when it succeeds, so a refused call -- cap too small is known only after the search -- leaves the
+// view of the plan before as it was.
 struct CutState {
-    struct Ws { float *e = nullptr, *E = nullptr; long long frames = 0; } ws[2];
+    DevBuf ws[2];                // e[F] then E[F] of the plan computed there
     int view = -1;               // the workspace of the last successful plan; -1: none yet
     long long F = 0;             // its frames
-    float *stage = nullptr; size_t stage_bytes = 0;   // staging of host PCM, at most 256 MiB
-    long long *starts = nullptr; int32_t *lens = nullptr; int32_t *count = nullptr;   // the search's outputs, [out_cap], [out_cap], [1]
-    long long out_cap = 0;
+    DevBuf out;                  // the search's outputs: starts[cap] (64-bit) then lens[cap]
+    int32_t *count = nullptr;    // [1], in ctx->allocs
 };
 
 struct nh_ctx {
@@ -170,11 +184,12 @@ struct nh_ctx {
     std::vector<KvCache> kv;    // [decoder_layers]; the weights are read from mdl
     // mel
     float *pcm = nullptr;
-    void *raw = nullptr; size_t raw_bytes = 0;   // native-sample staging of nh_logmel_samples
-    // nh_resample: native staging of host frames and the per-clip records of a call; allocated by the first call that needs
-    // them (contexts that never resample hold nothing), freed by nh_destroy
-    void *rs_stage = nullptr; size_t rs_stage_bytes = 0;
-    ResampleClip *rs_clips = nullptr;
+    // The one staging of host audio on its way to the PCM rows or the cut energies (nh_logmel_samples, nh_resample*,
+    // nh_cut_plan): at most NH_STAGE_BYTES, except a single resample clip that alone needs more.  Every use is a copy on the
+    // context's stream with the kernel that reads it queued right behind, so the stream orders the next copy, whoever
+    // makes it, behind the kernel that read the bytes before.
+    DevBuf stage;
+    ResampleClip *rs_clips = nullptr;   // [max_batch] per-clip records of a resample call, made by the first one
     CutState cut;               // nh_cut_plan, nh_cut_energy
     int32_t *nsamp = nullptr;
     float *mel32 = nullptr;
@@ -245,9 +260,25 @@ static T *dalloc_into(std::vector<void *> &allocs, size_t n, bool zero = true) {
 template <typename T>
 static T *dalloc(nh_ctx *ctx, size_t n, bool zero = true) { return dalloc_into<T>(ctx->allocs, n, zero); }
 
+#define NH_STAGE_BYTES (256ull << 20)   // ctx->stage per group of clips or frames (the alignment workspace's figure)
+
+inline int DevBuf::reserve(nh_ctx *ctx, size_t need, const char *what) {
+    if (bytes >= need) return NH_OK;
+    HIPCHK(hipStreamSynchronize(ctx->st));   // nothing may still read what goes away
+    if (p) hipFree(p);
+    p = nullptr; bytes = 0;
+    if (hipMalloc(&p, need) != hipSuccess) { p = nullptr; return ctx->fail(NH_ERR_NOMEM, std::string("hipMalloc(") + what + ")"); }
+    bytes = need;
+    return NH_OK;
+}
+
 void drop_graphs(nh_ctx *ctx, int first = 0);   // nh_decode.hip
 void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr = nullptr, bool final_ln = true, bool skip_done = false,
                   const AlignHeadSet *keep = nullptr);   // nh_decode.hip
 int ensure_decoder_repack(nh_ctx *ctx);         // nh_model.hip
-// nh_encode.hip: log-mel of `batch` clips of device PCM into rows row0 .. (what nh_logmel_device_rows does after its checks)
+// nh_encode.hip: may `batch` clips of these lengths become rows row0 .. of the context's mel batch?  Row range, clip lengths,
+// equal mel frames, the pool and row-gap rules.  Changes nothing in the context: every entry point that fills PCM rows
+// calls it before its first copy or launch.
+int check_batch(nh_ctx *ctx, const int32_t *n_samples, int batch, int row0 = 0);
+// ... and what follows an accepted check: the batch becomes the context's, then the log-mel of the clips of device PCM
 int run_logmel(nh_ctx *ctx, const float *pcm_dev, const int32_t *n_samples, int64_t stride, int batch, int row0 = 0);

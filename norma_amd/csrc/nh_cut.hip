@@ -3,45 +3,8 @@
 // the planned clips to the log-mel.  The contract is in the header and in DESIGN.md 11.
 #include "nh_ctx.h"
 
-#define CUT_STAGE_BYTES (256ull << 20)    // staging of host PCM per group of frames (nh_resample's figure)
-#define CUT_STAGE_FRAMES ((long long)(CUT_STAGE_BYTES / (sizeof(float) * NH_CUT_HOP)))
+#define CUT_STAGE_FRAMES ((long long)(NH_STAGE_BYTES / (sizeof(float) * NH_CUT_HOP)))
 static_assert(NH_CUT_HOP == NH_CUT_FRAME, "the public hop is the kernels' frame");
-
-// room for F frames in workspace w; the view's workspace is never the one that grows
-static int cut_workspace(nh_ctx *ctx, CutState::Ws &w, long long F) {
-    if (w.frames >= F) return NH_OK;
-    HIPCHK(hipStreamSynchronize(ctx->st));   // nothing may still read what goes away
-    if (w.e) hipFree(w.e);
-    if (w.E) hipFree(w.E);
-    w.e = w.E = nullptr; w.frames = 0;
-    if (hipMalloc(reinterpret_cast<void **>(&w.e), sizeof(float) * (size_t)F) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&w.E), sizeof(float) * (size_t)F) != hipSuccess) {
-        if (w.e) hipFree(w.e);
-        w.e = w.E = nullptr;
-        return ctx->fail(NH_ERR_NOMEM, "hipMalloc(frame energies)");
-    }
-    w.frames = F;
-    return NH_OK;
-}
-
-static int cut_outputs(nh_ctx *ctx, long long cap) {
-    CutState &cs = ctx->cut;
-    if (!cs.count && hipMalloc(reinterpret_cast<void **>(&cs.count), sizeof(int32_t)) != hipSuccess)
-        return ctx->fail(NH_ERR_NOMEM, "hipMalloc(chunk count)");
-    if (cs.out_cap >= cap) return NH_OK;
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    if (cs.starts) hipFree(cs.starts);
-    if (cs.lens) hipFree(cs.lens);
-    cs.starts = nullptr; cs.lens = nullptr; cs.out_cap = 0;
-    if (hipMalloc(reinterpret_cast<void **>(&cs.starts), sizeof(long long) * (size_t)cap) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&cs.lens), sizeof(int32_t) * (size_t)cap) != hipSuccess) {
-        if (cs.starts) hipFree(cs.starts);
-        cs.starts = nullptr;
-        return ctx->fail(NH_ERR_NOMEM, "hipMalloc(chunk records)");
-    }
-    cs.out_cap = cap;
-    return NH_OK;
-}
 
 extern "C" int nh_cut_plan(nh_ctx *ctx, const float *pcm, int on_device, int64_t n_samples, const nh_cut_params *p,
                            int64_t *starts, int32_t *lens, int cap, int32_t *n_chunks) {
@@ -54,33 +17,31 @@ extern "C" int nh_cut_plan(nh_ctx *ctx, const float *pcm, int on_device, int64_t
     hipSetDevice(ctx->dev);
     CutState &cs = ctx->cut;
     const long long N = n_samples, F = (N + NH_CUT_HOP - 1) / NH_CUT_HOP;
-    CutState::Ws &w = cs.ws[cs.view == 0 ? 1 : 0];
-    if (int rc = cut_workspace(ctx, w, F)) return rc;
+    const int into = cs.view == 0 ? 1 : 0;   // the view's workspace is never the one that grows
+    if (int rc = cs.ws[into].reserve(ctx, sizeof(float) * 2 * (size_t)F, "frame energies")) return rc;
+    float *const e = static_cast<float *>(cs.ws[into].p), *const E = e + F;
     // a chunk that is not the last holds at least min_frames frames; the device records at most what the caller can take
     const long long bound = F / q.min_frames + 1;
     const long long kcap = std::min(bound, (long long)std::max(cap, 1));
-    if (int rc = cut_outputs(ctx, kcap)) return rc;
+    if (!cs.count && !(cs.count = dalloc<int32_t>(ctx, 1, false))) return ctx->fail(NH_ERR_NOMEM, "hipMalloc(chunk count)");
+    if (int rc = cs.out.reserve(ctx, (sizeof(long long) + sizeof(int32_t)) * (size_t)kcap, "chunk records")) return rc;
+    long long *const d_starts = static_cast<long long *>(cs.out.p);
+    int32_t *const d_lens = reinterpret_cast<int32_t *>(d_starts + kcap);
     if (on_device) {
-        launch_cut_energy(pcm, N, w.e, F, ctx->st);
+        launch_cut_energy(pcm, N, e, F, ctx->st);
     } else {
-        const size_t need = sizeof(float) * (size_t)std::min(N, CUT_STAGE_FRAMES * NH_CUT_HOP);
-        if (cs.stage_bytes < need) {
-            HIPCHK(hipStreamSynchronize(ctx->st));
-            if (cs.stage) hipFree(cs.stage);
-            cs.stage = nullptr; cs.stage_bytes = 0;
-            if (hipMalloc(reinterpret_cast<void **>(&cs.stage), need) != hipSuccess) return ctx->fail(NH_ERR_NOMEM, "hipMalloc(PCM staging)");
-            cs.stage_bytes = need;
-        }
-        for (long long f0 = 0; f0 < F; f0 += CUT_STAGE_FRAMES) {   // the stream orders a group's copy behind the kernel that read the one before
+        if (int rc = ctx->stage.reserve(ctx, sizeof(float) * (size_t)std::min(N, CUT_STAGE_FRAMES * NH_CUT_HOP), "PCM staging")) return rc;
+        float *const stage = static_cast<float *>(ctx->stage.p);
+        for (long long f0 = 0; f0 < F; f0 += CUT_STAGE_FRAMES) {
             const long long nf = std::min(CUT_STAGE_FRAMES, F - f0), ns = std::min(nf * NH_CUT_HOP, N - f0 * NH_CUT_HOP);
-            HIPCHK(hipMemcpyAsync(cs.stage, pcm + f0 * NH_CUT_HOP, sizeof(float) * (size_t)ns, hipMemcpyHostToDevice, ctx->st));
-            launch_cut_energy(cs.stage, ns, w.e + f0, nf, ctx->st);
+            HIPCHK(hipMemcpyAsync(stage, pcm + f0 * NH_CUT_HOP, sizeof(float) * (size_t)ns, hipMemcpyHostToDevice, ctx->st));
+            launch_cut_energy(stage, ns, e + f0, nf, ctx->st);
         }
     }
-    launch_cut_window(w.e, w.E, F, q.half_window, ctx->st);
+    launch_cut_window(e, E, F, q.half_window, ctx->st);
     CutSearch s{};
-    s.E = w.E; s.F = F; s.min_frames = q.min_frames; s.max_frames = q.max_frames; s.n_samples = N;
-    s.starts = cs.starts; s.lens = cs.lens; s.count = cs.count; s.cap = kcap;
+    s.E = E; s.F = F; s.min_frames = q.min_frames; s.max_frames = q.max_frames; s.n_samples = N;
+    s.starts = d_starts; s.lens = d_lens; s.count = cs.count; s.cap = kcap;
     launch_cut_search(s, ctx->st);
     HIPCHK(hipGetLastError());
     int32_t n = 0;
@@ -88,10 +49,10 @@ extern "C" int nh_cut_plan(nh_ctx *ctx, const float *pcm, int on_device, int64_t
     HIPCHK(hipStreamSynchronize(ctx->st));
     *n_chunks = n;
     if (n > cap) return ctx->fail(NH_ERR_INVALID, "nh_cut_plan: the plan has " + std::to_string(n) + " chunks, cap is " + std::to_string(cap));
-    HIPCHK(hipMemcpyAsync(starts, cs.starts, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipMemcpyAsync(lens, cs.lens, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipMemcpyAsync(starts, d_starts, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipMemcpyAsync(lens, d_lens, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipStreamSynchronize(ctx->st));
-    cs.view = (int)(&w - cs.ws);
+    cs.view = into;
     cs.F = F;
     return NH_OK;
 }
@@ -102,9 +63,9 @@ extern "C" int nh_cut_energy(nh_ctx *ctx, float *e, float *E, int64_t cap_frames
     if (cs.view < 0) return ctx->fail(NH_ERR_STATE, "nh_cut_energy: no plan yet");
     if (cap_frames < cs.F) return ctx->fail(NH_ERR_INVALID, "nh_cut_energy: the last plan has " + std::to_string(cs.F) + " frames");
     hipSetDevice(ctx->dev);
-    const CutState::Ws &w = cs.ws[cs.view];
-    if (e) HIPCHK(hipMemcpyAsync(e, w.e, sizeof(float) * (size_t)cs.F, hipMemcpyDeviceToHost, ctx->st));
-    if (E) HIPCHK(hipMemcpyAsync(E, w.E, sizeof(float) * (size_t)cs.F, hipMemcpyDeviceToHost, ctx->st));
+    const float *w = static_cast<const float *>(cs.ws[cs.view].p);   // e[F] then E[F]
+    if (e) HIPCHK(hipMemcpyAsync(e, w, sizeof(float) * (size_t)cs.F, hipMemcpyDeviceToHost, ctx->st));
+    if (E) HIPCHK(hipMemcpyAsync(E, w + cs.F, sizeof(float) * (size_t)cs.F, hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipStreamSynchronize(ctx->st));
     return NH_OK;
 }
@@ -114,11 +75,9 @@ extern "C" int nh_logmel_chunks_rows(nh_ctx *ctx, const float *pcm, int on_devic
     if (!ctx || !pcm || !starts || !n_samples) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_logmel_chunks_rows: bad arguments") : NH_ERR_INVALID;
     hipSetDevice(ctx->dev);
     if (!ctx->mdl->have_filters) return ctx->fail(NH_ERR_STATE, "nh_logmel_chunks_rows: mel filters not set");
-    if (batch < 1 || row0 < 0 || row0 + batch > ctx->B) return ctx->fail(NH_ERR_INVALID, "rows [row0, row0 + batch) must lie in [0, max_batch]");
-    for (int b = 0; b < batch; b++) {
+    if (int rc = check_batch(ctx, n_samples, batch, row0)) return rc;
+    for (int b = 0; b < batch; b++)
         if (starts[b] < 0) return ctx->fail(NH_ERR_INVALID, "nh_logmel_chunks_rows: negative start");
-        if (n_samples[b] < 1 || n_samples[b] > NH_N_SAMPLES) return ctx->fail(NH_ERR_INVALID, "clip length must be in [1, 480000] samples");
-    }
     float *dst = ctx->pcm + (size_t)row0 * NH_N_SAMPLES;
     for (int b = 0; b < batch; b++)
         HIPCHK(hipMemcpyAsync(dst + (size_t)b * NH_N_SAMPLES, pcm + starts[b], sizeof(float) * (size_t)n_samples[b],

@@ -17,46 +17,50 @@ static int reframe(nh_ctx *ctx) {
 }
 
 // ---- log-mel -------------------------------------------------------------------------------------------
+static int clip_mel_frames(int n_samples) {   // narrow(2, 0, min(3000, frames)), model.rs:88
+    const long f = mel_frames_for(n_samples);
+    return f > NH_N_FRAMES ? NH_N_FRAMES : (int)f;
+}
+
 // row0 > 0: the clips join the rows already filled (several encoder batches of one joint decode, nh_logmel_device_rows)
-static int prepare_batch(nh_ctx *ctx, const int32_t *n_samples, int batch, int row0 = 0) {
+int check_batch(nh_ctx *ctx, const int32_t *n_samples, int batch, int row0) {
     if (batch < 1 || row0 < 0 || row0 + batch > ctx->B) return ctx->fail(NH_ERR_INVALID, "rows [row0, row0 + batch) must lie in [0, max_batch]");
-    long fr = -1;
     for (int b = 0; b < batch; b++) {
         if (n_samples[b] < 1 || n_samples[b] > NH_N_SAMPLES)
             return ctx->fail(NH_ERR_INVALID, "clip length must be in [1, 480000] samples");
-        long f = mel_frames_for(n_samples[b]);
-        if (f > NH_N_FRAMES) f = NH_N_FRAMES;  // narrow(2, 0, min(3000, frames)), model.rs:88
-        if (fr < 0) fr = f;
-        else if (fr != f) return ctx->fail(NH_ERR_INVALID, "clips of one batch must produce the same number of mel frames");
+        if (clip_mel_frames(n_samples[b]) != clip_mel_frames(n_samples[0]))
+            return ctx->fail(NH_ERR_INVALID, "clips of one batch must produce the same number of mel frames");
     }
-    ctx->live.lock_valid = false;   // a lockstep decode's captured sequences (nh_align_decoded) end with the batch they belong to
+    const int fr = clip_mel_frames(n_samples[0]);
     if (ctx->pool.rows > 0 && row0 >= ctx->pool.rows) {  // decode pool: encoder staging rows above the decoding ones
-        if (ctx->frames < 0) {
-            ctx->frames = (int)fr; ctx->S = (int)((fr + 2 - 3) / 2 + 1);
-            if (int rc = reframe(ctx)) return rc;
-        } else if ((int)fr != ctx->frames) return ctx->fail(NH_ERR_INVALID, "all clips of one decode pool must produce the same number of mel frames");
-        if (row0 + batch > ctx->cur_batch) ctx->cur_batch = row0 + batch;
-        ctx->have_enc = false;
-        return NH_OK;
-    }
-    if (row0 > 0) {
+        if (ctx->frames >= 0 && fr != ctx->frames) return ctx->fail(NH_ERR_INVALID, "all clips of one decode pool must produce the same number of mel frames");
+    } else if (row0 > 0) {
         if (row0 > ctx->cur_batch) return ctx->fail(NH_ERR_STATE, "row0 leaves a gap after the rows filled so far");
-        if ((int)fr != ctx->frames) return ctx->fail(NH_ERR_INVALID, "all rows of one joint decode must produce the same number of mel frames");
-        if (row0 + batch > ctx->cur_batch) ctx->cur_batch = row0 + batch;
-        ctx->have_enc = false;
-        return NH_OK;
+        if (fr != ctx->frames) return ctx->fail(NH_ERR_INVALID, "all rows of one joint decode must produce the same number of mel frames");
     }
-    ctx->cur_batch = batch; ctx->frames = (int)fr; ctx->S = (int)((fr + 2 - 3) / 2 + 1);
-    ctx->have_mel = false; ctx->have_enc = false;
+    return NH_OK;
+}
+
+// an accepted batch (check_batch) becomes the context's
+static int commit_batch(nh_ctx *ctx, const int32_t *n_samples, int batch, int row0) {
+    const int fr = clip_mel_frames(n_samples[0]);
+    ctx->live.lock_valid = false;   // a lockstep decode's captured sequences (nh_align_decoded) end with the batch they belong to
+    ctx->have_enc = false;
+    if (row0 > 0) {   // pool staging rows or the next rows of a joint decode
+        if (row0 + batch > ctx->cur_batch) ctx->cur_batch = row0 + batch;
+        if (ctx->frames >= 0) return NH_OK;
+        ctx->frames = fr; ctx->S = (fr + 2 - 3) / 2 + 1;   // the first clips of a pool set its frame count
+        return reframe(ctx);
+    }
+    ctx->cur_batch = batch; ctx->frames = fr; ctx->S = (fr + 2 - 3) / 2 + 1;
+    ctx->have_mel = false;
     ctx->pool.rows = 0;  // a fresh batch ends a decode pool
     ctx->seq_lang.clear();
     return reframe(ctx);
 }
 
 int run_logmel(nh_ctx *ctx, const float *pcm_dev, const int32_t *n_samples, int64_t stride, int batch, int row0) {
-    if (!ctx->mdl->have_filters) return ctx->fail(NH_ERR_STATE, "nh_logmel: mel filters not set");
-    int rc = prepare_batch(ctx, n_samples, batch, row0);
-    if (rc) return rc;
+    if (int rc = commit_batch(ctx, n_samples, batch, row0)) return rc;
     const int nm = ctx->c.num_mel_bins;
     int32_t *nsamp = ctx->nsamp + row0;
     unsigned *cmax = ctx->chunk_max + row0;
@@ -73,75 +77,38 @@ int run_logmel(nh_ctx *ctx, const float *pcm_dev, const int32_t *n_samples, int6
     return NH_OK;
 }
 
+// nh_logmel, nh_logmel_rows and their _device forms after the pointer checks: every refusal, then (host PCM) the copies
+// into the PCM rows, then the log-mel
+static int logmel_rows(nh_ctx *ctx, const float *pcm, bool on_device, const int32_t *n_samples, int64_t stride, int batch, int row0) {
+    hipSetDevice(ctx->dev);
+    if (!ctx->mdl->have_filters) return ctx->fail(NH_ERR_STATE, "nh_logmel: mel filters not set");
+    if (int rc = check_batch(ctx, n_samples, batch, row0)) return rc;
+    if (on_device) return run_logmel(ctx, pcm, n_samples, stride, batch, row0);
+    float *dst = ctx->pcm + (size_t)row0 * NH_N_SAMPLES;
+    for (int b = 0; b < batch; b++)
+        HIPCHK(hipMemcpyAsync(dst + (size_t)b * NH_N_SAMPLES, pcm + (size_t)b * stride, sizeof(float) * n_samples[b],
+                              hipMemcpyHostToDevice, ctx->st));
+    return run_logmel(ctx, dst, n_samples, NH_N_SAMPLES, batch, row0);
+}
+
 extern "C" int nh_logmel_device_rows(nh_ctx *ctx, const float *pcm_dev, const int32_t *n_samples, int64_t stride, int batch, int row0) {
     if (!ctx || !pcm_dev || !n_samples) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_logmel_device_rows: bad arguments") : NH_ERR_INVALID;
-    hipSetDevice(ctx->dev);
-    return run_logmel(ctx, pcm_dev, n_samples, stride, batch, row0);
+    return logmel_rows(ctx, pcm_dev, true, n_samples, stride, batch, row0);
 }
 
 extern "C" int nh_logmel_device(nh_ctx *ctx, const float *pcm_dev, const int32_t *n_samples, int64_t stride, int batch) {
     if (!ctx || !pcm_dev || !n_samples) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_logmel_device: bad arguments") : NH_ERR_INVALID;
-    hipSetDevice(ctx->dev);
-    return run_logmel(ctx, pcm_dev, n_samples, stride, batch);
-}
-
-static int logmel_host_rows(nh_ctx *ctx, const float *pcm, const int32_t *n_samples, int64_t stride, int batch, int row0) {
-    hipSetDevice(ctx->dev);
-    if (batch < 1 || row0 < 0 || row0 + batch > ctx->B) return ctx->fail(NH_ERR_INVALID, "rows [row0, row0 + batch) must lie in [0, max_batch]");
-    float *dst = ctx->pcm + (size_t)row0 * NH_N_SAMPLES;
-    for (int b = 0; b < batch; b++) {
-        if (n_samples[b] < 1 || n_samples[b] > NH_N_SAMPLES) return ctx->fail(NH_ERR_INVALID, "clip length must be in [1, 480000] samples");
-        HIPCHK(hipMemcpyAsync(dst + (size_t)b * NH_N_SAMPLES, pcm + (size_t)b * stride, sizeof(float) * n_samples[b],
-                              hipMemcpyHostToDevice, ctx->st));
-    }
-    return run_logmel(ctx, dst, n_samples, NH_N_SAMPLES, batch, row0);
+    return logmel_rows(ctx, pcm_dev, true, n_samples, stride, batch, 0);
 }
 
 extern "C" int nh_logmel(nh_ctx *ctx, const float *pcm, const int32_t *n_samples, int64_t stride, int batch) {
     if (!ctx || !pcm || !n_samples) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_logmel: bad arguments") : NH_ERR_INVALID;
-    return logmel_host_rows(ctx, pcm, n_samples, stride, batch, 0);
+    return logmel_rows(ctx, pcm, false, n_samples, stride, batch, 0);
 }
 
 extern "C" int nh_logmel_rows(nh_ctx *ctx, const float *pcm, const int32_t *n_samples, int64_t stride, int batch, int row0) {
     if (!ctx || !pcm || !n_samples) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_logmel_rows: bad arguments") : NH_ERR_INVALID;
-    return logmel_host_rows(ctx, pcm, n_samples, stride, batch, row0);
-}
-
-extern "C" int nh_sample_size(int dt) {
-    switch (dt) {
-        case NH_SAMPLE_F32: case NH_SAMPLE_I32: case NH_SAMPLE_U32: return 4;
-        case NH_SAMPLE_F64: case NH_SAMPLE_I64: case NH_SAMPLE_U64: return 8;
-        case NH_SAMPLE_I16: case NH_SAMPLE_U16: return 2;
-        case NH_SAMPLE_I8: case NH_SAMPLE_U8: return 1;
-        default: return 0;
-    }
-}
-
-// src/dtype.rs + dasp_sample's Sample::to_sample::<f32> (src/lib.rs:180,207), on the device: the native samples cross PCIe
-// as they are and become Model::Data (f32) in HBM
-extern "C" int nh_logmel_samples(nh_ctx *ctx, const void *pcm, int sample_dtype, const int32_t *n_samples, int64_t stride, int batch) {
-    if (!ctx || !pcm || !n_samples) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_logmel_samples: bad arguments") : NH_ERR_INVALID;
-    const size_t es = (size_t)nh_sample_size(sample_dtype);
-    if (!es) return ctx->fail(NH_ERR_INVALID, "nh_logmel_samples: unknown sample type " + std::to_string(sample_dtype));
-    if (sample_dtype == NH_SAMPLE_F32) return nh_logmel(ctx, reinterpret_cast<const float *>(pcm), n_samples, stride, batch);
-    hipSetDevice(ctx->dev);
-    if (batch < 1 || batch > ctx->B) return ctx->fail(NH_ERR_INVALID, "batch must be in [1, max_batch]");
-    const size_t need = (size_t)ctx->B * NH_N_SAMPLES * es;
-    if (ctx->raw_bytes < need) {   // staging for the native samples, sized for the widest type seen so far
-        void *p = nullptr;
-        if (hipMalloc(&p, need) != hipSuccess) return ctx->fail(NH_ERR_NOMEM, "hipMalloc(native sample staging)");
-        ctx->allocs.push_back(p);
-        ctx->raw = p; ctx->raw_bytes = need;
-    }
-    for (int b = 0; b < batch; b++) {
-        if (n_samples[b] < 1 || n_samples[b] > NH_N_SAMPLES) return ctx->fail(NH_ERR_INVALID, "clip length must be in [1, 480000] samples");
-        char *dst = reinterpret_cast<char *>(ctx->raw) + (size_t)b * NH_N_SAMPLES * es;
-        HIPCHK(hipMemcpyAsync(dst, reinterpret_cast<const char *>(pcm) + (size_t)b * (size_t)stride * es, (size_t)n_samples[b] * es,
-                              hipMemcpyHostToDevice, ctx->st));
-        launch_convert_samples(dst, ctx->pcm + (size_t)b * NH_N_SAMPLES, n_samples[b], sample_dtype, ctx->st);
-    }
-    HIPCHK(hipGetLastError());
-    return run_logmel(ctx, ctx->pcm, n_samples, NH_N_SAMPLES, batch);
+    return logmel_rows(ctx, pcm, false, n_samples, stride, batch, row0);
 }
 
 extern "C" int nh_get_mel(nh_ctx *ctx, int b, float *out) {
@@ -158,8 +125,8 @@ extern "C" int nh_set_mel(nh_ctx *ctx, const float *mel, int batch) {
     if (!ctx || !mel) return NH_ERR_INVALID;
     hipSetDevice(ctx->dev);
     std::vector<int32_t> ns(batch > 0 ? batch : 1, NH_N_SAMPLES);
-    int rc = prepare_batch(ctx, ns.data(), batch);
-    if (rc) return rc;
+    if (int rc = check_batch(ctx, ns.data(), batch)) return rc;
+    if (int rc = commit_batch(ctx, ns.data(), batch, 0)) return rc;
     size_t per = (size_t)ctx->c.num_mel_bins * NH_N_FRAMES;
     HIPCHK(hipMemcpyAsync(ctx->mel32, mel, per * batch * 4, hipMemcpyHostToDevice, ctx->st));
     launch_mel_finish_ex(ctx->mel32, ctx->chunk_max, ctx->mel_img, batch, ctx->c.num_mel_bins, ctx->frames, 0, ctx->st);

@@ -205,10 +205,12 @@ void launch_embed(const int32_t *tokens, int tok_stride, const half_t *E, const 
                   int Tn, int t0, const int32_t *pos_ptr, int d, hipStream_t st);
 
 // ---- sample conversion (src/dtype.rs / dasp_sample): native capture samples -> f32 PCM -------------------------------
-// src: `count` samples of NH_SAMPLE_* type `dtype` (device memory); dst: f32
-void launch_convert_samples(const void *src, float *dst, long count, int dtype, hipStream_t st);
 #ifdef __HIPCC__
-// the conversions themselves (k_elem.hip has their derivation), shared by convert_samples_kernel and resample_kernel
+// dasp_sample's conversions to f32 (the capture side of the reference converts every native sample type to Model::Data with
+// Sample::to_sample, src/lib.rs:180,207; the admissible types are src/dtype.rs:37-45).  Signed: s / 2^(bits - 1); unsigned:
+// (s - 2^(bits - 1)) / 2^(bits - 1), the subtraction in integers; f64: round to nearest.  Integer -> float conversions
+// round to nearest even (v_cvt_f32_i32, and the compiler's i64 sequence), like Rust's `as f32`; the divisions are by
+// powers of two, i.e. exact.  resample_kernel is their one user: nh_logmel_samples is a resample at 16 kHz, one channel.
 template <typename T> __device__ __forceinline__ float sample_to_f32(T v);
 template <> __device__ __forceinline__ float sample_to_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ float sample_to_f32<double>(double v) { return (float)v; }

@@ -47,11 +47,6 @@ extern "C" void nh_destroy(nh_ctx *ctx) {
     for (void *p : ctx->allocs) hipFree(p);
     for (void *p : ctx->al.allocs) hipFree(p);
     if (ctx->align_q) hipFree(ctx->align_q);
-    if (ctx->rs_stage) hipFree(ctx->rs_stage);
-    if (ctx->rs_clips) hipFree(ctx->rs_clips);
-    for (auto &w : ctx->cut.ws) { if (w.e) hipFree(w.e); if (w.E) hipFree(w.E); }
-    for (void *p : {(void *)ctx->cut.stage, (void *)ctx->cut.starts, (void *)ctx->cut.lens, (void *)ctx->cut.count})
-        if (p) hipFree(p);
     drop_graphs(ctx);
     if (ctx->h_done) hipHostFree(ctx->h_done);
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);
@@ -59,7 +54,7 @@ extern "C" void nh_destroy(nh_ctx *ctx) {
     if (ctx->enc_done) hipEventDestroy(ctx->enc_done);
     if (ctx->st) hipStreamDestroy(ctx->st);
     ctx->mdl.reset();  // the last context of a model frees its weights (~nh_model)
-    delete ctx;
+    delete ctx;        // ... and every DevBuf of the context frees itself
 }
 
 static bool build_mel_tables(nh_model *m, std::string &err) {

@@ -1,6 +1,6 @@
-// nh_resample.hip -- the C ABI of include/norma_hip.h, part 5: audio ingest.  Channel mixdown and resampling to 16 kHz on the
-// device (k_resample.hip), in front of the log-mel: the filter design and its per-rate tables, the staging of host frames,
-// nh_resample and nh_logmel_resampled_rows.  The contract is in the header and in DESIGN.md 10.
+// nh_resample.hip -- the C ABI of include/norma_hip.h, part 5: audio ingest.  Sample conversion, channel mixdown and resampling
+// to 16 kHz on the device (k_resample.hip), in front of the log-mel: the filter design and its per-rate tables, the staging of
+// host frames, nh_resample, nh_logmel_resampled_rows and nh_logmel_samples.  The contract is in the header and in DESIGN.md 10.
 #include "nh_ctx.h"
 
 #define RS_TARGET_HZ 16000
@@ -8,7 +8,6 @@
 #define RS_ROLLOFF 0.92
 #define RS_BETA 8.6
 #define RS_MAX_TABLE (1 << 20)            // entries: a 4 MB table
-#define RS_STAGE_BYTES (256ull << 20)     // native staging of host frames per group of clips (the alignment workspace's figure)
 
 struct RsDesign { int L = 0, M = 0, T = 0; double c = 0, W = 0; };
 
@@ -89,20 +88,35 @@ extern "C" int nh_resample_table(nh_ctx *ctx, int src_hz, float *coef, int32_t *
     return NH_OK;
 }
 
-// Every check of the contract, then the launches: clips -> PCM rows row0 .. of the context.  n_final[batch] receives the
-// outputs written per clip.  Nothing is launched or allocated before every argument has passed.
-static int resample_rows(nh_ctx *ctx, const char *who, const void *frames, int on_device, int dt, int channels, int src_hz,
-                         const int32_t *n_frames, int64_t stride_frames, int batch, const int64_t *num0, const int32_t *n_out,
-                         int row0, int32_t *n_final) {
+extern "C" int nh_sample_size(int dt) {
+    switch (dt) {
+        case NH_SAMPLE_F32: case NH_SAMPLE_I32: case NH_SAMPLE_U32: return 4;
+        case NH_SAMPLE_F64: case NH_SAMPLE_I64: case NH_SAMPLE_U64: return 8;
+        case NH_SAMPLE_I16: case NH_SAMPLE_U16: return 2;
+        case NH_SAMPLE_I8: case NH_SAMPLE_U8: return 1;
+        default: return 0;
+    }
+}
+
+// what a call says of its frames, whatever its clips: sample type, channels, rate (-> d), stride
+static int resample_format(nh_ctx *ctx, const char *who, int dt, int channels, int src_hz, int64_t stride_frames, RsDesign &d) {
     const std::string w(who);
-    const size_t es = (size_t)nh_sample_size(dt);
-    if (!es) return ctx->fail(NH_ERR_INVALID, w + ": unknown sample type " + std::to_string(dt));
+    if (!nh_sample_size(dt)) return ctx->fail(NH_ERR_INVALID, w + ": unknown sample type " + std::to_string(dt));
     if (channels < 1 || channels > 8) return ctx->fail(NH_ERR_INVALID, w + ": channels must be in [1, 8]");
-    RsDesign d;
     if (src_hz < 8000 || src_hz > 192000) return ctx->fail(NH_ERR_INVALID, w + ": src_hz must be in [8000, 192000]");
     if (!resample_design(src_hz, d)) return ctx->fail(NH_ERR_INVALID, w + ": the filter of this rate has more than 2^20 entries");
-    if (batch < 1 || row0 < 0 || row0 + batch > ctx->B) return ctx->fail(NH_ERR_INVALID, w + ": rows [row0, row0 + batch) must lie in [0, max_batch]");
     if (stride_frames < 0) return ctx->fail(NH_ERR_INVALID, w + ": negative stride");
+    if (resample_lds_bytes(d.L, d.M, d.T) > (size_t)NH_LDS_EXCLUSIVE) return ctx->fail(NH_ERR_INVALID, w + ": the window of one tile does not fit the LDS");
+    return NH_OK;
+}
+
+// The clips' own checks, then the launches: clips -> PCM rows row0 .. of the context, after resample_format and with rows the
+// caller has checked (check_batch, or nh_resample's range test).  n_final[batch], when given, receives the outputs written per
+// clip.  Nothing is launched or allocated before every clip has passed.
+static int resample_rows(nh_ctx *ctx, const char *who, const RsDesign &d, const void *frames, int on_device, int dt, int channels,
+                         int src_hz, const int32_t *n_frames, int64_t stride_frames, int batch, const int64_t *num0,
+                         const int32_t *n_out, int row0, int32_t *n_final) {
+    const std::string w(who);
     std::vector<ResampleClip> clips((size_t)batch);
     int max_out = 0;
     for (int b = 0; b < batch; b++) {
@@ -112,19 +126,16 @@ static int resample_rows(nh_ctx *ctx, const char *who, const void *frames, int o
         const long long z = num0 ? (long long)num0[b] : 0;
         if (z < 0) return ctx->fail(NH_ERR_INVALID, w + ": num0 must not be negative");
         clips[b] = ResampleClip{(long long)b * stride_frames, z, n_frames[b], (int)no};
-        n_final[b] = (int32_t)no;
+        if (n_final) n_final[b] = (int32_t)no;
         if ((int)no > max_out) max_out = (int)no;
     }
-    if (resample_lds_bytes(d.L, d.M, d.T) > (size_t)NH_LDS_EXCLUSIVE) return ctx->fail(NH_ERR_INVALID, w + ": the window of one tile does not fit the LDS");
     const float *coef = nullptr;
     if (int rc = resample_table(ctx, src_hz, d, &coef)) return rc;
-    if (!ctx->rs_clips) {
-        if (hipMalloc(reinterpret_cast<void **>(&ctx->rs_clips), sizeof(ResampleClip) * (size_t)ctx->B) != hipSuccess)
-            return ctx->fail(NH_ERR_NOMEM, "hipMalloc(resample clip records)");
-    }
+    if (!ctx->rs_clips && !(ctx->rs_clips = dalloc<ResampleClip>(ctx, (size_t)ctx->B, false)))
+        return ctx->fail(NH_ERR_NOMEM, "hipMalloc(resample clip records)");
     ResampleParams p{};
     p.dtype = dt; p.channels = channels; p.coef = coef; p.L = d.L; p.M = d.M; p.T = d.T; p.out_stride = NH_N_SAMPLES;
-    const size_t fb = es * (size_t)channels;   // bytes per frame
+    const size_t fb = (size_t)nh_sample_size(dt) * (size_t)channels;   // bytes per frame
     if (on_device) {
         HIPCHK(hipMemcpyAsync(ctx->rs_clips, clips.data(), sizeof(ResampleClip) * (size_t)batch, hipMemcpyHostToDevice, ctx->st));
         p.frames = frames; p.clips = ctx->rs_clips; p.batch = batch; p.max_out = max_out;
@@ -133,24 +144,18 @@ static int resample_rows(nh_ctx *ctx, const char *who, const void *frames, int o
         HIPCHK(hipGetLastError());
         return NH_OK;
     }
-    // host frames: groups of clips packed back to back in the native staging, one launch per group
+    // host frames: groups of clips packed back to back in the staging, one launch per group
     std::vector<std::pair<int, int>> groups;   // [first, last); a clip larger than the cap is staged alone
     size_t need = 0, run = 0;
     int g0 = 0;
     for (int b = 0; b < batch; b++) {
         const size_t bytes = (size_t)n_frames[b] * fb;
-        if (b > g0 && run + bytes > RS_STAGE_BYTES) { groups.emplace_back(g0, b); g0 = b; run = 0; }
+        if (b > g0 && run + bytes > NH_STAGE_BYTES) { groups.emplace_back(g0, b); g0 = b; run = 0; }
         run += bytes;
         need = std::max(need, run);
     }
     groups.emplace_back(g0, batch);
-    if (ctx->rs_stage_bytes < need) {
-        HIPCHK(hipStreamSynchronize(ctx->st));   // nothing may still read the staging that goes away
-        if (ctx->rs_stage) hipFree(ctx->rs_stage);
-        ctx->rs_stage = nullptr; ctx->rs_stage_bytes = 0;
-        if (hipMalloc(&ctx->rs_stage, need) != hipSuccess) return ctx->fail(NH_ERR_NOMEM, "hipMalloc(native frame staging)");
-        ctx->rs_stage_bytes = need;
-    }
+    if (int rc = ctx->stage.reserve(ctx, need, "native frame staging")) return rc;
     for (const auto &g : groups) {   // a clip's frames start where the previous clip of its group ends
         long long off = 0;
         for (int b = g.first; b < g.second; b++) { clips[b].off = off; off += n_frames[b]; }
@@ -159,12 +164,12 @@ static int resample_rows(nh_ctx *ctx, const char *who, const void *frames, int o
     for (const auto &g : groups) {
         int gmax = 0;
         for (int b = g.first; b < g.second; b++) {
-            HIPCHK(hipMemcpyAsync(reinterpret_cast<char *>(ctx->rs_stage) + (size_t)clips[b].off * fb,
+            HIPCHK(hipMemcpyAsync(reinterpret_cast<char *>(ctx->stage.p) + (size_t)clips[b].off * fb,
                                   reinterpret_cast<const char *>(frames) + (size_t)b * (size_t)stride_frames * fb,
                                   (size_t)n_frames[b] * fb, hipMemcpyHostToDevice, ctx->st));
             gmax = std::max(gmax, clips[b].n_out);
         }
-        p.frames = ctx->rs_stage; p.clips = ctx->rs_clips + g.first; p.batch = g.second - g.first; p.max_out = gmax;
+        p.frames = ctx->stage.p; p.clips = ctx->rs_clips + g.first; p.batch = g.second - g.first; p.max_out = gmax;
         p.out = ctx->pcm + (size_t)(row0 + g.first) * NH_N_SAMPLES;
         if (!launch_resample(p, ctx->st)) return ctx->fail(NH_ERR_INVALID, w + ": launch refused");
     }
@@ -177,8 +182,11 @@ extern "C" int nh_resample(nh_ctx *ctx, const void *frames, int on_device, int s
                            float *out_host, int64_t out_stride) {
     if (!ctx || !frames || !n_frames) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_resample: bad arguments") : NH_ERR_INVALID;
     hipSetDevice(ctx->dev);
-    std::vector<int32_t> n(batch > 0 ? (size_t)batch : 1);
-    if (int rc = resample_rows(ctx, "nh_resample", frames, on_device, sample_dtype, channels, src_hz, n_frames, stride_frames, batch,
+    RsDesign d;
+    if (int rc = resample_format(ctx, "nh_resample", sample_dtype, channels, src_hz, stride_frames, d)) return rc;
+    if (batch < 1 || batch > ctx->B) return ctx->fail(NH_ERR_INVALID, "nh_resample: rows [row0, row0 + batch) must lie in [0, max_batch]");
+    std::vector<int32_t> n((size_t)batch);
+    if (int rc = resample_rows(ctx, "nh_resample", d, frames, on_device, sample_dtype, channels, src_hz, n_frames, stride_frames, batch,
                                num0, n_out, 0, n.data()))
         return rc;
     if (!out_host) return NH_OK;
@@ -194,9 +202,31 @@ extern "C" int nh_logmel_resampled_rows(nh_ctx *ctx, const void *frames, int on_
     if (!ctx || !frames || !n_frames) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_logmel_resampled_rows: bad arguments") : NH_ERR_INVALID;
     hipSetDevice(ctx->dev);
     if (!ctx->mdl->have_filters) return ctx->fail(NH_ERR_STATE, "nh_logmel_resampled_rows: mel filters not set");
-    std::vector<int32_t> n(batch > 0 ? (size_t)batch : 1);
-    if (int rc = resample_rows(ctx, "nh_logmel_resampled_rows", frames, on_device, sample_dtype, channels, src_hz, n_frames,
-                               stride_frames, batch, nullptr, nullptr, row0, n.data()))
+    RsDesign d;
+    if (int rc = resample_format(ctx, "nh_logmel_resampled_rows", sample_dtype, channels, src_hz, stride_frames, d)) return rc;
+    std::vector<int32_t> n(batch > 0 ? (size_t)batch : 0);
+    for (size_t b = 0; b < n.size(); b++) n[b] = nh_resample_len(src_hz, n_frames[b]);   // -1: no frames, or more than a row holds
+    if (int rc = check_batch(ctx, n.data(), batch, row0)) return rc;
+    if (int rc = resample_rows(ctx, "nh_logmel_resampled_rows", d, frames, on_device, sample_dtype, channels, src_hz, n_frames,
+                               stride_frames, batch, nullptr, nullptr, row0, nullptr))
         return rc;
     return run_logmel(ctx, ctx->pcm + (size_t)row0 * NH_N_SAMPLES, n.data(), NH_N_SAMPLES, batch, row0);
+}
+
+// src/dtype.rs + dasp_sample's Sample::to_sample::<f32> (src/lib.rs:180,207), on the device: the native samples cross PCIe
+// as they are and become Model::Data (f32) in HBM.  At 16 kHz and one channel the resample kernel takes no division and no
+// tap: y[n] = sample_to_f32(s[n]).
+extern "C" int nh_logmel_samples(nh_ctx *ctx, const void *pcm, int sample_dtype, const int32_t *n_samples, int64_t stride, int batch) {
+    if (!ctx || !pcm || !n_samples) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_logmel_samples: bad arguments") : NH_ERR_INVALID;
+    if (!nh_sample_size(sample_dtype)) return ctx->fail(NH_ERR_INVALID, "nh_logmel_samples: unknown sample type " + std::to_string(sample_dtype));
+    if (sample_dtype == NH_SAMPLE_F32) return nh_logmel(ctx, reinterpret_cast<const float *>(pcm), n_samples, stride, batch);
+    hipSetDevice(ctx->dev);
+    if (!ctx->mdl->have_filters) return ctx->fail(NH_ERR_STATE, "nh_logmel: mel filters not set");
+    RsDesign d;
+    if (int rc = resample_format(ctx, "nh_logmel_samples", sample_dtype, 1, RS_TARGET_HZ, stride, d)) return rc;
+    if (int rc = check_batch(ctx, n_samples, batch)) return rc;
+    if (int rc = resample_rows(ctx, "nh_logmel_samples", d, pcm, 0, sample_dtype, 1, RS_TARGET_HZ, n_samples, stride, batch, nullptr,
+                               nullptr, 0, nullptr))
+        return rc;
+    return run_logmel(ctx, ctx->pcm, n_samples, NH_N_SAMPLES, batch);
 }

@@ -303,6 +303,10 @@ class HipWhisper:
         self._chk(self.L.nh_logmel(self._h, _fp(buf), _ip(ns), stride, B))
         self.batch = B
 
+    def _filled(self, row0: int, n: int):
+        """what an accepted nh_logmel*_rows call leaves as the context's batch: row 0 starts a batch, higher rows join one"""
+        self.batch = row0 + n if row0 > 0 else n
+
     def logmel_array(self, pcm: np.ndarray, n_samples: Optional[Sequence[int]] = None):
         """pcm: contiguous f32 [batch][stride] in HOST memory, handed to nh_logmel as is (no staging copy here)."""
         assert pcm.dtype == np.float32 and pcm.ndim == 2 and pcm.flags.c_contiguous
@@ -364,7 +368,7 @@ class HipWhisper:
         """nh_logmel_resampled_rows: whole clips of native frames -> 16 kHz mono -> log-mel of rows [row0, row0 + B)"""
         ptr, dev, dt, ch, nf, stride, keep = self._frames(frames, n_frames, stride_frames, dtype, channels)
         self._chk(self.L.nh_logmel_resampled_rows(self._h, ptr, dev, dt, ch, int(src_hz), _ip(nf), stride, len(nf), int(row0)))
-        self.batch = row0 + len(nf) if row0 > 0 else len(nf)
+        self._filled(row0, len(nf))
 
     def logmel_resampled(self, frames, src_hz: int, n_frames: Optional[Sequence[int]] = None, stride_frames: int = 0,
                          dtype=None, channels: int = 1):
@@ -415,7 +419,7 @@ class HipWhisper:
         if keep is not None and len(st):
             assert int(st.min()) >= 0 and int((st + ns).max()) <= len(keep), "a clip leaves the recording"
         self._chk(self.L.nh_logmel_chunks_rows(self._h, ptr, dev, st.ctypes.data_as(C.POINTER(C.c_int64)), _ip(ns), len(ns), int(row0)))
-        self.batch = row0 + len(ns) if row0 > 0 else len(ns)
+        self._filled(row0, len(ns))
 
     def logmel_device(self, pcm_dev_ptr: int, n_samples: Sequence[int], stride: int):
         """PCM already resident in HBM (device pointer, f32 [batch][stride])."""
@@ -427,7 +431,7 @@ class HipWhisper:
         """Clips for rows [row0, row0 + len(n_samples)) of the context (several encoder batches, one joint decode)."""
         ns = np.asarray(n_samples, dtype=np.int32)
         self._chk(self.L.nh_logmel_device_rows(self._h, C.c_void_p(pcm_dev_ptr), _ip(ns), stride, len(ns), row0))
-        self.batch = row0 + len(ns) if row0 > 0 else len(ns)
+        self._filled(row0, len(ns))
 
     def logmel_array_rows(self, pcm: np.ndarray, row0: int):
         """pcm: contiguous f32 [batch][stride] in HOST memory -> rows [row0, row0 + batch)."""
@@ -435,7 +439,7 @@ class HipWhisper:
         B, stride = pcm.shape
         ns = np.full(B, stride, dtype=np.int32)
         self._chk(self.L.nh_logmel_rows(self._h, _fp(pcm), _ip(ns), stride, B, row0))
-        self.batch = row0 + B if row0 > 0 else B
+        self._filled(row0, B)
 
     def encode_rows(self, row0: int, batch: int):
         self._chk(self.L.nh_encode_rows(self._h, row0, batch))

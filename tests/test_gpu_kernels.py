@@ -38,7 +38,10 @@ def test_native_sample_types_are_converted_like_dasp_sample():
     """src/dtype.rs + `Sample::to_sample::<f32>` (src/lib.rs:180,207) on the GPU: nh_logmel_samples on native samples must give
     bit for bit the log-mel of nh_logmel on the f32 samples a numpy restatement of dasp_sample's conversions produces
     (signed: s / 2^(bits-1); unsigned: (s - 2^(bits-1)) / 2^(bits-1); f64: round to nearest).  dasp_sample is not vendored
-    in the reference, so the formulas are restated from its published behaviour: parity unpinned for this conversion."""
+    in the reference, so the formulas are restated from its published behaviour: parity unpinned for this conversion.
+    Every type also at the lengths around one tile of the conversion's kernel (2048 outputs per workgroup) and at two
+    clips below one hop, all inside rows wider than the clips; refused calls leave the mel of the batch before alone."""
+    import ctypes as C
     import numpy as np
     import common
     from norma_amd import assets_io, config, synth
@@ -52,11 +55,12 @@ def test_native_sample_types_are_converted_like_dasp_sample():
     ns = [48000, 31999]
 
     def check(native, as_f32):
-        hm.logmel_samples(np.ascontiguousarray(native), ns)
-        got = [hm.get_mel(b) for b in range(2)]
-        hm.logmel_array(np.ascontiguousarray(as_f32, dtype=np.float32), ns)
-        for b in range(2):
-            assert np.array_equal(got[b], hm.get_mel(b)), native.dtype
+        for lens in (ns, [2047, 2048], [2049, 2047], [1, 159]):
+            hm.logmel_samples(np.ascontiguousarray(native), lens)
+            got = [hm.get_mel(b) for b in range(2)]
+            hm.logmel_array(np.ascontiguousarray(as_f32, dtype=np.float32), lens)
+            for b in range(2):
+                assert np.array_equal(got[b], hm.get_mel(b)), (native.dtype, lens)
     for dt, bits in ((np.int8, 8), (np.int16, 16), (np.int32, 32), (np.int64, 64)):
         half = 2.0 ** (bits - 1)
         v = np.clip(np.round(base * (half - 1)), -half, half - 1).astype(dt)
@@ -71,6 +75,15 @@ def test_native_sample_types_are_converted_like_dasp_sample():
     f32 = base.astype(np.float32)
     check(f32, f32)
     assert [hip.load_library().nh_sample_size(c) for c in range(11)] == [4, 8, 1, 2, 4, 8, 1, 2, 4, 8, 0]
+    # refusals: nothing of the batch before (the f32 one above) changes
+    before = [hm.get_mel(b) for b in range(2)]
+    wide = np.zeros((2, 480001), dtype=np.int16)
+    for what, dt, lens in (("type code 10", 10, ns), ("a clip of 0 samples", 3, [48000, 0]), ("a clip of 480001 samples", 3, [480001, 48000])):
+        n = np.asarray(lens, dtype=np.int32)
+        rc = hm.L.nh_logmel_samples(hm._h, wide.ctypes.data_as(C.c_void_p), dt, n.ctypes.data_as(C.POINTER(C.c_int32)), wide.shape[1], 2)
+        assert rc == 1 and hm.L.nh_last_error(hm._h), what
+        for b in range(2):
+            assert np.array_equal(before[b], hm.get_mel(b)), what
     hm.close()
 
 

@@ -9,7 +9,7 @@ import pytest
 
 import common
 import resample_ref as RR
-from norma_amd import config, hip, host, synth
+from norma_amd import assets_io, config, hip, host, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -189,6 +189,41 @@ def test_bit_identity_alone_in_batch_host_and_device(hm, src_hz, kind):
     dev.free()
 
 
+# ---- one staging for every host-fed route ---------------------------------------------------------------------------------------
+def test_one_staging_serves_resample_cut_plan_and_logmel_samples(hm):
+    """one fresh context, its calls back to back: resample (makes the staging), cut_plan of a recording larger than that
+    staging (grows it), logmel_samples and a resample right behind it with no synchronise in between (the second copy lands
+    where the first kernel reads), then the view of the plan.  Every result equals the same call on device-memory input or
+    on f32 host input, neither of which is staged."""
+    cfg = config.preset("test-d128")
+    stereo = random_clip("stereo i16", 3001, "staging")
+    rec = rng("staging", "recording").uniform(-0.5, 0.5, size=80000 + 37).astype(np.float32)   # about 5 s, 27 times the 3001 frames
+    mono = np.stack([random_clip("stereo i16", 5000, "staging", k)[:, 0] for k in range(2)])
+    cut = (300, 100, 15)
+    d_stereo, d_rec = hip.DeviceBuffer(stereo), hip.DeviceBuffer(rec)
+    want_rs = hm.resample(d_stereo.ptr, 48000, n_frames=[3001], stride_frames=3001, dtype=np.int16, channels=2)[0]
+    want_plan = hm.cut_plan(d_rec.ptr, len(rec), cut)
+    want_e = hm.cut_energy()
+    hm.logmel_array(np.ascontiguousarray(mono.astype(np.float32) / np.float32(32768)))
+    want_mel = [hm.get_mel(b) for b in range(2)]
+    d_stereo.free()
+    d_rec.free()
+    one = hip.HipWhisper(cfg, device=0, max_batch=2)
+    one.set_mel_filters(assets_io.mel_filters(cfg.num_mel_bins))
+    first = one.resample(stereo[None], 48000)[0]
+    plan = one.cut_plan(rec, params=cut)
+    one.logmel_samples(np.ascontiguousarray(mono))
+    again = one.resample(stereo[None], 48000)[0]
+    e, E = one.cut_energy()
+    mel = [one.get_mel(b) for b in range(2)]
+    one.close()
+    assert len(want_rs) == 1001 and same_bits(first, want_rs) and same_bits(again, want_rs)
+    assert len(plan[0]) >= 2 and plan[0].tolist() == want_plan[0].tolist() and plan[1].tolist() == want_plan[1].tolist()
+    assert same_bits(e, want_e[0]) and same_bits(E, want_e[1]), "cut_energy is not the view of the plan"
+    for b in range(2):
+        assert same_bits(mel[b], want_mel[b]), f"log-mel of clip {b}"
+
+
 # ---- tones ------------------------------------------------------------------------------------------------------------------------
 def test_analytic_tones(hm):
     """tones sampled analytically at 48 kHz come out as their analytic 16 kHz samples, up to the filter's own gain error at
@@ -329,3 +364,52 @@ def test_refusals_leave_everything_untouched(hm):
     assert after[0]["tokens"] == before[0]["tokens"]
     assert np.float64(after[0]["avg_logprob"]).view(np.int64) == np.float64(before[0]["avg_logprob"]).view(np.int64)
     assert np.float64(after[0]["no_speech_prob"]).view(np.int64) == np.float64(before[0]["no_speech_prob"]).view(np.int64)
+
+
+def test_refused_logmel_calls_queue_nothing(hm):
+    """every host-fed route into the PCM rows, refused for unequal mel frames (100 samples beside 48000), for a zero-length
+    clip and -- where the call has a row0 -- for a row gap: the mel of the batch before, what it decodes to, and the
+    captured sequences of its lockstep decode (align_decoded) are what they were"""
+    L = hm.L
+    vp, i32, i64, f32 = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float)
+    pcm = np.stack([synth.synth_pcm(k, 48000) for k in range(2)]).astype(np.float32)
+    other = np.ascontiguousarray(pcm[::-1] * np.float32(0.5))     # what a refused call would leave in the rows
+    other16 = np.round(other * 32767).astype(np.int16)
+    frames48 = np.ascontiguousarray(np.repeat(other16, 3, axis=1)[:, :, None].repeat(2, axis=2))   # [2][144000][2]
+    starts = np.array([0, 48000], dtype=np.int64)
+
+    def ns(lens, scale=1):
+        return (np.asarray(lens, dtype=np.int32) * scale).ctypes.data_as(i32)
+
+    calls = {
+        "logmel_array": lambda lens, row0: L.nh_logmel(hm._h, other.ctypes.data_as(f32), ns(lens), 48000, len(lens)),
+        "logmel_array_rows": lambda lens, row0: L.nh_logmel_rows(hm._h, other.ctypes.data_as(f32), ns(lens), 48000, len(lens), row0),
+        "logmel_samples": lambda lens, row0: L.nh_logmel_samples(hm._h, other16.ctypes.data_as(vp), 3, ns(lens), 48000, len(lens)),
+        "logmel_chunks_rows": lambda lens, row0: L.nh_logmel_chunks_rows(hm._h, other.ctypes.data_as(vp), 0, starts.ctypes.data_as(i64),
+                                                                         ns(lens), len(lens), row0),
+        "logmel_resampled_rows": lambda lens, row0: L.nh_logmel_resampled_rows(hm._h, frames48.ctypes.data_as(vp), 0, 3, 2, 48000,
+                                                                               ns(lens, 3), 144000, len(lens), row0),
+    }
+    hm.align_capture([(0, 1), (1, 0)])
+    try:
+        hm.logmel_array(pcm)
+        mel = [hm.get_mel(b) for b in range(2)]
+        hm.encode()
+        tokens = [r["tokens"] for r in hm.decode_greedy()]
+        first, last = hm.align_decoded()
+        assert (first >= 0).any()
+        for name, call in calls.items():
+            cases = [("unequal mel frames", [100, 48000], 0, 1), ("a zero-length clip", [48000, 0], 0, 1)]
+            if name.endswith("_rows"):
+                cases.append(("a row gap", [48000], 4, 3))
+            for why, lens, row0, status in cases:
+                what = f"{name} refused for {why}"
+                assert call(lens, row0) == status and L.nh_last_error(hm._h), what
+                f, l = hm.align_decoded()
+                assert np.array_equal(f, first) and np.array_equal(l, last), what
+                for b in range(2):
+                    assert same_bits(hm.get_mel(b), mel[b]), what
+                hm.encode()
+                assert [r["tokens"] for r in hm.decode_greedy()] == tokens, what
+    finally:
+        hm.align_capture([])

@@ -5,6 +5,8 @@ f32, on a test-d128 context (nothing here depends on the model's size: the log-m
                                                                # byte floor at R GB/s (the read rate tools/bin/peaks attains)
     python tools/dbg/resample_cost.py logmel                   # logmel_resampled against logmel_device on pre-resampled PCM and
                                                                # logmel on host f32; the same batch as host native frames
+    python tools/dbg/resample_cost.py samples                  # logmel_samples on 32 x 30 s of host mono i16 at 16 kHz (the
+                                                               # conversion route: nothing to mix down or resample)
     python tools/dbg/resample_cost.py scipy                    # the host alternative: scipy.signal.resample_poly, 16 threads
 
 Prints one JSON line per format.  Times are host wall time around calls followed by a stream synchronisation, medians of
@@ -108,6 +110,20 @@ def logmel_part(reps):
     hm.close()
 
 
+def samples_part(reps):
+    hm = context()
+    t = np.arange(16000 * SECONDS) / 16000.0
+    pcm = np.stack([np.round(32767 * (0.3 * np.sin(2 * np.pi * (200 + 37 * b) * t) + 0.2 * np.sin(2 * np.pi * (2100 + 91 * b) * t)))
+                    for b in range(B)]).astype(np.int16)
+
+    def run():
+        hm.logmel_samples(pcm)
+        hm.synchronize()
+    print(json.dumps({"part": "samples", "format": "16000 Hz mono i16", "clips": B, "logmel_samples_host_ms": med(run, reps),
+                      "host_samples_mb": pcm.nbytes / 1e6}), flush=True)
+    hm.close()
+
+
 def scipy_part(reps, threads=16):
     from concurrent.futures import ThreadPoolExecutor
     import resample_ref as RR
@@ -132,7 +148,7 @@ def scipy_part(reps, threads=16):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("part", choices=["launch", "logmel", "scipy"])
+    ap.add_argument("part", choices=["launch", "logmel", "samples", "scipy"])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--read-gbs", type=float, default=0.0, help="read rate of tools/bin/peaks on this device, GB/s")
     a = ap.parse_args()
@@ -140,5 +156,7 @@ if __name__ == "__main__":
         launch_part(a.reps, a.read_gbs)
     elif a.part == "logmel":
         logmel_part(a.reps)
+    elif a.part == "samples":
+        samples_part(a.reps)
     else:
         scipy_part(a.reps)
