@@ -26,6 +26,9 @@
  *   nh_cut_plan, nh_logmel_chunks_rows
  *                                 (no counterpart: the reference re-seeks sequentially, model.rs:100-146) the clips of a long
  *                                 recording for the batched path, cut in pauses
+ *   nh_vad_plan, nh_logmel_pieces_rows
+ *                                 (no counterpart) the same clips without the recording's silence: a speech map over the
+ *                                 cut planner's energies, packed into clips of at most 30 s
  *   nh_encode                     Type::encoder_forward (model.rs:168, :455-464)
  *   nh_decode_greedy              Model::decode at t = 0 (model.rs:279-389) including the logit
  *                                 rules (model.rs:212-277), batched, on device
@@ -229,6 +232,70 @@ int nh_cut_energy(nh_ctx *ctx, float *e, float *E, int64_t cap_frames);
  * nh_logmel*; of a plan only the final chunk can be that short. */
 int nh_logmel_chunks_rows(nh_ctx *ctx, const float *pcm, int on_device, const int64_t *starts,
                           const int32_t *n_samples, int batch, int row0);
+/* ---- long recordings: keep the speech, drop the silence, on the device -------------------------------------
+ * nh_cut_plan sends every sample of a recording through the encoder and the decode loop.  nh_vad_plan keeps the speech only:
+ * a speech map over the same energies, packed into clips of at most 30 s, each clip a concatenation of pieces of the
+ * recording.  A recording is N >= 1 f32 mono samples at 16 kHz, in host or device memory; F = ceil(N / 160) analysis frames;
+ * e[f] and E[f] are EXACTLY stages 1 and 2 of nh_cut_plan (W = half_window): same arithmetic, same bits.  All float steps
+ * are single IEEE f32 operations, everything else is integer, so numpy reproduces every bit.
+ *   1 Levels.  S = the non-NaN values of E sorted ascending, F' = |S|.  Q_lo = S[lo_permille (F' - 1) / 1000], Q_hi =
+ *     S[hi_permille (F' - 1) / 1000] (integer division in int64).  a = lo_ratio * Q_lo; b = hi_ratio * Q_hi; r = (b < a) ? b : a;
+ *     T = (r > abs_floor) ? r : abs_floor.  F' = 0: T = abs_floor (and the view shows Q_lo = Q_hi = 0).  The two ratios are a
+ *     floor taken from the quiet end and a ceiling taken from the loud end, and the smaller wins: a recording that is speech
+ *     throughout loses only what lies 20 dB below its loud level, one whose noise is within 20 dB of its speech loses
+ *     nothing.  The rule errs toward keeping audio.
+ *   2 Raw flags.  raw[f] = !(E[f] <= T).  A NaN frame is speech: what cannot be judged is kept.
+ *   3 Shaping, in this order, on frame indices.  (a) a maximal run of raw shorter than min_speech_frames is cleared: v1.
+ *     (b) v2[f] is true if any v1[g] with |g - f| <= pad_frames and 0 <= g < F is true.  (c) a maximal run of !v2 that lies
+ *     strictly between two speech runs and is shorter than min_gap_frames becomes speech: v3.  Leading and trailing silence
+ *     are never filled.  Regions are the maximal runs [a, b) of v3, ascending.
+ *   4 Pieces.  For each region in order: s = a; while b - s > max_frames: c* by stage 3 of nh_cut_plan over c = s + min_frames
+ *     .. s + max_frames (the latest least E[c], a NaN never chosen, s + max_frames if nothing qualifies), emit [s, c*), s = c*;
+ *     emit [s, b).  Piece j starts at sample 160 s_j and is min(160 len_j, N - 160 s_j) samples long.
+ *   5 Chunks.  Greedy, in order: a chunk takes the next piece while it is empty or while its frame total plus that piece
+ *     stays <= max_frames.  chunk_first[k] is the index of chunk k's first piece, chunk_first[n_chunks] = n_pieces.  A
+ *     recording with no speech has 0 pieces and 0 chunks (chunk_first[0] = 0); that is not an error.
+ *   6 No host round trip between the stages; only the piece and chunk records and the two counts come back, and the call
+ *     returns when they are on the host.
+ *   7 Refusals and subnormals as for nh_cut_plan.  NH_ERR_INVALID, nothing launched, outputs and the view untouched:
+ *     n_samples outside 1 .. 2^31 - 1; max_frames, min_frames, half_window outside nh_cut_plan's ranges; lo_permille or
+ *     hi_permille outside 0 .. 1000 or lo > hi; a ratio or abs_floor that is negative or not finite; min_speech_frames or
+ *     min_gap_frames outside 1 .. 3000; pad_frames outside 0 .. 3000; a negative cap.  A cap smaller than its count looks the
+ *     same to the caller, but BOTH *n_pieces and *n_chunks are set to what is needed (the plan ran in a second workspace that
+ *     becomes the view only when the call succeeds).  Results for samples whose squares are subnormal are unspecified up to
+ *     a flush to zero.
+ * The defaults -- the quiet decile x 4, the loud decile - 20 dB, 0.1 s of speech, 0.2 s of padding, gaps of 1 s -- are design
+ * choices that have not been tuned on real speech; what is tested is this arithmetic, not recognition accuracy.
+ * The call owns its state (allocated by the first call, grown on demand), leaves the view of nh_cut_energy as it found it,
+ * touches nothing else in the context and is legal in any state, like nh_cut_plan; host PCM goes through the context's one
+ * staging in the same groups. */
+typedef struct nh_vad_params {
+    int32_t max_frames, min_frames, half_window;            /* as nh_cut_params, same ranges */
+    int32_t lo_permille, hi_permille;                       /* 0..1000, lo <= hi */
+    float   lo_ratio, hi_ratio, abs_floor;                  /* finite, >= 0 */
+    int32_t min_speech_frames, pad_frames, min_gap_frames;  /* 1..3000, 0..3000, 1..3000 */
+} nh_vad_params;                                            /* 44 bytes */
+/* p == NULL: the defaults {3000, 2000, 15, 100, 900, 4.0f, 0.01f, 0.0f, 10, 20, 100}.  piece_starts: host i64 [cap_pieces],
+ * piece_lens: host i32 [cap_pieces], chunk_first: host i32 [cap_chunks + 1], n_pieces / n_chunks: host i32 [1]. */
+int nh_vad_plan(nh_ctx *ctx, const float *pcm, int on_device, int64_t n_samples, const nh_vad_params *p,
+                int64_t *piece_starts, int32_t *piece_lens, int cap_pieces, int32_t *n_pieces,
+                int32_t *chunk_first /* cap_chunks + 1 */, int cap_chunks, int32_t *n_chunks);
+/* Parity view of the LAST successful plan; any pointer may be NULL.  E: F floats, speech: v3, F bytes of 0 / 1 (cap_frames >=
+ * F when either is given), levels: Q_lo, Q_hi, T, regions: a, b pairs in frames, *n_regions: their number (set whenever the
+ * pointer is given).  NH_ERR_STATE before any plan; NH_ERR_INVALID, nothing else written, for too little room. */
+int nh_vad_view(nh_ctx *ctx, float *E, uint8_t *speech /* v3 */, int64_t cap_frames, float levels[3] /* Q_lo, Q_hi, T */,
+                int64_t *regions /* a, b pairs */, int cap_regions, int32_t *n_regions);
+/* PCM row row0 + b = the concatenation of chunk b's pieces pcm[piece_starts[j] .. + piece_lens[j]), j = chunk_first[b] ..
+ * chunk_first[b + 1] - 1, of a recording in host or device (on_device != 0) memory; then exactly what nh_logmel_device_rows
+ * does on those rows with n_samples[b] = the chunk's total: the bits of a log-mel of the concatenation.  No copy back, no
+ * synchronisation.  Device PCM: the piece table goes up in one copy and one launch gathers the whole batch (16-byte copies
+ * when pcm is 16-byte aligned and no piece boundary inside a row falls off a multiple of 4 samples -- every plan's pieces
+ * start at multiples of 160 samples, and only a recording's final piece, last in its row, has a ragged length --, dwords
+ * otherwise); host PCM: one copy per piece.  Refused before anything is queued: a chunk_first that does not ascend, a chunk
+ * with no piece, a piece length below 1, a negative start, a chunk total above 480 000, and what every nh_logmel*_rows
+ * refuses (row range, a chunk below 160 samples beside longer ones). */
+int nh_logmel_pieces_rows(nh_ctx *ctx, const float *pcm, int on_device, const int64_t *piece_starts,
+                          const int32_t *piece_lens, const int32_t *chunk_first /* batch + 1 */, int batch, int row0);
 /* Same, but pcm is a DEVICE pointer (already resident in HBM; no copy). */
 int nh_logmel_device(nh_ctx *ctx, const float *pcm_dev, const int32_t *n_samples, int64_t stride, int batch);
 /* Encoder forward over the mel of the last nh_logmel call (flush = true semantics: the cross

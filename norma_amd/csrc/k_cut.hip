@@ -69,49 +69,21 @@ __global__ __launch_bounds__(256) void cut_window_kernel(const float *e, float *
     E[f] = acc;
 }
 
-// (best, c) of two candidates under "least E, then greatest c"; c < 0: that side has found nothing.  Neither best is ever a
-// NaN: `v <= best` is false for one.
-__device__ __forceinline__ void cut_merge(float &best, int &c, float ob, int oc) {
-    if (oc >= 0 && (c < 0 || ob < best || (ob == best && oc > c))) { best = ob; c = oc; }
-}
-
-// One workgroup.  Per chunk: thread t looks at candidates s + min + t, + 256, .. ascending with the contract's `<=`, which
-// leaves it the latest of its least; the 64 lanes of a wave meet by shuffles, the 4 waves in LDS, thread 0 writes the chunk
-// and the next start.  Candidates are kept relative to s (at most 3000: an int).  Every candidate lies below F, because the
-// loop runs only while s + max < F.
+// One workgroup walks the chunks; each search is cut_search_range (nh_kernels.h), thread 0 writes the chunk.  Every candidate
+// lies below F, because the loop runs only while s + max < F.
 __global__ __launch_bounds__(256) void cut_search_kernel(CutSearch p) {
     __shared__ float w_best[4];
     __shared__ int w_c[4];
-    __shared__ long long s_next;
     const int tid = threadIdx.x;
     long long s = 0, k = 0;
     while (p.F - s > (long long)p.max_frames) {
-        float best = INFINITY;
-        int c = -1;
-        for (int r = p.min_frames + tid; r <= p.max_frames; r += 256) {
-            const float v = p.E[s + r];
-            if (v <= best) { best = v; c = r; }
+        const long long nxt = s + cut_search_range(p.E, s, p.min_frames, p.max_frames, w_best, w_c);
+        if (tid == 0 && k < p.cap) {
+            p.starts[k] = s * NH_CUT_FRAME;
+            const long long len = (nxt - s) * NH_CUT_FRAME, left = p.n_samples - s * NH_CUT_FRAME;
+            p.lens[k] = (int32_t)(len < left ? len : left);
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ob = __shfl_xor(best, off);
-            const int oc = __shfl_xor(c, off);
-            cut_merge(best, c, ob, oc);
-        }
-        if ((tid & 63) == 0) { w_best[tid >> 6] = best; w_c[tid >> 6] = c; }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < 4; w++) cut_merge(best, c, w_best[w], w_c[w]);
-            const long long nxt = s + (c < 0 ? p.max_frames : c);
-            if (k < p.cap) {
-                p.starts[k] = s * NH_CUT_FRAME;
-                const long long len = (nxt - s) * NH_CUT_FRAME, left = p.n_samples - s * NH_CUT_FRAME;
-                p.lens[k] = (int32_t)(len < left ? len : left);
-            }
-            s_next = nxt;
-        }
-        __syncthreads();   // s_next is next written after the following iteration's first barrier, w_* after this one
-        s = s_next;
+        s = nxt;
         k++;
     }
     if (tid == 0) {

@@ -1,7 +1,7 @@
-// nh_ctx.h -- the state behind the C ABI of include/norma_hip.h, shared by the six files that implement it: nh_model.hip
+// nh_ctx.h -- the state behind the C ABI of include/norma_hip.h, shared by the seven files that implement it: nh_model.hip
 // (create / destroy, weights, tokens, options, timings), nh_encode.hip (log-mel, encoder), nh_decode.hip (decoder step,
 // lockstep decode, decode pool, parity views), nh_align.hip (token-level timestamps), nh_resample.hip (audio ingest),
-// nh_cut.hip (cutting long recordings).  It also holds the two things every audio route into the PCM rows shares: the
+// nh_cut.hip (cutting long recordings), nh_vad.hip (their speech map).  It also holds the two things every audio route into the PCM rows shares: the
 // grow-on-demand device buffer (DevBuf: the one staging of host audio, the cut workspaces) and the batch check
 // (check_batch) that runs before anything is queued.  No torch, no candle, no CPU fallback: an entry point runs the HIP
 // path or fails.
@@ -166,6 +166,18 @@ struct CutState {
     int32_t *count = nullptr;    // [1], in ctx->allocs
 };
 
+// nh_vad_plan: everything it owns, beside and apart from CutState (the view of nh_cut_energy is not its to change).  Two view
+// workspaces for the same reason as there: the counts are known only after the walk, and a refused plan shows nothing.
+struct VadState {
+    DevBuf ws[2];                // of the plan computed there: regions (a, b pairs, 64-bit), levels[3] + the region count, E[F], v3[F]
+    int view = -1;               // the workspace of the last successful plan; -1: none yet
+    long long F = 0;             // its frames
+    DevBuf tmp;                  // e[F], the select's state, the per-tile scan records, two flag buffers
+    DevBuf out;                  // piece starts (64-bit), piece lengths, chunk_first, the two counts
+    DevBuf tab;                  // nh_logmel_pieces_rows: the piece table of a batch of device PCM
+    std::vector<long long> h_tab;   // ... and its host side, alive until the next call's copy
+};
+
 struct nh_ctx {
     int dev = 0;
     std::shared_ptr<nh_model> mdl;
@@ -191,6 +203,7 @@ struct nh_ctx {
     DevBuf stage;
     ResampleClip *rs_clips = nullptr;   // [max_batch] per-clip records of a resample call, made by the first one
     CutState cut;               // nh_cut_plan, nh_cut_energy
+    VadState vad;               // nh_vad_plan, nh_vad_view, nh_logmel_pieces_rows
     int32_t *nsamp = nullptr;
     float *mel32 = nullptr;
     unsigned *chunk_max = nullptr;
@@ -282,3 +295,5 @@ int ensure_decoder_repack(nh_ctx *ctx);         // nh_model.hip
 int check_batch(nh_ctx *ctx, const int32_t *n_samples, int batch, int row0 = 0);
 // ... and what follows an accepted check: the batch becomes the context's, then the log-mel of the clips of device PCM
 int run_logmel(nh_ctx *ctx, const float *pcm_dev, const int32_t *n_samples, int64_t stride, int batch, int row0 = 0);
+// nh_cut.hip: e[F] and E[F] of a recording in host (staged in groups) or device memory, queued on the context's stream
+int cut_energies(nh_ctx *ctx, const float *pcm, int on_device, long long N, float *e, float *E, long long F, int half_window);

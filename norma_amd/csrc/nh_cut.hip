@@ -6,6 +6,24 @@
 #define CUT_STAGE_FRAMES ((long long)(NH_STAGE_BYTES / (sizeof(float) * NH_CUT_HOP)))
 static_assert(NH_CUT_HOP == NH_CUT_FRAME, "the public hop is the kernels' frame");
 
+// Stages 1 and 2 of the contract, queued on the context's stream: e[F] and E[F] (device) of a recording of N samples.  Host PCM
+// goes through the context's one staging in groups of whole frames, one energy launch per group.  nh_vad_plan starts here too.
+int cut_energies(nh_ctx *ctx, const float *pcm, int on_device, long long N, float *e, float *E, long long F, int half_window) {
+    if (on_device) {
+        launch_cut_energy(pcm, N, e, F, ctx->st);
+    } else {
+        if (int rc = ctx->stage.reserve(ctx, sizeof(float) * (size_t)std::min(N, CUT_STAGE_FRAMES * NH_CUT_HOP), "PCM staging")) return rc;
+        float *const stage = static_cast<float *>(ctx->stage.p);
+        for (long long f0 = 0; f0 < F; f0 += CUT_STAGE_FRAMES) {
+            const long long nf = std::min(CUT_STAGE_FRAMES, F - f0), ns = std::min(nf * NH_CUT_HOP, N - f0 * NH_CUT_HOP);
+            HIPCHK(hipMemcpyAsync(stage, pcm + f0 * NH_CUT_HOP, sizeof(float) * (size_t)ns, hipMemcpyHostToDevice, ctx->st));
+            launch_cut_energy(stage, ns, e + f0, nf, ctx->st);
+        }
+    }
+    launch_cut_window(e, E, F, half_window, ctx->st);
+    return NH_OK;
+}
+
 extern "C" int nh_cut_plan(nh_ctx *ctx, const float *pcm, int on_device, int64_t n_samples, const nh_cut_params *p,
                            int64_t *starts, int32_t *lens, int cap, int32_t *n_chunks) {
     if (!ctx || !pcm || !starts || !lens || !n_chunks) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_cut_plan: bad arguments") : NH_ERR_INVALID;
@@ -27,18 +45,7 @@ extern "C" int nh_cut_plan(nh_ctx *ctx, const float *pcm, int on_device, int64_t
     if (int rc = cs.out.reserve(ctx, (sizeof(long long) + sizeof(int32_t)) * (size_t)kcap, "chunk records")) return rc;
     long long *const d_starts = static_cast<long long *>(cs.out.p);
     int32_t *const d_lens = reinterpret_cast<int32_t *>(d_starts + kcap);
-    if (on_device) {
-        launch_cut_energy(pcm, N, e, F, ctx->st);
-    } else {
-        if (int rc = ctx->stage.reserve(ctx, sizeof(float) * (size_t)std::min(N, CUT_STAGE_FRAMES * NH_CUT_HOP), "PCM staging")) return rc;
-        float *const stage = static_cast<float *>(ctx->stage.p);
-        for (long long f0 = 0; f0 < F; f0 += CUT_STAGE_FRAMES) {
-            const long long nf = std::min(CUT_STAGE_FRAMES, F - f0), ns = std::min(nf * NH_CUT_HOP, N - f0 * NH_CUT_HOP);
-            HIPCHK(hipMemcpyAsync(stage, pcm + f0 * NH_CUT_HOP, sizeof(float) * (size_t)ns, hipMemcpyHostToDevice, ctx->st));
-            launch_cut_energy(stage, ns, e + f0, nf, ctx->st);
-        }
-    }
-    launch_cut_window(e, E, F, q.half_window, ctx->st);
+    if (int rc = cut_energies(ctx, pcm, on_device, N, e, E, F, q.half_window)) return rc;
     CutSearch s{};
     s.E = E; s.F = F; s.min_frames = q.min_frames; s.max_frames = q.max_frames; s.n_samples = N;
     s.starts = d_starts; s.lens = d_lens; s.count = cs.count; s.cap = kcap;

@@ -2,6 +2,7 @@
 // kernels.  Not part of the public ABI (that is include/norma_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include <atomic>
@@ -267,6 +268,93 @@ struct CutSearch {
 };
 // one workgroup walks the chunks (the sequential loop of the contract, each search a parallel arg-min)
 void launch_cut_search(const CutSearch &p, hipStream_t st);
+#ifdef __HIPCC__
+// (best, c) of two candidates under "least E, then greatest c"; c < 0: that side has found nothing.  Neither best is ever a
+// NaN: `v <= best` is false for one.
+__device__ __forceinline__ void cut_merge(float &best, int &c, float ob, int oc) {
+    if (oc >= 0 && (c < 0 || ob < best || (ob == best && oc > c))) { best = ob; c = oc; }
+}
+// One search of the contract's stage 3, by the 256 threads of a workgroup, shared by cut_search_kernel (k_cut.hip) and
+// vad_pieces_kernel (k_vad.hip): returns c* - s to every thread.  Thread t looks at candidates s + min + t, + 256, ..
+// ascending with the contract's `<=`, which leaves it the latest of its least; the 64 lanes of a wave meet by shuffles, the 4
+// waves in w_best[4] / w_c[4] (LDS), which are free again when the call returns.  Candidates are kept relative to s (at most
+// 3000: an int); the caller guarantees s + max_frames < F.
+__device__ __forceinline__ int cut_search_range(const float *E, long long s, int min_frames, int max_frames, float *w_best, int *w_c) {
+    const int tid = threadIdx.x;
+    float best = INFINITY;
+    int c = -1;
+    for (int r = min_frames + tid; r <= max_frames; r += 256) {
+        const float v = E[s + r];
+        if (v <= best) { best = v; c = r; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ob = __shfl_xor(best, off);
+        const int oc = __shfl_xor(c, off);
+        cut_merge(best, c, ob, oc);
+    }
+    if ((tid & 63) == 0) { w_best[tid >> 6] = best; w_c[tid >> 6] = c; }
+    __syncthreads();
+    best = w_best[0]; c = w_c[0];
+    for (int w = 1; w < 4; w++) cut_merge(best, c, w_best[w], w_c[w]);
+    __syncthreads();   // w_* are next written after this
+    return c < 0 ? max_frames : c;
+}
+#endif
+
+// ---- long recordings: the speech map, its pieces and chunks, and the gather (k_vad.hip; the contract is DESIGN.md 12) -------
+#define NH_VAD_HIST_TILE 4096   // frames per workgroup of the select's histogram kernel
+#define NH_VAD_TILE 2048        // frames per workgroup of the shaping kernels: 256 threads x 8 consecutive frames
+// The state of the radix select over the monotone uint32 key of E: two ranks (Q_lo, Q_hi) walk the key's four bytes from the
+// top; they share one histogram while their prefixes agree.  Zeroed before the first pass.
+struct VadSelect {
+    unsigned hist[2][256];   // counts of the current pass, combined over the workgroups with integer atomics
+    unsigned prefix[2];      // the key bytes chosen so far (low bytes 0)
+    long long rank[2];       // the rank still to find among the keys under the prefix
+    int parted;              // the two prefixes differ: each rank counts into its own histogram
+    int n_valid;             // F': the frames whose E is no NaN
+};
+struct VadLevels {
+    int lo_permille, hi_permille;
+    float lo_ratio, hi_ratio, abs_floor;
+};
+// one pass: the histogram of byte `shift / 8` of the keys under each rank's prefix ...
+void launch_vad_hist(const float *E, long long F, int shift, VadSelect *sel, hipStream_t st);
+// ... and the digit of both ranks; shift == 24 derives the ranks from F', shift == 0 writes levels[3] = Q_lo, Q_hi, T
+void launch_vad_pick(VadSelect *sel, int shift, const VadLevels &lv, float *levels, hipStream_t st);
+struct VadShape {
+    const float *E; const float *levels;   // step 0 reads T = levels[2]
+    long long F;
+    const uint8_t *in; uint8_t *out;       // flags of whole tiles (the buffers are padded to NH_VAD_TILE; frames past F are 0)
+    const int *carry_l, *carry_r;          // per tile: nearest set input frame below / above the tile (-1 / F: none)
+    int *tile_l, *tile_r;                  // per tile: last / first set frame of `out` (-1 / F: none); steps 4: tile_l = starts
+    int min_speech, pad, min_gap;
+    long long *regions; const int *carry_n;   // step 5: a, b pairs, and the regions that start below each tile
+};
+// step 0: out = (E <= T), the silence flags; 1: out = v1 (in: silence); 2: out = v2 (in: v1); 3: out = v3 (in: v2); 4: region
+// starts per tile (in: v3); 5: the region list (in: v3).  Steps 0 - 2 also leave tile_l / tile_r of what they wrote.
+void launch_vad_shape(int step, const VadShape &p, hipStream_t st);
+// one workgroup: carry_l[t] = max(tile_l[0 .. t)), carry_r[t] = min(tile_r(t .. n)) (sum == 0), or carry_l[t] = the sum of
+// tile_l[0 .. t) and *total = the sum of all (sum != 0)
+void launch_vad_carry(const int *tile_l, const int *tile_r, int *carry_l, int *carry_r, int n_tiles, long long F, int sum, int *total, hipStream_t st);
+struct VadPieces {
+    const float *E; const long long *regions; const int *n_regions;
+    int min_frames, max_frames;
+    long long n_samples;
+    long long *starts; int32_t *lens; long long cap_pieces;   // piece k, for k < cap_pieces
+    int32_t *chunk_first; long long cap_chunks;                // entries 0 .. cap_chunks
+    int32_t *counts;                                           // [2]: pieces and chunks, written last, whatever the caps are
+};
+// one workgroup walks the regions: pieces (cut_search_range inside regions longer than max_frames) and the greedy chunks
+void launch_vad_pieces(const VadPieces &p, hipStream_t st);
+struct VadGather {
+    const float *src; float *dst; long long dst_stride;   // chunk b's samples go to dst + b * dst_stride
+    const long long *tab;   // [batch + 1] first piece of every chunk, then per piece its first sample in src, then per piece the
+                            // samples of its chunk before it; the table ends with one more such entry per chunk: its total
+    int n_pieces, vec4;     // vec4: src is 16-byte aligned and every piece boundary is a multiple of 4 samples
+};
+// one launch: PCM row b = the concatenation of chunk b's pieces; max_total: the longest row in samples
+void launch_vad_gather(const VadGather &p, int batch, long long max_total, hipStream_t st);
 
 // ---- log-mel -------------------------------------------------------------------------------------------
 struct MelTables {     // device pointers, built once on the host with libm (bit-identical twiddles)

@@ -68,6 +68,23 @@ class NhCutParams(C.Structure):
     _fields_ = [("max_frames", C.c_int32), ("min_frames", C.c_int32), ("half_window", C.c_int32)]
 
 
+class NhVadParams(C.Structure):
+    """nh_vad_params (nh_vad_plan): nh_cut_params, then the levels' ranks and ratios, then the shaping in frames of 160 samples;
+    the defaults are {3000, 2000, 15, 100, 900, 4.0, 0.01, 0.0, 10, 20, 100}"""
+    _fields_ = [("max_frames", C.c_int32), ("min_frames", C.c_int32), ("half_window", C.c_int32),
+                ("lo_permille", C.c_int32), ("hi_permille", C.c_int32),
+                ("lo_ratio", C.c_float), ("hi_ratio", C.c_float), ("abs_floor", C.c_float),
+                ("min_speech_frames", C.c_int32), ("pad_frames", C.c_int32), ("min_gap_frames", C.c_int32)]
+
+    @classmethod
+    def of(cls, params):
+        """an NhVadParams as is, or a tuple in field order"""
+        if isinstance(params, cls):
+            return params
+        v = list(params)
+        return cls(*[int(x) for x in v[:5]], *[float(x) for x in v[5:8]], *[int(x) for x in v[8:]])
+
+
 class NhTimings(C.Structure):
     _fields_ = [("mel_ms", C.c_float), ("encoder_ms", C.c_float), ("cross_kv_ms", C.c_float),
                 ("decode_ms", C.c_float), ("decode_steps", C.c_int32), ("gemm_ms", C.c_float),
@@ -128,6 +145,10 @@ def load_library() -> C.CDLL:
     L.nh_cut_plan.argtypes = [vp, vp, C.c_int, C.c_int64, C.POINTER(NhCutParams), i64p, ip, C.c_int, ip]
     L.nh_cut_energy.argtypes = [vp, fp, fp, C.c_int64]
     L.nh_logmel_chunks_rows.argtypes = [vp, vp, C.c_int, i64p, ip, C.c_int, C.c_int]
+    u8p = C.POINTER(C.c_uint8)
+    L.nh_vad_plan.argtypes = [vp, vp, C.c_int, C.c_int64, C.POINTER(NhVadParams), i64p, ip, C.c_int, ip, ip, C.c_int, ip]
+    L.nh_vad_view.argtypes = [vp, fp, u8p, C.c_int64, fp, i64p, C.c_int, ip]
+    L.nh_logmel_pieces_rows.argtypes = [vp, vp, C.c_int, i64p, ip, ip, C.c_int, C.c_int]
     L.nh_encode.argtypes = [vp]
     L.nh_decode_greedy.argtypes = [vp, ip, C.POINTER(NhDecodeResult), C.c_int]
     L.nh_decode_sampled.argtypes = [vp, ip, C.POINTER(NhDecodeResult), C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_uint32]
@@ -420,6 +441,52 @@ class HipWhisper:
             assert int(st.min()) >= 0 and int((st + ns).max()) <= len(keep), "a clip leaves the recording"
         self._chk(self.L.nh_logmel_chunks_rows(self._h, ptr, dev, st.ctypes.data_as(C.POINTER(C.c_int64)), _ip(ns), len(ns), int(row0)))
         self._filled(row0, len(ns))
+
+    # -- long recordings without their silence (include/norma_hip.h: nh_vad_plan, nh_logmel_pieces_rows)
+    def vad_plan(self, pcm, n_samples: Optional[int] = None, params=None):
+        """nh_vad_plan: (piece_starts i64 [n_pieces], piece_lens i32 [n_pieces], chunk_first i32 [n_chunks + 1]) of the speech
+        of a 16 kHz mono recording -- a host f32 array, or a device pointer with n_samples.  params: None (the defaults), an
+        NhVadParams, or a tuple in its field order."""
+        ptr, dev, n, keep = self._recording(pcm, n_samples)
+        q = None if params is None else NhVadParams.of(params)
+        cap_p = cap_c = max(4, 2 * (n // (NH_CUT_HOP * (q.max_frames if q is not None and q.max_frames > 0 else N_FRAMES))) + 2)
+        while True:
+            starts, lens, first = np.zeros(cap_p, dtype=np.int64), np.zeros(cap_p, dtype=np.int32), np.zeros(cap_c + 1, dtype=np.int32)
+            n_p, n_c = C.c_int32(0), C.c_int32(0)
+            rc = self.L.nh_vad_plan(self._h, ptr, dev, n, None if q is None else C.byref(q), starts.ctypes.data_as(C.POINTER(C.c_int64)),
+                                    _ip(lens), cap_p, C.byref(n_p), _ip(first), cap_c, C.byref(n_c))
+            if rc != 0 and (n_p.value > cap_p or n_c.value > cap_c):   # refused for the caps alone: the call says what it needs
+                cap_p, cap_c = max(cap_p, int(n_p.value)), max(cap_c, int(n_c.value))
+                continue
+            self._chk(rc)
+            self._vad_frames = -(-n // NH_CUT_HOP)
+            return starts[:n_p.value].copy(), lens[:n_p.value].copy(), first[:n_c.value + 1].copy()
+
+    def vad_view(self):
+        """(E f32 [F], speech u8 [F], levels f32 [3] = Q_lo, Q_hi, T, regions i64 [n][2]) of the last vad_plan (nh_vad_view)"""
+        F = getattr(self, "_vad_frames", 0)
+        E, speech, levels, cnt = np.zeros(F, dtype=np.float32), np.zeros(F, dtype=np.uint8), np.zeros(3, dtype=np.float32), C.c_int32(0)
+        self._chk(self.L.nh_vad_view(self._h, _fp(E), speech.ctypes.data_as(C.POINTER(C.c_uint8)), F, _fp(levels), None, 0, C.byref(cnt)))
+        regions = np.zeros((cnt.value, 2), dtype=np.int64)
+        self._chk(self.L.nh_vad_view(self._h, None, None, 0, None, regions.ctypes.data_as(C.POINTER(C.c_int64)), cnt.value, None))
+        return E, speech, levels, regions
+
+    def logmel_pieces_rows(self, pcm, piece_starts: Sequence[int], piece_lens: Sequence[int], chunk_first: Sequence[int], row0: int = 0):
+        """nh_logmel_pieces_rows: row row0 + b = the concatenation of the pieces chunk_first[b] .. chunk_first[b + 1] - 1 of a
+        recording (host f32 array or device pointer) -> log-mel of rows [row0, row0 + len(chunk_first) - 1).  chunk_first may be
+        a slice of a plan's: the pieces it names are rebased here."""
+        ptr, dev, _, keep = self._recording(pcm, 0)
+        cf = np.ascontiguousarray(chunk_first, dtype=np.int32)
+        assert len(cf) >= 2, "chunk_first holds batch + 1 entries"
+        j0, j1 = int(cf[0]), int(cf[-1])
+        st = np.ascontiguousarray(np.asarray(piece_starts, dtype=np.int64)[j0:j1])
+        ns = np.ascontiguousarray(np.asarray(piece_lens, dtype=np.int32)[j0:j1])
+        cf = cf - np.int32(j0)
+        assert len(st) == len(ns) == j1 - j0, "chunk_first names pieces that are not there"
+        if keep is not None and len(st):
+            assert int(st.min()) >= 0 and int((st + ns).max()) <= len(keep), "a piece leaves the recording"
+        self._chk(self.L.nh_logmel_pieces_rows(self._h, ptr, dev, st.ctypes.data_as(C.POINTER(C.c_int64)), _ip(ns), _ip(cf), len(cf) - 1, int(row0)))
+        self._filled(row0, len(cf) - 1)
 
     def logmel_device(self, pcm_dev_ptr: int, n_samples: Sequence[int], stride: int):
         """PCM already resident in HBM (device pointer, f32 [batch][stride])."""

@@ -1,6 +1,8 @@
 """One call for a whole recording: plan the cuts on the device (HipWhisper.cut_plan: the quietest frame near the end of every
 clip of at most 30 s), run the chunks through log-mel, encoder and greedy decode in groups, and join the chunks' segments on
-one time axis.  The contract of the cuts is in include/norma_hip.h and DESIGN.md 11.
+one time axis.  The contract of the cuts is in include/norma_hip.h and DESIGN.md 11.  transcribe_speech / stitch_speech are the
+same call on the recording's speech alone (HipWhisper.vad_plan): a chunk is then a concatenation of pieces of the
+recording, and to_recording maps a time inside a chunk back to the recording's own axis.
 
 The reference walks a recording sequentially and re-seeks to its last timestamp (`model.rs:100-146`); here the chunks are
 independent, which is what lets them be batched.  `stitch` delimits segments the way `model.rs:100-105` does.
@@ -54,6 +56,26 @@ def transcribe_recording(hm, pcm, params=None, max_new_tokens: int = 0, align: b
     return out
 
 
+def _segments(tokens, v):
+    """(s, e) index pairs of the boundary tokens that delimit a chunk's segments, the way model.rs:100-105 does: a boundary
+    token is a timestamp or eot, a segment runs from one boundary token to the next, and eot opens none"""
+    def boundary(t):
+        return t > tokens.no_timestamps or t == tokens.eot
+
+    i = 0
+    while True:
+        s = next((j for j in range(i, len(v)) if boundary(v[j])), None)
+        if s is None or v[s] == tokens.eot:
+            return
+        e = next((j for j in range(s + 1, len(v)) if boundary(v[j])), None)
+        if e is None:
+            return
+        yield s, e
+        if v[e] == tokens.eot:
+            return
+        i = e + 1
+
+
 def stitch(results: Sequence[dict], tokens) -> List[Tuple[float, float, List[int]]]:
     """results: what transcribe_recording returned; tokens: the vocabulary's special tokens (eot, no_timestamps).
     Returns (start_s, end_s, token_ids) per segment, in order, on the recording's own time axis: a chunk's tokens are split
@@ -61,28 +83,80 @@ def stitch(results: Sequence[dict], tokens) -> List[Tuple[float, float, List[int
     runs from one boundary token to the next, both excluded from token_ids), and a timestamp token `t` of a chunk stands for
     start_sample / 16000 + 0.02 * (t - no_timestamps - 1) seconds.  A segment the decode left open (closed by eot instead of
     a timestamp) ends with its chunk.  Segments without text and chunks ended by the no-speech exit contribute nothing."""
-    def boundary(t):
-        return t > tokens.no_timestamps or t == tokens.eot
-
     out = []
     for r in results:
         if r.get("no_speech_exit"):
             continue
         t0 = r["start_sample"] / SAMPLE_RATE
         v = list(r["tokens"])
-        i = 0
-        while True:
-            s = next((j for j in range(i, len(v)) if boundary(v[j])), None)
-            if s is None or v[s] == tokens.eot:
-                break
-            e = next((j for j in range(s + 1, len(v)) if boundary(v[j])), None)
-            if e is None:
-                break
+        for s, e in _segments(tokens, v):
             start = t0 + 0.02 * (v[s] - tokens.no_timestamps - 1)
             end = (r["start_sample"] + r["n_samples"]) / SAMPLE_RATE if v[e] == tokens.eot else t0 + 0.02 * (v[e] - tokens.no_timestamps - 1)
             if e > s + 1:
                 out.append((start, end, v[s + 1:e]))
+    return out
+
+
+def transcribe_speech(hm, pcm, params=None, max_new_tokens: int = 0, align: bool = False) -> List[dict]:
+    """transcribe_recording on the recording's speech alone.  params: the parameters of HipWhisper.vad_plan.  Returns one dict
+    per chunk (none for a recording without speech): the fields of decode_greedy plus pieces = [(offset_in_chunk, start_sample,
+    n_samples)], n_samples = the chunk's total, n_keys = ceil(n_samples / 320), and with align=True token_first / token_last."""
+    if isinstance(pcm, np.ndarray):
+        rec, n = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1), None
+    else:
+        rec, n = int(pcm[0]), int(pcm[1])
+    starts, lens, first = hm.vad_plan(rec, n, params)
+    pieces = []
+    for k in range(len(first) - 1):
+        off, row = 0, []
+        for j in range(int(first[k]), int(first[k + 1])):
+            row.append((off, int(starts[j]), int(lens[j])))
+            off += int(lens[j])
+        pieces.append(row)
+    totals = [row[-1][0] + row[-1][2] for row in pieces]
+    out = []
+    for a, b in _groups(totals, hm.max_batch):
+        hm.logmel_pieces_rows(rec, starts, lens, first[a:b + 1], 0)
+        hm.encode()
+        res = hm.decode_greedy(max_new_tokens)
+        keys = [-(-v // KEY_SAMPLES) for v in totals[a:b]]
+        if align:
+            tf, tl = hm.align_decoded(n_keys=keys)
+        for i, r in enumerate(res):
+            r.update(pieces=pieces[a + i], n_samples=totals[a + i], n_keys=keys[i])
+            if align:
+                r.update(token_first=tf[i].copy(), token_last=tl[i].copy())
+            out.append(r)
+    return out
+
+
+def to_recording(pieces: Sequence[Tuple[int, int, int]], tau_samples: float, end: bool = False) -> float:
+    """A time inside a chunk (samples from the chunk's start) on the recording's axis (samples).  pieces: (offset_in_chunk,
+    start_sample, n_samples) in order.  A start maps through the piece with off <= tau < off + len, an end through the piece
+    with off < tau <= off + len: a segment that ends exactly at a piece's end stays in front of the dropped silence, one that
+    starts there begins behind it.  Past the last piece: that piece's end."""
+    for off, start, n in pieces:
+        if (off < tau_samples <= off + n) if end else (off <= tau_samples < off + n):
+            return start + (tau_samples - off)
+    off, start, n = pieces[-1] if tau_samples > 0 else pieces[0]
+    return start + min(max(tau_samples - off, 0), n)
+
+
+def stitch_speech(results: Sequence[dict], tokens) -> List[Tuple[float, float, List[int]]]:
+    """stitch for what transcribe_speech returned: the same segment rules, every time mapped through to_recording -- a
+    segment's first timestamp as a start, its closing one as an end.  A segment closed by eot ends at the end of its chunk's
+    last piece."""
+    out = []
+    for r in results:
+        if r.get("no_speech_exit"):
+            continue
+        v, pieces = list(r["tokens"]), r["pieces"]
+        for s, e in _segments(tokens, v):
+            start = to_recording(pieces, KEY_SAMPLES * (v[s] - tokens.no_timestamps - 1)) / SAMPLE_RATE
             if v[e] == tokens.eot:
-                break
-            i = e + 1
+                end = (pieces[-1][1] + pieces[-1][2]) / SAMPLE_RATE
+            else:
+                end = to_recording(pieces, KEY_SAMPLES * (v[e] - tokens.no_timestamps - 1), end=True) / SAMPLE_RATE
+            if e > s + 1:
+                out.append((start, end, v[s + 1:e]))
     return out
