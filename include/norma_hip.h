@@ -40,6 +40,9 @@
  *   nh_pool_detect_languages, nh_pool_languages
  *                                 the same for the clips of a decode pool, each in its own first decode step
  *   nh_reset                      Type::reset_kv_cache (model.rs:485-490)
+ *   nh_set_prompts, nh_decoder_forward_onepass
+ *                                 (no counterpart: every reference decode starts from [sot, lang?, task], model.rs:285-289)
+ *                                 tokens in front of the prompt, consumed in one pass
  */
 #ifndef NORMA_HIP_H
 #define NORMA_HIP_H
@@ -90,7 +93,7 @@ typedef struct nh_tokens {
 
 /* Result of one greedy decode (model.rs:494-499 DecodingResult, compression_ratio is always NaN). */
 typedef struct nh_decode_result {
-    int32_t n_tokens;       /* tokens written for this sequence, prompt and eot included */
+    int32_t n_tokens;       /* tokens written for this sequence, prompt and eot included (a prefix of nh_set_prompts is not) */
     int32_t no_speech_exit; /* 1: early return of model.rs:308-315 */
     double avg_logprob;
     double no_speech_prob;
@@ -386,7 +389,8 @@ int nh_pool_languages(nh_ctx *ctx, const int32_t *rows, int n_rows, int32_t *out
  *            TEMPERATURES (decode_with_fallback, model.rs:175);
  *   choice   the first token whose cumulative weight exceeds u * total (WeightedIndex::sample's partition_point),
  *            cumulated in f64 over 1024 chunks of ceil(V / 1024) consecutive tokens, then inside the chunk;
- *   all masked: eot is pushed and the sequence stops (model.rs:343-346).  Log-prob bookkeeping as for t = 0. */
+ *   all masked: eot is pushed and the sequence stops (model.rs:343-346).  Log-prob bookkeeping as for t = 0.
+ * Under a prefix (nh_set_prompts) `step` is the PHYSICAL token count, the prefix included. */
 int nh_decode_sampled(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *results, int max_new_tokens,
                       float temperature, uint64_t seed, uint32_t clip0, uint32_t attempt);
 /* Model::detect_language (model.rs:194-210) for every clip of the batch: one decoder step on [sot], softmax over the
@@ -396,6 +400,30 @@ int nh_decode_sampled(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *result
 int nh_detect_language(nh_ctx *ctx, const int32_t *lang_tokens, int n, int32_t *out_lang, float *out_probs);
 /* Per-sequence language tokens for the next decode (host i32 [batch]); NULL: back to nh_tokens.lang for all. */
 int nh_set_languages(nh_ctx *ctx, const int32_t *langs);
+/* ---- decoder prompts ---------------------------------------------------------------------------------------
+ * Tokens in front of [sot, lang?, task] for the next nh_decode_greedy / nh_decode_sampled of the current lockstep batch: an
+ * initial prompt (vocabulary, style), or the previous window's text when a stream is transcribed in sequence.  ONE prefix
+ * length per batch, the contents per clip.
+ * tokens: host i32, clip b's prefix at tokens + b * stride, n_prefix entries, taken verbatim (the caller puts
+ * <|startofprev|> first if it wants Whisper's convention).  n_prefix == 0 or tokens == NULL: none.
+ * What a prefix means: decoder positions 0 .. n_prefix - 1 consume it; [sot, lang?, task] sit at n_prefix ..; the no-speech
+ * probe (model.rs:293-305) reads the logits at sot's position, n_prefix; generation starts at n_prefix + P - 1; the rules,
+ * the forced first timestamp and max_new_tokens see prompt_len = n_prefix + P; the length cap (model.rs:367) applies to the
+ * physical sequence, prefix included.  What comes back is the sequence from sot on: out_tokens and n_tokens exclude the
+ * prefix, avg_logprob is divided by that n_tokens (so n_prefix == 0 gives the bits of a decode that never saw a prompt, and a
+ * prefix does not dilute the fallback test), no_speech_exit as ever.  nh_detect_language ignores the prefix (the reference
+ * detects on [sot] alone).
+ * The prefix positions go through the one-pass forward (nh_decoder_forward_onepass's arithmetic; the last decoder block stops
+ * once its K/V are cached), or -- under NH_OPT_PROMPT_STEPWISE = 1, for prefixes of fewer than 4 tokens (measured: the one
+ * pass does not pay below that), at widths the one pass does not cover (d_model % 128 != 0) and under NH_OPT_ABSORBED_XATTN --
+ * through the decode step position by position; the positions from sot on are decode steps
+ * either way.
+ * Lifetime: bound to the batch, like nh_set_languages: cleared by nh_logmel* with row0 == 0, nh_set_mel, nh_reset and
+ * nh_pool_begin; a decode whose batch differs from the one the prefix was set for (rows joined since) is NH_ERR_STATE.
+ * After a prompted decode nh_align_decoded refuses (NH_ERR_STATE): the kept queries sit at physical positions.
+ * Refused, nothing launched, state unchanged.  NH_ERR_INVALID: batch != the current batch; n_prefix outside
+ * 0 .. max_target_positions / 2 - 1; a token id outside the vocabulary; stride < n_prefix.  NH_ERR_STATE: a running pool. */
+int nh_set_prompts(nh_ctx *ctx, const int32_t *tokens, int n_prefix, int64_t stride, int batch);
 /* Device-resident log-mel -> encoder -> decode without intermediate host syncs (bench path). */
 int nh_transcribe_batch(nh_ctx *ctx, const float *pcm_dev, const int32_t *n_samples, int64_t stride,
                         int batch, int32_t *out_tokens, nh_decode_result *results, int max_new_tokens);
@@ -412,6 +440,12 @@ int nh_encoder_output(nh_ctx *ctx, int b, float *out);
 /* TextDecoder::forward for every clip over a teacher-forced prefix: tokens i32 [batch][T] ->
  * hidden f32 [batch][T][d_model] (after the final LayerNorm). */
 int nh_decoder_forward(nh_ctx *ctx, const int32_t *tokens, int T, float *hidden_out);
+/* nh_decoder_forward's contract (same arguments, same state afterwards: self K/V of positions 0 .. T-1 and the device-side
+ * tokens overwritten), computed in one pass over the T positions: rows (clip, position) through the MFMA GEMM, a causal
+ * self-attention and a cross-attention kernel over all positions of a clip (DESIGN.md 13 has the roundings, which are not
+ * the decode step's: the two agree within tolerances, not bit for bit).  A clip's rows are bit-identical whatever the batch.
+ * NH_ERR_STATE also for d_model % 128 != 0 and under NH_OPT_ABSORBED_XATTN. */
+int nh_decoder_forward_onepass(nh_ctx *ctx, const int32_t *tokens, int T, float *hidden_out);
 /* TextDecoder::final_linear on host-provided rows: x f32 [rows][d_model] -> logits f32 [rows][V] */
 int nh_final_linear(nh_ctx *ctx, const float *x, int rows, float *logits_out);
 /* The logit rules on device: probs f32 [V] (already soft-maxed), tokens so far, last timestamp
@@ -525,6 +559,8 @@ int nh_set_profile_gemm(nh_ctx *ctx, int enable);
  * batch is held: NH_ERR_NOMEM when that does not fit); 0 (default): clips are processed in groups that keep the workspace at
  * or under 256 MiB, and the views refuse. */
 #define NH_OPT_ALIGN_KEEP 4
+/* Decoder prompts.  1: the prefix goes through the decode step position by position (the A/B screen); 0 (default): one pass */
+#define NH_OPT_PROMPT_STEPWISE 5
 int nh_set_option(nh_ctx *ctx, int option, int value);
 
 #ifdef __cplusplus

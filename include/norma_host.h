@@ -141,6 +141,19 @@ int nm_model_checkpoint_alignment_heads(const nm_model *m, int32_t *layer_head_p
 /* (start, end) in seconds from the start of its slice for every token the last nm_model_transcribe wrote to out_tokens, in that
  * order (the -1 separators have no entry).  Writes up to cap pairs, returns how many there are: 0 with alignment off. */
 int nm_model_last_token_times(const nm_model *m, float *start, float *end, int cap);
+/* Decoder prompts (nh_set_prompts of norma_hip.h; no counterpart in the reference).  set_prompt_tokens: an initial prompt --
+ * n token ids (the tokenizer here only decodes), n = 0: none -- for every slice.  set_condition_on_previous: inside
+ * nm_model_transcribe the text tokens of the emitted segments are kept as history, and a slice decodes under
+ * [<|startofprev|>] + (initial prompt + history) cut to its last max_target_positions / 2 - 2 ids, the same for every
+ * temperature of decode_with_fallback; the history is dropped on final_chunk and after a slice accepted at a temperature
+ * above 0.5.  Both off (the default): the calls and the bits of a model without them.  <|startofprev|> is looked up by
+ * nm_definition_blocking_try_to_model_from_dir (token_to_id); a model made from tensors is told it with
+ * nm_model_set_startofprev_token.  Slices decoded under a prefix get no token times (nm_model_set_alignment_heads).
+ * nm_model_prompt_prefix: the prefix the NEXT slice would decode under (up to cap ids are written; returns its length). */
+void nm_model_set_prompt_tokens(nm_model *m, const int32_t *ids, int n);
+void nm_model_set_condition_on_previous(nm_model *m, int enable);
+void nm_model_set_startofprev_token(nm_model *m, int32_t id);
+int nm_model_prompt_prefix(const nm_model *m, int32_t *ids, int cap);
 /* DecodingResult of the last decoded slice + whether the reference would have entered its sampled fallback */
 void nm_model_last_result(const nm_model *m, double *avg_logprob, double *no_speech_prob, int *needed_fallback,
                           int *n_tokens);

@@ -1,6 +1,6 @@
-// nh_ctx.h -- the state behind the C ABI of include/norma_hip.h, shared by the seven files that implement it: nh_model.hip
+// nh_ctx.h -- the state behind the C ABI of include/norma_hip.h, shared by the eight files that implement it: nh_model.hip
 // (create / destroy, weights, tokens, options, timings), nh_encode.hip (log-mel, encoder), nh_decode.hip (decoder step,
-// lockstep decode, decode pool, parity views), nh_align.hip (token-level timestamps), nh_resample.hip (audio ingest),
+// lockstep decode, decode pool, parity views), nh_prefill.hip (decoder prompts, the one-pass forward), nh_align.hip (token-level timestamps), nh_resample.hip (audio ingest),
 // nh_cut.hip (cutting long recordings), nh_vad.hip (their speech map).  It also holds the two things every audio route into the PCM rows shares: the
 // grow-on-demand device buffer (DevBuf: the one staging of host audio, the cut workspaces) and the batch check
 // (check_batch) that runs before anything is queued.  No torch, no candle, no CPU fallback: an entry point runs the HIP
@@ -240,6 +240,11 @@ struct nh_ctx {
     int align_q_heads = 0;
     int dec_layer_limit = 0;    // parity view (NH_OPT_DECODER_LAYER_LIMIT): run only the first n decoder blocks; 0 = all
     std::vector<int32_t> seq_lang;  // per-sequence language tokens (LanguageState::Detect), empty = tk.lang for all
+    // nh_set_prompts: what the next decodes of the current lockstep batch put in front of [sot, lang?, task]: n_prefix ids per
+    // clip, [prompt_batch][n_prefix].  Bound to the batch like seq_lang (clear_prompt); n_prefix == 0: none.
+    std::vector<int32_t> prompt;
+    int n_prefix = 0, prompt_batch = 0;
+    bool opt_prompt_stepwise = false;   // NH_OPT_PROMPT_STEPWISE
     int32_t *d_lang_tokens = nullptr, *d_lang_out = nullptr;
     float *d_lang_probs = nullptr;
     RuleTokens tk{};
@@ -289,6 +294,17 @@ void drop_graphs(nh_ctx *ctx, int first = 0);   // nh_decode.hip
 void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr = nullptr, bool final_ln = true, bool skip_done = false,
                   const AlignHeadSet *keep = nullptr);   // nh_decode.hip
 int ensure_decoder_repack(nh_ctx *ctx);         // nh_model.hip
+// nh_prefill.hip: TextDecoder::forward over positions 0 .. T-1 of ds.tokens for the rows of the lockstep batch in one pass:
+// self K/V of those positions land in the caches.  hidden == nullptr (a decode's prefix): the last block stops once its K/V
+// are written; otherwise everything, the final LayerNorm included, and the B * T rows are copied to `hidden` (host f32).
+bool prefill_supported(const nh_ctx *ctx);
+// Shortest prefix the default route sends through the one pass.  Its fifteen-odd launches on a handful of rows cost 0.64 - 0.76 ms
+// at distil-large-v3's shape with 32 clips whatever the length, a decode step 0.18 ms: measured 0.64 / 0.67 / 0.71 ms against
+// 0.17 / 0.36 / 0.73 ms stepwise at 1 / 2 / 4 tokens (tools/dbg/prompt_cost.py, profiles/prompt_cost.json): the crossover
+// lies between 2 and 4.
+#define NH_PREFILL_MIN_PREFIX 4
+int prefill_forward(nh_ctx *ctx, int T, float *hidden);
+inline void clear_prompt(nh_ctx *ctx) { ctx->prompt.clear(); ctx->n_prefix = 0; ctx->prompt_batch = 0; }
 // nh_encode.hip: may `batch` clips of these lengths become rows row0 .. of the context's mel batch?  Row range, clip lengths,
 // equal mel frames, the pool and row-gap rules.  Changes nothing in the context: every entry point that fills PCM rows
 // calls it before its first copy or launch.

@@ -93,8 +93,11 @@ static void logits_from_dxn(nh_ctx *ctx, int R) {
 }
 
 // what Model::decode returns for one sequence from the state its loop left behind (model.rs:308-315, 373-381)
-static void finish_sequence(nh_ctx *ctx, int32_t *t, int n, int done, double slp, double nsp, int32_t *out_tokens, nh_decode_result &r) {
+// skip: the prefix of a prompted decode (nh_set_prompts), which is not part of what comes back: tokens, their count and the
+// divisor of avg_logprob are those of the sequence from sot on
+static void finish_sequence(nh_ctx *ctx, int32_t *t, int n, int done, double slp, double nsp, int32_t *out_tokens, nh_decode_result &r, int skip = 0) {
     const int C = ctx->c.max_target_positions;
+    t += skip; n -= skip;
     r.no_speech_prob = nsp;
     r.no_speech_exit = (done == 2);
     if (done == 2) { r.avg_logprob = 0.0; }  // model.rs:308-315
@@ -103,12 +106,12 @@ static void finish_sequence(nh_ctx *ctx, int32_t *t, int n, int done, double slp
         while (n >= 2 && t[n - 2] > ctx->tk.no_timestamps) { t[n - 2] = t[n - 1]; n--; }  // :375-381
     }
     r.n_tokens = n;
-    memcpy(out_tokens, t, sizeof(int32_t) * C);
+    memcpy(out_tokens, t, sizeof(int32_t) * (C - skip));
     for (int i = n; i < C; i++) out_tokens[i] = 0;
 }
 
 // device state -> results of the sequences in rows[0 .. n) (rows == nullptr: rows 0 .. n - 1); only those token rows cross
-static int read_results(nh_ctx *ctx, const int32_t *rows, int n, int32_t *out_tokens, nh_decode_result *results) {
+static int read_results(nh_ctx *ctx, const int32_t *rows, int n, int32_t *out_tokens, nh_decode_result *results, int skip = 0) {
     const int C = ctx->c.max_target_positions, B = rows ? ctx->pool.rows : n;
     std::vector<int32_t> toks((size_t)n * C), nt(B), done(B);
     std::vector<double> slp(B), nsp(B);
@@ -126,7 +129,7 @@ static int read_results(nh_ctx *ctx, const int32_t *rows, int n, int32_t *out_to
     if (!rows) { ctx->live.n.assign(n, 0); ctx->live.done.assign(n, 0); }
     for (int i = 0; i < n; i++) {
         const int b = rows ? rows[i] : i;
-        finish_sequence(ctx, toks.data() + (size_t)i * C, nt[b], done[b], slp[b], nsp[b], out_tokens + (size_t)i * C, results[i]);
+        finish_sequence(ctx, toks.data() + (size_t)i * C, nt[b], done[b], slp[b], nsp[b], out_tokens + (size_t)i * C, results[i], skip);
         // what nh_align_decoded aligns: the sequence as returned
         if (rows) { PoolRow &r = ctx->pool.row[b]; r.n = results[i].n_tokens; r.done = done[b]; }
         else { ctx->live.n[i] = results[i].n_tokens; ctx->live.done[i] = done[b]; }
@@ -203,6 +206,8 @@ static int decode_impl(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *resul
     if (!ctx->have_enc) return ctx->fail(NH_ERR_STATE, "nh_decode: call nh_encode first");
     if (!ctx->have_tokens) return ctx->fail(NH_ERR_STATE, "nh_decode: call nh_set_tokens first");
     if (ctx->pool.rows > 0) return ctx->fail(NH_ERR_STATE, "nh_decode: the context runs a decode pool (nh_pool_begin); a batch submitted with row0 = 0 ends it");
+    const int NP = ctx->n_prefix;   // nh_set_prompts: tokens in front of the prompt; 0: none, and everything below is the plain decode
+    if (NP > 0 && ctx->prompt_batch != ctx->cur_batch) return ctx->fail(NH_ERR_STATE, "nh_decode: the prefix was set for another batch (rows joined since nh_set_prompts)");
     hipSetDevice(ctx->dev);
     if (int rc = ensure_decoder_repack(ctx)) return rc;
     ctx->live.lock_valid = false;
@@ -210,10 +215,12 @@ static int decode_impl(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *resul
     // model.rs:285-289: prompt = [sot, lang?, task]
     const bool per_seq = (int)ctx->seq_lang.size() == B;
     const int P = (per_seq || ctx->tk.lang >= 0) ? 3 : 2;  // 2 or 3, so position 0 is never a generation step
-    std::vector<int32_t> toks((size_t)B * C, 0), nt(B, P);
+    const int PL = NP + P;   // the physical prompt: what the rules, the forced first timestamp and max_new_tokens count from
+    std::vector<int32_t> toks((size_t)B * C, 0), nt(B, PL);
     for (int b = 0; b < B; b++) {
         int32_t *t = toks.data() + (size_t)b * C;
-        int i = 0;
+        int i = NP;
+        if (NP > 0) memcpy(t, ctx->prompt.data() + (size_t)b * NP, sizeof(int32_t) * NP);
         t[i++] = ctx->tk.sot;
         if (P == 3) t[i++] = per_seq ? ctx->seq_lang[b] : ctx->tk.lang;
         t[i++] = ctx->tk.task;
@@ -234,12 +241,23 @@ static int decode_impl(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *resul
     int steps = 0;
     // Prompt phase (eager): position pos consumes tokens[pos]; pos 0 also yields no_speech_prob
     // (model.rs:293-305: logits at position 0 of the flush = true pass).
-    for (int pos = 0; pos < P - 1; pos++) {
+    // Under a prefix, positions 0 .. NP-1 consume it first: in one pass over all of them (nh_prefill.hip: the caches of those
+    // positions are all the later ones need), or through the step one by one (NH_OPT_PROMPT_STEPWISE, prefixes too short for
+    // the one pass to pay, widths and options it does not cover); sot then sits at position NP, and the probe reads ITS logits.
+    if (NP > 0) {
+        if (!ctx->opt_prompt_stepwise && NP >= NH_PREFILL_MIN_PREFIX && prefill_supported(ctx)) {
+            if (int rc = prefill_forward(ctx, NP, nullptr)) return rc;
+        } else {
+            for (int pos = 0; pos < NP; pos++) decoder_step(ctx, pos, nullptr, false, true, kept_heads(ctx));
+        }
+        steps += NP;
+    }
+    for (int pos = NP; pos < PL - 1; pos++) {
         decoder_step(ctx, pos, nullptr, true, true, kept_heads(ctx));
         steps++;
-        if (pos == 0) {
+        if (pos == NP) {
             logits_from_dxn(ctx, B);
-            launch_logit_step(ctx->logits, V, ctx->ds, ctx->tk, B, C, cap, max_new_tokens, P, 0, ctx->lpart, ctx->ltick, nullptr, ctx->st);
+            launch_logit_step(ctx->logits, V, ctx->ds, ctx->tk, B, C, cap, max_new_tokens, PL, 0, ctx->lpart, ctx->ltick, nullptr, ctx->st);
         }
     }
     // Generation phase: one token per step from pos = P-1 on.  The length cap (model.rs:367) forces eot once
@@ -247,15 +265,15 @@ static int decode_impl(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *resul
     // reads the position from device memory (the eager loop is host-launch-bound at ~5 us per tiny kernel).
     const bool no_graph = !ctx->opt_graphs || inv_t > 0.f;
     if (!no_graph)
-        if (int rc = ensure_step_graphs(ctx, StepKey{B, ctx->S, max_new_tokens, P, ctx->token_gen, 0, false, false, ctx->live.gen})) return rc;
-    const int32_t first_pos = P - 1;
+        if (int rc = ensure_step_graphs(ctx, StepKey{B, ctx->S, max_new_tokens, PL, ctx->token_gen, 0, false, false, ctx->live.gen})) return rc;
+    const int32_t first_pos = PL - 1;
     for (int b = 0; b < B; b++) ctx->h_done[128 + b] = first_pos;  // every sequence of a batch starts generating at the same position
     HIPCHK(hipMemcpyAsync(ctx->d_pos, ctx->h_done + 128, sizeof(int32_t) * B, hipMemcpyHostToDevice, ctx->st));
     // positions first_pos .. cap - 2; the host looks at the done flags every 16 steps (and after the last one)
     for (int pos = first_pos; pos <= cap - 2;) {
         int n = 1;
         if (no_graph) {
-            emit_token_step(ctx, StepSpec{B, max_new_tokens, P, 1, inv_t > 0.f, pos, nullptr, inv_t, seed, clip0, attempt});
+            emit_token_step(ctx, StepSpec{B, max_new_tokens, PL, 1, inv_t > 0.f, pos, nullptr, inv_t, seed, clip0, attempt});
         } else if (pos + NH_GRAPH_STEPS - 1 <= cap - 2) {
             HIPCHK(hipGraphLaunch(ctx->graphs[0].multi, ctx->st));
             n = NH_GRAPH_STEPS;
@@ -275,9 +293,10 @@ static int decode_impl(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *resul
     }
     HIPCHK(hipEventRecord(ctx->ev[6], ctx->st));
     HIPCHK(hipGetLastError());
-    if (int rc = read_results(ctx, nullptr, B, out_tokens, results)) return rc;
+    if (int rc = read_results(ctx, nullptr, B, out_tokens, results, NP)) return rc;
     ctx->tm.decode_steps = steps;
-    ctx->live.lock_valid = kept_heads(ctx) != nullptr; ctx->live.P = P;
+    // after a prompted decode the kept queries sit at physical positions, which nh_align_decoded does not map: it refuses
+    ctx->live.lock_valid = kept_heads(ctx) != nullptr && NP == 0; ctx->live.P = P;
     return NH_OK;
 }
 
@@ -310,6 +329,7 @@ extern "C" int nh_pool_begin(nh_ctx *ctx, int rows, int max_new_tokens, int per_
     ctx->cur_batch = rows; ctx->frames = -1; ctx->S = 0; ctx->have_mel = false; ctx->have_enc = false;
     ctx->live.lock_valid = false;
     ctx->seq_lang.clear();
+    clear_prompt(ctx);
     for (int b = 0; b < rows; b++) ctx->h_done[128 + b] = 3;  // 3: empty row (skipped like a finished one)
     HIPCHK(hipMemcpyAsync(ctx->ds.done, ctx->h_done + 128, sizeof(int32_t) * rows, hipMemcpyHostToDevice, ctx->st));
     HIPCHK(hipMemsetAsync(ctx->d_pos, 0, sizeof(int32_t) * rows, ctx->st));

@@ -56,6 +56,7 @@ static int commit_batch(nh_ctx *ctx, const int32_t *n_samples, int batch, int ro
     ctx->have_mel = false;
     ctx->pool.rows = 0;  // a fresh batch ends a decode pool
     ctx->seq_lang.clear();
+    clear_prompt(ctx);   // a prefix belongs to the batch it was set for (nh_set_prompts)
     return reframe(ctx);
 }
 

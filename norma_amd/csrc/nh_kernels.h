@@ -161,7 +161,7 @@ bool launch_layernorm_sliced(const float *x, const float *w, const float *b, hal
 void launch_repack_tiles(const half_t *W, half_t *out, int N, int K, hipStream_t st);
 
 // ---- kernels that do not share their CU's LDS: skinny_lds_kernel, skinny_ldsp_kernel (k_skinny.hip: the "two logits kernels
-// above" of the finding below, written beside them) and xabs_main_kernel (k_dec_attn.hip) -----------------------------------------
+// above" of the finding below, written beside them), xabs_main_kernel (k_dec_attn.hip) and prefill_attn_kernel (k_prefill.hip) -------
 // The two logits kernels above keep their activations in LDS and feed every MFMA from a `ds_read_b128` -- 512 threads, 288-358
 // of a SIMD's 512 registers, 40-120 KB of LDS: other kernels' workgroups fit beside them on a CU.  r03 found that they must not:
 // the log-mel kernel of ANOTHER context (37 KB of LDS, 4 waves) gave wrong spectra in 1-250 frames of a clip whenever one of these
@@ -391,6 +391,16 @@ void launch_enc_attention(const half_t *q, const half_t *k, long ld, const half_
 void launch_dec_attention(const half_t *q, const half_t *kc, const half_t *vc, half_t *out, int B, int Tn,
                           int H, int d, int ctx, int Tk, const int32_t *pos_ptr, hipStream_t st, int kv_head_major = 0,
                           const int32_t *done = nullptr);
+
+// ---- attention of the one-pass decoder forward (k_prefill.hip): T query positions per clip at once ---------------------
+// q, k, v: fp16 [B*T][ld] as the qkv GEMM leaves them (head h at column 64 h); out fp16 [B*T][ldo].  Query i of a clip sees
+// the clip's keys 0 .. i; softmax(q . k / 8) in f32.  Also writes K and V of positions 0 .. T-1 into the head-major self
+// cache ck / cv [b][h][C][64].  false (nothing launched): a shape it does not cover (T < 1, T > C).
+bool launch_prefill_self_attention(const half_t *q, const half_t *k, const half_t *v, long ld, half_t *out, long ldo, half_t *ck,
+                                   half_t *cv, int B, int T, int H, int C, hipStream_t st);
+// q: fp16 [B*T][ldq]; ck, cv: the head-major cross K/V [b][h][S][64]; every query sees the S keys of its clip
+bool launch_prefill_cross_attention(const half_t *q, long ldq, const half_t *ck, const half_t *cv, half_t *out, long ldo, int B, int T,
+                                    int H, int S, hipStream_t st);
 
 // numerics prototype of cross-attention on the encoder output itself (NH_OPT_ABSORBED_XATTN; k_dec_attn.hip): Wkv = the fused
 // [2 d][d] cross K/V projection (K rows first), bkv its bias, xa fp16 [B][S][d], U scratch fp16 [B][H][d]

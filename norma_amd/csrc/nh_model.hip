@@ -449,6 +449,7 @@ extern "C" int nh_set_tokens(nh_ctx *ctx, const nh_tokens *tk, const int32_t *su
 extern "C" int nh_reset(nh_ctx *ctx) {  // Type::reset_kv_cache (model.rs:485-490)
     if (!ctx) return NH_ERR_INVALID;
     ctx->have_enc = false;
+    clear_prompt(ctx);
     return NH_OK;
 }
 
@@ -494,6 +495,7 @@ extern "C" int nh_set_option(nh_ctx *ctx, int option, int value) {
         ctx->live.gen++; ctx->live.lock_valid = false;
     }
     else if (option == NH_OPT_ALIGN_KEEP) ctx->opt_align_keep = value != 0;
+    else if (option == NH_OPT_PROMPT_STEPWISE) ctx->opt_prompt_stepwise = value != 0;
     else return ctx->fail(NH_ERR_INVALID, "nh_set_option: unknown option " + std::to_string(option));
     return NH_OK;
 }

@@ -230,6 +230,21 @@ void nm_model_set_temperature_fallback(nm_model *m, int enable, uint64_t seed) {
     if (m && m->m) m->m->set_temperature_fallback(enable != 0, seed);
 }
 
+void nm_model_set_prompt_tokens(nm_model *m, const int32_t *ids, int n) {
+    if (m && m->m) m->m->set_prompt_tokens(ids && n > 0 ? std::vector<int32_t>(ids, ids + n) : std::vector<int32_t>());
+}
+void nm_model_set_condition_on_previous(nm_model *m, int enable) {
+    if (m && m->m) m->m->set_condition_on_previous(enable != 0);
+}
+void nm_model_set_startofprev_token(nm_model *m, int32_t id) {
+    if (m && m->m) m->m->set_startofprev_token(id);
+}
+int nm_model_prompt_prefix(const nm_model *m, int32_t *ids, int cap) {
+    const std::vector<int32_t> p = m->m->prompt_prefix();
+    for (int i = 0; i < (int)p.size() && i < cap && ids; i++) ids[i] = p[i];
+    return (int)p.size();
+}
+
 int nm_model_set_alignment_heads(nm_model *m, const int32_t *layer_head_pairs, int n) {
     if (!m || !m->m || n < 0 || n > NH_ALIGN_MAX_HEADS || (n > 0 && !layer_head_pairs)) return 1;
     std::vector<nh_align_head> heads;

@@ -240,7 +240,8 @@ class Model {
     Model(nh_ctx *ctx, nh_config cfg, nh_tokens tk) : ctx_(ctx), cfg_(cfg), tk_(tk) {}
     Model(Model &&o) noexcept : ctx_(o.ctx_), cfg_(o.cfg_), tk_(o.tk_), buf_(std::move(o.buf_)), detok_(std::move(o.detok_)),
                                 align_heads_(std::move(o.align_heads_)), checkpoint_heads_(std::move(o.checkpoint_heads_)), capture_stale_(o.capture_stale_),
-                                src_hz_(o.src_hz_), channels_(o.channels_), resampler_(std::move(o.resampler_)) { o.ctx_ = nullptr; }
+                                src_hz_(o.src_hz_), channels_(o.channels_), resampler_(std::move(o.resampler_)),
+                                prompt_tokens_(std::move(o.prompt_tokens_)), history_(std::move(o.history_)), condition_(o.condition_), sop_token_(o.sop_token_) { o.ctx_ = nullptr; }
     Model(const Model &) = delete;
     ~Model() { if (ctx_) nh_destroy(ctx_); }
 
@@ -259,6 +260,30 @@ class Model {
     // Remembered, not enabled: hand it to set_alignment_heads to turn the timestamps on.
     const std::vector<nh_align_head> &checkpoint_alignment_heads() const { return checkpoint_heads_; }
     void set_checkpoint_alignment_heads(std::vector<nh_align_head> heads) { checkpoint_heads_ = std::move(heads); }
+
+    // Decoder prompts (nh_set_prompts; no counterpart in the reference, whose every decode starts from [sot, lang?, task]).
+    // set_prompt_tokens: an initial prompt -- token ids, the tokenizer here only decodes -- for every slice.
+    // set_condition_on_previous: inside transcribe the text tokens of the segments it emits are kept as history, and a slice
+    // decodes under [<|startofprev|>] + (initial prompt + history) cut to its last max_target_positions / 2 - 2 ids; every
+    // temperature of decode_with_fallback uses that same prefix.  The history is dropped on final_chunk and after a slice
+    // that was accepted at a temperature above 0.5 (what it says is not to be trusted as context).  Both off (the default):
+    // the calls and the bits of a model without them.  Under a prefix a slice's tokens get no times (set_alignment_heads):
+    // nh_align_decoded does not cover prompted decodes.
+    void set_prompt_tokens(std::vector<int32_t> ids) { prompt_tokens_ = std::move(ids); }
+    void set_condition_on_previous(bool on) { condition_ = on; if (!on) history_.clear(); }
+    void set_startofprev_token(int32_t id) { sop_token_ = id; }   // <|startofprev|> (token_to_id at load; -1: unknown)
+    // what the next slice decodes under; empty: no prefix
+    std::vector<int32_t> prompt_prefix() const {
+        std::vector<int32_t> body(prompt_tokens_);
+        if (condition_) body.insert(body.end(), history_.begin(), history_.end());
+        std::vector<int32_t> out;
+        if (body.empty()) return out;
+        const size_t room = (size_t)std::max(0, cfg_.max_target_positions / 2 - 2);
+        const size_t from = body.size() > room ? body.size() - room : 0;
+        out.push_back(sop_token_);
+        out.insert(out.end(), body.begin() + (long)from, body.end());
+        return out;
+    }
 
     // The format of the frames transcribe_frames takes: the capture device's rate and channel count (src/lib.rs:172-216 reads
     // them from the stream's config).  The default, 16 000 Hz mono, is what transcribe takes.  A new format starts a new stream.
@@ -296,6 +321,7 @@ class Model {
             Error e = decode_with_fallback(buf_.data(), slice_len, dr, have);
             if (e) return e;
             if (!have) { drain(slice_len); continue; }                // :90-93
+            const size_t first_new = out.size();                      // the segments this slice appends are the history's
             if (dr.no_speech_prob > NO_SPEECH_THRESHOLD && dr.avg_logprob < LOGPROB_THRESHOLD) { drain(slice_len); continue; }  // :95-98
             bool drained = false;
             for (auto seg : inclusive_boxed_by(dr.tokens, [&](uint32_t t) { return t > (uint32_t)tk_.no_timestamps || t == (uint32_t)tk_.eot; })) {
@@ -329,9 +355,14 @@ class Model {
             // tokens hold no timestamp, or segments that all close on a timestamp) leaves `buf` untouched in the
             // reference, which then spins forever on the same slice.  Deviation: drain the slice and go on.
             if (!stop && !drained) drain(slice_len);
+            if (condition_) {
+                if (TEMPERATURES[accepted_] > 0.5f) history_.clear();
+                else for (size_t i = first_new; i < out.size(); i++) history_.insert(history_.end(), out[i].tokens.begin(), out[i].tokens.end());
+            }
         }
         if (final_chunk) {                                            // :153-156
             if (detect_) lang_token_ = -1;                            // self.lang.clear()
+            history_.clear();
             int rc = nh_reset(ctx_);
             if (rc) return backend_error();
         }
@@ -359,6 +390,12 @@ class Model {
             if (nh_align_capture(ctx_, align_heads_.data(), (int)align_heads_.size())) return backend_error();
             capture_stale_ = false;
         }
+        // the prefix of this slice (nh_logmel above cleared the one before); the same for every temperature below
+        const std::vector<int32_t> prefix = prompt_prefix();
+        if (!prefix.empty()) {
+            if (sop_token_ < 0) return Error{Error::Backend, "a decoder prompt needs the <|startofprev|> token (set_startofprev_token)"};
+            if (nh_set_prompts(ctx_, prefix.data(), (int)prefix.size(), (int64_t)prefix.size(), 1)) return backend_error();
+        }
         std::vector<int32_t> toks(cfg_.max_target_positions);
         have = false;
         const uint32_t clip = slices_++;
@@ -372,10 +409,10 @@ class Model {
             // :177-187 -- accept unless avg_logprob < -1 (compression_ratio is NaN, so that test is always false)
             const bool needs_fallback = dr.avg_logprob < LOGPROB_THRESHOLD;
             if (a == 0) needs_fallback_ = needs_fallback && !(dr.no_speech_prob > NO_SPEECH_THRESHOLD);
-            if (!needs_fallback || dr.no_speech_prob > NO_SPEECH_THRESHOLD || !fallback_) have = true;
+            if (!needs_fallback || dr.no_speech_prob > NO_SPEECH_THRESHOLD || !fallback_) { have = true; accepted_ = a; }
             dr.first_frame.clear(); dr.last_frame.clear();
             const int P = (detect_ || tk_.lang >= 0) ? 3 : 2;                    // [sot, lang?, task], model.rs:285-289
-            if (have && !align_heads_.empty() && r.n_tokens > P) {               // the accepted attempt; a no-speech exit holds the prompt alone
+            if (have && !align_heads_.empty() && r.n_tokens > P && prefix.empty()) {               // the accepted attempt; a no-speech exit holds the prompt alone
                 const int32_t nt = r.n_tokens;
                 const int32_t nk = (int32_t)std::min<size_t>((size_t)cfg_.max_source_positions, (n + 319) / 320);   // frames that hold audio
                 std::vector<int32_t> first(cfg_.max_target_positions), last(cfg_.max_target_positions);
@@ -413,6 +450,10 @@ class Model {
     uint32_t src_hz_ = SAMPLE_RATE;
     int channels_ = 1;
     std::unique_ptr<Resampler> resampler_;   // made by the first transcribe_frames
+    std::vector<int32_t> prompt_tokens_, history_;   // the initial prompt; the text tokens emitted since the last final_chunk
+    bool condition_ = false;
+    int32_t sop_token_ = -1;
+    int accepted_ = 0;                       // index into TEMPERATURES of the attempt the last decode_with_fallback accepted
 };
 
 // One tensor handed to the loader (HF name, f32 or f16 data) -- stands in for the safetensors mmap of
@@ -522,6 +563,7 @@ class Definition {
         if (e) return e;
         (*out)->set_detokenizer([tok](const uint32_t *ids, size_t n) { return tok->decode(ids, n); });  // model.rs:147
         if (detect_language) (*out)->enable_language_detection(std::move(lang_tokens));
+        (*out)->set_startofprev_token(tok->token_to_id("<|startofprev|>"));   // -1 where the vocabulary has none: prompts are refused
         // generation_config.json, when the checkpoint has one: alignment_heads = [[layer, head], ...] (remembered, not enabled)
         {
             assets::MappedFile gf;

@@ -28,6 +28,7 @@ NH_ERR_NOMEM = 4
 NH_LANG_DETECT = -2   # `lang` of pool_admit*: the row detects its language in its first step (pool_detect_languages)
 NH_OPT_DECODE_GRAPHS, NH_OPT_FUSE_DECODE_LAYERNORM, NH_OPT_DECODER_LAYER_LIMIT, NH_OPT_ABSORBED_XATTN = 0, 1, 2, 3
 NH_OPT_ALIGN_KEEP = 4      # 1: align() keeps every clip's weights and matrix for align_weights / align_matrix
+NH_OPT_PROMPT_STEPWISE = 5  # 1: a decode's prefix (set_prompts) goes through the decode step position by position; 0: one pass
 NH_ALIGN_MAX_HEADS = 32
 # NH_SAMPLE_* of include/norma_hip.h (the types of src/dtype.rs)
 SAMPLE_DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.int8): 2, np.dtype(np.int16): 3,
@@ -162,6 +163,8 @@ def load_library() -> C.CDLL:
     L.nh_set_mel.argtypes = [vp, fp, C.c_int]
     L.nh_encoder_output.argtypes = [vp, C.c_int, fp]
     L.nh_decoder_forward.argtypes = [vp, ip, C.c_int, fp]
+    L.nh_decoder_forward_onepass.argtypes = [vp, ip, C.c_int, fp]
+    L.nh_set_prompts.argtypes = [vp, ip, C.c_int, C.c_int64, C.c_int]
     L.nh_final_linear.argtypes = [vp, fp, C.c_int, fp]
     L.nh_apply_rules.argtypes = [vp, fp, ip, C.c_int, C.c_int, fp, ip]
     L.nh_align.argtypes = [vp, ip, ip, C.c_int, C.POINTER(NhAlignHead), C.c_int, ip, ip, ip]
@@ -634,6 +637,19 @@ class HipWhisper:
             a = np.ascontiguousarray(langs, dtype=np.int32)
             self._chk(self.L.nh_set_languages(self._h, _ip(a)))
 
+    def set_prompts(self, prompts: Optional[Sequence[Sequence[int]]]):
+        """nh_set_prompts: one list of token ids per clip of the batch, all of ONE length, put in front of [sot, lang?, task]
+        by the next decode_greedy / decode_sampled (taken verbatim: <|startofprev|> first is the caller's to add); None or
+        empty lists: no prefix.  The results exclude the prefix."""
+        if prompts is None:
+            self._chk(self.L.nh_set_prompts(self._h, None, 0, 0, self.batch))
+            return
+        n = len(prompts[0]) if len(prompts) else 0
+        if any(len(p) != n for p in prompts):
+            raise ValueError("set_prompts: one prefix length per batch (ragged prefixes are not supported)")
+        a = np.ascontiguousarray(np.asarray(prompts, dtype=np.int32).reshape(len(prompts), n))
+        self._chk(self.L.nh_set_prompts(self._h, _ip(a) if n else None, n, n, len(prompts)))
+
     def reset(self):
         self._chk(self.L.nh_reset(self._h))
 
@@ -647,6 +663,15 @@ class HipWhisper:
         assert B == self.batch
         out = np.zeros((B, T, self.cfg.d_model), dtype=np.float32)
         self._chk(self.L.nh_decoder_forward(self._h, _ip(tokens), T, _fp(out)))
+        return out
+
+    def decoder_forward_onepass(self, tokens: np.ndarray) -> np.ndarray:
+        """decoder_forward's contract computed in one pass over the T positions (nh_decoder_forward_onepass)"""
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        B, T = tokens.shape
+        assert B == self.batch
+        out = np.zeros((B, T, self.cfg.d_model), dtype=np.float32)
+        self._chk(self.L.nh_decoder_forward_onepass(self._h, _ip(tokens), T, _fp(out)))
         return out
 
     def final_linear(self, x: np.ndarray) -> np.ndarray:

@@ -109,6 +109,13 @@ def _lib():
                                           C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.c_char_p, C.c_int]
         L.nm_model_set_alignment_heads.argtypes = [vp, C.POINTER(C.c_int32), C.c_int]
         L.nm_model_checkpoint_alignment_heads.argtypes = [vp, C.POINTER(C.c_int32), C.c_int]
+        L.nm_model_set_prompt_tokens.argtypes = [vp, C.POINTER(C.c_int32), C.c_int]
+        L.nm_model_set_prompt_tokens.restype = None
+        L.nm_model_set_condition_on_previous.argtypes = [vp, C.c_int]
+        L.nm_model_set_condition_on_previous.restype = None
+        L.nm_model_set_startofprev_token.argtypes = [vp, C.c_int32]
+        L.nm_model_set_startofprev_token.restype = None
+        L.nm_model_prompt_prefix.argtypes = [vp, C.POINTER(C.c_int32), C.c_int]
         L.nm_model_last_token_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]
         L.nm_model_last_result.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),
                                            C.POINTER(C.c_int)]
@@ -227,6 +234,26 @@ class Model:
     def set_temperature_fallback(self, enable: bool, seed: int = 0):
         """decode_with_fallback's sampled attempts (model.rs:175-188) on/off; draws follow the seeded sampling contract."""
         _lib().nm_model_set_temperature_fallback(self._h, int(enable), int(seed))
+
+    def set_prompt_tokens(self, ids: Sequence[int]):
+        """An initial prompt (token ids; the tokenizer only decodes) every slice decodes under, behind <|startofprev|>; [] = none."""
+        a = np.ascontiguousarray(ids, dtype=np.int32)
+        _lib().nm_model_set_prompt_tokens(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), len(a))
+
+    def set_condition_on_previous(self, enable: bool):
+        """Carry the text of the segments transcribe emits into the following slices' prompt (dropped on final_chunk and
+        after a slice accepted at a temperature above 0.5)."""
+        _lib().nm_model_set_condition_on_previous(self._h, int(enable))
+
+    def set_startofprev_token(self, token: int):
+        """<|startofprev|> for a model made from tensors (a checkpoint directory's tokenizer is asked by the loader)"""
+        _lib().nm_model_set_startofprev_token(self._h, int(token))
+
+    def prompt_prefix(self) -> List[int]:
+        """the prefix the next slice would decode under ([] = none)"""
+        a = np.zeros(self._ctx_len, dtype=np.int32)
+        n = _lib().nm_model_prompt_prefix(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), len(a))
+        return a[:n].tolist()
 
     def set_alignment_heads(self, heads: Sequence[Tuple[int, int]]):
         """Token-level timestamps: [(decoder layer, head)] switches them on for every slice transcribe decodes, an empty

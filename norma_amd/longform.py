@@ -30,11 +30,21 @@ def _groups(lens: Sequence[int], max_batch: int) -> List[Tuple[int, int]]:
     return out
 
 
-def transcribe_recording(hm, pcm, params=None, max_new_tokens: int = 0, align: bool = False) -> List[dict]:
+def _set_prompt(hm, prompt, n: int, align: bool):
+    """one id list in front of every chunk of the group just encoded (HipWhisper.set_prompts; a new batch starts without one)"""
+    if prompt is not None and len(prompt):
+        if align:
+            raise ValueError("align=True does not cover prompted decodes (align_decoded refuses after one)")
+        hm.set_prompts([list(prompt)] * n)
+
+
+def transcribe_recording(hm, pcm, params=None, max_new_tokens: int = 0, align: bool = False, prompt=None) -> List[dict]:
     """hm: a HipWhisper with weights, filters and tokens set.  pcm: a host f32 array (16 kHz mono), or (device pointer,
     n_samples).  params: the cut parameters (HipWhisper.cut_plan).  Returns one dict per chunk: the fields of decode_greedy
     plus start_sample, n_samples and n_keys = ceil(n_samples / 320), the encoder frames that hold audio.  align=True (the
-    caller has set hm.align_capture): token_first / token_last of align_decoded(n_keys=...) as well."""
+    caller has set hm.align_capture): token_first / token_last of align_decoded(n_keys=...) as well.
+    prompt: token ids every chunk decodes under (taken verbatim: <|startofprev|> first is the caller's to add; at most
+    max_target_positions / 2 - 1 of them); the results exclude them.  Not together with align=True."""
     if isinstance(pcm, np.ndarray):
         rec, n = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1), None
     else:
@@ -44,6 +54,7 @@ def transcribe_recording(hm, pcm, params=None, max_new_tokens: int = 0, align: b
     for a, b in _groups(lens, hm.max_batch):
         hm.logmel_chunks_rows(rec, starts[a:b], lens[a:b], 0)
         hm.encode()
+        _set_prompt(hm, prompt, b - a, align)
         res = hm.decode_greedy(max_new_tokens)
         keys = [-(-int(v) // KEY_SAMPLES) for v in lens[a:b]]
         if align:
@@ -97,10 +108,11 @@ def stitch(results: Sequence[dict], tokens) -> List[Tuple[float, float, List[int
     return out
 
 
-def transcribe_speech(hm, pcm, params=None, max_new_tokens: int = 0, align: bool = False) -> List[dict]:
+def transcribe_speech(hm, pcm, params=None, max_new_tokens: int = 0, align: bool = False, prompt=None) -> List[dict]:
     """transcribe_recording on the recording's speech alone.  params: the parameters of HipWhisper.vad_plan.  Returns one dict
     per chunk (none for a recording without speech): the fields of decode_greedy plus pieces = [(offset_in_chunk, start_sample,
-    n_samples)], n_samples = the chunk's total, n_keys = ceil(n_samples / 320), and with align=True token_first / token_last."""
+    n_samples)], n_samples = the chunk's total, n_keys = ceil(n_samples / 320), and with align=True token_first / token_last.  prompt: as
+    for transcribe_recording."""
     if isinstance(pcm, np.ndarray):
         rec, n = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1), None
     else:
@@ -118,6 +130,7 @@ def transcribe_speech(hm, pcm, params=None, max_new_tokens: int = 0, align: bool
     for a, b in _groups(totals, hm.max_batch):
         hm.logmel_pieces_rows(rec, starts, lens, first[a:b + 1], 0)
         hm.encode()
+        _set_prompt(hm, prompt, b - a, align)
         res = hm.decode_greedy(max_new_tokens)
         keys = [-(-v // KEY_SAMPLES) for v in totals[a:b]]
         if align:
