@@ -393,6 +393,42 @@ int nh_pool_languages(nh_ctx *ctx, const int32_t *rows, int n_rows, int32_t *out
  * Under a prefix (nh_set_prompts) `step` is the PHYSICAL token count, the prefix included. */
 int nh_decode_sampled(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *results, int max_new_tokens,
                       float temperature, uint64_t seed, uint32_t clip0, uint32_t attempt);
+/* ---- beam search ---------------------------------------------------------------------------------------------
+ * Model::decode at t = 0 with K = beam_size hypotheses per clip instead of one, chosen on the device.  Acts on the current
+ * lockstep batch of B clips after nh_encode*; out_tokens / results have nh_decode_greedy's shape and hold the best hypothesis
+ * of every clip.  At K = 1 it is nh_decode_greedy's search (tokens identical, avg_logprob within 1e-5: the selection kernel
+ * sums the softmax in another order than logit_step_kernel).
+ *   rows     hypothesis j of clip b lives in context row j * B + b (beam-major).  Beam 0 is the clip's own row; the cross K/V
+ *            of rows j >= 1 are device-to-device copies of row b, made once per decode.  Afterwards the context is a lockstep
+ *            batch of B clips again, rows 0 .. B-1 hold their cross K/V: a following nh_decode_greedy, nh_decode_sampled,
+ *            nh_align or nh_detect_language behaves as after a greedy decode.  nh_align_decoded refuses (kept queries are not
+ *            reordered with their hypotheses).
+ *   prompt   exactly the greedy decode's, on the B clip rows: no-speech probe and exit, per-clip languages, a prefix from
+ *            nh_set_prompts.  Generation starts with beam 0 live at score 0.0, beams 1 .. K-1 dead.
+ *   step     per live hypothesis h: q = its rule-masked probabilities (the rules, rule state and f32 softmax of the greedy
+ *            step, the row's own n_tokens / last timestamp / last two tokens); its K + 1 best tokens by q (equal q: the
+ *            higher id first; q == 0 is no candidate) are candidates with score s_h + log((double)q).  Per clip the <= K (K+1)
+ *            candidates are ordered by score descending, then lower parent beam, then higher token id, and walked until K
+ *            live children are chosen: an eot candidate becomes a finished hypothesis if the clip holds fewer than K (else
+ *            it is dropped); any other becomes the next live hypothesis with the greedy step's bookkeeping -- a forced eot at
+ *            the length cap (model.rs:367) or at max_new_tokens adds no log-probability and finishes it under the same
+ *            room-for-K rule.  Hypothesis state and self-attention caches move with the hypothesis.
+ *   end      a clip is done with K finished hypotheses or no live one.  Its result is the finished hypothesis with the
+ *            greatest sum_logprob / n (n counts prompt and eot, model.rs:373, not a prefix), the earliest on ties, through
+ *            the greedy decode's trailing-timestamp trim.  A no-speech exit returns what greedy returns.  A clip in which
+ *            everything was masked before anything finished returns its best prefix + the last vocabulary index with
+ *            avg_logprob -inf (the greedy step's all-masked convention), and ends there.
+ * Refused, nothing launched, state untouched.  NH_ERR_INVALID: beam_size outside 1 .. NH_MAX_BEAMS; batch * beam_size >
+ * max_batch; NULL outputs.  NH_ERR_STATE: no encoder output; no tokens; a running decode pool; NH_OPT_ABSORBED_XATTN != 0; a
+ * prefix set for another batch.  The beam buffers are allocated by the first call; other decodes allocate and launch nothing new. */
+#define NH_MAX_BEAMS 8
+int nh_decode_beam(nh_ctx *ctx, int beam_size, int32_t *out_tokens, nh_decode_result *results, int max_new_tokens);
+/* The finished hypotheses of clip b from the last nh_decode_beam, in finishing order, untrimmed, from sot on (a prefix is not
+ * part of them): tokens host i32 [beam_size][max_target_positions] (zero-filled past each end), n_tokens i32 [beam_size],
+ * sum_logprob f64 [beam_size], *n_finished how many there are.  beam_size is that of the decode reported on, not an argument:
+ * every one of its rows is written, so buffers of NH_MAX_BEAMS rows always suffice.  NH_ERR_STATE without a beam decode to
+ * report on. */
+int nh_beam_hypotheses(nh_ctx *ctx, int b, int32_t *tokens, int32_t *n_tokens, double *sum_logprob, int32_t *n_finished);
 /* Model::detect_language (model.rs:194-210) for every clip of the batch: one decoder step on [sot], softmax over the
  * n language-token logits (lang_tokens in `Language::iter()` order, multilingual.rs:395-398), first maximum.
  * out_lang: host i32 [batch]; out_probs: host f32 [batch][n] or NULL.  The detected tokens become the per-sequence
@@ -456,6 +492,22 @@ int nh_apply_rules(nh_ctx *ctx, const float *probs, const int32_t *tokens, int n
 /* The sampler alone: rules + one draw on a soft-maxed probability vector (token_out = -1: everything masked). */
 int nh_sample_rules(nh_ctx *ctx, const float *probs, const int32_t *tokens, int n_tokens, int last_timestamp,
                     float temperature, uint64_t seed, uint32_t clip, uint32_t attempt, int32_t *token_out);
+
+/* One beam step on host-provided logits and hypothesis state: exactly the selection and merge kernels of nh_decode_beam (the
+ * hypothesis state moves in the merge).  K = beam_size, B = batch, rows beam-major (j * B + b), K * B <= max_batch.
+ * logits f32 [K*B][V] (uploaded with NaN in the device buffer's pad columns).  In and out, per row: tokens i32
+ * [K*B][max_target_positions], n_tokens, have_last (0 | 1), last_ts, live (0 | 1; a live row holds 1 .. max_target_positions - 2
+ * tokens), score f64.  max_new_tokens and prompt_len as in a decode.  Out: parent i32 [K*B] (the row each live row's
+ * hypothesis came from, -1 for a dead row; a row that stays dead keeps its state), n_finished i32 [B] (in: finished
+ * hypotheses the clip already holds; out: after the step), and the records of the newly finished in slots n_finished_in ..
+ * n_finished_out - 1 of fin_tokens i32 [B][K][max_target_positions], fin_n i32 [B][K], fin_score f64 [B][K]. */
+int nh_beam_step(nh_ctx *ctx, int beam_size, int batch, const float *logits, int32_t *tokens, int32_t *n_tokens,
+                 int32_t *have_last, int32_t *last_ts, int32_t *live, double *score, int max_new_tokens, int prompt_len,
+                 int32_t *parent, int32_t *n_finished, int32_t *fin_tokens, int32_t *fin_n, double *fin_score);
+/* The cache reorder of a beam step alone: `cache` (host fp16 bits [K*B][heads][max_target_positions][64]) is uploaded into
+ * the self-attention K (which = 0) or V (1) cache of decoder layer `layer`, row r takes positions 0 .. n_pos-1 of row
+ * parent[r] in every layer's caches (parent[r] < 0, == r or outside the clip's rows: the row stays), and that cache comes back. */
+int nh_beam_reorder(nh_ctx *ctx, int beam_size, int batch, const int32_t *parent, int n_pos, int layer, int which, uint16_t *cache);
 
 /* ---- token-level timestamps ------------------------------------------------------------------------ */
 /* The decoder yields one timestamp token per segment boundary; nh_align gives every token a time, the way Whisper runtimes

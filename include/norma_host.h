@@ -94,6 +94,10 @@ int nm_model_language_token(const nm_model *m); /* current language token, -1 = 
  * fixes the draws (seeded sampling contract of norma_hip.h; the reference's draws cannot be reproduced, only their
  * distribution); enable = 0 returns the t = 0 result and nm_model_last_result reports needed_fallback. */
 void nm_model_set_temperature_fallback(nm_model *m, int enable, uint64_t seed);
+/* Beam search for the t = 0 attempt of decode_with_fallback (nh_decode_beam, norma_hip.h): k hypotheses, 1 <= k <= 8.  k = 1
+ * (the default) is the greedy decode of the reference and changes nothing; the sampled attempts are never beams.  A slice
+ * decoded by the beam carries no token times.  Returns 0, or 1 (k out of range, no device memory for a context of k rows). */
+int nm_model_set_beam_size(nm_model *m, int k);
 /* text of the last nm_model_transcribe call (empty without a tokenizer); returns its length */
 int nm_model_last_text(const nm_model *m, char *buf, int cap);
 void nm_model_free(nm_model *m);

@@ -178,6 +178,21 @@ struct VadState {
     std::vector<long long> h_tab;   // ... and its host side, alive until the next call's copy
 };
 
+// nh_decode_beam: everything it owns.  One allocation made by the first beam decode (or beam view), sized by max_batch
+// alone (K * B rows never exceed it); a context that never searches holds nothing.  The host side keeps the finished lists
+// of the last beam decode for nh_beam_hypotheses.
+struct BeamState {
+    DevBuf buf;
+    BeamBufs bb{};
+    int32_t *cand_tok = nullptr, *cand_n = nullptr;   // [max_batch][NH_MAX_BEAMS + 1], [max_batch]
+    float *cand_q = nullptr;
+    half_t **caches = nullptr;                        // [2 * decoder_layers] sk, sv of every layer
+    bool valid = false;                               // the vectors below are the last beam decode's
+    int B = 0, K = 0, skip = 0;
+    std::vector<int32_t> fin_tokens, fin_n, fin_count;
+    std::vector<double> fin_score;
+};
+
 struct nh_ctx {
     int dev = 0;
     std::shared_ptr<nh_model> mdl;
@@ -234,6 +249,7 @@ struct nh_ctx {
     bool opt_align_keep = false; // NH_OPT_ALIGN_KEEP
     AlignState al;               // nh_align, nh_align_decoded
     AlignLive live;              // nh_align_capture
+    BeamState beam;              // nh_decode_beam
     // The context's one query buffer, fp16 [align_q_heads][C - 1][max_batch][64]: nh_align's teacher-forced pass and the decodes
     // under nh_align_capture both write it, stages 2 - 6 read it.  Grown by align_q_buffer alone, freed by nh_destroy.
     half_t *align_q = nullptr;
@@ -294,6 +310,13 @@ void drop_graphs(nh_ctx *ctx, int first = 0);   // nh_decode.hip
 void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr = nullptr, bool final_ln = true, bool skip_done = false,
                   const AlignHeadSet *keep = nullptr);   // nh_decode.hip
 int ensure_decoder_repack(nh_ctx *ctx);         // nh_model.hip
+// nh_decode.hip, shared with nh_beam.hip: the refusals and the prompt phase every lockstep decode begins with, the logits of
+// the R rows of the last decoder_step(..., final_ln = false), and what Model::decode returns for one sequence
+struct DecodePrompt { int B, NP, P, PL, steps; };   // batch, prefix length, prompt length (2 | 3), NP + P, decoder steps so far
+int decode_refusals(nh_ctx *ctx);
+int decode_prompt_phase(nh_ctx *ctx, int max_new_tokens, DecodePrompt &dp);
+void logits_from_dx(nh_ctx *ctx, int R);
+void finish_sequence(nh_ctx *ctx, int32_t *t, int n, int done, double slp, double nsp, int32_t *out_tokens, nh_decode_result &r, int skip = 0);
 // nh_prefill.hip: TextDecoder::forward over positions 0 .. T-1 of ds.tokens for the rows of the lockstep batch in one pass:
 // self K/V of those positions land in the caches.  hidden == nullptr (a decode's prefix): the last block stops once its K/V
 // are written; otherwise everything, the final LayerNorm included, and the B * T rows are copied to `hidden` (host f32).

@@ -82,7 +82,7 @@ void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr, bool final_ln, b
 
 // TextDecoder::final_linear on LN(dx) of the R rows of the last decoder_step(..., final_ln = false)
 static LinW tied_embedding(nh_ctx *ctx) { return LinW{ctx->mdl->tok_emb, nullptr, ctx->mdl->tok_emb_t}; }  // no bias (final_linear)
-static void logits_from_dx(nh_ctx *ctx, int R) {
+void logits_from_dx(nh_ctx *ctx, int R) {
     const int d = ctx->c.d_model;
     ln_skinny(ctx, ctx->mdl->dec_ln, tied_embedding(ctx), R, ctx->c.vocab_size, d, SK_F32, ctx->logits, nullptr, nullptr, ctx->VP, 0, 0, nullptr);
 }
@@ -95,7 +95,7 @@ static void logits_from_dxn(nh_ctx *ctx, int R) {
 // what Model::decode returns for one sequence from the state its loop left behind (model.rs:308-315, 373-381)
 // skip: the prefix of a prompted decode (nh_set_prompts), which is not part of what comes back: tokens, their count and the
 // divisor of avg_logprob are those of the sequence from sot on
-static void finish_sequence(nh_ctx *ctx, int32_t *t, int n, int done, double slp, double nsp, int32_t *out_tokens, nh_decode_result &r, int skip = 0) {
+void finish_sequence(nh_ctx *ctx, int32_t *t, int n, int done, double slp, double nsp, int32_t *out_tokens, nh_decode_result &r, int skip) {
     const int C = ctx->c.max_target_positions;
     t += skip; n -= skip;
     r.no_speech_prob = nsp;
@@ -198,16 +198,20 @@ static int ensure_step_graphs(nh_ctx *ctx, const StepKey &key) {
     return NH_OK;
 }
 
-// Model::decode (model.rs:279-389) for the whole batch.  inv_t == 0: t = 0, greedy (hipGraph replay); inv_t > 0: every
-// token is sampled at temperature 1 / inv_t under the seeded contract (eager launches: the fallback path is rare).
-static int decode_impl(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *results, int max_new_tokens, float inv_t,
-                       unsigned long long seed, unsigned clip0, unsigned attempt) {
-    if (!ctx || !out_tokens || !results) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_decode: bad arguments") : NH_ERR_INVALID;
+// What a decode of the lockstep batch refuses before it touches anything (nh_decode_greedy, nh_decode_sampled, nh_decode_beam)
+int decode_refusals(nh_ctx *ctx) {
     if (!ctx->have_enc) return ctx->fail(NH_ERR_STATE, "nh_decode: call nh_encode first");
     if (!ctx->have_tokens) return ctx->fail(NH_ERR_STATE, "nh_decode: call nh_set_tokens first");
     if (ctx->pool.rows > 0) return ctx->fail(NH_ERR_STATE, "nh_decode: the context runs a decode pool (nh_pool_begin); a batch submitted with row0 = 0 ends it");
+    if (ctx->n_prefix > 0 && ctx->prompt_batch != ctx->cur_batch) return ctx->fail(NH_ERR_STATE, "nh_decode: the prefix was set for another batch (rows joined since nh_set_prompts)");
+    return NH_OK;
+}
+
+// How every decode of the lockstep batch begins (model.rs:285-305): the state of the B clip rows starts over, the prompt
+// [prefix.., sot, lang?, task] is written and consumed up to its last token, the no-speech probe reads sot's logits.  On
+// return the rows stand before their first generation step at position dp.PL - 1, the stream not yet drained.
+int decode_prompt_phase(nh_ctx *ctx, int max_new_tokens, DecodePrompt &dp) {
     const int NP = ctx->n_prefix;   // nh_set_prompts: tokens in front of the prompt; 0: none, and everything below is the plain decode
-    if (NP > 0 && ctx->prompt_batch != ctx->cur_batch) return ctx->fail(NH_ERR_STATE, "nh_decode: the prefix was set for another batch (rows joined since nh_set_prompts)");
     hipSetDevice(ctx->dev);
     if (int rc = ensure_decoder_repack(ctx)) return rc;
     ctx->live.lock_valid = false;
@@ -260,6 +264,20 @@ static int decode_impl(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *resul
             launch_logit_step(ctx->logits, V, ctx->ds, ctx->tk, B, C, cap, max_new_tokens, PL, 0, ctx->lpart, ctx->ltick, nullptr, ctx->st);
         }
     }
+    dp = DecodePrompt{B, NP, P, PL, steps};
+    return NH_OK;
+}
+
+// Model::decode (model.rs:279-389) for the whole batch.  inv_t == 0: t = 0, greedy (hipGraph replay); inv_t > 0: every
+// token is sampled at temperature 1 / inv_t under the seeded contract (eager launches: the fallback path is rare).
+static int decode_impl(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *results, int max_new_tokens, float inv_t,
+                       unsigned long long seed, unsigned clip0, unsigned attempt) {
+    if (!ctx || !out_tokens || !results) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_decode: bad arguments") : NH_ERR_INVALID;
+    if (int rc = decode_refusals(ctx)) return rc;
+    DecodePrompt dp{};
+    if (int rc = decode_prompt_phase(ctx, max_new_tokens, dp)) return rc;
+    const int B = dp.B, NP = dp.NP, P = dp.P, PL = dp.PL, cap = ctx->c.max_target_positions - 1;
+    int steps = dp.steps;
     // Generation phase: one token per step from pos = P-1 on.  The length cap (model.rs:367) forces eot once
     // pos + 2 >= cap, so pos never exceeds cap - 2.  The ~20-launch step is captured (once, and 8 steps back to back) into hipGraphs that
     // reads the position from device memory (the eager loop is host-launch-bound at ~5 us per tiny kernel).

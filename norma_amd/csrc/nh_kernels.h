@@ -522,3 +522,28 @@ bool launch_align_reduce(const float *W, long w_clip_stride, long w_head_stride,
 bool launch_align_dtw(const float *M, long m_clip_stride, long ldm, const int32_t *n_rows, const int32_t *n_keys, int P, int max_rows, int S,
                       int nclips, int clip0, uint8_t *trace, long t_clip_stride, int32_t *first, int32_t *last, int ldo, const int32_t *row_map,
                       hipStream_t st);
+
+// ---- beam search (k_beam.hip) ---------------------------------------------------------------------------------
+#ifndef NH_MAX_BEAMS
+#define NH_MAX_BEAMS 8   // include/norma_hip.h
+#endif
+// what a beam decode keeps beside DecodeState, all device pointers; rows are beam-major (hypothesis j of clip b: row j * B + b)
+struct BeamBufs {
+    int32_t *parent;      // [K * B] the row each row's hypothesis came from in the last step; -1: the row is dead
+    int32_t *fin_tokens;  // [B][K][ctx] finished hypotheses of every clip, in finishing order, untrimmed
+    int32_t *fin_n;       // [B][K]
+    double *fin_score;    // [B][K] sum of log-probabilities
+    int32_t *fin_count;   // [B]
+};
+// per live row (done == 0) its K1 <= NH_MAX_BEAMS + 1 best candidates under the logit rules: cand_tok / cand_q
+// [R][NH_MAX_BEAMS + 1] (token, masked probability, best first), cand_n [R].  logits f32 [R][nh_logits_ld(V)], V <= NH_MAX_VOCAB.
+void launch_beam_select(const float *logits, int V, DecodeState s, RuleTokens tk, int R, int ctx, int K1, int32_t *cand_tok,
+                        float *cand_q, int32_t *cand_n, hipStream_t st);
+// per clip: merge the candidates of its K rows, write the next hypotheses into rows j * B + b (state moves with its
+// hypothesis), the parent map and the finished records.  A live row holds 1 <= n_tokens <= cap - 1 tokens.
+void launch_beam_merge(DecodeState s, RuleTokens tk, int V, int B, int K, int ctx, int cap, int max_new, int prompt_len,
+                       const int32_t *cand_tok, const float *cand_q, const int32_t *cand_n, BeamBufs bb, hipStream_t st);
+// caches: device table of n_caches pointers to head-major self-attention caches fp16 [rows][H][C][64]; row r takes positions
+// 0 .. npos-1 of row parent[r] in each (npos <= C; parent[r] < 0 or == r: the row stays).  Any parent map inside a clip.
+void launch_beam_reorder(half_t *const *caches, int n_caches, const int32_t *parent, int B, int K, int H, int C, int npos,
+                         hipStream_t st);

@@ -138,15 +138,16 @@ int nm_resample_plan(int src_hz, int64_t received, int64_t emitted, int64_t firs
     return 0;
 }
 
-struct nm_resampler { Resampler r; std::vector<float> out; };
+struct nm_resampler { Resampler r; std::vector<float> out; nm_model *m; };   // m: the model whose context the stream borrows
 nm_resampler *nm_resampler_new(nm_model *m, int src_hz, int channels, int sample_dtype) {
     if (!m || !m->m) return nullptr;
-    return new nm_resampler{Resampler(m->m->context(), src_hz, channels, sample_dtype), {}};
+    return new nm_resampler{Resampler(m->m->context(), src_hz, channels, sample_dtype), {}, m};
 }
 void nm_resampler_free(nm_resampler *r) { delete r; }
 int64_t nm_resampler_push(nm_resampler *r, const void *frames, size_t n, int final_push, char *err, int err_len) {
     NM_TRY
     r->out.clear();
+    r->r.rebind(r->m->m->context());   // Model::set_beam_size may have replaced it since the last push
     if (!r->r.push(frames, n, final_push != 0, r->out)) { r->out.clear(); put_err(err, err_len, r->r.last_error()); return -1; }
     return (int64_t)r->out.size();
     NM_CATCH({ put_err(err, err_len, "resampler_push: " + what_); return -1; })
@@ -230,6 +231,10 @@ void nm_model_set_temperature_fallback(nm_model *m, int enable, uint64_t seed) {
     if (m && m->m) m->m->set_temperature_fallback(enable != 0, seed);
 }
 
+int nm_model_set_beam_size(nm_model *m, int k) {
+    if (!m || !m->m) return 1;
+    return m->m->set_beam_size(k) ? 1 : 0;
+}
 void nm_model_set_prompt_tokens(nm_model *m, const int32_t *ids, int n) {
     if (m && m->m) m->m->set_prompt_tokens(ids && n > 0 ? std::vector<int32_t>(ids, ids + n) : std::vector<int32_t>());
 }

@@ -173,6 +173,9 @@ class Resampler {
     long long emitted() const { return emitted_; }
     size_t kept_frames() const { return frame_bytes_ ? kept_.size() / frame_bytes_ : 0; }
     const char *last_error() const { return nh_last_error(ctx_); }
+    // the stream lives on the host (kept frames, counters); the context only lends its device buffers, so a stream goes on
+    // across a change of context (Model::set_beam_size replaces the model's)
+    void rebind(nh_ctx *ctx) { ctx_ = ctx; }
     // frames: n frames of `channels` interleaved samples of the resampler's type.  Appends to `out`.  false: the backend
     // refused (nh_last_error has the message); the stream is reset.
     bool push(const void *frames, size_t n, bool final_push, std::vector<float> &out) {
@@ -241,7 +244,8 @@ class Model {
     Model(Model &&o) noexcept : ctx_(o.ctx_), cfg_(o.cfg_), tk_(o.tk_), buf_(std::move(o.buf_)), detok_(std::move(o.detok_)),
                                 align_heads_(std::move(o.align_heads_)), checkpoint_heads_(std::move(o.checkpoint_heads_)), capture_stale_(o.capture_stale_),
                                 src_hz_(o.src_hz_), channels_(o.channels_), resampler_(std::move(o.resampler_)),
-                                prompt_tokens_(std::move(o.prompt_tokens_)), history_(std::move(o.history_)), condition_(o.condition_), sop_token_(o.sop_token_) { o.ctx_ = nullptr; }
+                                prompt_tokens_(std::move(o.prompt_tokens_)), history_(std::move(o.history_)), condition_(o.condition_), sop_token_(o.sop_token_),
+                                suppress_(std::move(o.suppress_)), suppress_known_(o.suppress_known_), beam_size_(o.beam_size_), ctx_rows_(o.ctx_rows_) { o.ctx_ = nullptr; }
     Model(const Model &) = delete;
     ~Model() { if (ctx_) nh_destroy(ctx_); }
 
@@ -377,6 +381,30 @@ class Model {
     // seed (reproducible tests); set_temperature_fallback(false, _) returns the t = 0 result even when the reference would
     // have gone on, and last_needed_fallback() says so.
     void set_temperature_fallback(bool enable, uint64_t seed) { fallback_ = enable; seed_ = seed; slices_ = 0; }
+    // Beam search for the t = 0 attempt (nh_decode_beam; the reference decodes greedily, Whisper runtimes default to 5 beams).
+    // k = 1, the default, is the greedy decode and changes nothing; at k > 1 attempt 0 of the TEMPERATURES loop keeps k
+    // hypotheses and returns the best, the sampled attempts stay as they are.  The context a model is made with decodes one
+    // row; the first k beyond its rows replaces it by one of k rows on the same weights (nh_create_shared), told the same
+    // tokens: a model whose suppress list was never recorded (set_suppress_tokens; the loaders call it) is refused there, not
+    // told an empty one.  A stream of transcribe_frames goes on across the change: its resampler is handed the new context.
+    // A slice decoded by the beam gets no token times (the kept queries are not reordered with the hypotheses).
+    Error set_beam_size(int k) {
+        if (k < 1 || k > NH_MAX_BEAMS) return Error{Error::Backend, "set_beam_size: 1 .. " + std::to_string(NH_MAX_BEAMS)};
+        if (k > ctx_rows_) {
+            if (!suppress_known_)
+                return Error{Error::Backend, "set_beam_size: the suppress list this model's context was told is not recorded (set_suppress_tokens)"};
+            nh_ctx *c = nullptr;
+            if (nh_create_shared(ctx_, k, &c)) return backend_error();
+            if (nh_set_tokens(c, &tk_, suppress_.data(), (int)suppress_.size())) { Error e{Error::Backend, nh_last_error(c)}; nh_destroy(c); return e; }
+            nh_destroy(ctx_);
+            ctx_ = c; ctx_rows_ = k;
+            if (resampler_) resampler_->rebind(c);
+            capture_stale_ = !align_heads_.empty();
+        }
+        beam_size_ = k;
+        return Error{};
+    }
+    void set_suppress_tokens(std::vector<int32_t> ids) { suppress_ = std::move(ids); suppress_known_ = true; }   // what the context was told (the loaders call it)
     Error decode_with_fallback(const float *pcm, size_t n, DecodingResult &dr, bool &have) {
         int32_t ns = (int32_t)n;
         if (nh_logmel(ctx_, pcm, &ns, (int64_t)n, 1)) return backend_error();   // audio::pcm_to_mel + narrow, :74-88
@@ -401,7 +429,9 @@ class Model {
         const uint32_t clip = slices_++;
         for (int a = 0; a < N_TEMPERATURES && !have; a++) {                      // for &t in m::TEMPERATURES, :175
             nh_decode_result r{};
-            if (a == 0) { if (nh_decode_greedy(ctx_, toks.data(), &r, 0)) return backend_error(); }   // decode(.., 0.0), :176
+            const bool beam = a == 0 && beam_size_ > 1;
+            if (beam) { if (nh_decode_beam(ctx_, beam_size_, toks.data(), &r, 0)) return backend_error(); }
+            else if (a == 0) { if (nh_decode_greedy(ctx_, toks.data(), &r, 0)) return backend_error(); }   // decode(.., 0.0), :176
             else if (nh_decode_sampled(ctx_, toks.data(), &r, 0, TEMPERATURES[a], seed_, clip, (uint32_t)a)) return backend_error();
             dr.tokens.assign(toks.begin(), toks.begin() + r.n_tokens);
             dr.avg_logprob = r.avg_logprob; dr.no_speech_prob = r.no_speech_prob;
@@ -412,7 +442,7 @@ class Model {
             if (!needs_fallback || dr.no_speech_prob > NO_SPEECH_THRESHOLD || !fallback_) { have = true; accepted_ = a; }
             dr.first_frame.clear(); dr.last_frame.clear();
             const int P = (detect_ || tk_.lang >= 0) ? 3 : 2;                    // [sot, lang?, task], model.rs:285-289
-            if (have && !align_heads_.empty() && r.n_tokens > P && prefix.empty()) {               // the accepted attempt; a no-speech exit holds the prompt alone
+            if (have && !beam && !align_heads_.empty() && r.n_tokens > P && prefix.empty()) {               // the accepted attempt; a no-speech exit holds the prompt alone
                 const int32_t nt = r.n_tokens;
                 const int32_t nk = (int32_t)std::min<size_t>((size_t)cfg_.max_source_positions, (n + 319) / 320);   // frames that hold audio
                 std::vector<int32_t> first(cfg_.max_target_positions), last(cfg_.max_target_positions);
@@ -454,6 +484,9 @@ class Model {
     bool condition_ = false;
     int32_t sop_token_ = -1;
     int accepted_ = 0;                       // index into TEMPERATURES of the attempt the last decode_with_fallback accepted
+    std::vector<int32_t> suppress_;          // the suppress list the context was told (a beam context is told again)
+    bool suppress_known_ = false;            // set_suppress_tokens was called: an empty list is then a list, not an omission
+    int beam_size_ = 1, ctx_rows_ = 1;       // set_beam_size; rows the context decodes (its max_batch)
 };
 
 // One tensor handed to the loader (HF name, f32 or f16 data) -- stands in for the safetensors mmap of
@@ -494,6 +527,7 @@ class Definition {
         if (nh_set_mel_filters(ctx, mel_filters, n_mel)) return fail();
         if (nh_set_tokens(ctx, &tk, suppress.data(), (int)suppress.size())) return fail();
         *out = new Model(ctx, cfg, tk);
+        (*out)->set_suppress_tokens(suppress);
         (*out)->set_input_format(src_hz_, channels_);
         return Error{};
     }

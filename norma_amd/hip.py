@@ -30,6 +30,7 @@ NH_OPT_DECODE_GRAPHS, NH_OPT_FUSE_DECODE_LAYERNORM, NH_OPT_DECODER_LAYER_LIMIT, 
 NH_OPT_ALIGN_KEEP = 4      # 1: align() keeps every clip's weights and matrix for align_weights / align_matrix
 NH_OPT_PROMPT_STEPWISE = 5  # 1: a decode's prefix (set_prompts) goes through the decode step position by position; 0: one pass
 NH_ALIGN_MAX_HEADS = 32
+NH_MAX_BEAMS = 8           # decode_beam: hypotheses per clip at most
 # NH_SAMPLE_* of include/norma_hip.h (the types of src/dtype.rs)
 SAMPLE_DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.int8): 2, np.dtype(np.int16): 3,
                  np.dtype(np.int32): 4, np.dtype(np.int64): 5, np.dtype(np.uint8): 6, np.dtype(np.uint16): 7,
@@ -173,6 +174,11 @@ def load_library() -> C.CDLL:
     L.nh_align_weights.argtypes = [vp, C.c_int, C.c_int, fp]
     L.nh_align_matrix.argtypes = [vp, C.c_int, fp]
     L.nh_align_path.argtypes = [vp, fp, C.c_int, C.c_int, ip, ip]
+    dp = C.POINTER(C.c_double)
+    L.nh_decode_beam.argtypes = [vp, C.c_int, ip, C.POINTER(NhDecodeResult), C.c_int]
+    L.nh_beam_hypotheses.argtypes = [vp, C.c_int, ip, ip, dp, ip]
+    L.nh_beam_step.argtypes = [vp, C.c_int, C.c_int, fp, ip, ip, ip, ip, ip, dp, C.c_int, C.c_int, ip, ip, ip, ip, dp]
+    L.nh_beam_reorder.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint16)]
     L.nh_get_timings.argtypes = [vp, C.POINTER(NhTimings)]
     L.nh_set_profile_gemm.argtypes = [vp, C.c_int]
     L.nh_set_option.argtypes = [vp, C.c_int, C.c_int]
@@ -609,6 +615,64 @@ class HipWhisper:
         self._chk(self.L.nh_decode_sampled(self._h, _ip(toks), res, max_new_tokens, float(temperature), int(seed),
                                            int(clip0), int(attempt)))
         return self._results(toks, res)
+
+    def decode_beam(self, beam_size: int, max_new_tokens: int = 0) -> List[dict]:
+        """Beam search at t = 0 (include/norma_hip.h): decode_greedy's dicts for the best hypothesis of every
+        clip, plus `hypotheses`: the clip's finished list [(tokens, sum_logprob)] in finishing order, untrimmed."""
+        B, Cn = self.batch, self.cfg.max_target_positions
+        toks = np.zeros((B, Cn), dtype=np.int32)
+        res = (NhDecodeResult * B)()
+        self._chk(self.L.nh_decode_beam(self._h, int(beam_size), _ip(toks), res, max_new_tokens))
+        out = self._results(toks, res)
+        for b in range(B):
+            out[b]["hypotheses"] = self.beam_hypotheses(b)
+        return out
+
+    def beam_hypotheses(self, b: int) -> List[Tuple[List[int], float]]:
+        """The finished list of clip b from the last beam decode (nh_beam_hypotheses).  The library writes one row per beam of
+        that decode, so the arrays hold NH_MAX_BEAMS rows whatever its beam size was."""
+        Cn = self.cfg.max_target_positions
+        ft = np.zeros((NH_MAX_BEAMS, Cn), dtype=np.int32)
+        fn = np.zeros(NH_MAX_BEAMS, dtype=np.int32)
+        fs = np.zeros(NH_MAX_BEAMS, dtype=np.float64)
+        nf = C.c_int32(0)
+        self._chk(self.L.nh_beam_hypotheses(self._h, int(b), _ip(ft), _ip(fn), fs.ctypes.data_as(C.POINTER(C.c_double)), C.byref(nf)))
+        return [(ft[f, :fn[f]].tolist(), float(fs[f])) for f in range(nf.value)]
+
+    def beam_step(self, beam_size: int, batch: int, logits: np.ndarray, state: dict, n_finished: Sequence[int],
+                  max_new_tokens: int = 0, prompt_len: int = 3) -> dict:
+        """One beam step on given logits f32 [K*B][V] and hypothesis state (parity view nh_beam_step).  state: tokens
+        [K*B][C], n_tokens, have_last, last_ts, live, score per row.  Returns the new state, parent, n_finished and the
+        newly finished records per clip [(tokens, sum_logprob)]."""
+        K, B, Cn = int(beam_size), int(batch), self.cfg.max_target_positions
+        R = K * B
+        lg = np.ascontiguousarray(logits, dtype=np.float32).reshape(R, self.cfg.vocab_size)
+        i32 = lambda k: np.ascontiguousarray(np.array(state[k], dtype=np.int32).reshape(R, -1))
+        toks = np.ascontiguousarray(np.array(state["tokens"], dtype=np.int32).reshape(R, Cn))
+        nt, hl, lt, lv = i32("n_tokens"), i32("have_last"), i32("last_ts"), i32("live")
+        sc = np.ascontiguousarray(np.array(state["score"], dtype=np.float64).reshape(R))
+        nf_in = np.array(n_finished, dtype=np.int32).reshape(B)
+        nf = nf_in.copy()
+        par = np.zeros(R, dtype=np.int32)
+        ft = np.zeros((B, K, Cn), dtype=np.int32)
+        fn = np.zeros((B, K), dtype=np.int32)
+        fs = np.zeros((B, K), dtype=np.float64)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        self._chk(self.L.nh_beam_step(self._h, K, B, _fp(lg), _ip(toks), _ip(nt), _ip(hl), _ip(lt), _ip(lv), dp(sc), int(max_new_tokens),
+                                      int(prompt_len), _ip(par), _ip(nf), _ip(ft), _ip(fn), dp(fs)))
+        fin = [[(ft[b, f, :fn[b, f]].tolist(), float(fs[b, f])) for f in range(int(nf_in[b]), int(nf[b]))] for b in range(B)]
+        return dict(tokens=toks, n_tokens=nt.reshape(R), have_last=hl.reshape(R), last_ts=lt.reshape(R), live=lv.reshape(R),
+                    score=sc, parent=par, n_finished=nf, finished=fin, fin_raw=(ft, fn, fs))
+
+    def beam_reorder(self, beam_size: int, batch: int, parent: Sequence[int], n_pos: int, layer: int, which: int,
+                     cache: np.ndarray) -> np.ndarray:
+        """The self-attention cache reorder of a beam step alone (nh_beam_reorder): cache fp16 [K*B][heads][C][64]."""
+        R = int(beam_size) * int(batch)
+        c = np.ascontiguousarray(cache, dtype=np.float16).reshape(R, self.cfg.decoder_attention_heads, self.cfg.max_target_positions, 64).copy()
+        par = np.array(parent, dtype=np.int32).reshape(R)
+        self._chk(self.L.nh_beam_reorder(self._h, int(beam_size), int(batch), _ip(par), int(n_pos), int(layer), int(which),
+                                         c.view(np.uint16).ctypes.data_as(C.POINTER(C.c_uint16))))
+        return c
 
     def transcribe_batch_device(self, pcm_dev_ptr: int, n_samples: Sequence[int], stride: int,
                                 max_new_tokens: int = 0) -> List[dict]:

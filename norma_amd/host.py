@@ -104,6 +104,7 @@ def _lib():
         L.nm_model_language_token.argtypes = [vp]
         L.nm_gguf_list.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
         L.nm_model_set_temperature_fallback.argtypes = [vp, C.c_int, C.c_uint64]
+        L.nm_model_set_beam_size.argtypes = [vp, C.c_int]
         L.nm_model_free.argtypes = [vp]
         L.nm_model_transcribe.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                           C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.c_char_p, C.c_int]
@@ -234,6 +235,12 @@ class Model:
     def set_temperature_fallback(self, enable: bool, seed: int = 0):
         """decode_with_fallback's sampled attempts (model.rs:175-188) on/off; draws follow the seeded sampling contract."""
         _lib().nm_model_set_temperature_fallback(self._h, int(enable), int(seed))
+
+    def set_beam_size(self, k: int):
+        """Beam search with k hypotheses for the t = 0 attempt (HipWhisper.decode_beam); k = 1, the default, is the greedy
+        decode.  The sampled fallback attempts are unchanged."""
+        if _lib().nm_model_set_beam_size(self._h, int(k)):
+            raise WhisperError(f"set_beam_size: 1 .. 8 hypotheses (and device memory for a context of that many rows), got {k}")
 
     def set_prompt_tokens(self, ids: Sequence[int]):
         """An initial prompt (token ids; the tokenizer only decodes) every slice decodes under, behind <|startofprev|>; [] = none."""

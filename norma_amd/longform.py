@@ -30,6 +30,15 @@ def _groups(lens: Sequence[int], max_batch: int) -> List[Tuple[int, int]]:
     return out
 
 
+def _beam_rows(hm, beam_size: int, align: bool) -> int:
+    """chunks per group: a beam of K spreads every chunk over K rows of the context (HipWhisper.decode_beam); 1: the greedy decode"""
+    if beam_size < 1 or beam_size > hm.max_batch:
+        raise ValueError(f"beam_size must lie in 1 .. max_batch ({hm.max_batch})")
+    if beam_size > 1 and align:
+        raise ValueError("align=True does not cover beam decodes (align_decoded refuses after one)")
+    return hm.max_batch // beam_size
+
+
 def _set_prompt(hm, prompt, n: int, align: bool):
     """one id list in front of every chunk of the group just encoded (HipWhisper.set_prompts; a new batch starts without one)"""
     if prompt is not None and len(prompt):
@@ -38,7 +47,8 @@ def _set_prompt(hm, prompt, n: int, align: bool):
         hm.set_prompts([list(prompt)] * n)
 
 
-def transcribe_recording(hm, pcm, params=None, max_new_tokens: int = 0, align: bool = False, prompt=None) -> List[dict]:
+def transcribe_recording(hm, pcm, params=None, max_new_tokens: int = 0, align: bool = False, prompt=None,
+                         beam_size: int = 1) -> List[dict]:
     """hm: a HipWhisper with weights, filters and tokens set.  pcm: a host f32 array (16 kHz mono), or (device pointer,
     n_samples).  params: the cut parameters (HipWhisper.cut_plan).  Returns one dict per chunk: the fields of decode_greedy
     plus start_sample, n_samples and n_keys = ceil(n_samples / 320), the encoder frames that hold audio.  align=True (the
@@ -51,11 +61,11 @@ def transcribe_recording(hm, pcm, params=None, max_new_tokens: int = 0, align: b
         rec, n = int(pcm[0]), int(pcm[1])
     starts, lens = hm.cut_plan(rec, n, params)
     out = []
-    for a, b in _groups(lens, hm.max_batch):
+    for a, b in _groups(lens, _beam_rows(hm, beam_size, align)):
         hm.logmel_chunks_rows(rec, starts[a:b], lens[a:b], 0)
         hm.encode()
         _set_prompt(hm, prompt, b - a, align)
-        res = hm.decode_greedy(max_new_tokens)
+        res = hm.decode_greedy(max_new_tokens) if beam_size == 1 else hm.decode_beam(beam_size, max_new_tokens)
         keys = [-(-int(v) // KEY_SAMPLES) for v in lens[a:b]]
         if align:
             first, last = hm.align_decoded(n_keys=keys)
@@ -108,7 +118,8 @@ def stitch(results: Sequence[dict], tokens) -> List[Tuple[float, float, List[int
     return out
 
 
-def transcribe_speech(hm, pcm, params=None, max_new_tokens: int = 0, align: bool = False, prompt=None) -> List[dict]:
+def transcribe_speech(hm, pcm, params=None, max_new_tokens: int = 0, align: bool = False, prompt=None,
+                      beam_size: int = 1) -> List[dict]:
     """transcribe_recording on the recording's speech alone.  params: the parameters of HipWhisper.vad_plan.  Returns one dict
     per chunk (none for a recording without speech): the fields of decode_greedy plus pieces = [(offset_in_chunk, start_sample,
     n_samples)], n_samples = the chunk's total, n_keys = ceil(n_samples / 320), and with align=True token_first / token_last.  prompt: as
@@ -127,11 +138,11 @@ def transcribe_speech(hm, pcm, params=None, max_new_tokens: int = 0, align: bool
         pieces.append(row)
     totals = [row[-1][0] + row[-1][2] for row in pieces]
     out = []
-    for a, b in _groups(totals, hm.max_batch):
+    for a, b in _groups(totals, _beam_rows(hm, beam_size, align)):
         hm.logmel_pieces_rows(rec, starts, lens, first[a:b + 1], 0)
         hm.encode()
         _set_prompt(hm, prompt, b - a, align)
-        res = hm.decode_greedy(max_new_tokens)
+        res = hm.decode_greedy(max_new_tokens) if beam_size == 1 else hm.decode_beam(beam_size, max_new_tokens)
         keys = [-(-v // KEY_SAMPLES) for v in totals[a:b]]
         if align:
             tf, tl = hm.align_decoded(n_keys=keys)
