@@ -12,7 +12,10 @@
 // ds_read_b128), its V transposed as [dim][key].  Per wave and block, with v_mfma_f32_16x16x32_f16:
 //   S^T[key][query] = K . Q^T     A = K rows from LDS, B = the wave's Q fragment (registers, loaded once from global memory)
 //   s = S^T / 8 in f32, masked (key > query under the causal form, key >= the key count) to -inf
-//   online softmax in f32 per query: m, and l summed from the UNROUNDED f32 weights
+//   online softmax in f32 per query: m, and l summed in f32 from the weights AS ROUNDED TO FP16 for the product below: numerator
+//                                 and denominator hold the same weights, so O / l is a convex combination of the V rows (summed
+//                                 from the unrounded weights, l would miss what the rounding does to all of them alike:
+//                                 up to 2^-11 |o| more, and not an average of V any more)
 //   O^T[dim][query] += V^T . P^T  A = V^T rows from LDS, B = P^T: the score accumulators themselves, rounded to fp16 -- an
 //                                 accumulator has its query on the lane and its keys in the registers, which is the B layout
 //                                 up to the order of the 32 keys inside a k-step, and the V^T fragment is read in that order
@@ -112,9 +115,9 @@ __global__ __launch_bounds__(64 * PF_MAX_WAVES) void prefill_attn_kernel(Prefill
         for (int t = 0; t < 4; t++) {
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                const float e = __builtin_amdgcn_exp2f((sc[t][r] - mn) * 1.4426950408889634f);   // masked keys: 0
-                ps += e;
-                pf[t >> 1][4 * (t & 1) + r] = (half_t)e;
+                const half_t e = (half_t)__builtin_amdgcn_exp2f((sc[t][r] - mn) * 1.4426950408889634f);   // masked keys: 0
+                ps += (float)e;
+                pf[t >> 1][4 * (t & 1) + r] = e;
             }
         }
         l = l * alpha + ps;   // per lane: the four lanes of a query meet after the last block

@@ -23,7 +23,8 @@ SKP_NONE, SKP_GEMM, SKP_LN, SKP_LDS, SKP_LDSP = 0, 1, 2, 3, 4      # SkinnyKind 
 PLAN_FIELDS = ("kind", "ncb", "nt", "ksplit", "sp", "grid_x", "grid_y", "block", "lds_used", "lds_exclusive")
 EPI_F16, EPI_GELU_F16, EPI_RESID_F32, EPI_CONV2_F32 = 0, 1, 2, 3
 WRAPPERS = ["kref_skinny", "kref_skinny_ln_supported", "kref_skinny_plan", "kref_dec_attention", "kref_xabs_attention", "kref_enc_attention",
-            "kref_gemm", "kref_layernorm", "kref_embed", "kref_logit_step", "kref_sample_step", "kref_lang_detect"]
+            "kref_gemm", "kref_layernorm", "kref_embed", "kref_logit_step", "kref_sample_step", "kref_lang_detect",
+            "kref_prefill_self_attention", "kref_prefill_cross_attention"]
 
 # ---- loader ----------------------------------------------------------------------------------------------------------------
 _lib = None
@@ -62,6 +63,8 @@ def _argtypes():
     L.kref_sample_step.argtypes = [vp, i, i, i, i, i, i, i, f, C.c_ulonglong, C.c_uint, C.c_uint, vp, vp, vp, vp, vp, vp, vp,
                                    vp, vp]
     L.kref_lang_detect.argtypes = [vp, i, i, vp, i, vp, vp]
+    L.kref_prefill_self_attention.argtypes = [vp, vp, vp, l, vp, l, vp, vp, i, i, i, i]
+    L.kref_prefill_cross_attention.argtypes = [vp, l, vp, vp, vp, l, i, i, i, i]
     return L
 
 
@@ -280,6 +283,246 @@ def enc_attention(q, k, v, B, S, H):
                 i1 = min(S, i0 + 256)
                 vdev[b * S + i0:b * S + i1, h] = np.einsum("ij,ijc->ic", p[i0:i1], np.abs(v[r, c][None] - o[r, c][i0:i1, None]))
     return o, sabs, (vdev, pv)
+
+
+# ---- the one-pass prefill attention (k_prefill.hip) -------------------------------------------------------------------------
+PF_KB = 64            # keys per block of prefill_attn_kernel: the unit of its running maximum
+
+
+def pf_natural_order(nk):
+    """the V row each key's weight would meet if the V^T fragment of a 32-key k-step were read in natural order: the score
+    accumulators put key 4 fq + j (j < 4) and 16 + 4 fq + j - 4 (j >= 4) of the step into k-slot 8 fq + j, and the kernel reads
+    V^T in that order; read 0, 1, 2 ... instead, key j's weight multiplies the V row of its SLOT.  Rows past the last key are
+    the clamped last row, as the staging leaves them.  (Keys 0 .. 3 of a step keep their place.)"""
+    j = np.arange(nk)
+    r = j % 32
+    fq, jj = (r % 16) // 4, r % 4 + 4 * (r // 16)
+    return np.minimum(j - r + 8 * fq + jj, nk - 1)
+
+
+def _pf_weights(qh, kh, nvis, first):
+    """scores / 8 of one (clip, head), masked to first[i] <= j < nvis[i]; returns (s, visible)"""
+    j = np.arange(kh.shape[0])[None, :]
+    vis = (j < nvis[:, None]) & (j >= first[:, None])
+    return np.where(vis, (qh @ kh.T) / 8.0, -np.inf), vis
+
+
+def prefill_attention(q, k, v, B, T, H, nk, causal, nvis=None, first=None, vperm=None, stats=True):
+    """prefill_attn_kernel in fp64: T queries per clip, q [B*T][64 H], over that clip's nk keys, k / v [B*nk][64 H] (row-major;
+    the cross form's head-major buffers go through head_major's inverse first); scores q.k / 8.  Query i of a clip sees keys
+    first[i] <= j < nvis[i]; nvis defaults to i + 1 under the causal form and to nk otherwise, first to 0, and vperm [nk]
+    (default: the identity) names the V row that key j's weight multiplies: a mask off by one, a tile that skips keys and a
+    wrong key order inside a k-step are this function with a changed argument.  Computed per (clip, head); returns o
+    [B*T][64 H], sabs [B*T][H] = max over the visible keys of sum_c |q_c||k_c| / 8, (vdev, pv) [B*T][H][64] = sum_j p_j |v_j - o|,
+    sum_j p_j |v_j| (zeros with stats=False: a mutated reference needs o only), and the visible-key count per row [B*T]."""
+    q, k, v = d64(q).reshape(B, T, H, NH_DH), d64(k).reshape(B, nk, H, NH_DH), d64(v).reshape(B, nk, H, NH_DH)
+    nvis = (np.arange(T) + 1 if causal else np.full(T, nk)) if nvis is None else np.asarray(nvis)
+    first = np.zeros(T, dtype=np.int64) if first is None else np.asarray(first)
+    o = np.zeros((B, T, H, NH_DH))
+    sabs = np.zeros((B, T, H))
+    vdev, pv = np.zeros((B, T, H, NH_DH)), np.zeros((B, T, H, NH_DH))
+    for b in range(B):
+        for h in range(H):
+            qh, kh, vh = q[b, :, h], k[b, :, h], v[b, :, h]
+            s, vis = _pf_weights(qh, kh, nvis, first)
+            p = np.exp(s - s.max(axis=-1, keepdims=True))
+            p /= p.sum(axis=-1, keepdims=True)
+            o[b, :, h] = p @ (vh if vperm is None else vh[vperm])
+            if not stats:
+                continue
+            sabs[b, :, h] = np.where(vis, np.abs(qh) @ np.abs(kh).T, 0).max(axis=-1) / 8.0
+            pv[b, :, h] = p @ np.abs(vh)
+            for i0 in range(0, T, 64):   # sum_j p_ij |v_j - o_i| in blocks of queries, over the keys any of them sees
+                i1 = min(T, i0 + 64)
+                j1 = int(nvis[i0:i1].max())
+                vdev[b, i0:i1, h] = np.einsum("ij,ijc->ic", p[i0:i1, :j1], np.abs(vh[None, :j1] - o[b, i0:i1, h][:, None]))
+    n = np.tile(nvis - first, B)
+    return o.reshape(B * T, H * NH_DH), sabs.reshape(B * T, H), (vdev.reshape(B * T, H, NH_DH), pv.reshape(B * T, H, NH_DH)), n
+
+
+def prefill_p16_floor(q, k, v, B, T, H, nk, causal):
+    """the fp16 subnormal floor of P, per element [B*T][H][64] (prefill_bound says what it is measured against):
+    sum_j min(w_j, 2^-25) a_j |v_j - o| / l over the visible keys whose weight w_j = exp(s_j - m_b), relative to the running maximum
+    m_b of their 64-key block, is below 2^-14, the smallest normal fp16.  There the rounding is absolute: up to 2^-25, and never
+    more than w_j itself.  a_j = exp(m_b - m) <= 1 is the later rescaling to the row's final maximum, l >= 1 the row sum."""
+    q, k, v = d64(q).reshape(B, T, H, NH_DH), d64(k).reshape(B, nk, H, NH_DH), d64(v).reshape(B, nk, H, NH_DH)
+    nvis = np.arange(T) + 1 if causal else np.full(T, nk)
+    floor = np.zeros((B, T, H, NH_DH))
+    blk = np.arange(nk) // PF_KB
+    for b in range(B):
+        for h in range(H):
+            s, vis = _pf_weights(q[b, :, h], k[b, :, h], nvis, np.zeros(T, dtype=np.int64))
+            m = s.max(axis=-1, keepdims=True)
+            run = np.full_like(s, -np.inf)
+            for kb in range(blk[-1] + 1):
+                c = blk == kb
+                prev = run[:, kb * PF_KB - 1:kb * PF_KB] if kb else np.full((T, 1), -np.inf)
+                run[:, c] = np.maximum(prev, s[:, c].max(axis=-1, keepdims=True))
+            w = np.where(vis, np.exp(s - run), 0.0)              # relative to the running maximum, as the kernel rounds it
+            e = np.exp(s - m)
+            l = e.sum(axis=-1, keepdims=True)
+            o = (e / l) @ v[b, :, h]
+            f = np.where(vis & (w < 2.0 ** -14), np.minimum(w, SUB16) * np.exp(run - m), 0.0) / l
+            for i0 in range(0, T, 64):
+                i1 = min(T, i0 + 64)
+                if f[i0:i1].any():
+                    floor[b, i0:i1, h] = np.einsum("ij,ijc->ic", f[i0:i1], np.abs(v[b, :, h][None] - o[i0:i1, None]))
+    return floor.reshape(B * T, H, NH_DH)
+
+
+def prefill_bound(o, sabs, n, vstat, floor=None):
+    """attn_bound(..., p16=True) with n the row's visible keys, re-derived for prefill_attn_kernel ("Where the
+    roundings sit").  Per query, in the order the kernel computes:
+      scores   two chained 32-deep MFMAs into one f32 accumulator: 64 products, <= 64 u sum_c |q_c||k_c|; the division by 8 is
+               exact.  The exponent (s - m) log2(e) adds 2 u |s - m| and v_exp_f32 a relative 2 u: with |s - m| <= 2 sabs that is
+               inside the dot term (an MFMA chain rounds far less than 64 times) and the 4 u.  A score error e moves o by
+               sum_j p_j e_j (v_j - o) to first order: 2 e sum_j p_j |v_j - o| with the second order.
+      P        w_j = exp(s_j - m_b) against the RUNNING maximum m_b of the key's 64-key block, rounded to fp16: w_j (1 + eps_j),
+               |eps_j| <= 2^-11 while w_j is normal; later blocks scale it by alpha <= 1 in f32 (counted under the sums).
+      l        summed in f32 from the ROUNDED weights, the ones the P.V product multiplies.  Numerator and denominator then
+               hold the same perturbed weights, o stays a convex combination of the V rows, and the perturbation acts like a
+               score error, only exactly: o' - o = sum_j p_j eps_j (v_j - o) / (1 + sum_j p_j eps_j), at most 2^-11 (1 + 2^-10)
+               sum_j p_j |v_j - o| -- a little over half of attn_bound's p16 term 2 * 2^-11 sum_j p_j |v_j - o|.  (Were l summed from the unrounded weights, as this kernel once did, the numerator alone
+               would see eps: o' = o + sum_j p_j eps_j v_j, which adds o sum_j p_j eps_j, up to 2^-11 |o| that the bound has
+               no term for.  An emulation of that arithmetic left the bound on a row of two keys whose V nearly agree.)
+      sums     l: per lane one rounding per visible key it holds, two per later block (l alpha + ps), two shuffles; O: one
+               addition per key inside the MFMAs (fp16 x fp16 products are exact in f32), one rescaling per block, then 1 / l and
+               one product: at most n + 2 ceil(n / 64) + 3 roundings on any path, relative to sum_j p_j |v_j| or |o|.  That is
+               <= 4 n u (pv + |o|) from n = 2 on, and everything is exact at n = 1: half of attn_bound's 8 n u (pv + |o|).
+      output   rounded once: <= max(2^-11 |o|, 2^-25), where attn_bound grants the sum of the two.
+      floor    the fp16 subnormal floor of P has no term of its own in attn_bound and strictly needs one: below 2^-14 the
+               rounding of w_j is absolute, up to 2^-25 (never more than w_j), which moves o by `floor` = sum_j min(w_j, 2^-25)
+               a_j |v_j - o| / l (prefill_p16_floor) -- at most n 2^-25 max_j |v_j - o|.  It is covered by what attn_bound grants
+               beyond need: 0.99 * 2^-11 sum_j p_j |v_j - o|, the unused part of the p16 term, 4 n u (pv + |o|), the unused half
+               of the sums term, and min(2^-11 |o|, 2^-25) of the output term -- on ordinary data by a wide margin, but not as a
+               theorem, so with `floor` given it is ASSERTED here, element by element, from the fp64 reference alone.
+    Nothing is added to the bound and nothing is fitted to the kernel's output."""
+    if floor is not None:
+        B, H = sabs.shape
+        ao = np.abs(o).reshape(B, H, NH_DH)
+        nn = np.asarray(n, dtype=np.float64).reshape(-1, 1, 1)
+        spare = 0.99 * U16 * vstat[0] + 4 * nn * U32 * (vstat[1] + ao) + np.minimum(U16 * ao, SUB16)
+        assert np.all(floor <= spare), (f"the fp16 subnormal floor of P needs a term of its own on this data: floor / spare up to "
+                                        f"{float(np.max(floor / np.maximum(spare, 1e-300)))}")
+    return attn_bound(o, sabs, n, vstat, p16=True)
+
+
+def prefill_mask_mutations(q, k, v, T, H, nk, causal):
+    """the two mask errors on (clip, head) units laid out as H heads of ONE clip, so that in the cross form the key past a head's
+    last is the next head's key 0, as in the flat head-major buffer (the last head: its own last key once more)"""
+    if causal:
+        i = np.arange(T)
+        return {"one key too few": prefill_attention(q, k, v, 1, T, H, nk, True, nvis=np.maximum(i, 1), stats=False)[0],
+                "one key too many": prefill_attention(q, k, v, 1, T, H, nk, True, nvis=np.minimum(i + 2, T), stats=False)[0]}
+    m = {}
+    if nk > 1:
+        m["one key too few"] = prefill_attention(q, k, v, 1, T, H, nk, False, nvis=np.full(T, nk - 1), stats=False)[0]
+    if H > 1:
+        k3, v3 = np.asarray(k).reshape(nk, H, NH_DH), np.asarray(v).reshape(nk, H, NH_DH)
+        kx = np.concatenate([k3, np.concatenate([k3[:1, 1:], k3[-1:, -1:]], axis=1)]).reshape(nk + 1, H * NH_DH)
+        vx = np.concatenate([v3, np.concatenate([v3[:1, 1:], v3[-1:, -1:]], axis=1)]).reshape(nk + 1, H * NH_DH)
+        m["one key too many"] = prefill_attention(q, kx, vx, 1, T, H, nk + 1, False, stats=False)[0]
+    return m
+
+
+def pf_units(a, B, n, H):
+    """[B*n][64 H] -> [n][B*H*64]: every (clip, head) as a head of ONE clip, in the order of the flat head-major buffer"""
+    return np.ascontiguousarray(np.asarray(a).reshape(B, n, H, 64).transpose(1, 0, 2, 3)).reshape(n, B * H * 64)
+
+
+def pf_from_head_major(c, B, H, S):
+    """[B][H][S][64] -> [S][B*H*64] (the unit layout)"""
+    return np.ascontiguousarray(c.reshape(B * H, S, 64).transpose(1, 0, 2)).reshape(S, B * H * 64)
+
+
+def prefill_cross_case(r, B, T, H, S):
+    """random q, K, V (head-major, exactly S keys per (clip, head)).  From S = 3 on, two planted keys per unit make both mask
+    errors matter to query 0 whatever S is: the unit's last key and the key right behind it in the flat buffer (the next unit's
+    key 0) each score the logsumexp of query 0's other scores, so each holds about half the weight when it is seen"""
+    U = B * H
+    q = f16(r.standard_normal((B * T, 64 * H)))
+    ck, cv = f16(r.standard_normal((U, S, 64))), f16(r.standard_normal((U, S, 64)))
+    if S >= 3:
+        q0 = d64(pf_units(q, B, T, H)[0].reshape(U, 64))
+        for u in range(U):
+            so = d64(ck[u, 1:S - 1]) @ q0[u] / 8.0
+            lse = so.max() + np.log(np.exp(so - so.max()).sum())
+            loud = f16(lse * 8.0 * q0[u] / (q0[u] @ q0[u]))
+            ck[u, S - 1] = loud
+            if u + 1 < U:
+                ck[u + 1, 0] = loud
+    return q, ck.reshape(B, H, S, 64), cv.reshape(B, H, S, 64)
+
+
+def prefill_cross_mutations(qu, ku, vu, B, T, H, S):
+    """in the unit layout ([n][B*H*64], one clip of B*H heads)"""
+    U = B * H
+    m = prefill_mask_mutations(qu, ku, vu, T, U, S, False)
+
+    def slab(shift):
+        kk, vv = (np.roll(a.reshape(S, U, 64), shift, axis=1).reshape(S, U * 64) for a in (ku, vu))
+        return prefill_attention(qu, kk, vv, 1, T, U, S, False, stats=False)[0]
+
+    if H > 1:
+        m["wrong head slab (kv_head): head h reads head h-1"] = slab(1)
+    if B > 1:
+        m["wrong clip slab (kv_clip): clip b reads clip b-1"] = slab(H)
+    return m
+
+
+PF_FAMILIES = ("dominant-last", "ascending", "dominant-first", "equal")
+
+
+def prefill_adversarial(r, nq, nk, causal):
+    """adversarial (clip, head) units for both forms of prefill_attn_kernel, one per PF_FAMILIES entry (+ a random filler unit
+    in the cross form): q [U][nq][64], k, v [U][nk][64] fp16.  The queries of unit u are g_u + noise orthogonal to g_u, all on
+    one half of the 64 dimensions (alternating by unit), so that a key a g_u 8 / (g_u.g_u) scores a for every query of the unit:
+      equal           all keys equal: uniform weights, every P exactly 1
+      ascending       key j scores 0.2 j: every 64-key block raises the maximum and rescales, and the low keys of a block sit
+                      on the fp16 subnormal floor relative to it
+      dominant-first  key 5 scores 40 above random rest: later blocks' P is zero in fp16 while l still counts them
+      dominant-last   causal: keys 63, 64 score 40 and keys nk - 2, nk - 1 score 80: queries 63 and nk - 2 have the dominating key
+                      last and an equally loud one first out of sight.  cross: key nk - 1 scores 40.
+    Cross form: key 0 of unit u + 1 is the first key past unit u's last in the flat [unit][key][64] buffer.  It carries, on
+    unit u's half of the dimensions, what makes it loud for unit u's queries (40 after the dominating families, 0.2 nk after
+    the ascending one, 6 after the equal one) and its own role on the other half."""
+    f = PF_FAMILIES
+    U = len(f) + (0 if causal else 1)
+    q, k = np.zeros((U, nq, 64)), r.standard_normal((U, nk, 64))
+    v = r.standard_normal((U, nk, 64))
+    g = np.zeros((U, 64))
+    for u in range(U):
+        half = slice(32 * (u % 2), 32 * (u % 2) + 32)
+        g[u, half] = r.standard_normal(32)
+        noise = 0.25 * r.standard_normal((nq, 32))
+        noise -= np.outer(noise @ g[u, half], g[u, half]) / (g[u] @ g[u])
+        q[u, :, half] = g[u, half] + noise
+
+    def loud(u, a):
+        return a * 8.0 * g[u] / (g[u] @ g[u])
+
+    for u, fam in enumerate(f):
+        if fam == "equal":
+            k[u] = k[u, 0]
+        elif fam == "ascending":
+            k[u] = np.arange(nk)[:, None] * loud(u, 0.2)[None]
+        elif fam == "dominant-first":
+            k[u, min(5, nk - 1)] = loud(u, 40.0)
+        elif causal:
+            if nk > 65:
+                k[u, 63:65] = loud(u, 40.0)
+            k[u, max(nk - 2, 0):] = loud(u, 80.0)
+        else:
+            k[u, nk - 1] = loud(u, 40.0)
+    if not causal:
+        past = {"dominant-last": 40.0, "ascending": 0.2 * nk, "dominant-first": 40.0, "equal": 6.0}
+        for u, fam in enumerate(f):
+            half = slice(32 * (u % 2), 32 * (u % 2) + 32)
+            if f[u + 1:u + 2] == ("equal",):
+                k[u + 1, :, half] = loud(u, past[fam])[half]      # every key of the equal unit: they stay equal
+            else:
+                k[u + 1, 0, half] = loud(u, past[fam])[half]
+    return f16(q), f16(k), f16(v)
 
 
 # ---- bounds ----------------------------------------------------------------------------------------------------------------

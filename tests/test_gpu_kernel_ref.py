@@ -541,6 +541,197 @@ def _enc_ref_keys(q, k, v, H):
     return o
 
 
+# ---- prefill attention (k_prefill.hip: the one-pass teacher-forced decoder forward) -----------------------------------------------
+# prefill_attn_kernel<true> / <false> through launch_prefill_self_attention / launch_prefill_cross_attention: one workgroup per
+# (256-query tile, head, clip), one wave per 16 queries, keys in blocks of 64, P.V in k-steps of 32 keys.  Reference and bound:
+# kref.prefill_attention / prefill_bound.  Canaries (7.25, -3.5) fill everything the kernel must not write.
+PF_C = 448
+# the wave (16), k-step (32), key-block (64) and query-tile (256) edges; 300: a second tile of three waves; 448: a second tile
+# of twelve live waves and four idle ones
+PF_T = [1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 223, 255, 256, 257, 300, 448]
+PF_SELF = [(1, 2, PF_T), (3, 6, [1, 17, 64, 65, 223, 257, 448]), (2, 20, [2, 33, 129, 300])]
+PF_WORST = {}      # worst |err| / bound per section, printed by each test (reported, never asserted)
+
+
+def _pf_report(section, got, ref, bound):
+    PF_WORST[section] = max(PF_WORST.get(section, 0.0), K.violation(ref, bound, got))
+    print(f"worst |err| / bound so far, {section}: {PF_WORST[section]:.3f}")
+
+
+def _pf_self_run(q, k, v, ld, B, T, H, C=PF_C, ldo=None, expect=0):
+    """one launch_prefill_self_attention; returns (out [B*T][ldo], ck, cv [B][H][C][64]); out is filled with 7.25, ck with
+    7.25 and cv with -3.5 beforehand"""
+    ldo = 64 * H if ldo is None else ldo
+    out = np.full((max(B * T, 1), ldo), np.float16(7.25), np.float16)
+    ck = np.full((B, H, C, 64), np.float16(7.25), np.float16)
+    cv = np.full((B, H, C, 64), np.float16(-3.5), np.float16)
+    rc = K.lib().kref_prefill_self_attention(K.ptr(q), K.ptr(k), K.ptr(v), ld, K.ptr(out), ldo, K.ptr(ck), K.ptr(cv), B, T, H, C)
+    if expect == 0:
+        K.check_rc(rc, f"launch_prefill_self_attention B={B} T={T} H={H}")
+    else:
+        assert rc == expect, rc
+    return out, ck, cv
+
+
+def _pf_cross_run(q, ck, cv, B, T, H, S, expect=0):
+    """one launch_prefill_cross_attention on head-major K/V of exactly S keys per (clip, head); returns (out, ck, cv) as the
+    wrapper copied them back"""
+    out = np.full((max(B * T, 1), 64 * H), np.float16(7.25), np.float16)
+    ck, cv = ck.copy(), cv.copy()
+    rc = K.lib().kref_prefill_cross_attention(K.ptr(q), 64 * H, K.ptr(ck), K.ptr(cv), K.ptr(out), 64 * H, B, T, H, S)
+    if expect == 0:
+        K.check_rc(rc, f"launch_prefill_cross_attention B={B} T={T} H={H} S={S}")
+    else:
+        assert rc == expect, rc
+    return out, ck, cv
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint16)
+
+
+def _pf_check_self_cache(ck, cv, k, v, B, T, H, what):
+    """slots 0 .. T-1 bit-equal to the input k / v rows of every (clip, head), slots T .. C-1 untouched"""
+    d = 64 * H
+    for name, cache, src, canary in (("ck", ck, k, 7.25), ("cv", cv, v, -3.5)):
+        want = K.head_major(np.ascontiguousarray(src).reshape(B, T, d), H)
+        assert np.array_equal(_bits(cache[:, :, :T]), _bits(want)), f"{what}: {name} slots 0..T-1 are not the input rows"
+        assert np.all(cache[:, :, T:] == np.float16(canary)), f"{what}: {name} written past slot T-1"
+
+
+def _pf_self_mutations(q, k, v, B, T, H):
+    d = 64 * H
+    i = np.arange(T)
+
+    def mut(kk=k, vv=v, **kw):
+        return K.prefill_attention(q, kk, vv, B, T, H, T, True, stats=False, **kw)[0]
+
+    m = {}
+    if T >= 2:
+        m["causal mask one key short (queries i >= 1)"] = mut(nvis=np.maximum(i, 1))
+        m["causal mask one key long (queries i < T-1)"] = mut(nvis=np.minimum(i + 2, T))
+    if H > 1:
+        vs = v.copy(); vs[:, d - 64:] = v[:, d - 128:d - 64]
+        m["last head reads the previous head's V"] = mut(vv=vs)
+    if B > 1:
+        m["clip b reads clip b-1's keys"] = mut(kk=np.roll(k.reshape(B, T, d), 1, axis=0), vv=np.roll(v.reshape(B, T, d), 1, axis=0))
+    if T >= 5:       # keys 0 .. 3 of a k-step sit in their natural slots
+        m["keys of a 32-key step reach V in natural order"] = mut(vperm=K.pf_natural_order(T))
+    if T > 256:
+        m["the second query tile ignores keys below 256"] = mut(first=np.where(i >= 256, 256, 0))
+    return m
+
+
+@pytest.mark.parametrize("B,H,Ts", PF_SELF, ids=[f"B{b}-H{h}" for b, h, _ in PF_SELF])
+def test_prefill_self_attention_matches_fp64(B, H, Ts):
+    """causal form, C = 448, separate q / k / v buffers (ld = ldo = 64 H): the output inside the bound, the self cache bit-equal
+    at slots 0 .. T-1 and untouched beyond -- at T = 300 and 448 too, where only the clip's last tile writes it"""
+    d = 64 * H
+    for T in Ts:
+        r = rng("pf-self", B, H, T)
+        q, k, v = (K.f16(r.standard_normal((B * T, d))) for _ in range(3))
+        ref, sabs, vst, n = K.prefill_attention(q, k, v, B, T, H, T, True)
+        bound = K.prefill_bound(ref, sabs, n, vst, floor=K.prefill_p16_floor(q, k, v, B, T, H, T, True))
+        muts = _pf_self_mutations(q, k, v, B, T, H)
+        assert muts or (B, H, T) == (1, 1, 1)
+        K.discriminates(ref, bound, muts)
+        out, ck, cv = _pf_self_run(q, k, v, d, B, T, H)
+        _pf_report("self", out, ref, bound)
+        K.within(out, ref, bound, f"prefill self B={B} H={H} T={T}")
+        _pf_check_self_cache(ck, cv, k, v, B, T, H, f"prefill self B={B} H={H} T={T}")
+
+
+@pytest.mark.parametrize("T", [33, 300])
+def test_prefill_self_attention_on_column_slices_of_one_qkv_buffer(T):
+    """ld = 3 * 64 H: q, k and v are column slices of one [B*T][3 d] buffer, and ldo > 64 H: the pad columns of out stay"""
+    B, H = 2, 6
+    d = 64 * H
+    r = rng("pf-self-qkv", T)
+    qkv = K.f16(r.standard_normal((B * T, 3 * d)))
+    q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
+    ref, sabs, vst, n = K.prefill_attention(q, k, v, B, T, H, T, True)
+    bound = K.prefill_bound(ref, sabs, n, vst, floor=K.prefill_p16_floor(q, k, v, B, T, H, T, True))
+    K.discriminates(ref, bound, _pf_self_mutations(np.ascontiguousarray(q), np.ascontiguousarray(k), np.ascontiguousarray(v), B, T, H))
+    # a row stride mistaken for d: row r of q would be read at r * d of the buffer
+    flat = qkv.reshape(-1)
+    wrong_q = np.stack([flat[r_ * d:r_ * d + d] for r_ in range(B * T)])
+    K.discriminates(ref, bound, {"q read with ld = d": K.prefill_attention(wrong_q, k, v, B, T, H, T, True, stats=False)[0]})
+    ldo = d + 64
+    out, ck, cv = _pf_self_run(q, k, v, 3 * d, B, T, H, ldo=ldo)
+    _pf_report("self", out[:, :d], ref, bound)
+    K.within(out[:, :d], ref, bound, f"prefill self on qkv slices T={T}")
+    assert np.all(out[:, d:] == np.float16(7.25)), "the pad columns of out were written"
+    _pf_check_self_cache(ck, cv, k, v, B, T, H, f"prefill self on qkv slices T={T}")
+
+
+# every S has a ragged last block but 64; 750 = 11 * 64 + 46, 1500 = 23 * 64 + 28; T: one query, one wave + 1, the longest prefix
+# of a decode (14 waves), two tiles
+PF_CROSS = [(2, 3, 17, 1), (2, 3, 1, 63), (3, 6, 17, 64), (2, 3, 223, 65), (2, 6, 300, 750), (1, 20, 17, 1500), (3, 2, 223, 1500),
+            (2, 3, 1, 750)]
+
+
+@pytest.mark.parametrize("B,H,T,S", PF_CROSS)
+def test_prefill_cross_attention_matches_fp64(B, H, T, S):
+    r = rng("pf-cross", B, H, T, S)
+    q, ck, cv = K.prefill_cross_case(r, B, T, H, S)
+    U = B * H
+    qu, ku, vu = K.pf_units(q, B, T, H), K.pf_from_head_major(ck, B, H, S), K.pf_from_head_major(cv, B, H, S)
+    ref, sabs, vst, n = K.prefill_attention(qu, ku, vu, 1, T, U, S, False)
+    bound = K.prefill_bound(ref, sabs, n, vst, floor=K.prefill_p16_floor(qu, ku, vu, 1, T, U, S, False))
+    muts = K.prefill_cross_mutations(qu, ku, vu, B, T, H, S)
+    assert "one key too many" in muts and ("one key too few" in muts or S == 1)
+    K.discriminates(ref, bound, muts)
+    out, ck2, cv2 = _pf_cross_run(q, ck, cv, B, T, H, S)
+    _pf_report("cross", K.pf_units(out, B, T, H), ref, bound)
+    K.within(K.pf_units(out, B, T, H), ref, bound, f"prefill cross B={B} H={H} T={T} S={S}")
+    assert np.array_equal(_bits(ck2), _bits(ck)) and np.array_equal(_bits(cv2), _bits(cv)), "the cross K/V were written"
+
+
+@pytest.mark.parametrize("causal", [True, False], ids=["self", "cross"])
+def test_prefill_attention_adversarial_scores(causal):
+    """kref.prefill_adversarial: one (clip, head) unit per family -- all keys equal; scores ascending by 0.2 per key over five
+    64-key blocks, so every block rescales; one key 40 above the rest in the first block, so later blocks' P is zero in fp16
+    while l still counts it; the dominating key last in sight with an equally loud one first out of sight.  Every unit must
+    catch both mask errors by itself (the cross form's dominant-first unit: a key too many only -- its last key holds e^-40
+    of the weight by construction)."""
+    r = rng("pf-adv", causal)
+    T, nk = (300, 300) if causal else (17, 300)
+    qa, ka, va = K.prefill_adversarial(r, T, nk, causal)
+    U = qa.shape[0]
+    qu, ku, vu = (np.ascontiguousarray(a.transpose(1, 0, 2)).reshape(a.shape[1], U * 64) for a in (qa, ka, va))
+    ref, sabs, vst, n = K.prefill_attention(qu, ku, vu, 1, T, U, nk, causal)
+    bound = K.prefill_bound(ref, sabs, n, vst, floor=K.prefill_p16_floor(qu, ku, vu, 1, T, U, nk, causal))
+    muts = K.prefill_mask_mutations(qu, ku, vu, T, U, nk, causal)
+    for u, fam in enumerate(K.PF_FAMILIES):
+        c = slice(64 * u, 64 * u + 64)
+        for name, m in muts.items():
+            if (causal, fam, name) != (False, "dominant-first", "one key too few"):
+                K.discriminates(ref[:, c], bound[:, c], {f"{fam}: {name}": m[:, c]})
+    if causal:
+        out, ck, cv = _pf_self_run(qu, ku, vu, 64 * U, 1, T, U)
+        _pf_check_self_cache(ck, cv, ku, vu, 1, T, U, "prefill self adversarial")
+    else:
+        out = _pf_cross_run(qu, ka, va, 1, T, U, nk)[0]       # [U][nk][64] IS the head-major buffer of one clip
+    _pf_report("adversarial", out, ref, bound)
+    K.within(out, ref, bound, f"prefill adversarial causal={causal}")
+
+
+def test_prefill_attention_refuses_empty_and_oversized_shapes():
+    """T = 0, T > C and S = 0 return false (the wrapper: -1) and leave out, ck and cv bit-identical"""
+    B, H = 2, 2
+    r = rng("pf-refuse")
+    for T, C in ((0, PF_C), (PF_C + 1, PF_C), (17, 16)):
+        rows = max(B * T, 1)
+        q, k, v = (K.f16(r.standard_normal((rows, 64 * H))) for _ in range(3))
+        out, ck, cv = _pf_self_run(q, k, v, 64 * H, B, T, H, C=C, expect=-1)
+        assert np.all(out == np.float16(7.25)) and np.all(ck == np.float16(7.25)) and np.all(cv == np.float16(-3.5)), (T, C)
+    for T, S in ((0, 5), (3, 0)):
+        q = K.f16(r.standard_normal((max(B * T, 1), 64 * H)))
+        ck = K.f16(r.standard_normal((B, H, max(S, 1), 64))); cv = K.f16(r.standard_normal((B, H, max(S, 1), 64)))
+        out, ck2, cv2 = _pf_cross_run(q, ck, cv, B, T, H, S, expect=-1)
+        assert np.all(out == np.float16(7.25)) and np.array_equal(_bits(ck2), _bits(ck)) and np.array_equal(_bits(cv2), _bits(cv))
+
+
 # ---- GEMM epilogues ---------------------------------------------------------------------------------------------------------
 def _gemm(kernel128, A, lda, a_rpb, a_bstride, W, bias, M, epi, outs, seg_n, ldo, o_rpb=0, o_bstride=0, o_off=0, vt_seg=-1,
           head_major=0, seg0_scale=0.0, S=0, H=0, pos=None):
@@ -559,8 +750,9 @@ def _gemm_muts(pre, Ar, W, bias, fn, M):
     if bias is not None:
         nb = pre.copy(); nb[:, -16:] -= K.d64(bias[-16:])
         m["bias missing on the last tile"] = fn(nb)
-    nr = pre.copy(); nr[M - 2] = pre[M - 1]
-    m["ragged rows: row reads the next row"] = fn(nr)
+    if M >= 2:
+        nr = pre.copy(); nr[M - 2] = pre[M - 1]
+        m["ragged rows: row reads the next row"] = fn(nr)
     return m
 
 
@@ -685,6 +877,85 @@ def test_gemm_conv_epilogues_with_row_maps(kernel128):
     K.discriminates(ref2, bound2, muts)
 
 
+# launch_gemm as prefill_forward calls it (nh_prefill.hip pf_gemm): M = B * T rows from 1 upward, a_rpb = o_rpb = S = M, so all
+# three nh_magic values are 0, the "quotient 0" encoding of nh_div.  Which kernel launch_gemm (kernel128 = 0) reaches, from
+# its condition `N % 256 == 0 && K % 128 == 0 && seg_ok && M >= 256` (seg_ok: seg_n % 256 == 0 under the fp16 epilogues; every
+# shape here has N, K and seg_n multiples of 256):
+#   M = 1, 3, 127, 128, 129, 255   gemm_f16_kernel (128 x 128 tiles): one partial row tile up to 127, one full at 128, one full + one
+#                                  ragged at 129 and 255
+#   M = 256, 257, 511              gemm256_f16_kernel<EPI>: one full tile at 256, one full + one ragged at 257 (1 row) and 511 (255)
+# From M = 256 on kernel128 = 1 runs the 128 x 128 kernel on the same shape too; below, both launchers reach that kernel.
+PF_GEMM = [(M, 256) for M in (1, 3, 127, 128, 129, 255, 256, 257, 511)] + [(3, 1280), (257, 1280)]
+PF_GEMM_CASES = [(k128, M, d) for M, d in PF_GEMM for k128 in ((0, 1) if M >= 256 else (0,))]
+
+
+def _reaches_gemm256(M, N, Kd, epi, seg_n):
+    """launch_gemm's dispatch condition (k_gemm.hip), restated"""
+    seg_ok = epi not in (K.EPI_F16, K.EPI_GELU_F16) or seg_n % 256 == 0
+    return N % 256 == 0 and Kd % 128 == 0 and seg_ok and M >= 256
+
+
+def test_prefill_gemm_cases_sit_on_both_sides_of_the_dispatch_edge():
+    through_launch_gemm = [(M, d) for k128, M, d in PF_GEMM_CASES if k128 == 0]
+    for N_of, K_of, epi in ((lambda d: 3 * d, lambda d: d, K.EPI_F16), (lambda d: 4 * d, lambda d: d, K.EPI_GELU_F16),
+                            (lambda d: d, lambda d: 4 * d, K.EPI_RESID_F32)):
+        big = {M for M, d in through_launch_gemm if _reaches_gemm256(M, N_of(d), K_of(d), epi, d if epi == K.EPI_F16 else N_of(d))}
+        small = {M for M, d in through_launch_gemm} - big
+        assert {256, 257, 511} <= big and {1, 3, 127, 128, 129, 255} <= small and max(small) + 1 == min(big) == 256
+
+
+def _canary_rows(M, n, dtype, value=7.25):
+    """an output buffer of M + 1 rows: the row past M must come back untouched"""
+    return np.full((M + 1, n), value, dtype=dtype)
+
+
+@pytest.mark.parametrize("kernel128,M,d", PF_GEMM_CASES)
+def test_gemm_at_prefill_shapes_plain_qkv_gelu_and_residual(kernel128, M, d):
+    """the prefill's three epilogues: q | k | v as three plain row-major fp16 segments (EPI_F16, seg_n = ldo = d, no V^T, no
+    head-major, no q scale), fc1 (EPI_GELU_F16, N = 4 d) and fc2 (EPI_RESID_F32, K = 4 d), every output with a canary row past M"""
+    r = rng("pf-gemm", M, d)                     # both launchers see the same data
+    H = d // 64
+    A = K.f16(r.standard_normal((M, d)))
+    W = K.f16(r.standard_normal((3 * d, d)) / np.sqrt(d))
+    bias = K.f32(r.standard_normal(3 * d) * 0.5)
+    pre, absdot = K.linear(A, W, bias)
+    bound = K.f16_out_bound(pre, absdot, d)
+    K.discriminates(pre, bound, _gemm_muts(pre, A, W, bias, lambda v: v, M))
+    swapped = np.concatenate([pre[:, d:2 * d], pre[:, :d], pre[:, 2 * d:]], axis=1)
+    K.discriminates(pre, bound, {"segments 0 and 1 swapped": swapped})
+    outs = [_canary_rows(M, d, np.float16) for _ in range(3)]
+    _gemm(kernel128, A, d, M, 0, W, bias, M, K.EPI_F16, outs, d, d, o_rpb=M, S=M, H=H)
+    for s_, name in enumerate("qkv"):
+        _pf_report("gemm qkv", outs[s_][:M], pre[:, s_ * d:(s_ + 1) * d], bound[:, s_ * d:(s_ + 1) * d])
+        K.within(outs[s_][:M], pre[:, s_ * d:(s_ + 1) * d], bound[:, s_ * d:(s_ + 1) * d], f"prefill {name} segment M={M} d={d}")
+        assert np.all(outs[s_][M] == np.float16(7.25)), f"prefill {name} segment M={M}: wrote the row past M"
+    # fc1 / fc2
+    W1 = K.f16(r.standard_normal((4 * d, d)) / np.sqrt(d))
+    b1 = K.f32(r.standard_normal(4 * d) * 0.5)
+    pre1, abs1 = K.linear(A, W1, b1)
+    bound1 = K.gelu_f16_bound(pre1, abs1, d)
+    K.discriminates(K.gelu(pre1), bound1, _gemm_muts(pre1, A, W1, b1, K.gelu, M))
+    hid = _canary_rows(M, 4 * d, np.float16)
+    _gemm(kernel128, A, d, M, 0, W1, b1, M, K.EPI_GELU_F16, [hid], 4 * d, 4 * d, o_rpb=M, S=M, H=H)
+    _pf_report("gemm gelu", hid[:M], K.gelu(pre1), bound1)
+    K.within(hid[:M], K.gelu(pre1), bound1, f"prefill fc1 M={M} d={d}")
+    assert np.all(hid[M] == np.float16(7.25)), f"prefill fc1 M={M}: wrote the row past M"
+    W2 = K.f16(r.standard_normal((d, 4 * d)) / np.sqrt(4 * d))
+    b2 = K.f32(r.standard_normal(d) * 0.5)
+    h_in = np.ascontiguousarray(hid[:M])
+    x0 = K.f32(r.standard_normal((M, d)))
+    pre2, abs2 = K.linear(h_in, W2, b2)
+    ref2 = pre2 + K.d64(x0)
+    bound2 = K.f32_out_bound(ref2, abs2, 4 * d, extra=x0)
+    K.discriminates(ref2, bound2, _gemm_muts(pre2, h_in, W2, b2, lambda v: v + K.d64(x0), M))
+    x = _canary_rows(M, d, np.float32)
+    x[:M] = x0
+    _gemm(kernel128, h_in, 4 * d, M, 0, W2, b2, M, K.EPI_RESID_F32, [x], d, d, o_rpb=M, S=M, H=H)
+    _pf_report("gemm resid", x[:M], ref2, bound2)
+    K.within(x[:M], ref2, bound2, f"prefill fc2 M={M} d={d}")
+    assert np.all(x[M] == np.float32(7.25)), f"prefill fc2 M={M}: wrote the row past M"
+
+
 # ---- LayerNorm and embed ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("sliced", [0, 1])
 @pytest.mark.parametrize("M", [1, 17, 96, 3000])
@@ -724,7 +995,8 @@ def _ln_partial(x, w, b, n):
 
 
 def test_embed_matches_fp64():
-    """embed_kernel: x = E[token] + P[position] in f32; token ids 0 and V - 1; per-row positions through pos_ptr"""
+    """embed_kernel: x = E[token] + P[position] in f32; token ids 0 and V - 1; per-row positions through pos_ptr; and the
+    prefill's call: Tn > 1 positions per clip from t0 = 0 without pos_ptr, row b * Tn + i = token (b, i) at position i"""
     L = K.lib()
     r = rng("embed")
     V, d, C, B = 51866, 384, 448, 7
@@ -744,3 +1016,19 @@ def test_embed_matches_fp64():
         off = at.copy(); off[1] = at[1] - 1
         wrong = K.d64(E[tokens[np.arange(B), off]]) + K.d64(P[off])
         assert K.violation(ref, bound + K.SUB16, wrong) > 2
+    tokens[3, 1] = 0; tokens[B - 1, 222] = V - 1
+    for Tn in (2, 33, 223):
+        x = np.full((B * Tn + 1, d), np.float32(7.25), np.float32)      # one canary row past the last
+        rc = L.kref_embed(K.ptr(tokens), C, K.ptr(E), V, K.ptr(P), C, K.ptr(x), B, Tn, 0, None, d)
+        K.check_rc(rc, f"embed Tn={Tn}")
+        i = np.arange(Tn)
+        ref = (K.d64(E[tokens[:, :Tn]]) + K.d64(P[:Tn])[None]).reshape(B * Tn, d)
+        bound = K.U32 * np.abs(ref)
+        _pf_report("embed", x[:B * Tn], ref, np.maximum(bound, 1e-300))
+        K.within(x[:B * Tn], ref, bound, f"embed Tn={Tn}")
+        assert np.all(x[B * Tn] == np.float32(7.25)), f"embed Tn={Tn}: wrote past the last row"
+        im = np.maximum(i - 1, 0)
+        muts = {"row (b, i) takes clip b's token at i - 1": (K.d64(E[tokens[:, im]]) + K.d64(P[:Tn])[None]).reshape(B * Tn, d),
+                "rows position-major (row r = clip r % B at position r // B)":
+                    K.d64(E[tokens[np.arange(B * Tn) % B, np.arange(B * Tn) // B]]) + K.d64(P[np.arange(B * Tn) // B])}
+        K.discriminates(ref, bound + K.SUB16, muts)

@@ -301,6 +301,164 @@ def test_xabs_bound_holds_for_an_f32_fp16_emulation_of_the_kernels():
     assert K.violation(ref, bound, K.xabs_attention(q, Wkv, bkv, xa[:, :-1], H)) > 0
 
 
+# ---- the one-pass prefill attention (prefill_attn_kernel): reference, bound, discrimination ---------------------------------
+def test_prefill_attention_is_a_per_query_softmax():
+    r = _r(10)
+    B, T, H = 2, 7, 2
+    for causal, nk in ((True, T), (False, 11)):
+        q, k, v = r.standard_normal((B * T, 128)), r.standard_normal((B * nk, 128)), r.standard_normal((B * nk, 128))
+        o, sabs, (vdev, pv), n = K.prefill_attention(q, k, v, B, T, H, nk, causal)
+        assert n.tolist() == ([1, 2, 3, 4, 5, 6, 7] * B if causal else [nk] * (B * T))
+        perm = r.permutation(nk)
+        op = K.prefill_attention(q, k, v, B, T, H, nk, causal, vperm=perm, stats=False)[0]
+        first = np.minimum(np.arange(T), 2)
+        of = K.prefill_attention(q, k, v, B, T, H, nk, causal, first=first, stats=False)[0]
+        for b in range(B):
+            for i in range(T):
+                for h in range(H):
+                    c = slice(64 * h, 64 * h + 64)
+                    vis = i + 1 if causal else nk
+                    kk, vv = k[b * nk:b * nk + vis, c], v[b * nk:b * nk + vis, c]
+                    want = _naive_attn(q[b * T + i, c], kk, vv, 1 / 8)
+                    assert np.allclose(o[b * T + i, c], want, rtol=0, atol=1e-12)
+                    s_ = kk @ q[b * T + i, c] / 8
+                    p_ = np.exp(s_ - s_.max()); p_ /= p_.sum()
+                    assert np.isclose(sabs[b * T + i, h], (np.abs(kk) @ np.abs(q[b * T + i, c])).max() / 8)
+                    assert np.allclose(vdev[b * T + i, h], p_ @ np.abs(vv - want), rtol=0, atol=1e-12)
+                    assert np.allclose(pv[b * T + i, h], p_ @ np.abs(vv), rtol=0, atol=1e-12)
+                    assert np.allclose(op[b * T + i, c], p_ @ v[b * nk:(b + 1) * nk, c][perm][:vis], rtol=0, atol=1e-12)
+                    f0 = int(first[i])
+                    assert np.allclose(of[b * T + i, c], _naive_attn(q[b * T + i, c], kk[f0:], vv[f0:], 1 / 8), rtol=0, atol=1e-12)
+    # the natural-order map: keys 0 .. 3 of a 32-key step keep their slot, key 4 sits in slot 8, key 16 in slot 4 (k_prefill.hip)
+    no = K.pf_natural_order(70)
+    assert no[:4].tolist() == [0, 1, 2, 3] and no[4] == 8 and no[16] == 4 and no[20] == 12 and no[31] == 31 and no[36] == 40
+    assert no[64 + 4] == 69 and no[64 + 5] == 69                      # past the last key: the clamped last row
+    assert sorted(K.pf_natural_order(64).tolist()) == list(range(64))  # a permutation of each whole step
+
+
+def _emulate_prefill(q, k, v, B, T, H, nk, causal, l_rounded=True):
+    """prefill_attn_kernel's arithmetic in NumPy f32 / fp16: 64-key blocks, the running maximum, alpha, P rounded to fp16, l
+    summed from the rounded weights (l_rounded=False: from the unrounded ones), O in f32, one final rounding"""
+    f, LOG2E = np.float32, np.float32(1.4426950408889634)
+    q, k, v = (a.astype(f) for a in (q.reshape(B, T, H, 64), k.reshape(B, nk, H, 64), v.reshape(B, nk, H, 64)))
+    out = np.zeros((B, T, H, 64), np.float16)
+    nvis = np.arange(T) + 1 if causal else np.full(T, nk)
+    for b in range(B):
+        for h in range(H):
+            m, l, o = np.full(T, -np.inf, f), np.zeros(T, f), np.zeros((T, 64), f)
+            for k0 in range(0, nk, 64):
+                k1 = min(nk, k0 + 64)
+                s = (q[b, :, h] @ k[b, k0:k1, h].T) * f(0.125)
+                s = np.where(np.arange(k0, k1)[None, :] < nvis[:, None], s, f(-np.inf))
+                mn = np.maximum(m, s.max(axis=-1))
+                live = np.isfinite(mn)                              # causal rows ahead of this block: the wave skips it
+                mn_ = np.where(live, mn, f(0))
+                alpha = np.exp2((np.where(live, m, f(0)) - mn_) * LOG2E).astype(f)
+                e = np.exp2((s - mn_[:, None]) * LOG2E).astype(f)
+                p16 = e.astype(np.float16).astype(f)
+                l = np.where(live, l * alpha + (p16 if l_rounded else e).sum(axis=-1, dtype=f), l)
+                o = np.where(live[:, None], o * alpha[:, None] + p16 @ v[b, k0:k1, h], o)
+                m = np.where(live, mn, m)
+            out[b, :, h] = (o * (f(1) / l)[:, None]).astype(np.float16)
+    return out.reshape(B * T, H * 64)
+
+
+def _prefill_families():
+    """(name, q, k, v, B, T, H, nk, causal): every data family of the GPU suite's prefill attention section, small"""
+    r = _r(11)
+    out = []
+    for name, scale in (("random", 1.0), ("loud", 4.0)):
+        B, T, H = 2, 130, 2
+        out.append((f"self {name}", K.f16(r.standard_normal((B * T, 128)) * scale), K.f16(r.standard_normal((B * T, 128))),
+                    K.f16(r.standard_normal((B * T, 128))), B, T, H, T, True))
+        nk = 1500 if name == "random" else 750
+        out.append((f"cross {name}", K.f16(r.standard_normal((B * 17, 128)) * scale), K.f16(r.standard_normal((B * nk, 128))),
+                    K.f16(r.standard_normal((B * nk, 128))), B, 17, H, nk, False))
+    # the GPU suite's own B = 1, H = 2, T = 127 self case (test_gpu_kernel_ref.rng("pf-self", 1, 2, 127)): the input on which
+    # l summed from the unrounded weights left the bound (row 1: two visible keys whose V nearly agree in one dimension)
+    r127 = np.random.default_rng(K.zlib_key("pf-self", 1, 2, 127))
+    out.append(("self T=127 of the GPU suite",) + tuple(K.f16(r127.standard_normal((127, 128))) for _ in range(3)) + (1, 127, 2, 127, True))
+    for causal, nq, nk in ((True, 300, 300), (False, 17, 300)):
+        q, k, v = K.prefill_adversarial(r, nq, nk, causal)
+        U = q.shape[0]
+        qq, kk, vv = (np.ascontiguousarray(a.transpose(1, 0, 2)).reshape(a.shape[1], U * 64) for a in (q, k, v))
+        out.append((f"{'self' if causal else 'cross'} adversarial", qq, kk, vv, 1, nq, U, nk, causal))
+    return out
+
+
+def test_prefill_bound_holds_for_an_f32_fp16_emulation_of_the_kernel():
+    """on every data family of the GPU tests: the fp16 subnormal floor of P fits into what attn_bound(p16) grants beyond need
+    (kref.prefill_bound asserts it on the data), and an emulation of the kernel's roundings stays inside the bound -- while the
+    same emulation with l summed from the UNROUNDED weights, the kernel's former arithmetic, does not"""
+    worst, former = {}, {}
+    for name, q, k, v, B, T, H, nk, causal in _prefill_families():
+        ref, sabs, vst, n = K.prefill_attention(q, k, v, B, T, H, nk, causal)
+        bound = K.prefill_bound(ref, sabs, n, vst, floor=K.prefill_p16_floor(q, k, v, B, T, H, nk, causal))
+        got = _emulate_prefill(q, k, v, B, T, H, nk, causal)
+        worst[name] = K.violation(ref, bound, got)
+        former[name] = K.violation(ref, bound, _emulate_prefill(q, k, v, B, T, H, nk, causal, l_rounded=False))
+        K.within(got, ref, bound, f"emulated prefill attention, {name}")
+    print("emulation, worst |err| / bound:", worst)
+    print("... with l from the unrounded weights:", former)
+    assert max(worst.values()) > 0.05, worst        # the bound is not orders of magnitude away from the arithmetic
+    assert former["self T=127 of the GPU suite"] > 1.0, former
+
+
+def test_prefill_mutations_leave_the_bound_on_their_designated_cases():
+    """each named bug of the GPU section, as the same reference with a changed argument, leaves the bound by more than 2x on the
+    case that is there to catch it (random data alone would not do: behind a loud q, or among 1500 keys, a key too few moves
+    the output by next to nothing, so the mask errors have designated cases: few keys, equal keys, ascending scores)"""
+    r = _r(12)
+    fams = {f[0]: f[1:] for f in _prefill_families()}
+    # mask errors: unit-variance q at few keys, equal keys, ascending scores; NOT the loud q
+    B, T, H = 2, 17, 2
+    q, k, v = (K.f16(r.standard_normal((B * T, 128))) for _ in range(3))
+    ref, sabs, vst, n = K.prefill_attention(q, k, v, B, T, H, T, True)
+    bound = K.prefill_bound(ref, sabs, n, vst)
+    i = np.arange(T)
+
+    def mut(**kw):
+        return K.prefill_attention(q, k, v, B, T, H, T, True, stats=False, **kw)[0]
+
+    vs = v.copy(); vs[:, 64:] = v[:, :64]
+    got = K.discriminates(ref, bound, {
+        "mask one key short": mut(nvis=np.maximum(i, 1)), "mask one key long": mut(nvis=np.minimum(i + 2, T)),
+        "natural key order": mut(vperm=K.pf_natural_order(T)),
+        "last head reads the previous head's V": K.prefill_attention(q, k, vs, B, T, H, T, True, stats=False)[0],
+        "clip b reads clip b-1's keys": K.prefill_attention(q, np.roll(k.reshape(B, T, 128), 1, 0), np.roll(v.reshape(B, T, 128), 1, 0),
+                                                            B, T, H, T, True, stats=False)[0]})
+    print("self, 17 keys:", got)
+    # the adversarial units: every family catches both mask errors alone (cross dominant-first: a key too many only -- its
+    # last key holds e^-40 of the weight by construction)
+    for form, causal in (("self", True), ("cross", False)):
+        qa, ka, va, Ba, Ta, Ha, nka, _ = fams[f"{form} adversarial"]
+        refa, sabsa, vsta, na = K.prefill_attention(qa, ka, va, Ba, Ta, Ha, nka, causal)
+        ba = K.prefill_bound(refa, sabsa, na, vsta)
+        for name, m in K.prefill_mask_mutations(qa, ka, va, Ta, Ha, nka, causal).items():
+            for u, fam in enumerate(K.PF_FAMILIES):
+                c = slice(64 * u, 64 * u + 64)
+                f = K.violation(refa[:, c], ba[:, c], m[:, c])
+                if (form, fam, name) == ("cross", "dominant-first", "one key too few"):
+                    assert f < 2
+                else:
+                    assert f > 2, (form, fam, name, f)
+    # the cross form on random data with its planted keys (kref.prefill_cross_case): both mask errors, the wrong head slab, the
+    # wrong clip slab, at a key count where random data alone would hide a key too few
+    Bc, Hc, Tc, Sc = 2, 2, 5, 750
+    qc, ckc, cvc = K.prefill_cross_case(r, Bc, Tc, Hc, Sc)
+    qu, ku, vu = K.pf_units(qc, Bc, Tc, Hc), K.pf_from_head_major(ckc, Bc, Hc, Sc), K.pf_from_head_major(cvc, Bc, Hc, Sc)
+    refc, sabsc, vstc, nc = K.prefill_attention(qu, ku, vu, 1, Tc, Bc * Hc, Sc, False)
+    mc = K.prefill_cross_mutations(qu, ku, vu, Bc, Tc, Hc, Sc)
+    assert len(mc) == 4, sorted(mc)
+    print("cross, 750 keys:", K.discriminates(refc, K.prefill_bound(refc, sabsc, nc, vstc), mc))
+    # T = 300: the second query tile ignores keys below 256
+    qa, ka, va, Ba, Ta, Ha, nka, _ = fams["self adversarial"]
+    refa, sabsa, vsta, na = K.prefill_attention(qa, ka, va, Ba, Ta, Ha, nka, True)
+    K.discriminates(refa, K.prefill_bound(refa, sabsa, na, vsta),
+                    {"second tile ignores keys below 256": K.prefill_attention(qa, ka, va, Ba, Ta, Ha, nka, True, stats=False,
+                                                                               first=np.where(np.arange(Ta) >= 256, 256, 0))[0]})
+
+
 # ---- token selection -------------------------------------------------------------------------------------------------------
 def _oracle(layout_name):
     import common

@@ -161,6 +161,46 @@ int kref_enc_attention(const void *q, const void *k, long ld, const void *vt, vo
     return (int)b.err;
 }
 
+// launch_prefill_self_attention: q, k, v rows (b, i) at base + (b * T + i) * ld, 64 H halfs each (three buffers, or column
+// slices of one q|k|v buffer with ld = 3 * 64 H: each is copied from its own base up to the end of its last row); out
+// [B*T][ldo], ck / cv the self cache [B][H][C][64].  out, ck and cv are copied in and back, after a refusal too.
+int kref_prefill_self_attention(const void *q, const void *k, const void *v, long ld, void *out, long ldo, void *ck, void *cv, int B,
+                                int T, int H, int C) {
+    Bufs b;
+    Stream st;
+    const long rows = (long)(B > 0 ? B : 0) * (T > 0 ? T : 0);
+    const size_t in_bytes = rows ? (size_t)((rows - 1) * ld + (long)H * NH_DH) * 2 : 0, out_bytes = (size_t)rows * ldo * 2;
+    const size_t cache_bytes = (size_t)B * H * C * NH_DH * 2;
+    const half_t *dq = b.in<half_t>(q, in_bytes), *dk = b.in<half_t>(k, in_bytes), *dv = b.in<half_t>(v, in_bytes);
+    half_t *dout = b.in<half_t>(out, out_bytes), *dck = b.in<half_t>(ck, cache_bytes), *dcv = b.in<half_t>(cv, cache_bytes);
+    KREF_CHECK(b);
+    const bool launched = launch_prefill_self_attention(dq, dk, dv, ld, dout, ldo, dck, dcv, B, T, H, C, st.s);
+    if (hipError_t e = st.finish()) return (int)e;
+    b.out(out, dout, out_bytes);
+    b.out(ck, dck, cache_bytes);
+    b.out(cv, dcv, cache_bytes);
+    return launched ? (int)b.err : -1;
+}
+
+// launch_prefill_cross_attention: q rows (b, i) at q + (b * T + i) * ldq; ck, cv head-major cross K/V [B][H][S][64], exactly S
+// keys per (clip, head); out [B*T][ldo].  out, ck and cv are copied in and back, after a refusal too.
+int kref_prefill_cross_attention(const void *q, long ldq, void *ck, void *cv, void *out, long ldo, int B, int T, int H, int S) {
+    Bufs b;
+    Stream st;
+    const long rows = (long)(B > 0 ? B : 0) * (T > 0 ? T : 0);
+    const size_t q_bytes = rows ? (size_t)((rows - 1) * ldq + (long)H * NH_DH) * 2 : 0, out_bytes = (size_t)rows * ldo * 2;
+    const size_t kv_bytes = (size_t)B * H * (S > 0 ? S : 0) * NH_DH * 2;
+    const half_t *dq = b.in<half_t>(q, q_bytes);
+    half_t *dck = b.in<half_t>(ck, kv_bytes), *dcv = b.in<half_t>(cv, kv_bytes), *dout = b.in<half_t>(out, out_bytes);
+    KREF_CHECK(b);
+    const bool launched = launch_prefill_cross_attention(dq, ldq, dck, dcv, dout, ldo, B, T, H, S, st.s);
+    if (hipError_t e = st.finish()) return (int)e;
+    b.out(out, dout, out_bytes);
+    b.out(ck, dck, kv_bytes);
+    b.out(cv, dcv, kv_bytes);
+    return launched ? (int)b.err : -1;
+}
+
 // launch_gemm (kernel128 = 0) or launch_gemm_128: A is a buffer of a_bytes that the row map (a_rpb, a_bstride, lda) reads,
 // out0..2 buffers of out_bytes each (copied in and back), pos f32 [S][N] for EPI_CONV2_F32
 int kref_gemm(int kernel128, const void *A, size_t a_bytes, long lda, int a_rpb, long a_bstride, const void *W, const float *bias,
