@@ -579,6 +579,39 @@ int nh_align_matrix(nh_ctx *ctx, int b, float *out);           /* f32 [n_tokens[
  * (S = max_source_positions when nothing is encoded yet); out_first / out_last host i32 [R] */
 int nh_align_path(nh_ctx *ctx, const float *matrix, int R, int nk, int32_t *out_first, int32_t *out_last);
 
+/* ---- transcript scoring ---------------------------------------------------------------------------- */
+/* How probable is every token of a GIVEN transcript under the model: what a word confidence, the score of a corrected
+ * transcript, re-ranking another model's hypotheses and a fallback test on the weakest span are built from.  All positions of
+ * all clips go through the decoder in one pass (nh_decoder_forward_onepass's arithmetic) and through one projection onto the
+ * vocabulary that is reduced on the fly: no logit reaches memory.
+ * For every clip of the current lockstep batch (after nh_encode / nh_encode_rows; a decode may or may not have run):
+ * tokens       host i32 [batch][max_target_positions]: the sequences as a decode returned them, or any others
+ * n_tokens     host i32 [batch], prompt_len < n_tokens[b] <= max_target_positions
+ * prompt_len   tokens [0, prompt_len) are given, not scored.  >= 1.  A prefix that stood in front of sot during the decode
+ *              (nh_set_prompts) is scored by passing it as part of `tokens`, with prompt_len = n_prefix + P; nh_score itself
+ *              ignores nh_set_prompts
+ * out_logprob  host f32 [batch][max_target_positions]: for prompt_len <= i < n_tokens[b], entry i is the natural log of the
+ *              probability of tokens[b][i] under the PLAIN softmax (no logit rules) over all V logits of position i - 1 -- the
+ *              quantity a decode adds to its sum of log-probabilities for the token it picks (its expf(l - m) / se is not
+ *              renormalised by the rules).  Every other entry is written as 0.0f
+ * Arithmetic, for clip b with n = n_tokens[b]:
+ *   1 positions 0 .. max_b(n) - 2 of all clips go through the one-pass forward up to the final LayerNorm's fp16 rows xn.
+ *     Positions past a clip's own n - 2 are padding: the self-attention is causal, so they reach no scored position, and
+ *     what the caller holds in tokens[b][n:] is never looked at
+ *   2 l[v] = sum_k xn[k] E[v][k]: fp16 operands, f32 accumulation, the k-steps added in ascending order into one
+ *     accumulator (the statement the GEMMs make: a logit does not depend on the number of rows)
+ *   3 m = max_v l and se = sum_v expf(l[v] - m) in f32, in an order fixed by v alone
+ *   4 out = (float)((double)(l[t] - m) - log((double)se)), which stays finite where expf(l[t] - m) underflows
+ * A clip's outputs are bit-identical whatever the batch around it and whatever sits in tokens[b][n_tokens[b]:].
+ * Afterwards the context is in the state nh_decoder_forward_onepass leaves: self K/V and the device-side tokens are
+ * overwritten, cross K/V and the encoder output untouched; nh_align_decoded refuses until the next decode.
+ * Refused, nothing launched, outputs untouched.  NH_ERR_STATE: no encoder output, a decode pool, d_model % 128 != 0,
+ * NH_OPT_ABSORBED_XATTN != 0.  NH_ERR_INVALID: NULL arguments, prompt_len < 1, n_tokens[b] outside
+ * (prompt_len, max_target_positions], a token id outside the vocabulary among the first n_tokens[b].
+ * Its buffers are one allocation made by the first call and freed with the context: a context that never scores allocates
+ * and launches nothing for it. */
+int nh_score(nh_ctx *ctx, const int32_t *tokens, const int32_t *n_tokens, int prompt_len, float *out_logprob);
+
 /* ---- instrumentation --------------------------------------------------------------------------- */
 /* Milliseconds (HIP events on the context's stream) spent in the phases of the last
  * nh_transcribe_batch / nh_logmel+nh_encode+nh_decode_greedy sequence. */

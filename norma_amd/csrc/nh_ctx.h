@@ -1,6 +1,6 @@
-// nh_ctx.h -- the state behind the C ABI of include/norma_hip.h, shared by the eight files that implement it: nh_model.hip
+// nh_ctx.h -- the state behind the C ABI of include/norma_hip.h, shared by the files that implement it: nh_model.hip
 // (create / destroy, weights, tokens, options, timings), nh_encode.hip (log-mel, encoder), nh_decode.hip (decoder step,
-// lockstep decode, decode pool, parity views), nh_prefill.hip (decoder prompts, the one-pass forward), nh_align.hip (token-level timestamps), nh_resample.hip (audio ingest),
+// lockstep decode, decode pool, parity views), nh_prefill.hip (decoder prompts, the one-pass forward), nh_score.hip (transcript scoring), nh_align.hip (token-level timestamps), nh_resample.hip (audio ingest),
 // nh_cut.hip (cutting long recordings), nh_vad.hip (their speech map).  It also holds the two things every audio route into the PCM rows shares: the
 // grow-on-demand device buffer (DevBuf: the one staging of host audio, the cut workspaces) and the batch check
 // (check_batch) that runs before anything is queued.  No torch, no candle, no CPU fallback: an entry point runs the HIP
@@ -193,6 +193,16 @@ struct BeamState {
     std::vector<double> fin_score;
 };
 
+// nh_score: everything it owns.  One allocation made by the first call, sized by max_batch alone; a context that never scores
+// holds nothing.
+struct ScoreState {
+    DevBuf buf;
+    int32_t *target = nullptr;   // [max_batch * (C - 1)] target column of every row (clip, position); -1: not scored
+    float *tlogit = nullptr;     // [max_batch * (C - 1)] the target's logit
+    float *out = nullptr;        // [max_batch][C] device side of out_logprob
+    float *part = nullptr;       // the tile partials of one row panel (launch_score_rows)
+};
+
 struct nh_ctx {
     int dev = 0;
     std::shared_ptr<nh_model> mdl;
@@ -250,6 +260,7 @@ struct nh_ctx {
     AlignState al;               // nh_align, nh_align_decoded
     AlignLive live;              // nh_align_capture
     BeamState beam;              // nh_decode_beam
+    ScoreState score;            // nh_score
     // The context's one query buffer, fp16 [align_q_heads][C - 1][max_batch][64]: nh_align's teacher-forced pass and the decodes
     // under nh_align_capture both write it, stages 2 - 6 read it.  Grown by align_q_buffer alone, freed by nh_destroy.
     half_t *align_q = nullptr;
@@ -320,13 +331,15 @@ void finish_sequence(nh_ctx *ctx, int32_t *t, int n, int done, double slp, doubl
 // nh_prefill.hip: TextDecoder::forward over positions 0 .. T-1 of ds.tokens for the rows of the lockstep batch in one pass:
 // self K/V of those positions land in the caches.  hidden == nullptr (a decode's prefix): the last block stops once its K/V
 // are written; otherwise everything, the final LayerNorm included, and the B * T rows are copied to `hidden` (host f32).
+// keep_rows (with hidden == nullptr; nh_score): everything as well, but the final LayerNorm's fp16 rows [B * T][d] stay in
+// ctx->xn, nothing is copied to the host and the stream is not waited for.
 bool prefill_supported(const nh_ctx *ctx);
 // Shortest prefix the default route sends through the one pass.  Its fifteen-odd launches on a handful of rows cost 0.64 - 0.76 ms
 // at distil-large-v3's shape with 32 clips whatever the length, a decode step 0.18 ms: measured 0.64 / 0.67 / 0.71 ms against
 // 0.17 / 0.36 / 0.73 ms stepwise at 1 / 2 / 4 tokens (tools/dbg/prompt_cost.py, profiles/prompt_cost.json): the crossover
 // lies between 2 and 4.
 #define NH_PREFILL_MIN_PREFIX 4
-int prefill_forward(nh_ctx *ctx, int T, float *hidden);
+int prefill_forward(nh_ctx *ctx, int T, float *hidden, bool keep_rows = false);
 inline void clear_prompt(nh_ctx *ctx) { ctx->prompt.clear(); ctx->n_prefix = 0; ctx->prompt_batch = 0; }
 // nh_encode.hip: may `batch` clips of these lengths become rows row0 .. of the context's mel batch?  Row range, clip lengths,
 // equal mel frames, the pool and row-gap rules.  Changes nothing in the context: every entry point that fills PCM rows

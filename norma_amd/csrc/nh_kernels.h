@@ -547,3 +547,15 @@ void launch_beam_merge(DecodeState s, RuleTokens tk, int V, int B, int K, int ct
 // 0 .. npos-1 of row parent[r] in each (npos <= C; parent[r] < 0 or == r: the row stays).  Any parent map inside a clip.
 void launch_beam_reorder(half_t *const *caches, int n_caches, const int32_t *parent, int B, int K, int H, int C, int npos,
                          hipStream_t st);
+
+// ---- transcript scoring (k_score.hip) -------------------------------------------------------------------------
+// Rows per launch pair: the partials [rows][ceil(V / 128)][2] f32 of a panel stay within 64 MB (a multiple of 128, >= 16384)
+int score_panel_rows(int V);
+// For every row m < M with target[m] >= 0: out[(m / T) * ldo + m % T + off] = log softmax(xn[m] . E^T)[target[m]], the
+// plain softmax over all V columns -- l[v] = sum_k xn[m][k] E[v][k] (fp16 operands, f32, k-steps ascending into one accumulator),
+// mx = max_v l, se = sum_v exp(l[v] - mx) in f32, (float)((double)(l[t] - mx) - log((double)se)).  Rows with target[m] < 0 write
+// nothing.  xn fp16 [M][d], E fp16 [V][d] as stored (rows >= M / >= V are never read), target i32 [M] (< V), tlogit f32 [M]
+// scratch, part f32 scratch for min(M, panel) rows x ceil(V / 128) x 2; panel_rows 0 = score_panel_rows(V), else a multiple
+// of 128 not above it.  No logit reaches memory.  false (nothing launched): d % 64 != 0, V outside 1 .. NH_MAX_VOCAB, M or T < 1.
+bool launch_score_rows(const half_t *xn, int M, int d, const half_t *E, int V, const int32_t *target, float *part, float *tlogit,
+                       int T, long ldo, int off, float *out, int panel_rows, hipStream_t st);

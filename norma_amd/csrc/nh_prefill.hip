@@ -32,7 +32,7 @@ static void pf_layernorm(nh_ctx *ctx, const LnW &ln, const float *x, half_t *y, 
     if (!launch_layernorm_sliced(x, ln.w, ln.b, y, y32, M, d, ctx->st)) launch_layernorm(x, ln.w, ln.b, y, y32, M, d, ctx->st);
 }
 
-int prefill_forward(nh_ctx *ctx, int T, float *hidden) {
+int prefill_forward(nh_ctx *ctx, int T, float *hidden, bool keep_rows) {
     const nh_model &m = *ctx->mdl;
     const int d = ctx->c.d_model, B = ctx->cur_batch, H = ctx->c.decoder_attention_heads, C = ctx->c.max_target_positions, S = ctx->S;
     if (!prefill_supported(ctx)) return ctx->fail(NH_ERR_STATE, "the one-pass decoder forward needs d_model % 128 == 0 and NH_OPT_ABSORBED_XATTN == 0");
@@ -40,7 +40,7 @@ int prefill_forward(nh_ctx *ctx, int T, float *hidden) {
     const int M = B * T;
     float *x = ctx->x;
     half_t *xn = ctx->xn, *q = ctx->q, *k = ctx->k, *v = ctx->hid, *att = ctx->att, *hid = ctx->hid;
-    const bool full = hidden != nullptr;
+    const bool full = hidden != nullptr || keep_rows;
     int layers = (int)m.dec.size();
     if (ctx->dec_layer_limit > 0 && ctx->dec_layer_limit < layers) layers = ctx->dec_layer_limit;   // depth profile of the parity tests
     launch_embed(ctx->ds.tokens, C, m.tok_emb, m.dec_pos, x, B, T, 0, nullptr, d, ctx->st);
@@ -62,7 +62,9 @@ int prefill_forward(nh_ctx *ctx, int T, float *hidden) {
         pf_gemm(ctx, xn, d, L.fc1, M, 4 * d, d, EPI_GELU_F16, hid, nullptr, nullptr, 4 * d, 4 * d);
         pf_gemm(ctx, hid, 4 * d, L.fc2, M, d, 4 * d, EPI_RESID_F32, x, nullptr, nullptr, d, d);
     }
-    if (full) {
+    if (keep_rows && !hidden) {
+        pf_layernorm(ctx, m.dec_ln, x, xn, nullptr, M, d);
+    } else if (full) {
         float *y32 = reinterpret_cast<float *>(ctx->hid);   // B * 1500 * 4 d halfs: room for 2 * B * 1500 * d floats
         pf_layernorm(ctx, m.dec_ln, x, xn, y32, M, d);
         HIPCHK(hipMemcpyAsync(hidden, y32, sizeof(float) * (size_t)M * d, hipMemcpyDeviceToHost, ctx->st));

@@ -174,6 +174,7 @@ def load_library() -> C.CDLL:
     L.nh_align_weights.argtypes = [vp, C.c_int, C.c_int, fp]
     L.nh_align_matrix.argtypes = [vp, C.c_int, fp]
     L.nh_align_path.argtypes = [vp, fp, C.c_int, C.c_int, ip, ip]
+    L.nh_score.argtypes = [vp, ip, ip, C.c_int, fp]
     dp = C.POINTER(C.c_double)
     L.nh_decode_beam.argtypes = [vp, C.c_int, ip, C.POINTER(NhDecodeResult), C.c_int]
     L.nh_beam_hypotheses.argtypes = [vp, C.c_int, ip, ip, dp, ip]
@@ -267,7 +268,7 @@ class HipWhisper:
             raise HipError(rc, self.L.nh_last_error(None).decode())
         self._h = h
         self.batch = 0
-        self._decoded, self._decoded_rows, self._task = [], {}, -1   # what the last decode / collects returned (align_decoded)
+        self._decoded, self._decoded_rows, self._task, self._eot = [], {}, -1, -1   # what the last decode / collects returned (align_decoded)
         self._experiment_switches()
 
     # -- lifetime ------------------------------------------------------------------------------
@@ -319,7 +320,7 @@ class HipWhisper:
                       tokens.zero_sec, tokens.one_sec)
         sup = np.asarray(self.cfg.suppress_tokens if suppress is None else suppress, dtype=np.int32)
         self._chk(self.L.nh_set_tokens(self._h, C.byref(tk), _ip(sup), len(sup)))
-        self._task = int(task)
+        self._task, self._eot = int(task), int(tokens.eot)
 
     # -- hot path ------------------------------------------------------------------------------
     def logmel(self, clips: Sequence[np.ndarray]):
@@ -788,6 +789,32 @@ class HipWhisper:
                                   _ip(first), _ip(last)))
         self._align_shape = (nt.copy(), int(prompt_len), np.full(B, self.cfg.max_source_positions, np.int32) if nk is None else nk.copy())
         return first, last
+
+    # -- transcript scoring --------------------------------------------------------------------------
+    def score(self, tokens: Sequence[Sequence[int]], n_tokens: Optional[Sequence[int]] = None, prompt_len: int = 3,
+              out: Optional[np.ndarray] = None) -> np.ndarray:
+        """nh_score for every clip of the batch: tokens = the sequences as decode_* returned them, or any others (lists, or an
+        i32 array [batch][max_target_positions] with n_tokens).  Returns f32 [batch][max_target_positions]: entry i of clip b,
+        prompt_len <= i < n_tokens[b], is ln p(tokens[b][i]) under the plain softmax of position i - 1; every other entry 0.
+        A prefix that stood in front of sot goes in front of `tokens`, with prompt_len = len(prefix) + 2 or 3.
+        out: the array to write (a refused call leaves it as it is)."""
+        B, Cn = self.batch, self.cfg.max_target_positions
+        if n_tokens is None:
+            n_tokens = [len(t) for t in tokens]
+        nt = np.ascontiguousarray(n_tokens, dtype=np.int32)
+        assert len(nt) == B and len(tokens) == B
+        if isinstance(tokens, np.ndarray) and tokens.shape == (B, Cn):
+            toks = np.ascontiguousarray(tokens, dtype=np.int32)   # as given, what lies past n_tokens included
+        else:
+            toks = np.zeros((B, Cn), dtype=np.int32)
+            for b in range(B):
+                n = max(0, min(int(nt[b]), Cn))
+                toks[b, :n] = np.asarray(tokens[b], dtype=np.int32)[:n]
+        if out is None:
+            out = np.zeros((B, Cn), dtype=np.float32)
+        assert out.dtype == np.float32 and out.shape == (B, Cn) and out.flags.c_contiguous
+        self._chk(self.L.nh_score(self._h, _ip(toks), _ip(nt), int(prompt_len), _fp(out)))
+        return out
 
     def align_capture(self, heads: Sequence[Tuple[int, int]]):
         """nh_align_capture: every following decode of this context (decode_greedy, decode_sampled, the rows of a pool) keeps

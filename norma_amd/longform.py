@@ -47,14 +47,32 @@ def _set_prompt(hm, prompt, n: int, align: bool):
         hm.set_prompts([list(prompt)] * n)
 
 
+def _score(hm, res, prompt) -> List[np.ndarray]:
+    """hm.score on the sequences a group's decode returned: per clip f32 [len(tokens)], entry i = ln p(tokens[i]), 0.0 for the
+    [sot, language?, task] prompt.  A prefix the decode ran under goes in front of them, as nh_score asks.  A clip that
+    generated nothing (the no-speech exit returns the bare prompt) has nothing to score: it goes in with eot appended, which
+    nh_score needs to accept the batch, and reports zeros."""
+    pre = list(prompt) if prompt is not None and len(prompt) else []
+    P = 2 if res[0]["tokens"][1] == hm._task else 3
+    seqs = [pre + list(r["tokens"]) + ([hm._eot] if len(r["tokens"]) <= P else []) for r in res]
+    lp = hm.score(seqs, prompt_len=len(pre) + P)
+    out = []
+    for i, r in enumerate(res):
+        n = len(r["tokens"])
+        out.append(lp[i, len(pre):len(pre) + n].copy() if n > P else np.zeros(n, dtype=np.float32))
+    return out
+
+
 def transcribe_recording(hm, pcm, params=None, max_new_tokens: int = 0, align: bool = False, prompt=None,
-                         beam_size: int = 1) -> List[dict]:
+                         beam_size: int = 1, score: bool = False) -> List[dict]:
     """hm: a HipWhisper with weights, filters and tokens set.  pcm: a host f32 array (16 kHz mono), or (device pointer,
     n_samples).  params: the cut parameters (HipWhisper.cut_plan).  Returns one dict per chunk: the fields of decode_greedy
     plus start_sample, n_samples and n_keys = ceil(n_samples / 320), the encoder frames that hold audio.  align=True (the
     caller has set hm.align_capture): token_first / token_last of align_decoded(n_keys=...) as well.
     prompt: token ids every chunk decodes under (taken verbatim: <|startofprev|> first is the caller's to add; at most
-    max_target_positions / 2 - 1 of them); the results exclude them.  Not together with align=True."""
+    max_target_positions / 2 - 1 of them); the results exclude them.  Not together with align=True.
+    score=True: token_logprob as well, f32 [len(tokens)]: ln p of every returned token under the model (HipWhisper.score on the
+    group's returned sequences, after its align_decoded; 0.0 for the prompt tokens)."""
     if isinstance(pcm, np.ndarray):
         rec, n = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1), None
     else:
@@ -69,7 +87,11 @@ def transcribe_recording(hm, pcm, params=None, max_new_tokens: int = 0, align: b
         keys = [-(-int(v) // KEY_SAMPLES) for v in lens[a:b]]
         if align:
             first, last = hm.align_decoded(n_keys=keys)
+        if score:
+            lps = _score(hm, res, prompt)
         for i, r in enumerate(res):
+            if score:
+                r.update(token_logprob=lps[i])
             r.update(start_sample=int(starts[a + i]), n_samples=int(lens[a + i]), n_keys=keys[i])
             if align:
                 r.update(token_first=first[i].copy(), token_last=last[i].copy())
@@ -119,11 +141,11 @@ def stitch(results: Sequence[dict], tokens) -> List[Tuple[float, float, List[int
 
 
 def transcribe_speech(hm, pcm, params=None, max_new_tokens: int = 0, align: bool = False, prompt=None,
-                      beam_size: int = 1) -> List[dict]:
+                      beam_size: int = 1, score: bool = False) -> List[dict]:
     """transcribe_recording on the recording's speech alone.  params: the parameters of HipWhisper.vad_plan.  Returns one dict
     per chunk (none for a recording without speech): the fields of decode_greedy plus pieces = [(offset_in_chunk, start_sample,
-    n_samples)], n_samples = the chunk's total, n_keys = ceil(n_samples / 320), and with align=True token_first / token_last.  prompt: as
-    for transcribe_recording."""
+    n_samples)], n_samples = the chunk's total, n_keys = ceil(n_samples / 320), and with align=True token_first / token_last.  prompt, score:
+    as for transcribe_recording."""
     if isinstance(pcm, np.ndarray):
         rec, n = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1), None
     else:
@@ -146,7 +168,11 @@ def transcribe_speech(hm, pcm, params=None, max_new_tokens: int = 0, align: bool
         keys = [-(-v // KEY_SAMPLES) for v in totals[a:b]]
         if align:
             tf, tl = hm.align_decoded(n_keys=keys)
+        if score:
+            lps = _score(hm, res, prompt)
         for i, r in enumerate(res):
+            if score:
+                r.update(token_logprob=lps[i])
             r.update(pieces=pieces[a + i], n_samples=totals[a + i], n_keys=keys[i])
             if align:
                 r.update(token_first=tf[i].copy(), token_last=tl[i].copy())
