@@ -1,6 +1,7 @@
 // nh_model.hip -- the C ABI of include/norma_hip.h, part 1: the device state of one Whisper model on one MI355X (weights in fp16,
 // f32 LayerNorm/bias parameters) and of its contexts (workspaces for `max_batch` 30-second clips); tokens, options, timings.
 #include "nh_ctx.h"
+#include "mel_host.h"
 
 // message of the last failed nh_create on THIS thread (contexts are created from one thread per GPU)
 static thread_local std::string g_create_error;
@@ -58,24 +59,9 @@ extern "C" void nh_destroy(nh_ctx *ctx) {
 }
 
 static bool build_mel_tables(nh_model *m, std::string &err) {
-    // host tables with libm, the same f32 expressions candle evaluates (see k_mel.hip)
-    std::vector<float> hann(400), dc(625), dsn(625), twc(375), tws(375);
-    const float two_pi = (float)M_PI + (float)M_PI;
-    for (int i = 0; i < 400; i++) hann[i] = 0.5f * (1.0f - cosf((two_pi * (float)i) / 400.0f));
-    for (int k = 0; k < 25; k++)
-        for (int j = 0; j < 25; j++) {
-            float angle = two_pi * (float)k * (float)j / 25.0f;
-            dc[k * 25 + j] = cosf(angle); dsn[k * 25 + j] = sinf(angle);
-        }
-    int off = 0;
-    for (int h = 25; h <= 200; h *= 2) {
-        float n_t = (float)(2 * h);
-        for (int k = 0; k < h; k++) {
-            float theta = two_pi * (float)k / n_t;
-            twc[off + k] = cosf(theta); tws[off + k] = -sinf(theta);
-        }
-        off += h;
-    }
+    // host tables with libm, the same f32 expressions candle evaluates (mel_host.h, see k_mel.hip)
+    std::vector<float> hann(MEL_N_HANN), dc(MEL_N_DFT), dsn(MEL_N_DFT), twc(MEL_N_TW), tws(MEL_N_TW);
+    mel_host_tables(hann.data(), dc.data(), dsn.data(), twc.data(), tws.data());
     float *d_h = dalloc_into<float>(m->allocs, 400), *d_dc = dalloc_into<float>(m->allocs, 625), *d_ds = dalloc_into<float>(m->allocs, 625);
     float *d_tc = dalloc_into<float>(m->allocs, 375), *d_ts = dalloc_into<float>(m->allocs, 375);
     if (!d_h || !d_dc || !d_ds || !d_tc || !d_ts) { err = "hipMalloc(mel tables)"; return false; }
@@ -410,16 +396,7 @@ extern "C" int nh_set_mel_filters(nh_ctx *ctx, const float *filters, int n_mel) 
     if (!df) return ctx->fail(NH_ERR_NOMEM, "hipMalloc(mel filters)");
     HIPCHK(hipMemcpy(df, filters, (size_t)n_mel * 201 * 4, hipMemcpyHostToDevice));
     std::vector<int32_t> grp(2 * n_mel);
-    for (int m = 0; m < n_mel; m++) {
-        int g0 = 50, g1 = 0;
-        for (int g = 0; g < 50; g++) {
-            bool nz = false;
-            for (int k = 4 * g; k < 4 * g + 4; k++) nz = nz || filters[(size_t)m * 201 + k] != 0.f;
-            if (nz) { if (g < g0) g0 = g; g1 = g + 1; }
-        }
-        if (g0 > g1) g0 = g1 = 0;
-        grp[2 * m] = g0; grp[2 * m + 1] = g1;
-    }
+    mel_host_groups(filters, n_mel, grp.data());
     HIPCHK(hipMemcpy(m.mel_grp, grp.data(), grp.size() * 4, hipMemcpyHostToDevice));
     m.mt.filters = df;
     m.have_filters = true;

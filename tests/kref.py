@@ -24,7 +24,8 @@ PLAN_FIELDS = ("kind", "ncb", "nt", "ksplit", "sp", "grid_x", "grid_y", "block",
 EPI_F16, EPI_GELU_F16, EPI_RESID_F32, EPI_CONV2_F32 = 0, 1, 2, 3
 WRAPPERS = ["kref_skinny", "kref_skinny_ln_supported", "kref_skinny_plan", "kref_dec_attention", "kref_xabs_attention", "kref_enc_attention",
             "kref_gemm", "kref_layernorm", "kref_embed", "kref_logit_step", "kref_sample_step", "kref_lang_detect",
-            "kref_prefill_self_attention", "kref_prefill_cross_attention"]
+            "kref_prefill_self_attention", "kref_prefill_cross_attention", "kref_mel_tables", "kref_mel_groups", "kref_logmel",
+            "kref_mel_finish"]
 
 # ---- loader ----------------------------------------------------------------------------------------------------------------
 _lib = None
@@ -65,6 +66,10 @@ def _argtypes():
     L.kref_lang_detect.argtypes = [vp, i, i, vp, i, vp, vp]
     L.kref_prefill_self_attention.argtypes = [vp, vp, vp, l, vp, l, vp, vp, i, i, i, i]
     L.kref_prefill_cross_attention.argtypes = [vp, l, vp, vp, vp, l, i, i, i, i]
+    L.kref_mel_tables.argtypes = [vp, vp, vp, vp, vp]
+    L.kref_mel_groups.argtypes = [vp, i, vp]
+    L.kref_logmel.argtypes = [vp, l, vp, i, vp, vp, vp, vp, vp, vp, vp, i, i, vp, l, l, vp, l, l]
+    L.kref_mel_finish.argtypes = [vp, l, l, vp, l, l, vp, l, l, i, i, i, i]
     return L
 
 
@@ -1253,3 +1258,321 @@ def sample_cases(layout, seed=0):
         c.K = 3
         out.append(c)
     return out
+
+
+# ---- log-mel: logmel_kernel, mel_finish_kernel (k_mel.hip) -----------------------------------------------------------------
+# The kernel evaluates, per frame of 400 samples, a LINEAR map that its five tables define -- 16 leaf DFTs of length 25 over the
+# samples l, l + 16, l + 32 .. and four radix-2 levels --, then |X|^2, the fold P[j] += P[400 - j], the filter sum and
+# S > 1e-10 ? log10 S : -10.  The reference below evaluates the same map in fp64 on the exact f32 PCM, table and filter values;
+# that the map IS the DFT (to the accuracy of the f32 tables) is a separate, derived statement (mel_matrix_bound), so the
+# reference cannot share a structural mistake with the kernel unnoticed.
+MEL_NFFT, MEL_HOP, MEL_BINS = 400, 160, 201
+MEL_FLOOR = 1e-10
+MEL_TW_OFF = (0, 25, 75, 175)          # twiddles of the levels with child length 25, 50, 100, 200
+MEL_C = 44.0                           # spectrum error constant, derived in mel_bound
+MEL_LOG10_ULPS = 3.0                   # device log10f, see mel_interval
+MEL_UNDERFLOW = 2.0 ** -110            # see mel_bound
+
+
+def mel_tables():
+    """the product's tables (norma_amd/csrc/mel_host.h through the wrapper library; pure host code, no GPU): a dict of f32
+    arrays hann [400], dft_cos / dft_sin [25][25], tw_cos / tw_sin [375] (tw_sin holds -sin)"""
+    t = {"hann": np.zeros(400, np.float32), "dft_cos": np.zeros((25, 25), np.float32), "dft_sin": np.zeros((25, 25), np.float32),
+         "tw_cos": np.zeros(375, np.float32), "tw_sin": np.zeros(375, np.float32)}
+    check_rc(lib().kref_mel_tables(*(ptr(t[k]) for k in ("hann", "dft_cos", "dft_sin", "tw_cos", "tw_sin"))), "kref_mel_tables")
+    return t
+
+
+def mel_groups(filters):
+    """the product's group scan of filters f32 [n_mel][201] -> i32 [n_mel][2] (first, last + 1 group of four bins with a tap)"""
+    filters = f32(filters)
+    grp = np.zeros((filters.shape[0], 2), np.int32)
+    check_rc(lib().kref_mel_groups(ptr(filters), filters.shape[0], ptr(grp)), "kref_mel_groups")
+    return grp
+
+
+def mel_table_angles():
+    """the f32 angles of the table entries, the expressions of mel_host.h restated in NumPy f32 (every step rounds to f32):
+    (two_pi k) j / 25 for the leaves, (two_pi k) / n for the twiddles, (two_pi i) / 400 for the window"""
+    two_pi = np.float32(np.pi) + np.float32(np.pi)
+    k = np.arange(25, dtype=np.float32)
+    leaf = (two_pi * k)[:, None] * k[None, :] / np.float32(25)
+    tw = np.concatenate([(two_pi * np.arange(h, dtype=np.float32)) / np.float32(2 * h) for h in (25, 50, 100, 200)])
+    hann = (two_pi * np.arange(400, dtype=np.float32)) / np.float32(400)
+    assert leaf.dtype == tw.dtype == hann.dtype == np.float32
+    return leaf, tw, hann
+
+
+def mel_matrix_bound():
+    """max |T - exp(-2 pi i n k / 400)| over the effective 400 x 400 matrix T of the table-defined map, derived.  Entry (k, n) of T
+    is a product of five table entries: one leaf entry cos - i sin of the angle 2 pi k' j / 25 and one twiddle per level (times an
+    exact sign).  An f32 angle is fl(fl(fl(two_pi k) j) / 25): three roundings, and two_pi = 2 fl(pi) carries the rounding of pi
+    (|fl(pi) - pi| / pi = 2.8e-8 <= u), so |angle - theta| <= theta ((1 + u)^4 - 1) (the twiddle angles have a rounding fewer).
+    cos and sin are 1-Lipschitz, so the complex entry moves by at most that; the table entry is then rounded once per component,
+    <= 2^-23 each (test_kref_cpu.py checks exactly this against fp64 cos / sin of the same f32 angle): sqrt 2 * 2^-23.  With
+    per-factor deviations d_i of factors of modulus <= 1 the product deviates by <= prod (1 + d_i) - 1.  theta <= 2 pi 24 24 / 25
+    for the leaves and < pi for the twiddles."""
+    ang = (1 + U32) ** 4 - 1
+    rnd = np.sqrt(2.0) * 2.0 ** -23
+    d_leaf = 2 * np.pi * 24 * 24 / 25 * ang + rnd
+    d_tw = np.pi * ang + rnd
+    return float((1 + d_leaf) * (1 + d_tw) ** 4 - 1)
+
+
+def mel_frames(pcm, n_samples, frames):
+    """the frames pcm_to_mel cuts: x[b][160 f + j], zero at and beyond n_samples[b]; pcm [B][stride] -> fp64 [B][frames][400]"""
+    pcm = d64(pcm)
+    B, stride = pcm.shape
+    idx = MEL_HOP * np.arange(frames)[:, None] + np.arange(MEL_NFFT)[None, :]
+    out = np.zeros((B, frames, MEL_NFFT))
+    for b in range(B):
+        ok = idx < int(n_samples[b])
+        out[b][ok] = pcm[b][idx[ok]]
+    return out
+
+
+def mel_spectrum(xw, t, drop_leaf_term=None, tw_shift_last=0):
+    """the table-defined linear map in fp64: xw [.., 400] (windowed frames) -> complex [.., 400].  Leaf l (0 .. 15) is the
+    25-point DFT of xw[l + 16 j] with the table entries cos - i sin; a level of child length h turns the nodes n and n + nodes
+    of the level below into node n: out[k] = e[k] + w[k] o[k], out[k + h] = e[k] - w[k] o[k], w = tw_cos + i tw_sin.
+    Mutations: drop_leaf_term = j leaves sample j out of every leaf sum; tw_shift_last = s reads the last level's twiddle
+    k + s (mod 200) instead of k."""
+    xw = d64(xw)
+    lead = xw.shape[:-1]
+    W = d64(t["dft_cos"]) - 1j * d64(t["dft_sin"])                     # [k][j]
+    if drop_leaf_term is not None:
+        W = W.copy(); W[:, drop_leaf_term] = 0
+    x = xw.reshape(lead + (25, 16))                                     # [.., j, l]
+    cur = np.einsum("...jl,kj->...lk", x, W)                           # [.., 16 nodes, 25]
+    tw = d64(t["tw_cos"]) + 1j * d64(t["tw_sin"])
+    for lvl, h in enumerate((25, 50, 100, 200)):
+        nodes = cur.shape[-2] // 2
+        w = tw[MEL_TW_OFF[lvl]:MEL_TW_OFF[lvl] + h]
+        if h == 200 and tw_shift_last:
+            w = np.roll(w, -tw_shift_last)
+        e, o = cur[..., :nodes, :], cur[..., nodes:, :]
+        cur = np.concatenate([e + w * o, e - w * o], axis=-1)
+    return cur[..., 0, :]
+
+
+def mel_fold(P, fold=True):
+    """P [.., 400] -> [.., 201]: P[j] + P[400 - j] for j in 1 .. 199 (fold=False: the mutation that omits it)"""
+    out = P[..., :MEL_BINS].copy()
+    if fold:
+        out[..., 1:200] += P[..., :200:-1]
+    return out
+
+
+def mel_power_sums(frames_x, t, filters, **mut):
+    """S [.., n_mel] = filters . fold(|X|^2) in fp64 of frames_x [.., 400] (unwindowed), with X, the windowed frames and the
+    folded power returned as well"""
+    fold = mut.pop("fold", True)
+    xw = d64(frames_x) * d64(t["hann"])
+    X = mel_spectrum(xw, t, **mut)
+    Pf = mel_fold(X.real ** 2 + X.imag ** 2, fold)
+    return Pf @ d64(filters).T, X, xw, Pf
+
+
+def mel_bound(X, xw, Pf, filters, grp, c=MEL_C):
+    """dS per output: how far the kernel's f32 filter sum may lie from the fp64 S.  u = 2^-24, A = sum_j |hann_j x_j| of the
+    frame, g_n = n u / (1 - n u).  logmel_kernel is compiled without contraction, every operation rounds once.
+      spectrum  the windowed sample is one product (1 rounding).  A leaf output is a sequential sum of 25 products: a term meets
+                its product's rounding and at most 24 adds (the first add, to 0, is exact): with the window, 26 roundings, and
+                the table entries have modulus <= 1 (+ 2^-23), so the complex leaf error is <= g_26 A_leaf, A_leaf the sum of
+                |hann x| over the leaf's samples.  A level computes (e + w_re o_re) - w_im o_im per component: two products and
+                two adds, at most 3 roundings on the way of any term, on |e| + |w_re o_re| + |w_im o_im| <= |e| + |o| per
+                component, so <= sqrt 2 g_3 (|e| + |o|) as a complex number, and it passes the children's errors on with factors
+                1 and |w| <= 1 + 2^-23.  |e| + |o| <= (1 + d) (A_e + A_o) with d = mel_matrix_bound, and A_e + A_o = A_node, so by
+                induction the error at the root is <= (26 + 4 * 3 sqrt 2) u A = 42.97 u A to first order; the second-order
+                terms (g_n against n u, the 2^-23 and d factors) are below 1e-4 relative, and c = 44 covers them:
+                |X^_k - X_k| <= D = c u A.
+      power     | |X^|^2 - |X|^2 | <= 2 |X| D + D^2, and re^2 + im^2 in f32 adds g_2 (|X| + D)^2: dP.
+      fold      one add: dPf_j = (dP_j + dP_400-j)(1 + u) + u (P_j + P_400-j) for 1 <= j <= 199, dP_j for j = 0, 200.
+      filters   sum += ((p0 f0 + p1 f1) + p2 f2) + p3 f3 over the G = g1 - g0 <= 50 groups of the filter, then the bin-200 term:
+                a term meets its product, at most 3 adds inside its group, at most G adds of the running sum and the last
+                add: n = G + 5 <= 55 roundings; all terms are >= 0 (checked), so the sum is off by <= g_n sum f (Pf + dPf),
+                on top of sum f dPf.
+      underflow an f32 result below 2^-126 may lose its low bits or be flushed: <= 2^-126 absolute per operation, < 2^10
+                operations carry into one output with factors <= 2 -- MEL_UNDERFLOW = 2^-110 covers it with room to spare.
+    X [.., 400] complex, xw [.., 400], Pf [.., 201] from mel_power_sums; returns dS [.., n_mel]."""
+    f = d64(filters)
+    assert (f >= 0).all()
+    A = np.abs(xw).sum(axis=-1, keepdims=True)
+    D = c * U32 * A
+    aX = np.abs(X)
+    g2 = 2 * U32 / (1 - 2 * U32)
+    dP = 2 * aX * D + D * D + g2 * (aX + D) ** 2
+    dPf = dP[..., :MEL_BINS].copy()
+    dPf[..., 1:200] = (dP[..., 1:200] + dP[..., :200:-1]) * (1 + U32) + U32 * Pf[..., 1:200]
+    n = (np.asarray(grp)[:, 1] - np.asarray(grp)[:, 0] + 5).astype(np.float64)
+    gn = n * U32 / (1 - n * U32)
+    return dPf @ f.T + gn * ((Pf + dPf) @ f.T) + MEL_UNDERFLOW
+
+
+def mel_interval(S, dS):
+    """[lo, hi] for the kernel's S^ > 1e-10 ? log10f(S^) : -10 given |S^ - S| <= dS: log10 max(S -+ dS, 1e-10) -+ e, no case
+    excluded.  e is the error of the device log10f: the ROCm device library (OCML) documents that its f32 functions meet the
+    OpenCL accuracy requirements, which allow log10 3 ulp; HIP's math API page lists 2 ulp for log10f.  The larger figure is
+    taken; it is DOCUMENTED, NOT MEASURED.  An ulp of a result v is <= 2^-23 |v|.  (The kernel compares with the f32 constant
+    1e-10f = 1e-10 (1 + 1.3e-8): a sum between the two gives -10 where the formula gives up to -10 + 6e-9, well inside e.)"""
+    lo = np.log10(np.maximum(S - dS, MEL_FLOOR))
+    hi = np.log10(np.maximum(S + dS, MEL_FLOOR))
+    e = MEL_LOG10_ULPS * 2.0 ** -23 * np.maximum(np.abs(lo), np.abs(hi))
+    return lo - e, hi + e
+
+
+def mel_reference(pcm, n_samples, frames, t, filters, grp):
+    """(lo, hi, ref) [B][n_mel][frames] (the kernel's mel32 layout) for launch_logmel_grp on pcm [B][stride]"""
+    S, X, xw, Pf = mel_power_sums(mel_frames(pcm, n_samples, frames), t, filters)
+    dS = mel_bound(X, xw, Pf, filters, grp)
+    lo, hi = mel_interval(S, dS)
+    tr = lambda a: np.ascontiguousarray(np.swapaxes(a, -1, -2))
+    return tr(lo), tr(hi), tr(np.log10(np.maximum(S, MEL_FLOOR)))
+
+
+def mel_inside(got, lo, hi, what, ref=None):
+    """every value finite and inside its interval; returns the largest |got - ref| / half-width (a measurement; ref defaults to
+    the interval's middle)"""
+    g = d64(got)
+    bad = ~(np.isfinite(g) & (g >= lo) & (g <= hi))
+    if bad.any():
+        i = tuple(int(v) for v in np.argwhere(bad)[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} of {g.size} outside their interval; first at {i}: got {g[i]!r}, "
+                             f"interval [{lo[i]!r}, {hi[i]!r}]")
+    return float(np.max(np.abs(g - (0.5 * (lo + hi) if ref is None else ref)) / (0.5 * (hi - lo))))
+
+
+def mel_emulate_f32(frames_x, t, filters, grp):
+    """NumPy f32 emulation of logmel_kernel's arithmetic, operation for operation and in its order (every NumPy f32 operation
+    rounds once, as the uncontracted kernel does): frames_x f32 [F][400] -> (X^ complex64-as-two-f32 [F][400][2], S^ f32
+    [F][n_mel]).  The CPU check that the bound is sound; it is not the reference."""
+    x = f32(frames_x)
+    F = x.shape[0]
+    s_in = t["hann"][None, :] * x
+    c, s = t["dft_cos"], t["dft_sin"]
+    xin = s_in.reshape(F, 25, 16)                                        # [F][j][leaf]
+    re = np.zeros((F, 16, 25), np.float32); im = np.zeros((F, 16, 25), np.float32)
+    for j in range(25):
+        v = xin[:, j, :, None]                                           # [F][leaf][1]
+        re = re + v * c[None, None, :, j]
+        im = im - v * s[None, None, :, j]
+    for lvl, h in enumerate((25, 50, 100, 200)):
+        nodes = re.shape[1] // 2
+        wr = t["tw_cos"][MEL_TW_OFF[lvl]:MEL_TW_OFF[lvl] + h]
+        wi = t["tw_sin"][MEL_TW_OFF[lvl]:MEL_TW_OFF[lvl] + h]
+        er, ei, orr, oi = re[:, :nodes], im[:, :nodes], re[:, nodes:], im[:, nodes:]
+        re = np.concatenate([er + wr * orr - wi * oi, er - wr * orr + wi * oi], axis=-1)
+        im = np.concatenate([ei + wr * oi + wi * orr, ei - wr * oi - wi * orr], axis=-1)
+    re, im = re[:, 0], im[:, 0]
+    pw = re * re + im * im
+    pf = pw[:, :MEL_BINS].copy()
+    pf[:, 1:200] = pw[:, 1:200] + pw[:, :200:-1]
+    f = f32(filters)
+    S = np.zeros((F, f.shape[0]), np.float32)
+    for m in range(f.shape[0]):
+        acc = np.zeros(F, np.float32)
+        for g in range(int(grp[m][0]), int(grp[m][1])):
+            k = 4 * g
+            acc = acc + (pf[:, k] * f[m, k] + pf[:, k + 1] * f[m, k + 1] + pf[:, k + 2] * f[m, k + 2] + pf[:, k + 3] * f[m, k + 3])
+        S[:, m] = acc + pf[:, 200] * f[m, 200]
+    assert S.dtype == re.dtype == np.float32
+    return np.stack([re, im], axis=-1), S
+
+
+def mel_log_f32(S):
+    """S^ > 1e-10f ? log10f(S^) : -10 in NumPy f32 (its log10 stands in for the device's within the 3 ulp of mel_interval)"""
+    S = f32(S)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(S > np.float32(1e-10), np.log10(np.maximum(S, np.float32(1e-30))), np.float32(-10.0)).astype(np.float32)
+
+
+def mel_impulse_expected(offsets, t, filters):
+    """a frame whose only non-zero sample is a 1 at offset o: the exact DFT has |X_k| = hann_o for every k, so
+    S_m = hann_o^2 sum_k w_k f[m][k] with w = 2 for the folded bins 1 .. 199 and 1 for bins 0 and 200 -- no FFT involved.
+    The table-defined map has |T| within d = mel_matrix_bound of 1, so S is off by <= (1 + d)^2 - 1 relative; the kernel adds
+    only zeros in its accumulations: one rounding in the leaf product, per level two products and an add on the one non-zero
+    child (<= 3 sqrt 2 u as a complex number), so |X^|^2 carries <= 2 (1 + 12 sqrt 2) u < 36 u; power 2 u, fold u, and the
+    filter sum its g_n <= 55 u: 100 u covers them.  Returns (S, dS) [len(offsets)][n_mel]."""
+    f = d64(filters)
+    w = np.full(MEL_BINS, 2.0); w[0] = w[200] = 1.0
+    S = (d64(t["hann"])[np.asarray(offsets)] ** 2)[:, None] * (f @ w)[None, :]
+    rel = (1 + mel_matrix_bound()) ** 2 - 1 + 100 * U32
+    return S, rel * S + MEL_UNDERFLOW
+
+
+def f32_ordered(v):
+    """the order-preserving u32 encoding of an f32 that logmel_kernel feeds to atomicMax (k_mel.hip f32_ordered)"""
+    u = f32(v).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def logmel(pcm, n_samples, frames, t, filters, grp, mel32=None, mel_off=0, chunk_max=None, cm_off=0):
+    """one launch_logmel_grp through the wrapper library; mel32 / chunk_max default to fresh buffers of exactly the window
+    (mel32 NaN-filled, chunk_max zero as the product's memset leaves it).  Returns (mel32, chunk_max) as given, written."""
+    pcm, filters = f32(pcm), f32(filters)
+    B, stride = pcm.shape
+    n_mel = filters.shape[0]
+    ns = np.ascontiguousarray(n_samples, dtype=np.int32)
+    grp = np.ascontiguousarray(grp, dtype=np.int32)
+    if mel32 is None:
+        mel32 = np.full(B * n_mel * frames, np.nan, np.float32)
+    if chunk_max is None:
+        chunk_max = np.zeros(B, np.uint32)
+    rc = lib().kref_logmel(ptr(pcm), stride, ptr(ns), B, ptr(t["hann"]), ptr(t["dft_cos"]), ptr(t["dft_sin"]), ptr(t["tw_cos"]),
+                           ptr(t["tw_sin"]), ptr(filters), ptr(grp), n_mel, frames, ptr(mel32), mel_off, mel32.size, ptr(chunk_max),
+                           cm_off, chunk_max.size)
+    check_rc(rc, f"launch_logmel_grp B={B} n_mel={n_mel} frames={frames}")
+    return mel32, chunk_max
+
+
+def mel_finish(mel32, mel_off, chunk_max, cm_off, img, img_off, B, n_mel, frames, normalise):
+    """one launch_mel_finish_ex through the wrapper library on windows of the three buffers (written in place)"""
+    rc = lib().kref_mel_finish(ptr(mel32), mel_off, mel32.size, ptr(chunk_max), cm_off, chunk_max.size, ptr(img), img_off, img.size,
+                               B, n_mel, frames, int(normalise))
+    check_rc(rc, f"launch_mel_finish_ex B={B} n_mel={n_mel} frames={frames} normalise={normalise}")
+
+
+# the signal families of tests/test_gpu_mel_ref.py; tests/test_kref_cpu.py runs the f32 emulation over the same data
+MEL_FRAMES = (1, 15, 16, 17, 33)        # a lone wave, dead waves (frames % 16 != 0), a full workgroup, one and two workgroups more
+MEL_FAMILIES = ("noise-0.1", "noise-3e-4", "burst", "dc", "square")
+MEL_BROADBAND = ("noise-0.1", "noise-3e-4")
+MEL_CANARY = 1.0e4                      # what the samples at and beyond n_samples hold: a read past the length shows
+
+
+def mel_full_length(frames):
+    return (frames - 1) * MEL_HOP + MEL_NFFT
+
+
+def mel_ragged_lengths(frames, B):
+    """n_samples of the ragged noise case: B = 1 the full clip; B = 3 the full clip, 16 * 160 + 1 (one sample into frame 16) and
+    399 (frame 0 one sample short); B = 4 those and a length that ends inside the last live frame"""
+    full = mel_full_length(frames)
+    return [full, 16 * MEL_HOP + 1, 399, full - 200][:B]
+
+
+def mel_case(family, frames, B, seed=0):
+    """(pcm f32 [B][stride], n_samples i32 [B]) of one family; stride exceeds the longest clip, and every sample at or beyond a
+    clip's n_samples holds MEL_CANARY"""
+    rng = np.random.default_rng(zlib_key("mel", family, frames, B, seed))
+    full = mel_full_length(frames)
+    stride = max(full, 16 * MEL_HOP + 1) + 67
+    ns = np.full(B, full, dtype=np.int32)
+    i = np.arange(stride)
+    if family == "noise-0.1":
+        pcm = 0.1 * rng.standard_normal((B, stride))
+        ns = np.asarray(mel_ragged_lengths(frames, B), dtype=np.int32)
+    elif family == "noise-3e-4":
+        pcm = 3e-4 * rng.standard_normal((B, stride))
+    elif family == "burst":            # a 0.5 tone over the first frame, then noise 94 dB below it
+        pcm = 1e-5 * rng.standard_normal((B, stride))
+        pcm[:, :MEL_NFFT] = 0.5 * np.sin(2 * np.pi * (440.0 + 300.0 * np.arange(B)[:, None]) * i[None, :MEL_NFFT] / 16000.0)
+    elif family == "dc":
+        pcm = np.full((B, stride), 0.7)
+    elif family == "square":           # full scale, period 50 + 14 b samples
+        pcm = np.stack([np.where((i // (25 + 7 * b)) % 2 == 0, 1.0, -1.0) for b in range(B)])
+    else:
+        raise ValueError(family)
+    pcm = f32(pcm)
+    for b in range(B):
+        pcm[b, ns[b]:] = MEL_CANARY
+    return pcm, ns

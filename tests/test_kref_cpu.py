@@ -575,3 +575,134 @@ def test_token_margins_flag_near_ties_and_accept_exact_ties():
     l[200] = np.nextafter(np.float32(5.0), np.float32(0))
     s = K.step_ref(l, [tk.sot, tk.en, tk.transcribe, tk.zero_sec, 11], 1, tk.zero_sec, sup, t, K.PATHS["logit_step"])
     assert s.next == 100 and not s.decided and s.ok == {100, 200}
+
+
+# ---- log-mel (k_mel.hip): the product's tables, the effective DFT matrix, the bound against an f32 emulation ------------------
+def _mel_setup(n_mel):
+    from norma_amd import assets_io
+    _make_wrapper_library()
+    t = K.mel_tables()
+    filt = assets_io.mel_filters(n_mel)
+    return t, filt, K.mel_groups(filt)
+
+
+def test_mel_tables_are_one_rounding_from_fp64_of_their_f32_angles():
+    """kref_mel_tables answers without a GPU with the product's tables (mel_host.h); every cos / sin entry lies within 2^-23 of
+    fp64 cos / sin of the same f32 angle, the window within 2^-23 of 0.5 (1 - cos) (cosf, the subtraction, an exact halving)"""
+    t, filt, grp = _mel_setup(80)
+    leaf, tw, hann = K.mel_table_angles()
+    ulp = 2.0 ** -23
+    assert np.abs(K.d64(t["dft_cos"]) - np.cos(K.d64(leaf))).max() <= ulp
+    assert np.abs(K.d64(t["dft_sin"]) - np.sin(K.d64(leaf))).max() <= ulp
+    assert np.abs(K.d64(t["tw_cos"]) - np.cos(K.d64(tw))).max() <= ulp
+    assert np.abs(K.d64(t["tw_sin"]) + np.sin(K.d64(tw))).max() <= ulp
+    assert np.abs(K.d64(t["hann"]) - 0.5 * (1 - np.cos(K.d64(hann)))).max() <= ulp
+    assert np.abs(K.d64(t["dft_cos"])).max() <= 1 and np.abs(K.d64(t["tw_sin"])).max() <= 1
+    assert t["hann"][0] == 0 and t["tw_cos"][0] == 1 and t["tw_sin"][0] == 0
+    # the f32 angles reach 145 rad: the tables are off the IDEAL angles by about 1e-5, which is part of the contract
+    k = np.arange(25)
+    off = np.abs(K.d64(t["dft_cos"]) - np.cos(2 * np.pi * np.outer(k, k) / 25)).max()
+    assert 1e-6 < off < K.mel_matrix_bound()
+
+
+@pytest.mark.parametrize("n_mel", [80, 128])
+def test_mel_groups_are_the_tap_ranges(n_mel):
+    t, filt, grp = _mel_setup(n_mel)
+    assert grp.shape == (n_mel, 2) and (filt >= 0).all()
+    for m in range(n_mel):
+        nz = np.flatnonzero(filt[m, :200])
+        want = (nz[0] // 4, nz[-1] // 4 + 1) if nz.size else (0, 0)
+        assert tuple(grp[m]) == want, m
+    assert (grp[:, 1] - grp[:, 0]).max() <= 50
+    assert tuple(K.mel_groups(np.zeros((2, 201), np.float32))[1]) == (0, 0)
+
+
+def test_mel_effective_matrix_is_the_dft_within_the_derived_distance():
+    """the recursion on the 400 unit impulses gives the effective matrix T of the table-defined map; it must be the DFT within
+    mel_matrix_bound (derived from the roundings of the angles and the entries, not from this measurement)"""
+    t, filt, grp = _mel_setup(80)
+    T = K.mel_spectrum(np.eye(400), t)                   # T[n][k]: input n -> bin k
+    n = np.arange(400)
+    exact = np.exp(-2j * np.pi * np.outer(n, n) / 400)
+    dev = np.abs(T - exact).max()
+    print(f"max |T - exp(-2 pi i n k / 400)| = {dev:.3e} (derived limit {K.mel_matrix_bound():.3e})")
+    assert dev <= K.mel_matrix_bound() < 5e-5
+    # the map is what the reference applies: a random frame through mel_spectrum equals x . T
+    x = _r(40).standard_normal((3, 400))
+    assert np.abs(K.mel_spectrum(x, t) - x @ T).max() < 1e-10
+    # and the whole operation reference against a naive evaluation with numpy's FFT, up to the tables' distance from it
+    S, X, xw, Pf = K.mel_power_sums(x, t, filt)
+    P = np.abs(np.fft.fft(x * K.d64(t["hann"]), axis=-1)) ** 2
+    naive = np.stack([[sum(filt[m, k] * (P[f, k] + (P[f, 400 - k] if 1 <= k <= 199 else 0)) for k in range(201)) for m in range(80)]
+                      for f in range(3)])
+    assert np.abs(S - naive).max() <= 3 * K.mel_matrix_bound() * np.abs(naive).max()
+
+
+def _mel_mutations(fx, t, filt):
+    return {"leaf term dropped": K.mel_power_sums(fx, t, filt, drop_leaf_term=24)[0],
+            "last-level twiddle off by one": K.mel_power_sums(fx, t, filt, tw_shift_last=1)[0],
+            "fold omitted": K.mel_power_sums(fx, t, filt, fold=False)[0]}
+
+
+@pytest.mark.parametrize("n_mel", [80, 128])
+def test_mel_f32_emulation_stays_inside_the_bound_and_bugs_leave_it(n_mel):
+    """the NumPy f32 emulation of logmel_kernel's arithmetic on every family of the GPU test: its spectrum within c u A, its
+    sums within dS, its logs inside the interval.  On the broadband families at least 99 % of the intervals are narrower than
+    1e-3 in log10, and three plausible bugs leave dS by more than 2x (kref.discriminates) on the same data."""
+    t, filt, grp = _mel_setup(n_mel)
+    worst_x = worst_s = 0.0
+    for family in K.MEL_FAMILIES:
+        narrow, total, left = 0, 0, {}
+        for frames in K.MEL_FRAMES:
+            pcm, ns = K.mel_case(family, frames, 4 if family == "noise-0.1" else 3)
+            fx = K.mel_frames(pcm, ns, frames).reshape(-1, 400)
+            assert np.abs(fx).max() < K.MEL_CANARY                            # no canary inside a frame
+            S, X, xw, Pf = K.mel_power_sums(fx, t, filt)
+            dS = K.mel_bound(X, xw, Pf, filt, grp)
+            lo, hi = K.mel_interval(S, dS)
+            X32, S32 = K.mel_emulate_f32(K.f32(fx), t, filt, grp)
+            A = np.abs(xw).sum(axis=-1, keepdims=True)
+            xerr = np.abs((K.d64(X32[..., 0]) + 1j * K.d64(X32[..., 1])) - X)
+            assert (xerr <= K.MEL_C * K.U32 * A).all(), (family, frames)
+            assert (np.abs(K.d64(S32) - S) <= dS).all(), (family, frames)
+            live = A[:, 0] > 0
+            if live.any():
+                worst_x = max(worst_x, float((xerr[live] / (K.U32 * A[live])).max()))
+                worst_s = max(worst_s, float((np.abs(K.d64(S32) - S) / dS).max()))
+            K.mel_inside(K.mel_log_f32(S32), lo, hi, f"f32 emulation {family} frames={frames}")
+            narrow += int(((hi - lo) < 1e-3).sum()); total += lo.size
+            if family in K.MEL_BROADBAND:
+                for k, v in K.discriminates(S, dS, _mel_mutations(fx, t, filt)).items():
+                    left[k] = max(left.get(k, 0.0), v)
+                if frames == 33:                                               # how many outputs each bug moves out, as information
+                    for k, m in _mel_mutations(fx, t, filt).items():
+                        print(f"  {family} n_mel={n_mel}: {k}: {100 * (np.abs(m - S) > 2 * dS).mean():.1f} % of the outputs leave 2 dS")
+        print(f"{family} n_mel={n_mel}: {100 * narrow / total:.2f} % of the intervals narrower than 1e-3")
+        if family in K.MEL_BROADBAND:
+            assert narrow >= 0.99 * total, (family, narrow, total)
+    print(f"n_mel={n_mel}: f32 emulation spectrum error up to {worst_x:.2f} u A, |S32 - S64| / dS up to {worst_s:.3f}")
+    # the conditions on the data that the GPU cases rely on: the quiet noise is negative throughout and (all but the odd output
+    # of a narrow filter) above the floor; the burst's quiet frames lie more than 8 below its maximum
+    pcm, ns = K.mel_case("noise-3e-4", 33, 3)
+    lo, hi, ref = K.mel_reference(pcm, ns, 33, t, filt, grp)
+    assert (hi < 0).all() and (lo > -10).mean() > 0.99
+    pcm, ns = K.mel_case("burst", 33, 3)
+    lo, hi, ref = K.mel_reference(pcm, ns, 33, t, filt, grp)
+    assert (ref.max(axis=(1, 2)) > 0).all() and ((hi < ref.max(axis=(1, 2), keepdims=True) - 8.01).mean(axis=(1, 2)) > 0.5).all()
+
+
+def test_mel_impulse_identity_and_ordered_encoding():
+    """one unit sample at offset o: the fp64 table map gives hann_o^2 sum_k w_k f[m][k] within the stated relative distance; the
+    ordered encoding is monotone and keeps -10, negative and positive values apart"""
+    t, filt, grp = _mel_setup(80)
+    offs = np.arange(400)
+    S, dS = K.mel_impulse_expected(offs, t, filt)
+    got = K.mel_power_sums(np.eye(400), t, filt)[0]
+    assert (np.abs(got - S) <= dS).all()
+    assert S[0].max() == 0 and S[200].min() > 0
+    # an impulse that misses the fold loses about half of every interior weight: far outside
+    assert (np.abs(K.mel_power_sums(np.eye(400), t, filt, fold=False)[0] - S)[1:] > 100 * dS[1:]).all()
+    v = np.array([-np.inf, -10.0, -9.999999, -1.0, -0.0, 0.0, 1e-30, 0.5, 3.25, np.inf], np.float32)
+    enc = K.f32_ordered(v).astype(np.int64)
+    assert (np.diff(enc) >= 0).all() and (np.diff(enc)[[0, 1, 2, 3, 5, 6, 7, 8]] > 0).all()
+    assert enc[1] == 0x3EDFFFFF and enc[7] == 0xBF000000

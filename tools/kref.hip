@@ -1,4 +1,4 @@
-// kref.hip -- test-only C entry points onto the shipped launchers of nh_kernels.h (tests/kref.py, tests/test_gpu_kernel_ref.py).
+// kref.hip -- test-only C entry points onto the shipped launchers of nh_kernels.h (tests/kref.py, tests/test_gpu_kernel_ref.py, tests/test_gpu_mel_ref.py).
 // Linked against the library's own objects (norma_amd/csrc/build/k_*.o): the kernels under test are the product's, not copies.
 // Every entry point takes host buffers (sizes in bytes), allocates device copies, copies every buffer in -- outputs too, so a
 // test can see what a kernel must leave alone (done rows, cache positions it does not own) --, launches on a stream of its own,
@@ -541,6 +541,82 @@ int kref_align_dtw_rows(const float *M, int n, int S, int max_rows, const int32_
     b.out(first, df, (size_t)n * ldo * 4);
     b.out(last, dl, (size_t)n * ldo * 4);
     return launched ? (int)b.err : -1;
+}
+
+}  // extern "C"
+
+// ---- log-mel (k_mel.hip) ----------------------------------------------------------------------------------------------------
+#include "../norma_amd/csrc/mel_host.h"
+
+extern "C" {
+
+// the product's tables (mel_host.h, what nh_model.hip uploads): hann [400], dft_cos / dft_sin [25][25], tw_cos / tw_sin [375].
+// Pure host code: no GPU needed.
+int kref_mel_tables(float *hann, float *dft_cos, float *dft_sin, float *tw_cos, float *tw_sin) {
+    if (!hann || !dft_cos || !dft_sin || !tw_cos || !tw_sin) return -1;
+    mel_host_tables(hann, dft_cos, dft_sin, tw_cos, tw_sin);
+    return 0;
+}
+
+// the group scan of nh_set_mel_filters: filters [n_mel][201] -> grp i32 [n_mel][2].  Pure host code.
+int kref_mel_groups(const float *filters, int n_mel, int32_t *grp) {
+    if (!filters || !grp || n_mel < 1) return -1;
+    mel_host_groups(filters, n_mel, grp);
+    return 0;
+}
+
+// launch_logmel_grp: pcm f32 [B][stride], n_samples i32 [B] (each in [0, stride]), the five tables, filters [n_mel][201],
+// grp [n_mel][2] -> mel32 f32 [B][n_mel][frames] and chunk_max u32 [B].  Both outputs are windows of larger host buffers,
+// copied in and back whole: the launch gets mel32 + mel_off of mel_total floats and chunk_max + cm_off of cm_total words, so a
+// test sees what lies before and after the window.  `frames` is free (the product passes 1500 or 3000).
+int kref_logmel(const float *pcm, long stride, const int32_t *n_samples, int B, const float *hann, const float *dft_cos,
+                const float *dft_sin, const float *tw_cos, const float *tw_sin, const float *filters, const int32_t *grp, int n_mel,
+                int frames, float *mel32, long mel_off, long mel_total, unsigned *chunk_max, long cm_off, long cm_total) {
+    // refuse what would read or write out of bounds
+    if (B < 1 || frames < 1 || n_mel < 1 || stride < 1 || !pcm || !n_samples || !filters || !grp || !mel32 || !chunk_max) return -1;
+    if (mel_off < 0 || mel_off + (long)B * n_mel * frames > mel_total || cm_off < 0 || cm_off + B > cm_total) return -1;
+    for (int b = 0; b < B; b++) if (n_samples[b] < 0 || n_samples[b] > stride) return -1;
+    for (int m = 0; m < n_mel; m++) if (grp[2 * m] < 0 || grp[2 * m] > grp[2 * m + 1] || grp[2 * m + 1] > 50) return -1;
+    Bufs b;
+    Stream st;
+    const float *dp = b.in<float>(pcm, (size_t)B * stride * 4);
+    const int32_t *dn = b.in<int32_t>(n_samples, (size_t)B * 4), *dg = b.in<int32_t>(grp, (size_t)n_mel * 2 * 4);
+    MelTables t{};
+    t.hann = b.in<float>(hann, MEL_N_HANN * 4);
+    t.dft_cos = b.in<float>(dft_cos, MEL_N_DFT * 4); t.dft_sin = b.in<float>(dft_sin, MEL_N_DFT * 4);
+    t.tw_cos = b.in<float>(tw_cos, MEL_N_TW * 4); t.tw_sin = b.in<float>(tw_sin, MEL_N_TW * 4);
+    t.filters = b.in<float>(filters, (size_t)n_mel * 201 * 4);
+    float *dm = b.in<float>(mel32, (size_t)mel_total * 4);
+    unsigned *dc = b.in<unsigned>(chunk_max, (size_t)cm_total * 4);
+    KREF_CHECK(b);
+    if (!t.hann || !t.dft_cos || !t.dft_sin || !t.tw_cos || !t.tw_sin) return -1;
+    launch_logmel_grp(dp, dn, stride, t, dg, n_mel, frames, dm + mel_off, dc + cm_off, B, st.s);
+    if (hipError_t e = st.finish()) return (int)e;
+    b.out(mel32, dm, (size_t)mel_total * 4);
+    b.out(chunk_max, dc, (size_t)cm_total * 4);
+    return (int)b.err;
+}
+
+// launch_mel_finish_ex: mel32 f32 [B][n_mel][frames] (normalised in place when `normalise`), chunk_max u32 [B] -> img fp16
+// [B][frames + 2][NH_MELP].  All three are windows (offset, total, in elements) of host buffers copied in and back whole.
+int kref_mel_finish(float *mel32, long mel_off, long mel_total, unsigned *chunk_max, long cm_off, long cm_total, void *img,
+                    long img_off, long img_total, int B, int n_mel, int frames, int normalise) {
+    if (B < 1 || frames < 1 || n_mel < 1 || n_mel > NH_MELP || !mel32 || !chunk_max || !img) return -1;
+    if (mel_off < 0 || mel_off + (long)B * n_mel * frames > mel_total || cm_off < 0 || cm_off + B > cm_total || img_off < 0 ||
+        img_off + (long)B * (frames + 2) * NH_MELP > img_total)
+        return -1;
+    Bufs b;
+    Stream st;
+    float *dm = b.in<float>(mel32, (size_t)mel_total * 4);
+    unsigned *dc = b.in<unsigned>(chunk_max, (size_t)cm_total * 4);
+    half_t *di = b.in<half_t>(img, (size_t)img_total * 2);
+    KREF_CHECK(b);
+    launch_mel_finish_ex(dm + mel_off, dc + cm_off, di + img_off, B, n_mel, frames, normalise, st.s);
+    if (hipError_t e = st.finish()) return (int)e;
+    b.out(mel32, dm, (size_t)mel_total * 4);
+    b.out(chunk_max, dc, (size_t)cm_total * 4);
+    b.out(img, di, (size_t)img_total * 2);
+    return (int)b.err;
 }
 
 }  // extern "C"
