@@ -18,7 +18,7 @@
 // The q/k pre-scaling by dh^-1/4 each and the change of base to exp2 are carried by q itself
 // (q arrives multiplied by dh^-1/2 log2(e), GemmParams::seg0_scale).  1500 keys are not a multiple of 64: the last
 // tile masks keys >= S; V^T pad is zero.
-#include "nh_kernels.h"
+#include "k_device.h"
 
 // tools/abench links several builds of this file in one process (A/B of kernel variants on one box): the symbol names are macros
 #ifndef ENC_ATTN_KERNEL
@@ -34,8 +34,6 @@
 #define NTHR (64 * ENC_ATTN_WAVES)
 #define NSLOT (NTHR >= 512 ? 1 : 512 / NTHR)   // 16-byte staging slots per thread per tile (a tile is 512 slots; threads >= 512 stage nothing)
 #define TILE_B 8192        // bytes per K or V^T tile
-
-__device__ __forceinline__ int swap23(int x) { return (x & ~12) | ((x & 4) << 1) | ((x & 8) >> 1); }
 
 #ifndef ENC_ATTN_MINWAVES
 #ifdef ENC_ATTN_PIPE

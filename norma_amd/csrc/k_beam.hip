@@ -6,7 +6,7 @@
 //                        finished records
 //   beam_reorder_kernel  self-attention caches of every layer: row r takes positions 0 .. p of row parent[r]
 // Rows are beam-major: hypothesis j of clip b is row j * B + b, so a clip's rows are touched by its own workgroup alone.
-#include "nh_kernels.h"
+#include "k_device.h"
 
 constexpr int BSEL_T = 1024;                       // threads of a selection workgroup: one row each
 constexpr int BSEL_LT = NH_MAX_VOCAB / BSEL_T;     // logits a thread holds in registers
@@ -15,29 +15,6 @@ constexpr int BCAND = NH_MAX_BEAMS * BK1;          // ... and per clip
 static_assert(BSEL_LT * BSEL_T == NH_MAX_VOCAB, "beam_select_kernel holds a whole row in registers");
 
 struct BeamRed { float f[BSEL_T / 64]; int i[BSEL_T / 64]; float of; int oi; };
-
-__device__ __forceinline__ float bsel_max(float v, BeamRed &sm) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm.f[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = sm.f[0];
-    for (int i = 1; i < BSEL_T / 64; i++) r = fmaxf(r, sm.f[i]);
-    return r;
-}
-__device__ __forceinline__ float bsel_sum(float v, BeamRed &sm) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm.f[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = sm.f[0];
-    for (int i = 1; i < BSEL_T / 64; i++) r += sm.f[i];
-    return r;
-}
-// larger value, then larger index (the reference's last-maximum rule); i < 0: nothing
-__device__ __forceinline__ void bsel_better(float &v, int &i, float v2, int i2) {
-    if (i2 >= 0 && (i < 0 || v2 > v || (v2 == v && i2 > i))) { v = v2; i = i2; }
-}
 
 // One workgroup per row.  The row's V logits live in registers (BSEL_LT per thread, clamped unconditional loads: the pad
 // columns V .. ldl-1 are never read).  Softmax statistics first; a row whose last token is text learns its rule from them
@@ -70,7 +47,7 @@ __global__ __launch_bounds__(BSEL_T) void beam_select_kernel(const float *__rest
     float mx = -INFINITY;
 #pragma unroll
     for (int u = 0; u < BSEL_LT; u++) if (tid + BSEL_T * u < V) mx = fmaxf(mx, lv[u]);
-    const float m = bsel_max(mx, sm);
+    const float m = block_max<BSEL_T / 64>(mx, sm.f);
     float se = 0.f, ts = 0.f, tsinf = 0.f, mt = -INFINITY;
 #pragma unroll
     for (int u = 0; u < BSEL_LT; u++) {
@@ -82,29 +59,21 @@ __global__ __launch_bounds__(BSEL_T) void beam_select_kernel(const float *__rest
         if (i > NT) { ts += e; if (sup) tsinf = 1.f; }   // p + (-inf) inside the summed slice: the sum is -inf
         else if (i < NT && !sup) mt = fmaxf(mt, lv[u]);  // max_text of model.rs:267-270 runs over i < no_timestamps
     }
-    se = bsel_sum(se, sm);
-    int rule;
-    if (!have_last) rule = 0;                                               // first generated token: the window
-    else if (l1 > NT) rule = (n >= 2 && l2 >= tk.eot) ? 1 : 2;              // text only / timestamps only
-    else {                                                                  // last token is text: decided by the masses
-        ts = bsel_sum(ts, sm);
-        tsinf = bsel_max(tsinf, sm);
-        mt = bsel_max(mt, sm);
+    se = block_sum<BSEL_T / 64>(se, sm.f);
+    int rule = rule_from_state(have_last, n, l1, l2, tk);
+    if (rule == RULE_BY_MASS) {                                             // last token is text: decided by the masses
+        ts = block_sum<BSEL_T / 64>(ts, sm.f);
+        tsinf = block_max<BSEL_T / 64>(tsinf, sm.f);
+        mt = block_max<BSEL_T / 64>(mt, sm.f);
         const float sum_ts = tsinf > 0.f ? -INFINITY : ts / se;
         const float max_text = mt > -INFINITY ? expf(mt - m) / se : -INFINITY;
-        rule = (sum_ts >= max_text) ? 2 : 3;
+        rule = (sum_ts >= max_text) ? RULE_NON_TS : RULE_PAST;
     }
 #pragma unroll
     for (int u = 0; u < BSEL_LT; u++) {
         const int i = tid + BSEL_T * u;
         const bool sup = (supbits >> u) & 1ull;
-        bool mk;
-        if (i >= V) mk = true;
-        else if (rule == 0) mk = (i < tk.zero_sec || i > tk.one_sec);          // model.rs:336-337
-        else if (rule == 1) mk = sup || i > NT;                                // :256-259
-        else if (rule == 2) mk = sup || i <= NT || i <= last_ts;               // :216-223
-        else mk = sup || (i > NT && i <= last_ts);                             // :225-243
-        if (mk) lv[u] = -INFINITY;
+        if (i >= V || rule_masks(rule, i, sup, tk, last_ts)) lv[u] = -INFINITY;
     }
     // K1 rounds: the best candidate strictly after the one before in (value desc, index desc)
     float pv = INFINITY; int pi = 0x7fffffff, cnt = 0;
@@ -114,14 +83,14 @@ __global__ __launch_bounds__(BSEL_T) void beam_select_kernel(const float *__rest
         for (int u = 0; u < BSEL_LT; u++) {
             const int i = tid + BSEL_T * u;
             const float l = lv[u];
-            if (l > -INFINITY && (l < pv || (l == pv && i < pi))) bsel_better(bv, bi, l, i);
+            if (l > -INFINITY && (l < pv || (l == pv && i < pi))) better(bv, bi, l, i);
         }
-        for (int o = 32; o > 0; o >>= 1) bsel_better(bv, bi, __shfl_xor(bv, o), __shfl_xor(bi, o));
+        for (int o = 32; o > 0; o >>= 1) better(bv, bi, __shfl_xor(bv, o), __shfl_xor(bi, o));
         __syncthreads();
         if ((tid & 63) == 0) { sm.f[tid >> 6] = bv; sm.i[tid >> 6] = bi; }
         __syncthreads();
         if (tid == 0) {
-            for (int w = 1; w < BSEL_T / 64; w++) bsel_better(bv, bi, sm.f[w], sm.i[w]);
+            for (int w = 1; w < BSEL_T / 64; w++) better(bv, bi, sm.f[w], sm.i[w]);
             sm.of = bv; sm.oi = bi;
             if (bi >= 0) { cand_tok[r * BK1 + k] = bi; cand_q[r * BK1 + k] = expf(bv - m) / se; }
         }

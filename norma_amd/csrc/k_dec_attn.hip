@@ -5,7 +5,7 @@
 //   dec_attn_kernel      qkv_attention of the decoder blocks (causal self-attention over the cache,
 //                        cross-attention over the K/V cached at flush time)
 // and holds the absorbed cross-attention prototype (xabs_*, NH_OPT_ABSORBED_XATTN 1 and 2).
-#include "nh_kernels.h"
+#include "k_device.h"
 
 // ---------------------------------------------------------------------------------------------------
 // decoder attention, one query row per (b, h): 4 waves split the keys, inside a wave 8 key slots x
@@ -218,7 +218,6 @@ void launch_xabs_attention(const half_t *q, const half_t *Wkv, const float *bkv,
 // which makes accumulator registers 0-7 / 8-15 of a lane the tile's keys 8 hh + 0..7 / 16 + 8 hh + 0..7, i.e. P is the B operand.
 #define XA_KT 32                 // keys per tile
 #define XA_LEAVES 4              // key ranges per row
-__device__ __forceinline__ int xa_swap23(int x) { return (x & ~12) | ((x & 4) << 1) | ((x & 8) >> 1); }
 __device__ __forceinline__ int xa_off(int panel, int row, int ch) { return panel * 8192 + 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
 
 // WkT[c][r] = Wk[r][c] (d x d): built once per model beside the tile-major repacks, so that u = Wk_h^T q reads 128 contiguous
@@ -287,7 +286,7 @@ __global__ __launch_bounds__(512) void xabs_main_kernel(const half_t *__restrict
     constexpr int NPAN = D / 128;
     u32x4 stg[NPAN];
     const int skk = tid >> 4, sch = tid & 15;
-    const int lds_st = xa_off(0, xa_swap23(skk), sch);
+    const int lds_st = xa_off(0, swap23(skk), sch);
     auto gload = [&](int t) {
         int key = k0 + t * XA_KT + skk; if (key >= S) key = S - 1;
         const half_t *gp = xr + (long)key * D + 8 * sch;

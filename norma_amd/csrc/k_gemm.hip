@@ -9,9 +9,8 @@
 //
 // Tile: 128 (M) x 128 (N) x 64 (K) per 256-thread workgroup (4 waves as 2 x 2, 64 x 64 per wave,
 // v_mfma_f32_16x16x32_f16).  Both operands are K-contiguous, so each lane's fragment is one 16-byte
-// LDS read.  LDS image: [128 rows][8 chunks of 16 B], chunk' = chunk ^ ((row >> 1) & 7) (conflict-free
-// ds_read_b128, MI355X LDS banking), double buffered (64 KiB).  Global->LDS is global_load_lds_dwordx4
-// (LDS-DMA, no VGPR round trip, no ds_write): the loads of tile t+1 are issued before the MFMAs of tile t.
+// LDS read.  The loop, its LDS image (64 KiB) and its LDS-DMA staging are tile128_mainloop (mfma_tile128.h),
+// which transcript scoring (k_score.hip) runs too.
 //
 // Orientation: by default the weight rows are the MFMA "A" operand, so a lane's 4 accumulator
 // registers are 4 consecutive output COLUMNS of one row -> 8-byte fp16 / 16-byte f32 row-major
@@ -20,12 +19,11 @@
 
 #include <atomic>
 
-#include "nh_kernels.h"
+#include "mfma_tile128.h"
 
 #define BM 128
 #define BN 128
 #define BK 64
-#define TILE_BYTES (BM * BK * 2)  // 16 KiB per operand tile
 
 __device__ __forceinline__ float gelu_tanh_f(float v) { return gelu_tanh_fast(v); }
 
@@ -35,79 +33,12 @@ __device__ __forceinline__ const half_t *a_row_ptr(const GemmParams &p, int m) {
     return p.A + (long)b * p.a_bstride + (long)r * p.lda;
 }
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
-
+// the 128 x 128 x 64 loop of mfma_tile128.h on tile (m0, n0): activation rows through the row map, tail rows clamped
+// (a_row_ptr); weight rows n0 .. n0 + 127 as they are (N is a multiple of BN)
 template <bool SWAP>
-__device__ __forceinline__ void gemm_mainloop(const GemmParams &p, char *smem, int m0, int n0,
-                                              f32x4 (&acc)[4][4]) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = w >> 1, wn = w & 1;
-    // staging map: slot s = tid + 256 i (i = 0..3): row = s >> 3, chunk' = s & 7 (tid & 7 for all i).
-    // One wave-instruction covers 64 consecutive slots = 1 KiB of the LDS image, in lane order -- exactly
-    // the (wave-uniform base + lane * 16) destination of global_load_lds; the swizzle lives in the SOURCE.
-    const int cq = tid & 7;
-    const half_t *ag[4], *wg[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        int row = (tid >> 3) + 32 * i;
-        int c = cq ^ ((row >> 1) & 7);
-        ag[i] = a_row_ptr(p, m0 + row) + c * 8;
-        int n = n0 + row;  // N is a multiple of BN
-        wg[i] = p.W + (long)n * p.K + c * 8;
-    }
-    const int nt = p.K / BK;
-    // fragment read offsets (bytes within a tile): row r, chunk 4*ks + (lane>>4), swizzled
-    const int fr = lane & 15, fq = lane >> 4;
-    int offA[4], offB[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        int rowA = wm * 64 + 16 * j + fr;  // activation rows (m)
-        int rowB = wn * 64 + 16 * j + fr;  // weight rows (n)
-        offA[j] = rowA * 128 + ((fq ^ ((rowA >> 1) & 7)) << 4);
-        offB[j] = rowB * 128 + ((fq ^ ((rowB >> 1) & 7)) << 4);
-    }
-    const int wbase = __builtin_amdgcn_readfirstlane(w) * 1024;  // this wave's 1 KiB run inside each 4 KiB group
-    auto stage = [&](int buf, int t) {
-        char *la = smem + buf * 2 * TILE_BYTES + wbase, *lb = la + TILE_BYTES;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            __builtin_amdgcn_global_load_lds((gbl_void *)(ag[i] + (long)t * BK), (lds_void *)(la + 4096 * i), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gbl_void *)(wg[i] + (long)t * BK), (lds_void *)(lb + 4096 * i), 16, 0, 0);
-        }
-    };
-    stage(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int cur = 0;
-    for (int t = 0; t < nt; t++) {
-        const bool more = (t + 1 < nt);
-        if (more) stage(cur ^ 1, t + 1);  // all waves left buf[cur^1] at the barrier that ended iteration t-1
-        const char *ta = smem + cur * 2 * TILE_BYTES, *tb = ta + TILE_BYTES;
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++) {
-            half8 fa[4], fb[4];
-            // chunk index 4*ks + fq; the xor only touches the low 3 bits, and (4*ks) flips bit 2:
-            // (4ks + fq) ^ g == (fq ^ g) ^ (4ks) because fq < 4 -> byte offset ^ (ks << 6)
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                fa[j] = *reinterpret_cast<const half8 *>(ta + (offA[j] ^ (ks << 6)));
-                fb[j] = *reinterpret_cast<const half8 *>(tb + (offB[j] ^ (ks << 6)));
-            }
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    if (SWAP)  // D[row = n (weights)][col = m (activations)]
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb[i], fa[j], acc[i][j], 0, 0, 0);
-                    else       // D[row = m][col = n]
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[j], fb[i], acc[i][j], 0, 0, 0);
-                }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA for tile t+1 has landed
-        __syncthreads();
-        cur ^= 1;
-    }
+__device__ __forceinline__ void gemm_mainloop(const GemmParams &p, char *smem, int m0, int n0, f32x4 (&acc)[4][4]) {
+    tile128_mainloop<SWAP>([&](int row) { return a_row_ptr(p, m0 + row); },
+                           [&](int row) { return p.W + (long)(n0 + row) * p.K; }, p.K / BK, smem, acc);
 }
 
 __device__ __forceinline__ long out_row(const GemmParams &p, int m) {
@@ -116,16 +47,11 @@ __device__ __forceinline__ long out_row(const GemmParams &p, int m) {
 }
 
 __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(GemmParams p) {
-    __shared__ __attribute__((aligned(16))) char smem[4 * TILE_BYTES];
+    __shared__ __attribute__((aligned(16))) char smem[T128_LDS];
     // XCD-aware tile order: blocks b and b+8 share an XCD (L2); give each XCD a contiguous run of
     // tiles so the N-tiles of one M-panel (same A rows) are neighbours in one L2.
     const int ntn = p.N / BN, ntm = (p.M + BM - 1) / BM;
-    const int nwg = ntn * ntm;
-    int bid = blockIdx.x;
-    {
-        int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int bid = xcd_contiguous(blockIdx.x, ntn * ntm);
     const int tm = bid / ntn, tn = bid - tm * ntn;
     const int m0 = tm * BM, n0 = tn * BN;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -389,13 +315,7 @@ __device__ __forceinline__ void pp_main(const GemmParams &p, char *smem, char *w
 // N-tiles: the A panels (4 x 256 x K) stay in that XCD's 4 MiB L2 for the whole N sweep and each streamed W tile is
 // shared by 4 workgroups (PMC: W was re-fetched once per M-panel from the Infinity Cache with a plain M-major order).
 __device__ __forceinline__ void pp_tile(int vb, int ntn, int ntm, int &tm, int &tn) {
-    const int nwg = ntn * ntm;
-    const int xcd = vb & 7, q = nwg >> 3, r = nwg & 7;
-    const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
-    const int per_group = G2_GM * ntn;
-    const int g = bid / per_group, rr = bid - g * per_group;
-    const int gm = min(G2_GM, ntm - g * G2_GM);  // the last group may hold fewer M-panels
-    tn = rr / gm; tm = g * G2_GM + (rr - tn * gm);
+    grouped_tile(xcd_contiguous(vb, ntn * ntm), ntn, ntm, G2_GM, tm, tn);
 }
 
 template <int EPI>

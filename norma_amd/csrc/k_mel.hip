@@ -19,21 +19,13 @@
 // another context) ran on the same CU (DESIGN.md 5 "A neighbour on the CU", tests/test_gpu_load.py).  With four 256-thread
 // workgroups of 37 KB each a CU had room for such a neighbour; one workgroup holding all of the LDS has the same sixteen waves per
 // CU and no LDS-using neighbour, whoever it might be.
-#include "nh_kernels.h"
+#include "k_device.h"
 #include <atomic>
 
 #define N_FFT 400
 #define HOP 160
 #define FRAMES_PER_WG 16
 #define MEL_LDS_BYTES (160 * 1024)
-
-__device__ __forceinline__ unsigned f32_ordered(float f) {
-    unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float f32_from_ordered(unsigned u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
 
 struct MelArgs {
     const float *pcm; const int32_t *n_samples; long stride;

@@ -7,22 +7,19 @@
 //   score_merge_kernel    one wave per row: the tiles' (maximum, sum) pairs merged in ascending tile order, then
 //                         (double)(l[target] - m) - log((double)se)
 //
-// The main loop is the 128 x 128 x 64 loop of k_gemm.hip (gemm_mainloop<true>: LDS-DMA into a swizzled double buffer, every
-// fragment one ds_read_b128, the 32-deep k-steps of an output added in ascending order into one accumulator), so a logit has
-// the bits that GEMM would give it and does not depend on M.  What differs is the guard on the B side: E holds exactly V rows
-// (51864 .. 51866 are no multiple of 128), so the rows of the last column tile are clamped to V - 1 the way the row tail is
-// clamped to the last row, and their columns are kept out of every statistic.
-#include "nh_kernels.h"
+// The main loop is the 128 x 128 x 64 loop of k_gemm.hip, the same function (tile128_mainloop<true>, mfma_tile128.h: LDS-DMA
+// into a swizzled double buffer, every fragment one ds_read_b128, the 32-deep k-steps of an output added in ascending order
+// into one accumulator), so a logit has the bits that GEMM would give it and does not depend on M.  What differs is the guard
+// on the B side: E holds exactly V rows (51864 .. 51866 are no multiple of 128), so the rows of the last column tile are
+// clamped to V - 1 the way the row tail is clamped to the last row, and their columns are kept out of every statistic.
+#include "k_device.h"
+#include "mfma_tile128.h"
 
 #define SC_BM 128
 #define SC_BN 128
 #define SC_BK 64
-#define SC_TILE_BYTES (SC_BM * SC_BK * 2)   // 16 KiB per operand tile
-#define SC_LDS (4 * SC_TILE_BYTES)          // two buffers of an A and a B tile; the epilogue's 2 KiB live in the first
+#define SC_LDS T128_LDS                     // two buffers of an A and a B tile; the epilogue's 2 KiB live in the first
 #define SC_GM 8                             // row panels whose column tiles are neighbours in the tile order
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
 
 struct ScoreParams {
     const half_t *xn;        // [M][d] final LayerNorm rows
@@ -41,15 +38,8 @@ __global__ __launch_bounds__(256) void score_logits_kernel(ScoreParams p) {
     // SC_GM row panels, column tile outer / row panel inner: the 8 workgroups that follow each other on an XCD read ONE
     // 128-row slab of the embedding (320 KB at d = 1280, 133 MB in all) and 8 row panels that stay in that L2 for the sweep.
     // Nothing below depends on it: any bijection of workgroups onto tiles computes the same.
-    int bid = blockIdx.x;
-    {
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
-    const int per_group = SC_GM * ntn;
-    const int g = bid / per_group, rr = bid - g * per_group;
-    const int gm = min(SC_GM, ntm - g * SC_GM);   // the last group may hold fewer row panels
-    const int tn = rr / gm, tm = g * SC_GM + (rr - tn * gm);
+    int tm, tn;
+    grouped_tile(xcd_contiguous(blockIdx.x, nwg), ntn, ntm, SC_GM, tm, tn);
     const int m0 = p.row0 + tm * SC_BM, n0 = tn * SC_BN;
     const int m_end = p.row0 + p.rows;            // rows at or past it are loaded from the last row and never stored
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -62,63 +52,9 @@ __global__ __launch_bounds__(256) void score_logits_kernel(ScoreParams p) {
 #pragma unroll
         for (int j = 0; j < 4; j++) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    {
-        // staging map of k_gemm.hip: slot s = tid + 256 i: row = s >> 3, chunk' = s & 7; the swizzle lives in the SOURCE
-        const int cq = tid & 7;
-        const half_t *ag[4], *wg[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int row = (tid >> 3) + 32 * i;
-            const int c = cq ^ ((row >> 1) & 7);
-            const int m = min(m0 + row, m_end - 1);   // clamped, not branched around: rows >= M are never read
-            const int n = min(n0 + row, p.V - 1);     // ... and neither are embedding rows >= V
-            ag[i] = p.xn + (long)m * p.d + c * 8;
-            wg[i] = p.E + (long)n * p.d + c * 8;
-        }
-        const int nt = p.d / SC_BK;
-        int offA[4], offB[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int rowA = wm * 64 + 16 * j + fr;   // activation rows (m)
-            const int rowB = wn * 64 + 16 * j + fr;   // embedding rows (v)
-            offA[j] = rowA * 128 + ((fq ^ ((rowA >> 1) & 7)) << 4);
-            offB[j] = rowB * 128 + ((fq ^ ((rowB >> 1) & 7)) << 4);
-        }
-        const int wbase = __builtin_amdgcn_readfirstlane(w) * 1024;
-        auto stage = [&](int buf, int t) {
-            char *la = smem + buf * 2 * SC_TILE_BYTES + wbase, *lb = la + SC_TILE_BYTES;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                __builtin_amdgcn_global_load_lds((gbl_void *)(ag[i] + (long)t * SC_BK), (lds_void *)(la + 4096 * i), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds((gbl_void *)(wg[i] + (long)t * SC_BK), (lds_void *)(lb + 4096 * i), 16, 0, 0);
-            }
-        };
-        stage(0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        int cur = 0;
-        for (int t = 0; t < nt; t++) {
-            if (t + 1 < nt) stage(cur ^ 1, t + 1);   // all waves left buf[cur ^ 1] at the barrier that ended iteration t - 1
-            const char *ta = smem + cur * 2 * SC_TILE_BYTES, *tb = ta + SC_TILE_BYTES;
-#pragma unroll
-            for (int ks = 0; ks < 2; ks++) {
-                half8 fa[4], fb[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    fa[j] = *reinterpret_cast<const half8 *>(ta + (offA[j] ^ (ks << 6)));
-                    fb[j] = *reinterpret_cast<const half8 *>(tb + (offB[j] ^ (ks << 6)));
-                }
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-#pragma unroll
-                    for (int j = 0; j < 4; j++)   // D[row = v][col = m]
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb[i], fa[j], acc[i][j], 0, 0, 0);
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA for tile t + 1 has landed
-            __syncthreads();
-            cur ^= 1;
-        }
-    }
+    // clamped, not branched around: rows >= M are never read, and neither are embedding rows >= V.  D[row = v][col = m]
+    tile128_mainloop<true>([&](int row) { return p.xn + (long)min(m0 + row, m_end - 1) * p.d; },
+                           [&](int row) { return p.E + (long)min(n0 + row, p.V - 1) * p.d; }, p.d / SC_BK, smem, acc);
 
     // ---- epilogue: acc[i][j][r] is column v = n0 + 64 wn + 16 i + 4 fq + r of row m = m0 + 64 wm + 16 j + fr.  A row's 128
     // columns sit in 4 lanes (fq) of each of the 2 waves wn: registers, two shuffles, one exchange through LDS.  Every order
@@ -167,13 +103,6 @@ __global__ __launch_bounds__(256) void score_logits_kernel(ScoreParams p) {
     }
 }
 
-// (m, s) <- the pair of the union of two column sets (merge_ms of k_token.hip without the timestamp mass)
-__device__ __forceinline__ void score_merge(float &m, float &s, float m2, float s2) {
-    const float mn = fmaxf(m, m2);
-    const float f1 = (m == -INFINITY) ? 0.f : __expf(m - mn), f2 = (m2 == -INFINITY) ? 0.f : __expf(m2 - mn);
-    s = s * f1 + s2 * f2; m = mn;
-}
-
 // one wave per row of the panel: lane-strided pass over the row's tiles in ascending order, the xor tree, and the double
 // tail.  out[(m / T) * ldo + m % T + off]: row m = b T + p of nh_score is entry p + 1 of clip b.
 __global__ __launch_bounds__(256) void score_merge_kernel(const float *__restrict__ part, const float *__restrict__ tlogit,
@@ -187,10 +116,10 @@ __global__ __launch_bounds__(256) void score_merge_kernel(const float *__restric
     float mx = -INFINITY, se = 0.f;
     for (int t = lane; t < ntn; t += 64) {
         const f32x2 v = pp[t];
-        score_merge(mx, se, v[0], v[1]);
+        merge_pair(mx, se, v[0], v[1]);
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) score_merge(mx, se, __shfl_xor(mx, o), __shfl_xor(se, o));
+    for (int o = 32; o > 0; o >>= 1) merge_pair(mx, se, __shfl_xor(mx, o), __shfl_xor(se, o));
     if (lane == 0) out[(long)(m / T) * ldo + (m % T) + off] = (float)((double)(tlogit[m] - mx) - log((double)se));
 }
 

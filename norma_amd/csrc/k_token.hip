@@ -7,7 +7,7 @@
 //   pool_admit_kernel, pool_retry_kernel           a pool row starts a clip / decodes its clip again, sampled
 //   lang_detect_kernel, pool_lang_detect_kernel    Model::detect_language (:194-210), batched / inside a pool step
 //   rules_only_kernel, sample_rules_kernel         parity views: the rules (and one draw) on a given probability vector
-#include "nh_kernels.h"
+#include "k_device.h"
 
 // ---------------------------------------------------------------------------------------------------
 // logit processor
@@ -18,28 +18,10 @@ __device__ __forceinline__ int total_key(float f) {
     return b ^ (int)(((unsigned)(b >> 31)) >> 1);
 }
 
-struct BlockRed {
+struct BlockRed {   // slots of block_max (fa) and block_sum (fb) of k_device.h, and of block_argmax
     float fa[16], fb[16]; int ia[16], ib[16];
 };
 
-__device__ __forceinline__ float block_max(float v, BlockRed &sm) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm.fa[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = sm.fa[0];
-    for (int i = 1; i < (int)(blockDim.x >> 6); i++) r = fmaxf(r, sm.fa[i]);
-    return r;
-}
-__device__ __forceinline__ float block_sum(float v, BlockRed &sm) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm.fb[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = sm.fb[0];
-    for (int i = 1; i < (int)(blockDim.x >> 6); i++) r += sm.fb[i];
-    return r;
-}
 // argmax under total_cmp, last maximum wins
 __device__ __forceinline__ void block_argmax(int key, int idx, BlockRed &sm, int &okey, int &oidx) {
     for (int o = 32; o > 0; o >>= 1) {
@@ -57,29 +39,18 @@ __device__ __forceinline__ void block_argmax(int key, int idx, BlockRed &sm, int
     okey = key; oidx = idx;
 }
 
-enum { RULE_FIRST = 0, RULE_SUP_TS = 1, RULE_NON_TS = 2, RULE_PAST = 3 };
-
 // masked probability of index i: p + (0 | -inf) exactly as the chain of broadcast_adds produces it
 __device__ __forceinline__ float masked_value(float p, int i, int rule, const uint8_t *sup, const RuleTokens &tk,
                                               int last_ts) {
-    bool m;
-    if (rule == RULE_FIRST) m = (i < tk.zero_sec || i > tk.one_sec);                    // model.rs:336-337
-    else if (rule == RULE_SUP_TS) m = sup[i] || i > tk.no_timestamps;                   // :256-259
-    else if (rule == RULE_NON_TS) m = sup[i] || i <= tk.no_timestamps || i <= last_ts;  // :216-223
-    else m = sup[i] || (i > tk.no_timestamps && i <= last_ts);                          // :225-243
-    return m ? p + (-INFINITY) : p;
+    return rule_masks(rule, i, rule != RULE_FIRST && sup[i], tk, last_ts) ? p + (-INFINITY) : p;
 }
 
 // which of the four mask chains of model.rs:331-338 / :245-277 applies.  probs(i) gives the soft-maxed probability.
 template <typename ProbFn>
 __device__ __forceinline__ int rules_decide(ProbFn probs, int V, const int32_t *tokens, int n, int have_last,
                                             const uint8_t *sup, const RuleTokens &tk, BlockRed &sm) {
-    if (!have_last) return RULE_FIRST;
-    int l = tokens[n - 1];
-    if (l > tk.no_timestamps) {
-        int sl = n >= 2 ? tokens[n - 2] : -1;
-        return (n >= 2 && sl >= tk.eot) ? RULE_SUP_TS : RULE_NON_TS;
-    }
+    const int rule = rule_from_state(have_last, n, tokens[n >= 1 ? n - 1 : 0], tokens[n >= 2 ? n - 2 : 0], tk);
+    if (rule != RULE_BY_MASS) return rule;
     float ps = 0.f, pm = -INFINITY;  // model.rs:263-270 on the suppress-masked probabilities
     for (int i = threadIdx.x; i < V; i += blockDim.x) {
         float p = probs(i);
@@ -87,8 +58,8 @@ __device__ __forceinline__ int rules_decide(ProbFn probs, int V, const int32_t *
         if (i > tk.no_timestamps) ps += pv;
         else if (i < tk.no_timestamps) pm = fmaxf(pm, pv);
     }
-    float sum_ts = block_sum(ps, sm);
-    float max_text = block_max(pm, sm);
+    float sum_ts = block_sum(ps, sm.fb);
+    float max_text = block_max(pm, sm.fa);
     return (sum_ts >= max_text) ? RULE_NON_TS : RULE_PAST;
 }
 
@@ -152,7 +123,7 @@ __device__ __forceinline__ int sample_masked(QFn q, int V, float inv_t, unsigned
     const int tid = threadIdx.x;
     float mx = -INFINITY;
     for (int i = tid; i < V; i += 1024) mx = fmaxf(mx, q(i));
-    const float qmax = block_max(mx, sh.red);
+    const float qmax = block_max(mx, sh.red.fa);
     if (!(qmax > -INFINITY)) { qout = 0.f; return -1; }
     const int CH = (V + 1023) / 1024;
     double sc = 0.0;
@@ -195,10 +166,10 @@ __global__ __launch_bounds__(1024) void sample_step_kernel(const float *__restri
     const float *lg = logits + (long)b * ldl;
     float mx = -INFINITY;
     for (int i = tid; i < V; i += 1024) mx = fmaxf(mx, lg[i]);
-    const float m = block_max(mx, sh.red);
+    const float m = block_max(mx, sh.red.fa);
     float se = 0.f;
     for (int i = tid; i < V; i += 1024) se += expf(lg[i] - m);
-    se = block_sum(se, sh.red);
+    se = block_sum(se, sh.red.fb);
     auto probs = [&](int i) { return expf(lg[i] - m) / se; };  // model.rs:331
     int32_t *toks = s.tokens + (long)b * ctx;
     const int n = s.n_tokens[b], have_last = s.have_last[b], last_ts = s.last_ts[b];
@@ -245,10 +216,10 @@ __global__ __launch_bounds__(1024) void pool_sample_step_kernel(const float *__r
     const float *lg = logits + (long)b * ldl;
     float mx = -INFINITY;
     for (int i = tid; i < V; i += 1024) mx = fmaxf(mx, lg[i]);
-    const float m = block_max(mx, sh.red);
+    const float m = block_max(mx, sh.red.fa);
     float se = 0.f;
     for (int i = tid; i < V; i += 1024) se += expf(lg[i] - m);
-    se = block_sum(se, sh.red);
+    se = block_sum(se, sh.red.fb);
     auto probs = [&](int i) { return expf(lg[i] - m) / se; };  // model.rs:331
     int32_t *toks = s.tokens + (long)b * ctx;
     const int n = s.n_tokens[b], have_last = s.have_last[b], last_ts = s.last_ts[b];
@@ -310,18 +281,15 @@ void launch_sample_rules(const float *probs_in, int32_t *token_out, const int32_
 constexpr int LMAX = 32;  // logits per thread: ceil(51866 / 8 / 256) = 26 for the largest Whisper vocabulary
 static_assert(NH_MAX_VOCAB == LSPLIT * 256 * LMAX, "logit_step_kernel holds exactly NH_MAX_VOCAB logits in registers");
 
-// what logit_step_kernel knows about a sequence BEFORE its sweep.  The first three are the RULE_* of the same name;
-// STEP_TEXT (the last token is text) becomes RULE_NON_TS or RULE_PAST only when the last workgroup compares sum_ts with
-// max_text, so RULE_PAST has no counterpart here; STEP_PROBE is mode 0, which selects no token.
-enum { STEP_FIRST = RULE_FIRST, STEP_SUP_TS = RULE_SUP_TS, STEP_NON_TS = RULE_NON_TS, STEP_TEXT = 3, STEP_PROBE = 4 };
+// what logit_step_kernel knows about a sequence BEFORE its sweep: what rule_from_state (k_device.h) says.  The first three
+// are the RULE_* of the same name; STEP_TEXT (the last token is text) becomes RULE_NON_TS or RULE_PAST only when the last
+// workgroup compares sum_ts with max_text, so RULE_PAST has no counterpart here; STEP_PROBE is mode 0, which selects no token.
+enum { STEP_FIRST = RULE_FIRST, STEP_SUP_TS = RULE_SUP_TS, STEP_NON_TS = RULE_NON_TS, STEP_TEXT = RULE_BY_MASS, STEP_PROBE = 5 };
 
 __device__ __forceinline__ void merge_ms(float &m, float &s, float &ts, float m2, float s2, float ts2) {
-    float mn = fmaxf(m, m2);
-    float f1 = (m == -INFINITY) ? 0.f : __expf(m - mn), f2 = (m2 == -INFINITY) ? 0.f : __expf(m2 - mn);
-    s = s * f1 + s2 * f2; ts = ts * f1 + ts2 * f2; m = mn;
-}
-__device__ __forceinline__ void better(float &v, int &i, float v2, int i2) {  // larger value, then larger index
-    if (i2 >= 0 && (i < 0 || v2 > v || (v2 == v && i2 > i))) { v = v2; i = i2; }
+    float f1, f2;  // the timestamp mass is a sum against the same maxima
+    merge_pair(m, s, m2, s2, f1, f2);
+    ts = ts * f1 + ts2 * f2;
 }
 
 __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict__ logits, int V, int ldl,
@@ -369,11 +337,7 @@ __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict
     }
     const int NT = tk.no_timestamps;
     // candidate sets: A = allowed non-timestamp tokens (or the first-token window), B = allowed timestamps
-    int kind;
-    if (mode == 0) kind = STEP_PROBE;
-    else if (!have_last) kind = STEP_FIRST;
-    else if (l1 > NT) kind = (n >= 2 && l2 >= tk.eot) ? STEP_SUP_TS : STEP_NON_TS;
-    else kind = STEP_TEXT;
+    const int kind = mode == 0 ? STEP_PROBE : rule_from_state(have_last, n, l1, l2, tk);
     float m = -INFINITY, se = 0.f, ts = 0.f, tsinf = 0.f, av = -INFINITY, bv = -INFINITY;
     int ai = -1, bi = -1;
     // slice maximum first, then one exp per element against it (the slice lives in registers)

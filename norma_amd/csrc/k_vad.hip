@@ -12,19 +12,12 @@
 // scans delivers.  All frame indices fit an int (F <= 2^31 / 160).
 #include <math.h>
 
-#include "nh_kernels.h"
+#include "k_device.h"
 
 extern __shared__ int vad_lds[];   // every kernel here that keeps data in LDS across a barrier is launched with its CU's whole LDS
 
 // ---- order statistics ---------------------------------------------------------------------------------------------------
-// ascending in the float's order: negative values with all bits flipped, the others with the sign bit set
-__device__ __forceinline__ unsigned vad_key(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float vad_unkey(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
+// (the monotone key is f32_ordered / f32_from_ordered of k_device.h)
 
 #define VAD_HIST_LOADS (NH_VAD_HIST_TILE / 256)   // frames per thread, all loaded before the first is counted
 
@@ -48,7 +41,7 @@ __global__ __launch_bounds__(256) void vad_hist_kernel(const float *E, long long
     }
 #pragma unroll
     for (int u = 0; u < VAD_HIST_LOADS; u++) {
-        const unsigned k = vad_key(v[u]), d = (k >> shift) & 255u;
+        const unsigned k = f32_ordered(v[u]), d = (k >> shift) & 255u;
         const bool in = f0 + tid + 256 * u < F && v[u] == v[u];
         if (in && (k & above) == p0) atomicAdd(&h[d], 1u);
         if (in && parted && (k & above) == p1) atomicAdd(&h[256 + d], 1u);
@@ -121,7 +114,7 @@ __global__ __launch_bounds__(256) void vad_pick_kernel(VadSelect *sel, int shift
     sel->n_valid = n;
     if (k0 != k1) sel->parted = 1;
     if (shift == 0) {
-        const float q_lo = n > 0 ? vad_unkey(k0) : 0.0f, q_hi = n > 0 ? vad_unkey(k1) : 0.0f;
+        const float q_lo = n > 0 ? f32_from_ordered(k0) : 0.0f, q_hi = n > 0 ? f32_from_ordered(k1) : 0.0f;
         const float a = lv.lo_ratio * q_lo;
         const float b = lv.hi_ratio * q_hi;
         const float r = (b < a) ? b : a;

@@ -139,31 +139,22 @@ extern "C" int nh_align(nh_ctx *ctx, const int32_t *tokens, const int32_t *n_tok
     if (ctx->pool.rows > 0) return ctx->fail(NH_ERR_STATE, "nh_align: the context runs a decode pool (nh_pool_begin)");
     if (!ctx->have_enc) return ctx->fail(NH_ERR_STATE, "nh_align: call nh_encode first");
     if (ctx->opt_absorbed) return ctx->fail(NH_ERR_STATE, "nh_align: NH_OPT_ABSORBED_XATTN keeps no cross K cache to align against");
-    const int B = ctx->cur_batch, C = ctx->c.max_target_positions, V = ctx->c.vocab_size, S = ctx->S, P = prompt_len;
+    const int B = ctx->cur_batch, C = ctx->c.max_target_positions, S = ctx->S, P = prompt_len;
     AlignHeadSet hs;
     if (int rc = align_head_set(ctx, "nh_align", heads, n_heads, 1, hs)) return rc;
     if (P < 1 || P >= C) return ctx->fail(NH_ERR_INVALID, "nh_align: prompt_len out of range");
     int maxn = 0;
-    std::vector<int32_t> toks((size_t)B * C, 0), keys(B);
+    std::vector<int32_t> keys(B);
     for (int b = 0; b < B; b++) {
         const int n = n_tokens[b], nk = n_keys ? n_keys[b] : S;
         if (n <= P || n > C) return ctx->fail(NH_ERR_INVALID, "nh_align: n_tokens must lie in (prompt_len, max_target_positions]");
         if (nk < 1 || nk > S) return ctx->fail(NH_ERR_INVALID, "nh_align: n_keys must lie in [1, S]");
-        for (int i = 0; i < n; i++) {
-            const int t = tokens[(size_t)b * C + i];
-            if (t < 0 || t >= V) return ctx->fail(NH_ERR_INVALID, "nh_align: token id outside the vocabulary");
-            toks[(size_t)b * C + i] = t;
-        }
         keys[b] = nk;
         maxn = std::max(maxn, n);
     }
-    hipSetDevice(ctx->dev);
-    if (int rc = ensure_decoder_repack(ctx)) return rc;
+    // the pass below overwrites the tokens and self K/V the last decode left, and the queries it kept
+    if (int rc = stage_given_tokens(ctx, "nh_align", tokens, C, 0, n_tokens)) return rc;
     if (int rc = align_q_buffer(ctx, "nh_align", hs.A)) return rc;
-    ctx->live.lock_valid = false;   // the pass below overwrites the tokens and self K/V the last decode left, and the queries it kept
-    HIPCHK(hipStreamWaitEvent(ctx->st, ctx->enc_done, 0));
-    HIPCHK(hipMemcpyAsync(ctx->ds.tokens, toks.data(), toks.size() * 4, hipMemcpyHostToDevice, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));   // host buffer of this frame
     // stage 1: the teacher-forced pass, every position enqueued back to back
     for (int pos = 0; pos <= maxn - 2; pos++) decoder_step(ctx, pos, nullptr, false, false, &hs);
     return align_run(ctx, "nh_align", hs, P, B, std::vector<int32_t>(n_tokens, n_tokens + B), keys, nullptr, out_first, out_last);

@@ -4,18 +4,15 @@
 // a step -- candidates, merge, reordering of hypothesis state and self-attention caches -- is k_beam.hip.
 #include "nh_ctx.h"
 
-static size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
-
 // the beam buffers, made by the first call that needs them
 static int ensure_beam_buffers(nh_ctx *ctx) {
     BeamState &bs = ctx->beam;
     if (bs.buf.p) return NH_OK;
     const size_t MB = ctx->B, C = ctx->c.max_target_positions, K1 = NH_MAX_BEAMS + 1, NL = ctx->kv.size();
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += up16(bytes); return o; };
-    const size_t o_par = take(MB * 4), o_ft = take(MB * C * 4), o_fn = take(MB * 4), o_fs = take(MB * 8), o_fc = take(MB * 4);
-    const size_t o_ct = take(MB * K1 * 4), o_cq = take(MB * K1 * 4), o_cn = take(MB * 4), o_tab = take(2 * NL * sizeof(half_t *));
-    if (int rc = bs.buf.reserve(ctx, off, "beam search")) return rc;
+    Carve cv;
+    const size_t o_par = cv.take(MB * 4), o_ft = cv.take(MB * C * 4), o_fn = cv.take(MB * 4), o_fs = cv.take(MB * 8), o_fc = cv.take(MB * 4);
+    const size_t o_ct = cv.take(MB * K1 * 4), o_cq = cv.take(MB * K1 * 4), o_cn = cv.take(MB * 4), o_tab = cv.take(2 * NL * sizeof(half_t *));
+    if (int rc = bs.buf.reserve(ctx, cv.off, "beam search")) return rc;
     char *p = static_cast<char *>(bs.buf.p);
     bs.bb.parent = reinterpret_cast<int32_t *>(p + o_par);
     bs.bb.fin_tokens = reinterpret_cast<int32_t *>(p + o_ft);
@@ -28,7 +25,7 @@ static int ensure_beam_buffers(nh_ctx *ctx) {
     bs.caches = reinterpret_cast<half_t **>(p + o_tab);
     std::vector<half_t *> tab;
     for (const KvCache &kv : ctx->kv) { tab.push_back(kv.sk); tab.push_back(kv.sv); }
-    HIPCHK(hipMemsetAsync(bs.buf.p, 0, off, ctx->st));
+    HIPCHK(hipMemsetAsync(bs.buf.p, 0, cv.off, ctx->st));
     HIPCHK(hipMemcpyAsync(bs.caches, tab.data(), tab.size() * sizeof(half_t *), hipMemcpyHostToDevice, ctx->st));
     HIPCHK(hipStreamSynchronize(ctx->st));   // tab is a local
     return NH_OK;
@@ -111,14 +108,9 @@ extern "C" int nh_decode_beam(nh_ctx *ctx, int beam_size, int32_t *out_tokens, n
     HIPCHK(hipEventRecord(ctx->ev[6], ctx->st));
     HIPCHK(hipGetLastError());
     // results: the clip rows' probe and exit, the finished records
-    std::vector<int32_t> toks((size_t)B * C), nt(B), done(B);
-    std::vector<double> slp(B), nsp(B);
+    HostDecodeState h;
     bs.fin_tokens.assign((size_t)B * K * C, 0); bs.fin_n.assign((size_t)B * K, 0); bs.fin_score.assign((size_t)B * K, 0.0); bs.fin_count.assign(B, 0);
-    HIPCHK(hipMemcpyAsync(toks.data(), ctx->ds.tokens, toks.size() * 4, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipMemcpyAsync(nt.data(), ctx->ds.n_tokens, B * 4, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipMemcpyAsync(done.data(), ctx->ds.done, B * 4, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipMemcpyAsync(slp.data(), ctx->ds.sum_logprob, B * 8, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipMemcpyAsync(nsp.data(), ctx->ds.no_speech, B * 8, hipMemcpyDeviceToHost, ctx->st));
+    if (int rc = queue_decode_state(ctx, nullptr, B, B, h)) return rc;
     HIPCHK(hipMemcpyAsync(bs.fin_tokens.data(), bs.bb.fin_tokens, bs.fin_tokens.size() * 4, hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipMemcpyAsync(bs.fin_n.data(), bs.bb.fin_n, bs.fin_n.size() * 4, hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipMemcpyAsync(bs.fin_score.data(), bs.bb.fin_score, bs.fin_score.size() * 8, hipMemcpyDeviceToHost, ctx->st));
@@ -126,8 +118,8 @@ extern "C" int nh_decode_beam(nh_ctx *ctx, int beam_size, int32_t *out_tokens, n
     HIPCHK(hipStreamSynchronize(ctx->st));
     std::vector<int32_t> win(C);
     for (int b = 0; b < B; b++) {
-        if (done[b] == 2) {   // the no-speech exit: what the greedy decode returns
-            finish_sequence(ctx, toks.data() + (size_t)b * C, nt[b], 2, slp[b], nsp[b], out_tokens + (size_t)b * C, results[b], NP);
+        if (h.done[b] == 2) {   // the no-speech exit: what the greedy decode returns
+            finish_sequence(ctx, h.toks.data() + (size_t)b * C, h.nt[b], 2, h.slp[b], h.nsp[b], out_tokens + (size_t)b * C, results[b], NP);
             continue;
         }
         // the finished hypothesis with the greatest sum_logprob / n (model.rs:373: prompt and eot count, a prefix does not),
@@ -138,7 +130,7 @@ extern "C" int nh_decode_beam(nh_ctx *ctx, int beam_size, int32_t *out_tokens, n
             if (a > c) best = f;
         }
         memcpy(win.data(), bs.fin_tokens.data() + ((size_t)b * K + best) * C, sizeof(int32_t) * C);   // the trim works in place
-        finish_sequence(ctx, win.data(), bs.fin_n[b * K + best], 1, bs.fin_score[b * K + best], nsp[b], out_tokens + (size_t)b * C, results[b], NP);
+        finish_sequence(ctx, win.data(), bs.fin_n[b * K + best], 1, bs.fin_score[b * K + best], h.nsp[b], out_tokens + (size_t)b * C, results[b], NP);
     }
     bs.valid = true; bs.B = B; bs.K = K; bs.skip = NP;
     ctx->tm.decode_steps = steps;

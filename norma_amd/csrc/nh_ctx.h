@@ -154,6 +154,12 @@ struct DevBuf {
     // room for `need` bytes (contents are not kept); on failure the buffer is empty and NH_ERR_NOMEM names `what`
     int reserve(nh_ctx *ctx, size_t need, const char *what);
 };
+// One DevBuf carved into 16-byte aligned pieces: take(bytes) is the piece's offset, `off` ends as the bytes to reserve
+static inline size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
+struct Carve {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off += up16(bytes); return o; }
+};
 
 // nh_cut_plan: everything it owns.  Two (e, E) workspaces: a plan computes into the one that is not the view of nh_cut_energy
 // and becomes the view only when it succeeds, so a refused call -- cap too small is known only after the search -- leaves the
@@ -327,6 +333,18 @@ struct DecodePrompt { int B, NP, P, PL, steps; };   // batch, prefix length, pro
 int decode_refusals(nh_ctx *ctx);
 int decode_prompt_phase(nh_ctx *ctx, int max_new_tokens, DecodePrompt &dp);
 void logits_from_dx(nh_ctx *ctx, int R);
+// LayerNorm of R rows of f32 x[R][K]: the sliced summation tree of the decode step where the width allows, so that the fused
+// and the stand-alone forms, every batch size and the one-pass forward give bit-identical rows
+void dec_layernorm(nh_ctx *ctx, const LnW &ln, const float *x, half_t *y, float *y32, int R, int K);
+// Given tokens onto the device: the zero-padded [cur_batch][max_target_positions] image of ds.tokens.  Clip b brings
+// tokens[b * stride + i], i < n_each[b] (n_each == nullptr: i < n_all for every clip).  Every id is checked against the
+// vocabulary (`who` names the caller in the refusal) before anything is touched; then the decoder repack, the wait for the
+// encoder, the copy, and the stream drained.  What the last decode left for nh_align_decoded is gone after it.
+int stage_given_tokens(nh_ctx *ctx, const char *who, const int32_t *tokens, size_t stride, int n_all, const int32_t *n_each = nullptr);
+// The decode state of rows 0 .. B-1 on its way to the host, queued on the context's stream (the caller drains it).  Token rows:
+// rows[0 .. n) of the context (rows == nullptr: rows 0 .. n-1), packed.
+struct HostDecodeState { std::vector<int32_t> toks, nt, done; std::vector<double> slp, nsp; };
+int queue_decode_state(nh_ctx *ctx, const int32_t *rows, int n, int B, HostDecodeState &h);
 void finish_sequence(nh_ctx *ctx, int32_t *t, int n, int done, double slp, double nsp, int32_t *out_tokens, nh_decode_result &r, int skip = 0);
 // nh_prefill.hip: TextDecoder::forward over positions 0 .. T-1 of ds.tokens for the rows of the lockstep batch in one pass:
 // self K/V of those positions land in the caches.  hidden == nullptr (a decode's prefix): the last block stops once its K/V

@@ -33,8 +33,8 @@ static void skinny(nh_ctx *ctx, const half_t *x, long ldx, const LinW &W, int R,
 
 // every decoder LayerNorm uses the "sliced" summation tree (nh_kernels.h) when the width allows, so that the fused and
 // the stand-alone forms, and every batch size, give bit-identical rows
-static void dec_layernorm(nh_ctx *ctx, const LnW &ln, half_t *y, float *y32, int R, int K) {
-    if (!launch_layernorm_sliced(ctx->dx, ln.w, ln.b, y, y32, R, K, ctx->st)) launch_layernorm(ctx->dx, ln.w, ln.b, y, y32, R, K, ctx->st);
+void dec_layernorm(nh_ctx *ctx, const LnW &ln, const float *x, half_t *y, float *y32, int R, int K) {
+    if (!launch_layernorm_sliced(x, ln.w, ln.b, y, y32, R, K, ctx->st)) launch_layernorm(x, ln.w, ln.b, y, y32, R, K, ctx->st);
 }
 
 // LayerNorm + projection of one decode step: fused into the skinny GEMM when the shape allows (the separate
@@ -44,7 +44,7 @@ static void ln_skinny(nh_ctx *ctx, const LnW &ln, const LinW &W, int R, int N, i
     if (ctx->opt_fuse_ln && skinny_ln_supported(R, N, K)) {
         skinny(ctx, nullptr, K, W, R, N, K, epi, o0, o1, o2, ldo, t0, ctxlen, pos_ptr, ctx->dx, ln.w, ln.b);
     } else {
-        dec_layernorm(ctx, ln, ctx->dxn, nullptr, R, K);
+        dec_layernorm(ctx, ln, ctx->dx, ctx->dxn, nullptr, R, K);
         skinny(ctx, ctx->dxn, K, W, R, N, K, epi, o0, o1, o2, ldo, t0, ctxlen, pos_ptr);
     }
 }
@@ -77,7 +77,7 @@ void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr, bool final_ln, b
         ln_skinny(ctx, L.ln3, L.fc1, B, 4 * d, d, SK_GELU_F16, ctx->dhid, nullptr, nullptr, 4 * d, 0, C, nullptr);
         skinny(ctx, ctx->dhid, 4 * d, L.fc2, B, d, 4 * d, SK_RESID_F32, ctx->dx, nullptr, nullptr, d, 0, C);
     }
-    if (final_ln) dec_layernorm(ctx, m.dec_ln, ctx->dxn, ctx->dy32, B, d);
+    if (final_ln) dec_layernorm(ctx, m.dec_ln, ctx->dx, ctx->dxn, ctx->dy32, B, d);
 }
 
 // TextDecoder::final_linear on LN(dx) of the R rows of the last decoder_step(..., final_ln = false)
@@ -110,29 +110,35 @@ void finish_sequence(nh_ctx *ctx, int32_t *t, int n, int done, double slp, doubl
     for (int i = n; i < C; i++) out_tokens[i] = 0;
 }
 
-// device state -> results of the sequences in rows[0 .. n) (rows == nullptr: rows 0 .. n - 1); only those token rows cross
-static int read_results(nh_ctx *ctx, const int32_t *rows, int n, int32_t *out_tokens, nh_decode_result *results, int skip = 0) {
-    const int C = ctx->c.max_target_positions, B = rows ? ctx->pool.rows : n;
-    std::vector<int32_t> toks((size_t)n * C), nt(B), done(B);
-    std::vector<double> slp(B), nsp(B);
-    if (!rows) HIPCHK(hipMemcpyAsync(toks.data(), ctx->ds.tokens, toks.size() * 4, hipMemcpyDeviceToHost, ctx->st));
+int queue_decode_state(nh_ctx *ctx, const int32_t *rows, int n, int B, HostDecodeState &h) {
+    const int C = ctx->c.max_target_positions;
+    h.toks.resize((size_t)n * C); h.nt.resize(B); h.done.resize(B); h.slp.resize(B); h.nsp.resize(B);
+    if (!rows) HIPCHK(hipMemcpyAsync(h.toks.data(), ctx->ds.tokens, h.toks.size() * 4, hipMemcpyDeviceToHost, ctx->st));
     else
         for (int i = 0; i < n; i++)
-            HIPCHK(hipMemcpyAsync(toks.data() + (size_t)i * C, ctx->ds.tokens + (size_t)rows[i] * C, sizeof(int32_t) * C, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipMemcpyAsync(nt.data(), ctx->ds.n_tokens, B * 4, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipMemcpyAsync(done.data(), ctx->ds.done, B * 4, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipMemcpyAsync(slp.data(), ctx->ds.sum_logprob, B * 8, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipMemcpyAsync(nsp.data(), ctx->ds.no_speech, B * 8, hipMemcpyDeviceToHost, ctx->st));
+            HIPCHK(hipMemcpyAsync(h.toks.data() + (size_t)i * C, ctx->ds.tokens + (size_t)rows[i] * C, sizeof(int32_t) * C, hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipMemcpyAsync(h.nt.data(), ctx->ds.n_tokens, B * 4, hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipMemcpyAsync(h.done.data(), ctx->ds.done, B * 4, hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipMemcpyAsync(h.slp.data(), ctx->ds.sum_logprob, B * 8, hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipMemcpyAsync(h.nsp.data(), ctx->ds.no_speech, B * 8, hipMemcpyDeviceToHost, ctx->st));
+    return NH_OK;
+}
+
+// device state -> results of the sequences in rows[0 .. n) (rows == nullptr: rows 0 .. n - 1); only those token rows cross
+static int read_results(nh_ctx *ctx, const int32_t *rows, int n, int32_t *out_tokens, nh_decode_result *results, int skip = 0) {
+    const int C = ctx->c.max_target_positions;
+    HostDecodeState h;
+    if (int rc = queue_decode_state(ctx, rows, n, rows ? ctx->pool.rows : n, h)) return rc;
     HIPCHK(hipStreamSynchronize(ctx->st));
     for (int i = 0; i < n; i++)
-        if (rows && done[rows[i]] != 1 && done[rows[i]] != 2) return ctx->fail(NH_ERR_STATE, "nh_pool_collect: that row has not finished (see nh_pool_step's done flags)");
+        if (rows && h.done[rows[i]] != 1 && h.done[rows[i]] != 2) return ctx->fail(NH_ERR_STATE, "nh_pool_collect: that row has not finished (see nh_pool_step's done flags)");
     if (!rows) { ctx->live.n.assign(n, 0); ctx->live.done.assign(n, 0); }
     for (int i = 0; i < n; i++) {
         const int b = rows ? rows[i] : i;
-        finish_sequence(ctx, toks.data() + (size_t)i * C, nt[b], done[b], slp[b], nsp[b], out_tokens + (size_t)i * C, results[i], skip);
+        finish_sequence(ctx, h.toks.data() + (size_t)i * C, h.nt[b], h.done[b], h.slp[b], h.nsp[b], out_tokens + (size_t)i * C, results[i], skip);
         // what nh_align_decoded aligns: the sequence as returned
-        if (rows) { PoolRow &r = ctx->pool.row[b]; r.n = results[i].n_tokens; r.done = done[b]; }
-        else { ctx->live.n[i] = results[i].n_tokens; ctx->live.done[i] = done[b]; }
+        if (rows) { PoolRow &r = ctx->pool.row[b]; r.n = results[i].n_tokens; r.done = h.done[b]; }
+        else { ctx->live.n[i] = results[i].n_tokens; ctx->live.done[i] = h.done[b]; }
     }
     return NH_OK;
 }
@@ -550,17 +556,11 @@ extern "C" int nh_detect_language(nh_ctx *ctx, const int32_t *lang_tokens, int n
     if (ctx->pool.rows > 0) return ctx->fail(NH_ERR_STATE, "nh_detect_language: the context runs a decode pool (nh_pool_begin)");
     if (!ctx->have_enc) return ctx->fail(NH_ERR_STATE, "nh_detect_language: call nh_encode first");
     if (!ctx->have_tokens) return ctx->fail(NH_ERR_STATE, "nh_detect_language: call nh_set_tokens first");
-    hipSetDevice(ctx->dev);
-    if (int rc = ensure_decoder_repack(ctx)) return rc;
-    const int B = ctx->cur_batch, C = ctx->c.max_target_positions, V = ctx->c.vocab_size;
-    ctx->live.lock_valid = false;
+    const int B = ctx->cur_batch, V = ctx->c.vocab_size;
     for (int i = 0; i < n; i++) if (lang_tokens[i] < 0 || lang_tokens[i] >= V) return ctx->fail(NH_ERR_INVALID, "nh_detect_language: token id outside the vocabulary");
-    std::vector<int32_t> toks((size_t)B * C, 0);
-    for (int b = 0; b < B; b++) toks[(size_t)b * C] = ctx->tk.sot;  // tokens = [[sot]], model.rs:195
-    HIPCHK(hipStreamWaitEvent(ctx->st, ctx->enc_done, 0));
-    HIPCHK(hipMemcpyAsync(ctx->ds.tokens, toks.data(), toks.size() * 4, hipMemcpyHostToDevice, ctx->st));
-    HIPCHK(hipMemcpyAsync(ctx->d_lang_tokens, lang_tokens, n * 4, hipMemcpyHostToDevice, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));
+    // tokens = [[sot]], model.rs:195: every clip the same one token
+    if (int rc = stage_given_tokens(ctx, "nh_detect_language", &ctx->tk.sot, 0, 1)) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->d_lang_tokens, lang_tokens, n * 4, hipMemcpyHostToDevice, ctx->st));   // the caller's, read before the drain below
     decoder_step(ctx, 0);
     logits_from_dxn(ctx, B);
     launch_lang_detect(ctx->logits, V, ctx->d_lang_tokens, n, out_probs ? ctx->d_lang_probs : nullptr, ctx->d_lang_out, B, ctx->st);
@@ -580,25 +580,33 @@ extern "C" int nh_transcribe_batch(nh_ctx *ctx, const float *pcm_dev, const int3
     return nh_decode_greedy(ctx, out_tokens, results, max_new_tokens);
 }
 
+int stage_given_tokens(nh_ctx *ctx, const char *who, const int32_t *tokens, size_t stride, int n_all, const int32_t *n_each) {
+    const int B = ctx->cur_batch, C = ctx->c.max_target_positions, V = ctx->c.vocab_size;
+    std::vector<int32_t> toks((size_t)B * C, 0);
+    for (int b = 0; b < B; b++) {
+        const int n = n_each ? n_each[b] : n_all;
+        for (int i = 0; i < n; i++) {
+            const int32_t t = tokens[(size_t)b * stride + i];
+            if (t < 0 || t >= V) return ctx->fail(NH_ERR_INVALID, std::string(who) + ": token id outside the vocabulary");
+            toks[(size_t)b * C + i] = t;
+        }
+    }
+    hipSetDevice(ctx->dev);
+    if (int rc = ensure_decoder_repack(ctx)) return rc;
+    HIPCHK(hipStreamWaitEvent(ctx->st, ctx->enc_done, 0));
+    ctx->live.lock_valid = false;   // the tokens, and the self K/V the caller's pass writes next, replace what the last decode left
+    HIPCHK(hipMemcpyAsync(ctx->ds.tokens, toks.data(), toks.size() * 4, hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));   // toks is a local
+    return NH_OK;
+}
+
 extern "C" int nh_decoder_forward(nh_ctx *ctx, const int32_t *tokens, int T, float *hidden_out) {
     if (!ctx || !tokens || !hidden_out) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_decoder_forward: bad arguments") : NH_ERR_INVALID;
     if (ctx->pool.rows > 0) return ctx->fail(NH_ERR_STATE, "nh_decoder_forward: the context runs a decode pool (nh_pool_begin)");
     if (!ctx->have_enc) return ctx->fail(NH_ERR_STATE, "nh_decoder_forward: call nh_encode first");
-    const int B = ctx->cur_batch, C = ctx->c.max_target_positions, d = ctx->c.d_model, V = ctx->c.vocab_size;
+    const int B = ctx->cur_batch, C = ctx->c.max_target_positions, d = ctx->c.d_model;
     if (T < 1 || T > C) return ctx->fail(NH_ERR_INVALID, "nh_decoder_forward: T out of range");
-    hipSetDevice(ctx->dev);
-    if (int rc = ensure_decoder_repack(ctx)) return rc;
-    HIPCHK(hipStreamWaitEvent(ctx->st, ctx->enc_done, 0));
-    ctx->live.lock_valid = false;
-    std::vector<int32_t> toks((size_t)B * C, 0);
-    for (int b = 0; b < B; b++)
-        for (int i = 0; i < T; i++) {
-            int t = tokens[(size_t)b * T + i];
-            if (t < 0 || t >= V) return ctx->fail(NH_ERR_INVALID, "nh_decoder_forward: token id outside the vocabulary");
-            toks[(size_t)b * C + i] = t;
-        }
-    HIPCHK(hipMemcpyAsync(ctx->ds.tokens, toks.data(), toks.size() * 4, hipMemcpyHostToDevice, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));
+    if (int rc = stage_given_tokens(ctx, "nh_decoder_forward", tokens, T, T)) return rc;
     std::vector<float> row((size_t)B * d);
     for (int pos = 0; pos < T; pos++) {
         decoder_step(ctx, pos);

@@ -28,10 +28,6 @@ static void pf_gemm(nh_ctx *ctx, const half_t *A, long lda, const LinW &W, int M
     launch_gemm(p, ctx->st);
 }
 
-static void pf_layernorm(nh_ctx *ctx, const LnW &ln, const float *x, half_t *y, float *y32, int M, int d) {
-    if (!launch_layernorm_sliced(x, ln.w, ln.b, y, y32, M, d, ctx->st)) launch_layernorm(x, ln.w, ln.b, y, y32, M, d, ctx->st);
-}
-
 int prefill_forward(nh_ctx *ctx, int T, float *hidden, bool keep_rows) {
     const nh_model &m = *ctx->mdl;
     const int d = ctx->c.d_model, B = ctx->cur_batch, H = ctx->c.decoder_attention_heads, C = ctx->c.max_target_positions, S = ctx->S;
@@ -47,26 +43,26 @@ int prefill_forward(nh_ctx *ctx, int T, float *hidden, bool keep_rows) {
     for (int l = 0; l < layers; l++) {
         const DecLayer &L = m.dec[l];
         const KvCache &kv = ctx->kv[l];
-        pf_layernorm(ctx, L.ln1, x, xn, nullptr, M, d);
+        dec_layernorm(ctx, L.ln1, x, xn, nullptr, M, d);
         pf_gemm(ctx, xn, d, L.qkv, M, 3 * d, d, EPI_F16, q, k, v, d, d);
         if (!launch_prefill_self_attention(q, k, v, d, att, d, kv.sk, kv.sv, B, T, H, C, ctx->st))
             return ctx->fail(NH_ERR_INVALID, "one-pass decoder forward: self-attention shape not covered");
         if (!full && l == layers - 1) break;   // a decode needs the prefix rows' K/V only: nothing below feeds a later position
         pf_gemm(ctx, att, d, L.o, M, d, d, EPI_RESID_F32, x, nullptr, nullptr, d, d);
-        pf_layernorm(ctx, L.ln2, x, xn, nullptr, M, d);
+        dec_layernorm(ctx, L.ln2, x, xn, nullptr, M, d);
         pf_gemm(ctx, xn, d, L.cq, M, d, d, EPI_F16, q, nullptr, nullptr, d, d);
         if (!launch_prefill_cross_attention(q, d, kv.ck, kv.cv, att, d, B, T, H, S, ctx->st))
             return ctx->fail(NH_ERR_INVALID, "one-pass decoder forward: cross-attention shape not covered");
         pf_gemm(ctx, att, d, L.co, M, d, d, EPI_RESID_F32, x, nullptr, nullptr, d, d);
-        pf_layernorm(ctx, L.ln3, x, xn, nullptr, M, d);
+        dec_layernorm(ctx, L.ln3, x, xn, nullptr, M, d);
         pf_gemm(ctx, xn, d, L.fc1, M, 4 * d, d, EPI_GELU_F16, hid, nullptr, nullptr, 4 * d, 4 * d);
         pf_gemm(ctx, hid, 4 * d, L.fc2, M, d, 4 * d, EPI_RESID_F32, x, nullptr, nullptr, d, d);
     }
     if (keep_rows && !hidden) {
-        pf_layernorm(ctx, m.dec_ln, x, xn, nullptr, M, d);
+        dec_layernorm(ctx, m.dec_ln, x, xn, nullptr, M, d);
     } else if (full) {
         float *y32 = reinterpret_cast<float *>(ctx->hid);   // B * 1500 * 4 d halfs: room for 2 * B * 1500 * d floats
-        pf_layernorm(ctx, m.dec_ln, x, xn, y32, M, d);
+        dec_layernorm(ctx, m.dec_ln, x, xn, y32, M, d);
         HIPCHK(hipMemcpyAsync(hidden, y32, sizeof(float) * (size_t)M * d, hipMemcpyDeviceToHost, ctx->st));
         HIPCHK(hipStreamSynchronize(ctx->st));
     }
@@ -78,22 +74,9 @@ extern "C" int nh_decoder_forward_onepass(nh_ctx *ctx, const int32_t *tokens, in
     if (!ctx || !tokens || !hidden_out) return ctx ? ctx->fail(NH_ERR_INVALID, "nh_decoder_forward_onepass: bad arguments") : NH_ERR_INVALID;
     if (ctx->pool.rows > 0) return ctx->fail(NH_ERR_STATE, "nh_decoder_forward_onepass: the context runs a decode pool (nh_pool_begin)");
     if (!ctx->have_enc) return ctx->fail(NH_ERR_STATE, "nh_decoder_forward_onepass: call nh_encode first");
-    const int B = ctx->cur_batch, C = ctx->c.max_target_positions, V = ctx->c.vocab_size;
-    if (T < 1 || T > C) return ctx->fail(NH_ERR_INVALID, "nh_decoder_forward_onepass: T out of range");
+    if (T < 1 || T > ctx->c.max_target_positions) return ctx->fail(NH_ERR_INVALID, "nh_decoder_forward_onepass: T out of range");
     if (!prefill_supported(ctx)) return ctx->fail(NH_ERR_STATE, "nh_decoder_forward_onepass: needs d_model % 128 == 0 and NH_OPT_ABSORBED_XATTN == 0");
-    std::vector<int32_t> toks((size_t)B * C, 0);
-    for (int b = 0; b < B; b++)
-        for (int i = 0; i < T; i++) {
-            const int t = tokens[(size_t)b * T + i];
-            if (t < 0 || t >= V) return ctx->fail(NH_ERR_INVALID, "nh_decoder_forward_onepass: token id outside the vocabulary");
-            toks[(size_t)b * C + i] = t;
-        }
-    hipSetDevice(ctx->dev);
-    if (int rc = ensure_decoder_repack(ctx)) return rc;
-    HIPCHK(hipStreamWaitEvent(ctx->st, ctx->enc_done, 0));
-    ctx->live.lock_valid = false;
-    HIPCHK(hipMemcpyAsync(ctx->ds.tokens, toks.data(), toks.size() * 4, hipMemcpyHostToDevice, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));   // toks is a local
+    if (int rc = stage_given_tokens(ctx, "nh_decoder_forward_onepass", tokens, T, T)) return rc;
     return prefill_forward(ctx, T, hidden_out);
 }
 

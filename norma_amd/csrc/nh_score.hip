@@ -3,18 +3,15 @@
 // hands them to the two kernels of k_score.hip: the vocabulary projection reduced to three numbers per row, and their merge.
 #include "nh_ctx.h"
 
-static size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
-
 // the score buffers, made by the first call
 static int ensure_score_buffers(nh_ctx *ctx) {
     ScoreState &sc = ctx->score;
     if (sc.buf.p) return NH_OK;
     const size_t C = ctx->c.max_target_positions, rows = (size_t)ctx->B * (C - 1), V = ctx->c.vocab_size;
     const size_t panel = std::min(rows, (size_t)score_panel_rows((int)V)), ntn = (V + 127) / 128;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += up16(bytes); return o; };
-    const size_t o_tg = take(rows * 4), o_tl = take(rows * 4), o_out = take((size_t)ctx->B * C * 4), o_part = take(panel * ntn * 8);
-    if (int rc = sc.buf.reserve(ctx, off, "transcript scoring")) return rc;
+    Carve cv;
+    const size_t o_tg = cv.take(rows * 4), o_tl = cv.take(rows * 4), o_out = cv.take((size_t)ctx->B * C * 4), o_part = cv.take(panel * ntn * 8);
+    if (int rc = sc.buf.reserve(ctx, cv.off, "transcript scoring")) return rc;
     char *p = static_cast<char *>(sc.buf.p);
     sc.target = reinterpret_cast<int32_t *>(p + o_tg);
     sc.tlogit = reinterpret_cast<float *>(p + o_tl);
@@ -34,27 +31,18 @@ extern "C" int nh_score(nh_ctx *ctx, const int32_t *tokens, const int32_t *n_tok
     for (int b = 0; b < B; b++) {
         const int n = n_tokens[b];
         if (n <= prompt_len || n > C) return ctx->fail(NH_ERR_INVALID, "nh_score: n_tokens outside (prompt_len, max_target_positions]");
-        for (int i = 0; i < n; i++)
-            if (tokens[(size_t)b * C + i] < 0 || tokens[(size_t)b * C + i] >= V) return ctx->fail(NH_ERR_INVALID, "nh_score: token id outside the vocabulary");
         T = std::max(T, n - 1);
     }
-    hipSetDevice(ctx->dev);
-    if (int rc = ensure_decoder_repack(ctx)) return rc;
+    // what lies past a clip's own tokens never reaches the device: positions n .. hold 0, and rows n - 1 .. have no target
+    if (int rc = stage_given_tokens(ctx, "nh_score", tokens, C, 0, n_tokens)) return rc;
     if (int rc = ensure_score_buffers(ctx)) return rc;
     ScoreState &sc = ctx->score;
-    // what lies past a clip's own tokens never reaches the device: positions n .. hold 0, and rows n - 1 .. have no target
-    std::vector<int32_t> toks((size_t)B * C, 0), target((size_t)B * T, -1);
-    for (int b = 0; b < B; b++) {
-        const int n = n_tokens[b];
-        memcpy(toks.data() + (size_t)b * C, tokens + (size_t)b * C, sizeof(int32_t) * n);
-        for (int i = prompt_len; i < n; i++) target[(size_t)b * T + i - 1] = tokens[(size_t)b * C + i];   // row i - 1 predicts token i
-    }
-    HIPCHK(hipStreamWaitEvent(ctx->st, ctx->enc_done, 0));
-    ctx->live.lock_valid = false;
-    HIPCHK(hipMemcpyAsync(ctx->ds.tokens, toks.data(), toks.size() * 4, hipMemcpyHostToDevice, ctx->st));
+    std::vector<int32_t> target((size_t)B * T, -1);
+    for (int b = 0; b < B; b++)
+        for (int i = prompt_len; i < n_tokens[b]; i++) target[(size_t)b * T + i - 1] = tokens[(size_t)b * C + i];   // row i - 1 predicts token i
     HIPCHK(hipMemcpyAsync(sc.target, target.data(), target.size() * 4, hipMemcpyHostToDevice, ctx->st));
     HIPCHK(hipMemsetAsync(sc.out, 0, sizeof(float) * (size_t)B * C, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));   // toks and target are locals
+    HIPCHK(hipStreamSynchronize(ctx->st));   // target is a local
     if (int rc = prefill_forward(ctx, T, nullptr, true)) return rc;
     if (!launch_score_rows(ctx->xn, B * T, d, ctx->mdl->tok_emb, V, sc.target, sc.part, sc.tlogit, T, C, 1, sc.out, 0, ctx->st))
         return ctx->fail(NH_ERR_INVALID, "nh_score: shape not covered");

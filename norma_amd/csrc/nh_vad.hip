@@ -4,8 +4,6 @@
 // header and in DESIGN.md 12.
 #include "nh_ctx.h"
 
-static inline size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
-
 // A view workspace of F frames: regions (a, b pairs, 64-bit; F frames hold at most F / 2 + 1 runs), levels[3] + the region
 // count, E[F], v3 (whole tiles)
 struct VadLayout { long long max_regions; size_t levels, E, v3, bytes; };
