@@ -178,7 +178,7 @@ __global__ __launch_bounds__(NTHR, (NTHR <= 512 ? ENC_ATTN_MINWAVES : 1)) void E
         const bool reb = (t == 0) || (mx > REBASE);
         if (__builtin_amdgcn_ballot_w64(reb) != 0) {   // rare after the first tile: move the reference of the queries that need it
             const float dlt = reb ? mx : 0.f;          // tile 0: m_ref = the tile's maximum (any sign); later: only upwards
-            const float alpha = __builtin_amdgcn_exp2f(-dlt);
+            const float alpha = t == 0 ? 1.f : __builtin_amdgcn_exp2f(-dlt);   // tile 0: O and l are still zero, and exp2(-mx) is inf for mx < -128 (0 x inf = NaN)
 #pragma unroll
             for (int i = 0; i < 16; i++) { o0[i] *= alpha; o1[i] *= alpha; s0[i] -= dlt; s1[i] -= dlt; }
             l_run *= alpha;

@@ -5,7 +5,9 @@ Every reference is plain NumPy in float64 on the exact fp16 / f32 values the ker
 derived from the kernel's arithmetic (the comments say how), never a constant fitted to what the GPU produced.  u = 2^-24 is the
 unit roundoff of f32, 2^-11 that of fp16.  A test also shows that its bound is tight enough to matter: `discriminates` rebuilds
 the reference under plausible bugs (a dropped k-step, a missing bias tile, a key too few ...) and requires each of them to leave
-the bound by a factor of two on the case's own data, so that a kernel with that bug would fail the case."""
+the bound by a factor of two on the case's own data, so that a kernel with that bug would fail the case.
+One stated limit: enc_attn_kernel clamps -m_ref to +-60000 log2 units (the largest fp16 pair it can subtract); encoder scores
+beyond that are out of scope of its reference, bound and cases."""
 import ctypes as C
 import os
 
@@ -288,6 +290,331 @@ def enc_attention(q, k, v, B, S, H):
                 i1 = min(S, i0 + 256)
                 vdev[b * S + i0:b * S + i1, h] = np.einsum("ij,ijc->ic", p[i0:i1], np.abs(v[r, c][None] - o[r, c][i0:i1, None]))
     return o, sabs, (vdev, pv)
+
+
+# ---- enc_attn_kernel's deferred-maximum softmax (k_attn_enc.hip) -------------------------------------------------------------
+# The kernel walks the keys in tiles of 64.  Its reference maximum m_ref is the tile maximum on tile 0 and moves afterwards only
+# where a tile's maximum exceeds it by more than 8 log2 units (a "rebase": O and l are rescaled, the tile's scores shifted, and
+# the pair of fp16 numbers that subtracts m_ref inside the score product rewritten); in between p = exp2(s - m_ref) runs up to
+# 256.  None of that changes the result in real arithmetic, so the value reference stays enc_attention; what follows is the
+# accounting that says which of these paths a case's inputs reach (enc_rebase_replay), the two bound terms the scheme adds
+# (attn_bound's mref and p_floor), the adversarial cases (enc_rebase_case), and a NumPy emulation of the kernel's arithmetic
+# with its rebase bugs (enc_emulate) for `discriminates`.
+# Out of scope: scores beyond +-60000 log2 units.  The kernel clamps -m_ref there (fp16 has no larger finite number); no case
+# here comes within a factor of 40 of it, and the bound has no term for the clamp.
+ENC_KT = 64            # `#define KT 64` (k_attn_enc.hip:28): keys per tile
+ENC_QW = 32            # `#define QW 32` (k_attn_enc.hip:29): queries per wave, one per lane of either half
+ENC_REBASE = 8.0       # `const float REBASE = 8.0f` (k_attn_enc.hip:135), used as `reb = (t == 0) || (mx > REBASE)` (:178)
+ENC_CLAMP = 60000.0    # `fminf(fmaxf(-m_ref, -60000.f), 60000.f)` (k_attn_enc.hip:186)
+ENC_KEY_HALF = (np.arange(ENC_KT) >> 3) & 1    # the lane half that owns in-tile key position j: bit 3 (rho = (i & 3) + 8 (i >> 2) + 4 hh
+#                                                is the LDS row, swap23(rho) the key: k_attn_enc.hip:163-164)
+ENC_DH_HALF = (np.arange(NH_DH) >> 2) & 1      # the lane half that owns output dimension c: bit 2 (`+ 4 * hh`, k_attn_enc.hip:267)
+ENC_REBASE_CASES = ("ramp", "spike", "threshold", "offset")
+ENC_REBASE_SHAPES = ((1, 750), (2, 750), (1, 1500))     # (B, S) at H = 2: the last tile holds 46 or 28 keys
+ENC_BUGS = {"rebase forgets to rescale l": "no_l", "rebase forgets to rescale O": "no_o",
+            "later tiles keep the old m_ref (qx not updated)": "no_qx", "the key halves do not share the maximum": "no_share"}
+ENC_THR_DELTA = 2.0 ** -6    # the threshold case's distance from REBASE; enc_rebase_case says why it is large enough
+ENC_SPIKE = 80.0             # the spike case's dominating score
+
+
+def _enc_tiles(s, S):
+    """scores [S][S] -> [S][nT][64], keys past S at -inf"""
+    nT = -(-S // ENC_KT)
+    p = np.full((s.shape[0], nT * ENC_KT), -np.inf)
+    p[:, :S] = s
+    return p.reshape(s.shape[0], nT, ENC_KT)
+
+
+def enc_rebase_replay(q, k, S, H):
+    """the kernel's rule for m_ref, replayed in fp64 for every (query, head) of q, k [B*S][64 H] (q pre-scaled): on tile 0 m_ref
+    is the tile maximum; on a later tile t it moves to the tile maximum only where gap[t] = max_t - m_ref > ENC_REBASE.  Coverage
+    accounting only: the output does not depend on these decisions.  Returns a dict of arrays over [B*S][H] (`rows`):
+      rebase [rows][nT]   the rebase map (tile 0: True)
+      gap [rows][nT]      tile maximum - m_ref before the decision (tile 0: 0); a non-rebasing tile's largest p is 2^gap
+      pos [rows][nT]      in-tile position of the tile's maximum
+      near [rows][nT]     |gap - 8| <= 2 e: the kernel may decide either way.  e = attn_score_error(sabs, mref = max |m_ref|) is
+                          the score error of attn_bound in log2 units; twice, because the kernel's m_ref is itself a computed
+                          score
+      decided [rows][nT]  no near pair at or before this tile: later tiles of a query inherit an undecided m_ref
+      p_max [rows]        the largest p of a decided, non-rebasing tile after tile 0 (0 where there is none)
+      m_final, m_absmax, margin (largest score - second largest over all keys), top_tile (the tile of the largest score), sabs,
+      e [rows]"""
+    q, k = d64(q), d64(k)
+    B = q.shape[0] // S
+    nT = -(-S // ENC_KT)
+    out = {n: np.zeros((B * S, H, nT), dt) for n, dt in (("rebase", bool), ("gap", float), ("pos", np.int64))}
+    for n in ("m_final", "m_absmax", "margin", "sabs"):
+        out[n] = np.zeros((B * S, H))
+    out["top_tile"] = np.zeros((B * S, H), np.int64)
+    for b in range(B):
+        r = slice(b * S, (b + 1) * S)
+        for h in range(H):
+            c = slice(h * NH_DH, (h + 1) * NH_DH)
+            s = q[r, c] @ k[r, c].T
+            top = np.partition(s, S - 2, axis=-1)
+            out["margin"][r, h] = top[:, S - 1] - top[:, S - 2]
+            out["top_tile"][r, h] = s.argmax(axis=-1) // ENC_KT
+            out["sabs"][r, h] = (np.abs(q[r, c]) @ np.abs(k[r, c]).T).max(axis=-1)
+            tiles = _enc_tiles(s, S)
+            tmax, out["pos"][r, h] = tiles.max(axis=-1), tiles.argmax(axis=-1)
+            m = tmax[:, 0].copy()
+            out["rebase"][r, h, 0] = True
+            mabs = np.abs(m)
+            for t in range(1, nT):
+                g = tmax[:, t] - m
+                rb = g > ENC_REBASE
+                out["gap"][r, h, t], out["rebase"][r, h, t] = g, rb
+                m = np.where(rb, tmax[:, t], m)
+                mabs = np.maximum(mabs, np.abs(m))
+            out["m_final"][r, h], out["m_absmax"][r, h] = m, mabs
+    out["e"] = attn_score_error(out["sabs"], mref=out["m_absmax"])
+    near = np.abs(out["gap"] - ENC_REBASE) <= 2 * out["e"][:, :, None]
+    near[:, :, 0] = False
+    out["near"] = near
+    out["decided"] = ~(np.cumsum(near, axis=-1) > 0)
+    quiet = out["decided"] & ~out["rebase"]
+    out["p_max"] = np.where(quiet, np.exp2(np.minimum(out["gap"], ENC_REBASE)), 0.0).max(axis=-1)
+    return out
+
+
+def enc_p16_floor(q, k, v, B, S, H):
+    """attn_bound's p_floor for enc_attn_kernel, [B*S][H][64]: 2^-25 sum |v_j| over the keys whose weight CAN be below 2^-14 when
+    the kernel rounds it to fp16.  m_ref never exceeds the running maximum of the tiles up to the key's own, so the kernel's
+    p_j = 2^(s_j - m_ref) >= 2^(s_j - running maximum): the keys with s_j - running maximum < -14 are a superset, whatever the
+    rebase decisions were.  Later rescalings multiply by alpha <= 1 and l >= 1."""
+    q, k, v = d64(q), d64(k), d64(v)
+    floor = np.zeros((B * S, H, NH_DH))
+    tile_of = np.arange(S) // ENC_KT
+    for b in range(B):
+        r = slice(b * S, (b + 1) * S)
+        for h in range(H):
+            c = slice(h * NH_DH, (h + 1) * NH_DH)
+            s = q[r, c] @ k[r, c].T
+            run = np.maximum.accumulate(_enc_tiles(s, S).max(axis=-1), axis=-1)
+            floor[r, h] = SUB16 * ((s - run[:, tile_of] < -14.0) @ np.abs(v[r, c]))
+    return floor
+
+
+def enc_attention_keys(q, k, v, B, S, H, nk):
+    """encoder attention of every query over the first nk keys of its clip only (a tile mask that ends early); o [B*S][64 H]"""
+    q, k, v = d64(q), d64(k), d64(v)
+    o = np.zeros_like(q)
+    for b in range(B):
+        r, rk = slice(b * S, (b + 1) * S), slice(b * S, b * S + nk)
+        for h in range(H):
+            c = slice(NH_DH * h, NH_DH * h + NH_DH)
+            o[r, c] = softmax_attend((q[r, c] @ k[rk, c].T) * np.log(2.0), v[rk, c])
+    return o
+
+
+def enc_emulate(q, k, v, B, S, H, bug=None, tile0_rescale=False):
+    """enc_attn_kernel's arithmetic in NumPy: f32 scores of the fp16 operands; -m_ref as hi + lo, two fp16 numbers added to the
+    score in f32; per query and per 64-key tile the maximum, the rebase rule, alpha = exp2(-dlt) on O and l, the tile's scores
+    shifted by dlt; p = exp2(s') in f32, summed into l as it is and rounded to fp16 for the P.V product; O in f32; O / l rounded
+    to fp16.  The two lane halves of a query are kept apart as the kernel keeps them: half hh owns the keys ENC_KEY_HALF == hh
+    (their maximum, their part of l), the output dimensions ENC_DH_HALF == hh and a copy of m_ref; hi and lo live in half 0.
+    bug: None, or a value of ENC_BUGS -- on rebases AFTER tile 0 "no_l" / "no_o" leave l / O unscaled and "no_qx" leaves hi, lo
+    at their earlier values; "no_share" drops the exchange of the maximum between the halves.
+    tile0_rescale=True is the kernel's former arithmetic: O and l, still zero, multiplied by alpha on tile 0 too -- 0 x inf = NaN
+    as soon as tile 0's maximum is below -128."""
+    f = np.float32
+    assert bug in (None,) + tuple(ENC_BUGS.values())
+    nT = -(-S // ENC_KT)
+    own = ENC_KEY_HALF
+    out = np.zeros((B * S, H * NH_DH), np.float16)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for b in range(B):
+            r = slice(b * S, (b + 1) * S)
+            for h in range(H):
+                c = slice(h * NH_DH, (h + 1) * NH_DH)
+                qq, kk = q[r, c].astype(f), np.zeros((nT * ENC_KT, NH_DH), f)
+                vv = np.zeros((nT * ENC_KT, NH_DH), f)
+                kk[:S], vv[:S] = k[r, c], v[r, c]
+                m, l, O = np.zeros((2, S), f), np.zeros((2, S), f), np.zeros((2, S, NH_DH), f)
+                hi, lo = np.zeros(S, f), np.zeros(S, f)
+                for t in range(nT):
+                    ks = slice(t * ENC_KT, (t + 1) * ENC_KT)
+                    s = ((qq @ kk[ks].T + hi[:, None]) + lo[:, None]).astype(f)
+                    s[:, np.arange(ks.start, ks.stop) >= S] = -np.inf
+                    mx = np.stack([s[:, own == 0].max(axis=-1), s[:, own == 1].max(axis=-1)])
+                    if bug != "no_share":
+                        mx = np.broadcast_to(np.maximum(mx[0], mx[1]), (2, S))
+                    reb = np.full((2, S), True) if t == 0 else mx > f(ENC_REBASE)
+                    dlt = np.where(reb, mx, f(0)).astype(f)
+                    alpha = np.exp2(-dlt).astype(f)
+                    if t == 0 and not tile0_rescale:
+                        alpha = np.ones((2, S), f)
+                    O *= (np.ones((2, S, 1), f) if bug == "no_o" and t else alpha[:, :, None])
+                    l *= (np.ones((2, S), f) if bug == "no_l" and t else alpha)
+                    s = (s - dlt[own].T).astype(f)
+                    m += dlt
+                    if not (bug == "no_qx" and t):
+                        nm = np.clip(-m[0], f(-ENC_CLAMP), f(ENC_CLAMP))
+                        hi = nm.astype(np.float16).astype(f)
+                        lo = (nm - hi).astype(np.float16).astype(f)
+                    p = np.exp2(s).astype(f)
+                    for hh in (0, 1):
+                        l[hh] += p[:, own == hh].sum(axis=-1, dtype=f)
+                    O += (p.astype(np.float16).astype(f) @ vv[ks])[None]
+                inv = f(1) / (l[0] + l[1])
+                out[r, c] = (np.where(ENC_DH_HALF == 0, O[0], O[1]) * inv[:, None]).astype(np.float16)
+    return out
+
+
+def _enc_units(r, H, signs=False):
+    """one unit direction per head, [H][64]: Gaussian, or all components +-1/8 (its multiples by n / 4 are exact in fp16)"""
+    if signs:
+        return r.choice([-0.125, 0.125], size=(H, NH_DH))
+    u = r.standard_normal((H, NH_DH))
+    return u / np.linalg.norm(u, axis=-1, keepdims=True)
+
+
+_ENC_CASES = {}
+
+
+def enc_rebase_case(name, B, S, H=2):
+    """the adversarial inputs of enc_attn_kernel's rebase tests: (q, k, v) fp16 [B*S][64 H], q pre-scaled; built once per (name,
+    B, S, H) and shared (read-only).  Gaussian q (sigma ENC_Q_SCALE) and k, v; u_h a unit direction per head; i, j the query and
+    key index in the clip, t = j // 64 the key's tile:
+      ramp       k_j += t u, q_i += a u with a = +11, +3, 0, -11 by i % 4: one wave holds queries whose scores rise by 11 a tile
+                 (a rebase every tile), by 3 (a rebase every third tile, p up to 256 in between), not at all, and fall by 11
+                 (no rebase; the later keys' weights sink through the fp16 subnormals to zero)
+      spike      every key is the dominating key of one query: q_i Gaussian directions of one length, k_pi(i) = ENC_SPIKE q_i /
+                 |q_i|^2 for a random permutation pi of the clip's keys (as test_dec_attention_adversarial_scores plants its
+                 keys): q_i scores ENC_SPIKE on its own key and ENC_SPIKE cos(q_i, q_i') on the others, at least 20 less (checked:
+                 `margin`).  Every in-tile position of every tile is some query's, key S - 1 and keys 31 / 32 of each tile
+                 among them; the rebase to the spike falls into tile 1, a middle tile or the masked last tile accordingly
+      threshold  u_h with components +-1/8; one key per tile is (8 + 2 t) u exactly, the last tile's is key S - 1; q_i = g_i +
+                 (4 +- delta / 2) u, + for even i, g_i Gaussian made orthogonal to u: the peak of tile t scores (4 +- delta / 2)
+                 (8 + 2 t), every tile's peak lies 8 +- delta above the one before.  Even queries rebase on every tile by
+                 8 + delta; odd ones stay on the odd tiles with p = 2^(8 - delta) and rebase by 16 - 2 delta on the even ones.
+                 delta = ENC_THR_DELTA = 2^-6: the peaks are exact products of fp16 numbers up to the rounding of q (about 1e-4
+                 in the gap), and 2 e < 2e-3 at the largest scores of the case (S = 1500: 4 * 54 = 216, e = 64 u 230 + ..), so
+                 both sides are decided; p stays above 2^(8 - 2 delta) = 250
+      offset     q_i += +-35 u (+ for even i), k_j += 32 u: every score of a query sits near +1120 or -1120, m_ref of either sign
+                 near 1100, hi and lo both in use.  The keys' own spread along u (sigma 35 log2 units) is common to all queries of
+                 one sign, so they agree on the winning key and key S - 1 would matter to none of them: per (clip, head) the last
+                 key is set to a multiple of one query's direction that scores the log2-sum-exp2 of that query's other scores
+                 (half the weight, as _xabs_case gives it); the query is even in head 0 and odd in head 1."""
+    key = (name, B, S, H)
+    if key in _ENC_CASES:
+        return _ENC_CASES[key]
+    assert name in ENC_REBASE_CASES
+    r = np.random.default_rng(zlib_key("enc-rebase", name, B, S, H))
+    d = H * NH_DH
+    i = np.arange(B * S) % S
+    tile = (i // ENC_KT).astype(np.float64)
+    q = r.standard_normal((B * S, H, NH_DH)) * ENC_Q_SCALE
+    k = r.standard_normal((B * S, H, NH_DH))
+    v = r.standard_normal((B * S, H, NH_DH))
+    u = _enc_units(r, H, signs=name == "threshold")
+    if name == "ramp":
+        q += np.array([11.0, 3.0, 0.0, -11.0])[i % 4][:, None, None] * u
+        k += tile[:, None, None] * u
+    elif name == "spike":
+        q *= 8.0 * ENC_Q_SCALE / np.linalg.norm(q, axis=-1, keepdims=True)
+        q = d64(f16(q))
+        for b in range(B):
+            for h in range(H):
+                pi = b * S + r.permutation(S)
+                qh = q[b * S:(b + 1) * S, h]
+                k[pi, h] = ENC_SPIKE * qh / (qh * qh).sum(axis=-1, keepdims=True)
+    elif name == "threshold":
+        nT = -(-S // ENC_KT)
+        q -= (q * u).sum(axis=-1, keepdims=True) * u
+        q += (4.0 + np.where(i % 2 == 0, 0.5, -0.5) * ENC_THR_DELTA)[:, None, None] * u
+        spots = (31, 32, 0, 63, 8, 55, 16, 47, 23, 40)
+        for b in range(B):
+            for t in range(nT):
+                j = S - 1 if t == nT - 1 else t * ENC_KT + spots[t % len(spots)]
+                k[b * S + j] = (8.0 + 2.0 * t) * u
+    else:
+        q += np.where(i % 2 == 0, 35.0, -35.0)[:, None, None] * u
+        k += 32.0 * u
+        q, k = d64(f16(q)), d64(f16(k))
+        for b in range(B):
+            for h in range(H):
+                qd = q[b * S + 2 * (S // 4) + h % 2, h]
+                so = k[b * S:(b + 1) * S - 1, h] @ qd
+                k[(b + 1) * S - 1, h] = (so.max() + np.log2(np.exp2(so - so.max()).sum())) * qd / (qd @ qd)
+    case = tuple(f16(a.reshape(B * S, d)) for a in (q, k, v))
+    for a in case:
+        a.setflags(write=False)
+    _ENC_CASES[key] = case
+    return case
+
+
+def enc_rebase_coverage(name, rep, S):
+    """what the case's inputs must reach, from the replay alone (conditions on the inputs, not measurements of the kernel),
+    counting only decided (query, tile) pairs; asserts and returns the counts.  rep: enc_rebase_replay's dict.
+      ramp       at least 1000 rebases after tile 0 in every (clip, head); every full wave mixed: on some later tile one of its 32
+                 queries rebases and another does not; a largest non-rebased p above 200
+      spike      every query's largest score leads the next by 20; the rebase onto it hits every in-tile position in tile 1, in
+                 the middle tiles and in the last tile, where "every" is the S - 64 (nT - 1) positions that hold a key
+      threshold  at least 32 pairs within 2 delta on either side of the threshold, and p above 250 on the quiet side
+      offset     a final m_ref beyond 1000 of either sign, and nothing within a factor of 40 of the clamp"""
+    rows, H, nT = rep["rebase"].shape
+    B = rows // S
+    later = np.arange(nT) > 0
+    moved = rep["decided"] & rep["rebase"] & later          # decided rebases after tile 0
+    quiet = rep["decided"] & ~rep["rebase"] & later         # decided tiles that keep m_ref
+    per_head = moved.reshape(B, S, H, nT).sum(axis=(1, 3))
+    cov = {"rebases after tile 0 per (clip, head)": int(per_head.min()), "largest non-rebased p": float(rep["p_max"].max()),
+           "largest |m_ref|": float(rep["m_absmax"].max()), "undecided pairs": int((~rep["decided"]).sum()),
+           "near-threshold pairs": int(rep["near"].sum())}
+    if name == "ramp":
+        full = S // ENC_QW                                   # full waves of a clip (a workgroup's waves start at multiples of 32)
+        mv = moved.reshape(B, S, H, nT)[:, :full * ENC_QW].reshape(B, full, ENC_QW, H, nT).any(axis=2)
+        qt = quiet.reshape(B, S, H, nT)[:, :full * ENC_QW].reshape(B, full, ENC_QW, H, nT).any(axis=2)
+        cov["full waves"], cov["mixed full waves"] = B * full * H, int((mv & qt).any(axis=-1).sum())
+        assert per_head.min() >= 1000, cov
+        assert cov["mixed full waves"] == cov["full waves"], cov
+        assert cov["largest non-rebased p"] > 200, cov
+    elif name == "spike":
+        assert rep["margin"].min() >= 20.0, float(rep["margin"].min())
+        # the rebase onto the dominating key, by the tile it falls into and its position there; key S - 1 is the last live
+        # position of the last tile, keys 31 and 32 are positions of every full tile
+        last = S - (nT - 1) * ENC_KT
+        classes = {"tile 1": ([1], ENC_KT), "middle tiles": (list(range(2, nT - 1)), ENC_KT), "last tile": ([nT - 1], last)}
+        for cname, (ts, npos) in classes.items():
+            for b in range(B):
+                for h in range(H):
+                    hit = set()
+                    for t in ts:
+                        sel = moved[b * S:(b + 1) * S, h, t] & (rep["top_tile"][b * S:(b + 1) * S, h] == t)
+                        hit |= set(rep["pos"][b * S:(b + 1) * S, h, t][sel].tolist())
+                    assert hit == set(range(npos)), (cname, b, h, sorted(set(range(npos)) - hit))
+            cov[f"positions hit, {cname}"] = npos
+    elif name == "threshold":
+        w = 2 * ENC_THR_DELTA
+        cov["decided pairs just below"] = int((quiet & (rep["gap"] > ENC_REBASE - w)).sum())
+        cov["decided pairs just above"] = int((moved & (rep["gap"] < ENC_REBASE + w)).sum())
+        assert cov["decided pairs just below"] >= 32 and cov["decided pairs just above"] >= 32, cov
+        assert cov["largest non-rebased p"] > 250, cov
+    else:
+        cov["m_ref range"] = (float(rep["m_final"].min()), float(rep["m_final"].max()))
+        assert rep["m_final"].min() <= -1000 and rep["m_final"].max() >= 1000, cov
+        assert cov["largest |m_ref|"] < ENC_CLAMP / 40, cov
+    return cov
+
+
+def enc_rebase_reference(name, B, S, H=2):
+    """everything a test of one case needs, computed once and shared: inputs, fp64 reference, replay, bound, mutations"""
+    key = ("ref", name, B, S, H)
+    if key not in _ENC_CASES:
+        q, k, v = enc_rebase_case(name, B, S, H)
+        ref, sabs, vstat = enc_attention(q, k, v, B, S, H)
+        rep = enc_rebase_replay(q, k, S, H)
+        bound = attn_bound(ref, sabs, np.full(B * S, S), vstat, p16=True, log2=True, mref=rep["m_absmax"],
+                           p_floor=enc_p16_floor(q, k, v, B, S, H))
+        vm = np.array(v)
+        vm[:, -NH_DH:] = v[:, -2 * NH_DH:-NH_DH]
+        muts = {"last key dropped": enc_attention_keys(q, k, v, B, S, H, S - 1),
+                "last head reads the previous head's V": enc_attention(q, k, vm, B, S, H)[0]}
+        for label, bug in ENC_BUGS.items():
+            muts[label] = enc_emulate(q, k, v, B, S, H, bug=bug)
+        _ENC_CASES[key] = {"q": q, "k": k, "v": v, "ref": ref, "rep": rep, "bound": bound, "mutations": muts}
+    return _ENC_CASES[key]
 
 
 # ---- the one-pass prefill attention (k_prefill.hip) -------------------------------------------------------------------------
@@ -576,25 +903,48 @@ def ln_f16_bound(x, w, b):
     return U16 * np.abs(y) + SUB16 + e, y
 
 
-def attn_bound(o, sabs, n, vstat, p16=False, s_extra=0.0, v_extra=0.0, log2=False):
+def attn_score_error(sabs, s_extra=0.0, mref=0.0):
+    """the score error e of attn_bound, in the scores' own units (before the x ln2 of log2 scores)"""
+    return 64 * U32 * sabs + s_extra + 4 * U32 + (U32 + 2.0 ** -22) * mref
+
+
+def attn_bound(o, sabs, n, vstat, p16=False, s_extra=0.0, v_extra=0.0, log2=False, mref=0.0, p_floor=0.0):
     """o = sum_j p_j v_j with p = softmax(s).  Perturbing the scores by e_j moves o by sum_j p_j (e_j - sum_k p_k e_k) v_j
     = sum_j p_j e_j (v_j - o) to first order, so |do| <= e_max sum_j p_j |v_j - o| (doubled for the second order).  With
       score error  e <= 64 u sum_c|q_c||k_c| (f32 dot of 64 products) + s_extra (rounded operands) + 4 u (fast exp's argument);
                    x ln2 when the scores are log2 units (the encoder's exp2)
-      weights      relative error of P <= 2^-11 when P is rounded to fp16 for the matrix pipe (p16): the same first-order form
+      mref         enc_attn_kernel subtracts its reference maximum m_ref INSIDE the score accumulator: one more k-step adds
+                   hi + lo, two fp16 numbers with hi + lo = -m_ref.  hi is off by <= 2^-11 |m_ref|, lo = fp16(-m_ref - hi) by
+                   2^-11 of that: a residual <= 2^-22 |m_ref|; the accumulator holds a number of size |m_ref| when the step is
+                   added: one f32 rounding, u |m_ref|.  The residual is the same for every key between two rebases but differs
+                   from one stretch to the next, so it does not cancel: e += (u + 2^-22) mref, mref [B][H] = the largest
+                   |m_ref| the query's walk reaches (enc_rebase_replay), in the scores' units.  Not in this term: `m_ref +=
+                   dlt` rounds once per rebase while O, l and the tile's scores move by dlt exactly, r u |m_ref| after r
+                   rebases.  |m_ref| is a computed score, <= sabs (1 + 64 u), so all of this is <= (r + 5) u sabs, r <= 23; it
+                   is granted nothing beyond the 64 u sabs of the dot (whose four MFMA k-steps round far less than 64 times)
+      weights      relative error of P <= 2^-11 when P is rounded to fp16 for the matrix pipe (p16): the same first-order form.
+                   (enc_attn_kernel sums l from the UNROUNDED weights, so the common part o sum_j p_j eps_j, <= 2^-11 |o|, has
+                   no term here.  The sums term carries it from n >= 595 on: its own need is <= (n + 64) u on either sum (one
+                   addition per key, one product per rebase, 1 / l), and sum_j p_j|v_j| >= |o|, so what it grants beyond need
+                   is (7 n - 64) u (sum p|v| + |o|) >= (14 n - 128) u |o| >= 2^-11 |o|.  The product runs the kernel at n = 750
+                   and 1500 only.)
+      p_floor      below 2^-14, the smallest normal fp16, the rounding of a weight is absolute: up to 2^-25 per key, where
+                   2^-11 relative would be less.  A kernel that rounds P for the numerator only and keeps l >= 1 (the maximum
+                   of the last rebased tile has weight exactly 1) moves o by at most 2^-25 sum |v_j| over those keys:
+                   p_floor [B][H][64] (enc_p16_floor), added as it stands
       sums         the online-softmax accumulations of numerator and denominator, n keys: <= 4 n u relative each, on
                    sum_j p_j |v_j| and |o|
     |o_k - o| <= 2^-11 |o| + 2^-25 (fp16 output) + (2 e + 2 2^-11 [p16]) sum_j p_j|v_j - o| + 8 n u (sum_j p_j|v_j| + |o|)
-    + v_extra.  sabs, s_extra: [B][H]; vstat = (vdev, pv) [B][H][64] from the reference; o [B][H*64]."""
+    + p_floor + v_extra.  sabs, s_extra, mref: [B][H]; vstat = (vdev, pv) [B][H][64] from the reference; o [B][H*64]."""
     vdev, pv = vstat
     B, H = sabs.shape
-    e = 64 * U32 * sabs + s_extra + 4 * U32
+    e = attn_score_error(sabs, s_extra, mref)
     if log2:
         e = e * np.log(2.0)
     w = 2 * e + (2 * U16 if p16 else 0.0)
     nn = np.asarray(n, dtype=np.float64).reshape(-1, 1, 1)
     ao = np.abs(o).reshape(B, H, NH_DH)
-    return (U16 * ao + SUB16 + w[:, :, None] * vdev + 8 * nn * U32 * (pv + ao)).reshape(B, H * NH_DH) + v_extra
+    return (U16 * ao + SUB16 + w[:, :, None] * vdev + 8 * nn * U32 * (pv + ao) + p_floor).reshape(B, H * NH_DH) + v_extra
 
 
 # ---- discrimination --------------------------------------------------------------------------------------------------------

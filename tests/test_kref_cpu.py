@@ -301,6 +301,107 @@ def test_xabs_bound_holds_for_an_f32_fp16_emulation_of_the_kernels():
     assert K.violation(ref, bound, K.xabs_attention(q, Wkv, bkv, xa[:, :-1], H)) > 0
 
 
+# ---- enc_attn_kernel's deferred-maximum rebase: replay, cases, bound, emulation, mutations -----------------------------------
+def test_enc_rebase_replay_is_the_per_query_rule():
+    """the vectorised replay against a loop over queries, tiles and keys on a small ramp (rebases, quiet tiles, a partial tile)"""
+    r = _r(20)
+    S, H = 150, 2
+    u = r.standard_normal((H, 64)); u /= np.linalg.norm(u, axis=-1, keepdims=True)
+    q = r.standard_normal((S, H, 64)) * K.ENC_Q_SCALE + np.array([11.0, 3.0, 0.0, -11.0])[np.arange(S) % 4][:, None, None] * u
+    k = r.standard_normal((S, H, 64)) + (np.arange(S) // 64)[:, None, None] * u
+    q, k = K.f16(q.reshape(S, 128)), K.f16(k.reshape(S, 128))
+    rep = K.enc_rebase_replay(q, k, S, H)
+    assert rep["rebase"].shape == (S, H, 3) and rep["rebase"][:, :, 0].all()
+    seen = set()
+    for i in range(S):
+        for h in range(H):
+            s = [float(np.dot(K.d64(q[i, 64 * h:64 * h + 64]), K.d64(kk[64 * h:64 * h + 64]))) for kk in k]
+            m = max(s[:64])
+            pmax, mabs = 0.0, abs(m)
+            for t in (1, 2):
+                tile = s[64 * t:64 * t + 64]
+                gap = max(tile) - m
+                assert np.isclose(rep["gap"][i, h, t], gap, rtol=0, atol=1e-9) and rep["pos"][i, h, t] == int(np.argmax(tile))
+                assert rep["rebase"][i, h, t] == (gap > 8.0)
+                seen.add(bool(gap > 8.0))
+                if gap > 8.0:
+                    m = max(tile)
+                elif rep["decided"][i, h, t]:
+                    pmax = max(pmax, 2.0 ** gap)
+                mabs = max(mabs, abs(m))
+            assert np.isclose(rep["m_final"][i, h], m) and np.isclose(rep["m_absmax"][i, h], mabs)
+            assert np.isclose(rep["p_max"][i, h], pmax)
+            assert rep["top_tile"][i, h] == int(np.argmax(s)) // 64
+            assert np.isclose(rep["margin"][i, h], sorted(s)[-1] - sorted(s)[-2])
+    assert seen == {True, False}
+    # near / decided: a gap within 2 e of the threshold is undecided, and so is every later tile of that query.  Two keys that
+    # score 16 and 24 + 2^-13 for every query (e = 64 u 24 + ..: 1e-4): tile 1 is near, tile 2 (gap -8 or 8 - 1e-4) inherits it
+    q2, k2 = np.zeros((130, 64), np.float16), np.zeros((130, 64), np.float16)
+    q2[:, 0], k2[5, 0], k2[70, 0], k2[70, 1] = 4.0, 4.0, 6.0, 1.0
+    q2[:, 1] = 2.0 ** -13
+    rep2 = K.enc_rebase_replay(q2, k2, 130, 1)
+    assert np.allclose(rep2["gap"][:, 0, 1], 8.0 + 2.0 ** -13) and 2.0 ** -13 < 2 * rep2["e"].min()
+    assert rep2["near"][:, 0, 1].all() and not rep2["near"][:, 0, 2].any() and not rep2["near"][:, 0, 0].any()
+    assert rep2["decided"][:, 0, 0].all() and not rep2["decided"][:, 0, 1:].any() and (rep2["p_max"] == 0).all()
+
+
+def test_gaussian_inputs_never_rebase_after_tile_0():
+    """why the adversarial cases exist: on the inputs of test_gpu_kernel_ref.py::test_enc_attention_matches_fp64[1-1500-6] m_ref is
+    set on tile 0 and never moves again, so the rescale of O and l and the rewrite of the fp16 pair run on no query"""
+    B, S, H = 1, 1500, 6
+    r = np.random.default_rng(K.zlib_key("enc", B, S, H))
+    q = K.f16(r.standard_normal((B * S, 64 * H)) * K.ENC_Q_SCALE)
+    k = K.f16(r.standard_normal((B * S, 64 * H)))
+    rep = K.enc_rebase_replay(q, k, S, H)
+    assert rep["rebase"][:, :, 0].all() and not rep["rebase"][:, :, 1:].any()
+    assert not rep["near"].any() and rep["p_max"].max() < 64 and rep["m_absmax"].max() < 16
+    print("Gaussian (1, 1500, 6): largest p", rep["p_max"].max(), "largest |m_ref|", rep["m_absmax"].max())
+
+
+@pytest.mark.parametrize("name", K.ENC_REBASE_CASES)
+def test_enc_rebase_cases_reach_their_paths_and_the_emulation_meets_the_bound(name):
+    """per adversarial case of tests/test_gpu_enc_attn_ref.py, without a GPU: the replay's coverage conditions hold at every
+    shape; at (1, 750) an emulation of the kernel's arithmetic lies inside the bound while each of its four rebase bugs, a
+    dropped last key and the wrong head's V leave it by more than 2x"""
+    for B, S in K.ENC_REBASE_SHAPES[1:]:
+        q, k, _ = K.enc_rebase_case(name, B, S)
+        print(name, B, S, K.enc_rebase_coverage(name, K.enc_rebase_replay(q, k, S, 2), S))
+    B, S = K.ENC_REBASE_SHAPES[0]
+    c = K.enc_rebase_reference(name, B, S)
+    print(name, B, S, K.enc_rebase_coverage(name, c["rep"], S))
+    got = K.enc_emulate(c["q"], c["k"], c["v"], B, S, 2)
+    print("emulation, |err| / bound:", K.violation(c["ref"], c["bound"], got))
+    K.within(got, c["ref"], c["bound"], f"emulated encoder attention, {name}")
+    assert set(c["mutations"]) == set(K.ENC_BUGS) | {"last key dropped", "last head reads the previous head's V"}
+    print(K.discriminates(c["ref"], c["bound"], c["mutations"]))
+    if name == "offset":
+        # the kernel's former arithmetic: alpha = exp2(-maximum) on tile 0 too, inf below -128, times O = l = 0
+        former = K.enc_emulate(c["q"], c["k"], c["v"], B, S, 2, tile0_rescale=True)
+        assert np.isnan(former[1::2].astype(np.float64)).all() and np.array_equal(former[0::2], got[0::2])
+
+
+def test_enc_bound_terms_for_the_deferred_maximum():
+    """attn_bound's mref and p_floor: each adds exactly its documented amount, and the floor counts the keys it should"""
+    r = _r(21)
+    B, S, H = 1, 130, 1
+    q, k, v = K.f16(r.standard_normal((S, 64)) * 0.5), K.f16(r.standard_normal((S, 64))), K.f16(r.standard_normal((S, 64)))
+    k[70] = K.f16(40.0 * K.d64(q[3]) / np.dot(K.d64(q[3]), K.d64(q[3])))          # query 3: key 70 scores 40
+    ref, sabs, vst = K.enc_attention(q, k, v, B, S, H)
+    base = K.attn_bound(ref, sabs, np.full(S, S), vst, p16=True, log2=True)
+    mref = np.full((S, H), 100.0)
+    with_m = K.attn_bound(ref, sabs, np.full(S, S), vst, p16=True, log2=True, mref=mref)
+    assert np.allclose(with_m - base, 2 * np.log(2.0) * (2.0 ** -24 + 2.0 ** -22) * 100.0 * vst[0].reshape(S, 64), rtol=1e-9, atol=1e-15)
+    floor = K.enc_p16_floor(q, k, v, B, S, H)
+    assert np.array_equal(K.attn_bound(ref, sabs, np.full(S, S), vst, p16=True, log2=True, p_floor=floor), base + floor.reshape(S, 64))
+    # query 3, by hand: tile 0's keys are rounded against tile 0's maximum, tile 1 and 2 against the running maximum 40
+    s = K.d64(k) @ K.d64(q[3])
+    run = np.where(np.arange(S) < 64, s[:64].max(), max(s[:64].max(), s[64:128].max()))
+    run[128:] = max(run[127], s[128:].max())
+    assert np.isclose(run[70], s[70]) and abs(s[70] - 40) < 0.1
+    want = 2.0 ** -25 * np.abs(K.d64(v))[s - run < -14].sum(axis=0)
+    assert np.allclose(floor[3, 0], want, rtol=1e-12, atol=0) and (s - run < -14)[64:].sum() > 50
+
+
 # ---- the one-pass prefill attention (prefill_attn_kernel): reference, bound, discrimination ---------------------------------
 def test_prefill_attention_is_a_per_query_softmax():
     r = _r(10)
