@@ -429,6 +429,55 @@ int nh_decode_beam(nh_ctx *ctx, int beam_size, int32_t *out_tokens, nh_decode_re
  * every one of its rows is written, so buffers of NH_MAX_BEAMS rows always suffice.  NH_ERR_STATE without a beam decode to
  * report on. */
 int nh_beam_hypotheses(nh_ctx *ctx, int b, int32_t *tokens, int32_t *n_tokens, double *sum_logprob, int32_t *n_finished);
+/* ---- repetition guard ----------------------------------------------------------------------------------------
+ * Four edits of a row's f32 logits between the step's logits and the selection kernels, from nothing but the tokens the row
+ * has generated; one kernel, in every decode mode (greedy, sampled, pool, beam).  With every component off (the default) a
+ * step launches nothing for it and every result keeps its bits.
+ * For a row that is running (done == 0) and stands at a generation position: PL = the physical prompt length of the step
+ * (prefix + [sot, lang?, task]), n = its token count, g = tokens[PL .. n), h = the entries of g with id < eot in order (text
+ * only: timestamps and specials are dropped, so a loop whose copies carry different timestamps is a loop), m = len(h).  In
+ * this order:
+ *   1 repetition_penalty r (r > 0, 1.0f off): for every DISTINCT v in h, once: x = logits[v]; logits[v] = x < 0 ? x * r : x / r
+ *     (one IEEE f32 multiply, or one correctly rounded divide).
+ *   2 bias (bias != 0): for every entry (v, beta) of the row's list (nh_guard_bias): logits[v] += beta in f32.
+ *   3 no_repeat_ngram N (1 .. 16, 0 off): if m >= N - 1, s = h[m-N+1 .. m); for every i in [0, m-N] with h[i .. i+N-1) == s:
+ *     logits[h[i+N-1]] = -inf.  N = 1 bans every token of h.
+ *   4 loop exit (loop_period Pmax 1 .. 64, 0 off; loop_repeats R 2 .. 16; Pmax * R <= 448): if some p <= Pmax has p * R <= m and
+ *     h[m-1-i] == h[m-1-i-p] for all 0 <= i < p * (R - 1), and the row's own rule state is "last token a timestamp, the one
+ *     before it no text" (text only) or "last token text" -- the two states in which the rules leave eot unmasked; in the
+ *     others (first generated token; a timestamp right after text, which a timestamp must follow) the exit waits for the
+ *     next step, h unchanged -- every logit except
+ *     eot's becomes -inf and the row's loop-exit flag is set.  The selection kernels then pick eot by themselves with
+ *     log-probability log 1 = 0.  The flag is cleared when the row stands at its first generation position (n == PL).
+ * Never edited: rows in their prompt phase or at the no-speech probe, finished rows, the pad columns, and anything in
+ * nh_detect_language, nh_score, nh_align and the nh_decoder_forward* views.  avg_logprob is the log of the softmax over the
+ * EDITED logits. */
+typedef struct nh_guard_params { int32_t no_repeat_ngram; float repetition_penalty; int32_t loop_period, loop_repeats; int32_t bias; } nh_guard_params;
+/* The context's guard (its own per context, nh_create_shared children included), kept until changed; NULL: off.  Refused, state
+ * untouched: NH_ERR_INVALID for a NaN, infinite or non-positive penalty or sizes out of range (with loop_period == 0,
+ * loop_repeats must be 0 or 2 .. 16 and is not used), NH_ERR_STATE while any pool row is busy (the captured step graphs carry
+ * whether the kernel is in them) and on a model with max_target_positions > 512 (the kernel holds a row's history in LDS).  A change takes effect in the next decode, under
+ * NH_OPT_DECODE_GRAPHS too. */
+int nh_set_guard(nh_ctx *ctx, const nh_guard_params *p);
+#define NH_GUARD_MAX_BIAS 256
+/* The bias list of context row `row` (host arrays of n entries; n == 0: clear), kept until replaced or cleared and applied
+ * while nh_guard_params.bias != 0; in a pool the caller sets it before nh_pool_admit of that row.  Under nh_decode_beam
+ * hypothesis row j * B + b uses clip b's list.  The device table is made by the first use.  Ordered on the context's stream;
+ * returns when the caller's buffers are no longer needed.  Refused (NH_ERR_INVALID), lists untouched: a row outside
+ * [0, max_batch), n outside 0 .. NH_GUARD_MAX_BIAS, an id twice, an id outside [0, V), a bias NaN or +inf (-inf is allowed). */
+int nh_guard_bias(nh_ctx *ctx, int row, const int32_t *tokens, const float *bias, int n);
+/* The loop-exit flags (host i32 [n]) of rows[0 .. n) (rows == NULL: rows 0 .. n-1): of the lockstep batch after a greedy or
+ * sampled decode; of pool rows while they run and after nh_pool_collect until the row is refilled.  NH_ERR_STATE after
+ * nh_decode_beam: the exit ends hypotheses there too, but the flag does not travel with a hypothesis. */
+int nh_guard_report(nh_ctx *ctx, const int32_t *rows, int n, int32_t *loop_exit);
+/* Parity view: the edit alone, by the kernel of the step, under the context's nh_set_guard parameters.  logits host f32
+ * [rows][V]; row r holds tokens[r * stride .. + n_tokens[r]) (prompt_len <= n_tokens[r] <= max_target_positions - 2), is edited
+ * only if active == NULL or active[r] != 0, and uses the bias list of context row bias_rows[r] (NULL or < 0: none).  Whether a
+ * timestamp has been generated is read off the tokens.  logits_out host f32 [rows][ld], ld = V rounded up to 64: the device
+ * rows whole, pad columns (uploaded as all-ones bit patterns) included; loop_exit host i32 [rows].  Overwrites the context's
+ * token rows and logits like nh_beam_step. */
+int nh_guard_apply(nh_ctx *ctx, int rows, const float *logits, const int32_t *tokens, const int32_t *n_tokens, int64_t stride,
+                   int prompt_len, const int32_t *active, const int32_t *bias_rows, float *logits_out, int32_t *loop_exit);
 /* Model::detect_language (model.rs:194-210) for every clip of the batch: one decoder step on [sot], softmax over the
  * n language-token logits (lang_tokens in `Language::iter()` order, multilingual.rs:395-398), first maximum.
  * out_lang: host i32 [batch]; out_probs: host f32 [batch][n] or NULL.  The detected tokens become the per-sequence

@@ -158,6 +158,15 @@ void nm_model_set_prompt_tokens(nm_model *m, const int32_t *ids, int n);
 void nm_model_set_condition_on_previous(nm_model *m, int enable);
 void nm_model_set_startofprev_token(nm_model *m, int32_t id);
 int nm_model_prompt_prefix(const nm_model *m, int32_t *ids, int cap);
+/* The repetition guard of every decode of the model (nh_set_guard of norma_hip.h; no counterpart in the reference):
+ * no-repeat n-gram, repetition penalty, loop exit (period, repeats) and whether the token bias applies.  (0, 1.0, 0, 0, 0), the
+ * default, is off: the calls and the bits of a model without it.  set_token_bias: n (id, bias) pairs for the model's single
+ * row, finite or -inf, applied while the guard's bias != 0; n = 0 clears.  Both return 0, or 1 when nh_set_guard /
+ * nh_guard_bias refuse (nothing changes).  last_loop_exit: 1 when the last decoded slice left by the loop exit (never under a
+ * beam: the flag does not travel with a hypothesis). */
+int nm_model_set_repetition_guard(nm_model *m, int no_repeat_ngram, float repetition_penalty, int loop_period, int loop_repeats, int bias);
+int nm_model_set_token_bias(nm_model *m, const int32_t *ids, const float *bias, int n);
+int nm_model_last_loop_exit(const nm_model *m);
 /* DecodingResult of the last decoded slice + whether the reference would have entered its sampled fallback */
 void nm_model_last_result(const nm_model *m, double *avg_logprob, double *no_speech_prob, int *needed_fallback,
                           int *n_tokens);

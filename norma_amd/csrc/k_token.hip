@@ -343,6 +343,11 @@ __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict
     // slice maximum first, then one exp per element against it (the slice lives in registers)
 #pragma unroll
     for (int u = 0; u < LMAX; u++) m = fmaxf(m, lv[u]);
+    // a thread whose logits are all -inf (the guard's loop exit leaves eot alone, k_guard.hip): exp(-inf - -inf) is NaN,
+    // exp(-inf + FLT_MAX) is 0, and its pair (-inf, 0) then merges as nothing.  A finite m is its own maximum with -FLT_MAX.
+    // Spelled as a maximum, not as a select on m == -inf: a select lets the compiler fold the merge factors below and drop
+    // the fused multiply-add of the first merge, which moves sums by an ulp.
+    const float me = fmaxf(m, -3.402823466e+38f);   // -FLT_MAX
 #pragma unroll
     for (int u = 0; u < LMAX; u++) {
         const int i = lo + tid + 256 * u;
@@ -350,7 +355,7 @@ __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict
         const float l = lv[u];
         const bool is_ts = i > NT;
         const bool sup = sv[u] != 0;
-        const float e = __expf(l - m);   // softmax mass, and the timestamp mass of model.rs:263-266
+        const float e = __expf(l - me);  // softmax mass, and the timestamp mass of model.rs:263-266
         se += e;
         if (is_ts) { ts += e; if (sup) tsinf = 1.f; }  // p + (-inf) inside the summed slice -> the sum is -inf
         if (kind == STEP_FIRST) { if (i >= tk.zero_sec && i <= tk.one_sec) better(av, ai, l, i); }

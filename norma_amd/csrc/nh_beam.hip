@@ -93,6 +93,7 @@ extern "C" int nh_decode_beam(nh_ctx *ctx, int beam_size, int32_t *out_tokens, n
         for (int pos = first_pos; pos <= cap - 2; pos++) {
             decoder_step(ctx, pos, nullptr, false, true, nullptr);
             logits_from_dx(ctx, R);
+            if (ctx->guard.on) emit_guard(ctx, R, PL, nullptr, B);   // hypothesis row j * B + b: clip b's bias list
             emit_beam_select_merge(ctx, B, K, max_new_tokens, PL);
             if (K > 1) emit_beam_reorder(ctx, B, K, pos + 1);
             steps++;
@@ -133,6 +134,7 @@ extern "C" int nh_decode_beam(nh_ctx *ctx, int beam_size, int32_t *out_tokens, n
         finish_sequence(ctx, win.data(), bs.fin_n[b * K + best], 1, bs.fin_score[b * K + best], h.nsp[b], out_tokens + (size_t)b * C, results[b], NP);
     }
     bs.valid = true; bs.B = B; bs.K = K; bs.skip = NP;
+    ctx->guard.after_beam = true;   // the loop-exit flag does not travel with a hypothesis (nh_guard_report)
     ctx->tm.decode_steps = steps;
     ctx->live.lock_valid = false; ctx->live.P = dp.P;   // the kept queries are not reordered with their hypotheses: nh_align_decoded refuses
     return NH_OK;

@@ -95,9 +95,10 @@ struct StepKey {
     int B = -1, S = -1, max_new = -1, P = -1, token_gen = -1, lang_n = -1;
     bool pool = false, sampled = false;
     int align_gen = 0;   // the alignment heads whose queries the steps keep go by value too (nh_align_capture)
+    int guard_gen = 0;   // ... and so do the guard's parameters, its tables, and whether its kernel is in the step (nh_set_guard)
     bool operator==(const StepKey &o) const {
         return B == o.B && S == o.S && max_new == o.max_new && P == o.P && token_gen == o.token_gen && lang_n == o.lang_n &&
-               pool == o.pool && sampled == o.sampled && align_gen == o.align_gen;
+               pool == o.pool && sampled == o.sampled && align_gen == o.align_gen && guard_gen == o.guard_gen;
     }
 };
 struct StepGraphs {
@@ -209,6 +210,19 @@ struct ScoreState {
     float *part = nullptr;       // the tile partials of one row panel (launch_score_rows)
 };
 
+// nh_set_guard / nh_guard_bias: the repetition guard of the context's decode steps.  on == false (the default): a step launches
+// nothing for it.  The flags are made by the first nh_set_guard that switches something on, the bias table by the first
+// nh_guard_bias (or by enabling the bias): a context that never calls them holds nothing.
+struct GuardState {
+    GuardSpec spec{0, 1.0f, 0, 0, 0};
+    bool on = false;
+    int gen = 0;                    // in StepKey; bumped whenever spec changes or a table is made
+    int32_t *loop_exit = nullptr;   // [max_batch]
+    int32_t *bias_tok = nullptr, *bias_n = nullptr, *bias_map = nullptr;   // [max_batch][NH_GUARD_MAX_BIAS], [max_batch], [max_batch] (nh_guard_apply)
+    float *bias_val = nullptr;
+    bool after_beam = false;        // the last lockstep decode was a beam search: nh_guard_report refuses
+};
+
 struct nh_ctx {
     int dev = 0;
     std::shared_ptr<nh_model> mdl;
@@ -267,6 +281,7 @@ struct nh_ctx {
     AlignLive live;              // nh_align_capture
     BeamState beam;              // nh_decode_beam
     ScoreState score;            // nh_score
+    GuardState guard;            // nh_set_guard, nh_guard_bias, nh_guard_report, nh_guard_apply
     // The context's one query buffer, fp16 [align_q_heads][C - 1][max_batch][64]: nh_align's teacher-forced pass and the decodes
     // under nh_align_capture both write it, stages 2 - 6 read it.  Grown by align_q_buffer alone, freed by nh_destroy.
     half_t *align_q = nullptr;
@@ -333,6 +348,10 @@ struct DecodePrompt { int B, NP, P, PL, steps; };   // batch, prefix length, pro
 int decode_refusals(nh_ctx *ctx);
 int decode_prompt_phase(nh_ctx *ctx, int max_new_tokens, DecodePrompt &dp);
 void logits_from_dx(nh_ctx *ctx, int R);
+// nh_guard.hip: the guard's launch on the R rows whose logits the step just wrote, ahead of the selection kernels.  Callers
+// check ctx->guard.on first: with the guard off a step emits nothing.  pos: a pool's per-row positions, nullptr otherwise;
+// clips: the batch's clips (row r uses the bias list of context row r % clips).
+void emit_guard(nh_ctx *ctx, int R, int prompt_len, const int32_t *pos, int clips);
 // LayerNorm of R rows of f32 x[R][K]: the sliced summation tree of the decode step where the width allows, so that the fused
 // and the stand-alone forms, every batch size and the one-pass forward give bit-identical rows
 void dec_layernorm(nh_ctx *ctx, const LnW &ln, const float *x, half_t *y, float *y32, int R, int K);

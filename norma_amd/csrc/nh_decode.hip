@@ -163,6 +163,7 @@ static void emit_token_step(nh_ctx *ctx, const StepSpec &s) {
     logits_from_dx(ctx, s.B);
     if (pool && ctx->pool.lang_n > 0)
         launch_pool_lang_detect(ctx->logits, V, ctx->ds, s.B, C, s.pos_ptr, PoolDetect{ctx->d_lang_flag, ctx->d_lang_tokens, ctx->pool.lang_n, ctx->d_lang_out, ctx->d_lang_probs}, ctx->st);
+    if (ctx->guard.on) emit_guard(ctx, s.B, s.P, pool ? s.pos_ptr : nullptr, s.B);   // nh_set_guard; off: nothing is launched
     if (s.sampled && !pool) {  // lockstep sampled: every sequence draws its token
         launch_sample_step(ctx->logits, V, ctx->ds, ctx->tk, s.B, C, cap, s.max_new, s.P, s.inv_t, s.seed, s.clip0, s.attempt, ctx->st);
         return;
@@ -289,7 +290,7 @@ static int decode_impl(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *resul
     // reads the position from device memory (the eager loop is host-launch-bound at ~5 us per tiny kernel).
     const bool no_graph = !ctx->opt_graphs || inv_t > 0.f;
     if (!no_graph)
-        if (int rc = ensure_step_graphs(ctx, StepKey{B, ctx->S, max_new_tokens, PL, ctx->token_gen, 0, false, false, ctx->live.gen})) return rc;
+        if (int rc = ensure_step_graphs(ctx, StepKey{B, ctx->S, max_new_tokens, PL, ctx->token_gen, 0, false, false, ctx->live.gen, ctx->guard.gen})) return rc;
     const int32_t first_pos = PL - 1;
     for (int b = 0; b < B; b++) ctx->h_done[128 + b] = first_pos;  // every sequence of a batch starts generating at the same position
     HIPCHK(hipMemcpyAsync(ctx->d_pos, ctx->h_done + 128, sizeof(int32_t) * B, hipMemcpyHostToDevice, ctx->st));
@@ -319,6 +320,7 @@ static int decode_impl(nh_ctx *ctx, int32_t *out_tokens, nh_decode_result *resul
     HIPCHK(hipGetLastError());
     if (int rc = read_results(ctx, nullptr, B, out_tokens, results, NP)) return rc;
     ctx->tm.decode_steps = steps;
+    ctx->guard.after_beam = false;
     // after a prompted decode the kept queries sit at physical positions, which nh_align_decoded does not map: it refuses
     ctx->live.lock_valid = kept_heads(ctx) != nullptr && NP == 0; ctx->live.P = P;
     return NH_OK;
@@ -450,7 +452,7 @@ extern "C" int nh_pool_step(nh_ctx *ctx, int n_steps, int32_t *done_out) {
         if (ctx->S < 1) return ctx->fail(NH_ERR_STATE, "nh_pool_step: rows are busy but nothing was ever encoded");
         const StepGraphs &g = ctx->graphs[sampled];
         for (int s = 0; ctx->opt_graphs && s <= (int)sampled; s++)   // the greedy pair also when this call replays the sampled one
-            if (int rc = ensure_step_graphs(ctx, StepKey{B, ctx->S, pl.max_new, pl.prompt, ctx->token_gen, pl.lang_n, true, s == 1, ctx->live.gen})) return rc;
+            if (int rc = ensure_step_graphs(ctx, StepKey{B, ctx->S, pl.max_new, pl.prompt, ctx->token_gen, pl.lang_n, true, s == 1, ctx->live.gen, ctx->guard.gen})) return rc;
         for (int left = n_steps; left > 0;) {
             if (!ctx->opt_graphs) {
                 emit_token_step(ctx, StepSpec{B, pl.max_new, pl.prompt, 2, sampled, 0, ctx->d_pos, 0.f, 0, 0, 0});

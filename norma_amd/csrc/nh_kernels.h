@@ -482,6 +482,25 @@ struct PoolDetect {
 };
 void launch_pool_lang_detect(const float *logits, int V, DecodeState s, int B, int ctx, const int32_t *pos, PoolDetect det,
                              hipStream_t st);
+// ---- repetition guard (k_guard.hip; contract: nh_set_guard in include/norma_hip.h) ----------------------------
+#define NH_GUARD_MAX_BIAS 256      // the public header's, token for token (both may be in one translation unit)
+#define NH_GUARD_MAX_PERIOD 64     // loop_period at most
+#define NH_GUARD_MAX_HISTORY 512   // generated tokens a row can hold: nh_set_guard refuses max_target_positions above it
+// nh_guard_params as the kernel takes it, by value (so part of what a captured step bakes in: StepKey::guard_gen)
+struct GuardSpec { int ngram; float penalty; int loop_period, loop_repeats, bias; };
+struct GuardBufs {
+    const int32_t *bias_tok;   // i32 [max_batch][NH_GUARD_MAX_BIAS] per context row; nullptr: no list was ever set
+    const float *bias_val;     // f32 [max_batch][NH_GUARD_MAX_BIAS]
+    const int32_t *bias_n;     // i32 [max_batch] entries of every row's list
+    const int32_t *bias_map;   // i32 [R] the context row whose list row r uses (< 0: none); nullptr: row r uses list r % bias_mod
+    int bias_mod;              // the clips of the batch (beam search: hypothesis row j * B + b uses clip b's list)
+    int32_t *loop_exit;        // i32 [R] set when the row takes the loop exit, cleared at its first generation position
+};
+// Goes between the step's logits [R][nh_logits_ld(V)] and the selection kernels.  Edits the rows with done == 0 that stand at
+// a generation position (pos == nullptr: all of them; decode pool: pos[r] >= prompt_len - 1); the pad columns, every other
+// row and all decode state but loop_exit stay as they are.  max_target_positions <= NH_GUARD_MAX_HISTORY.
+void launch_guard(float *logits, int V, DecodeState s, RuleTokens tk, int R, int ctx, int prompt_len, const int32_t *pos, GuardSpec g,
+                  GuardBufs gb, hipStream_t st);
 // parity helper: apply rules to one already soft-maxed probability vector
 void launch_rules_only(const float *probs_in, float *masked_out, int32_t *argmax_out, const int32_t *tokens,
                        int n_tokens, int last_ts, const uint8_t *suppress, RuleTokens tk, int V, hipStream_t st);

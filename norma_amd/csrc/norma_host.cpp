@@ -235,6 +235,15 @@ int nm_model_set_beam_size(nm_model *m, int k) {
     if (!m || !m->m) return 1;
     return m->m->set_beam_size(k) ? 1 : 0;
 }
+int nm_model_set_repetition_guard(nm_model *m, int no_repeat_ngram, float repetition_penalty, int loop_period, int loop_repeats, int bias) {
+    if (!m || !m->m) return 1;
+    return m->m->set_repetition_guard(nh_guard_params{no_repeat_ngram, repetition_penalty, loop_period, loop_repeats, bias}) ? 1 : 0;
+}
+int nm_model_set_token_bias(nm_model *m, const int32_t *ids, const float *bias, int n) {
+    if (!m || !m->m || n < 0 || (n > 0 && (!ids || !bias))) return 1;
+    return m->m->set_token_bias(ids, bias, n) ? 1 : 0;
+}
+int nm_model_last_loop_exit(const nm_model *m) { return m && m->m && m->m->last_result().loop_exit ? 1 : 0; }
 void nm_model_set_prompt_tokens(nm_model *m, const int32_t *ids, int n) {
     if (m && m->m) m->m->set_prompt_tokens(ids && n > 0 ? std::vector<int32_t>(ids, ids + n) : std::vector<int32_t>());
 }

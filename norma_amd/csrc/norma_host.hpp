@@ -230,6 +230,7 @@ struct DecodingResult {  // model.rs:494-499
     // with alignment heads set (Model::set_alignment_heads): first and last 20 ms encoder frame of every token, -1 for the
     // prompt; empty otherwise (no counterpart in the reference, whose timing stops at the segment)
     std::vector<int32_t> first_frame, last_frame;
+    bool loop_exit = false;   // the decode left by the repetition guard's loop exit (Model::set_repetition_guard; never under a beam)
 };
 
 // one `<ts> text <ts|eot>` span, model.rs:100-149.  token_start / token_end: seconds from the start of the slice the segment was
@@ -245,7 +246,8 @@ class Model {
                                 align_heads_(std::move(o.align_heads_)), checkpoint_heads_(std::move(o.checkpoint_heads_)), capture_stale_(o.capture_stale_),
                                 src_hz_(o.src_hz_), channels_(o.channels_), resampler_(std::move(o.resampler_)),
                                 prompt_tokens_(std::move(o.prompt_tokens_)), history_(std::move(o.history_)), condition_(o.condition_), sop_token_(o.sop_token_),
-                                suppress_(std::move(o.suppress_)), suppress_known_(o.suppress_known_), beam_size_(o.beam_size_), ctx_rows_(o.ctx_rows_) { o.ctx_ = nullptr; }
+                                suppress_(std::move(o.suppress_)), suppress_known_(o.suppress_known_), beam_size_(o.beam_size_), ctx_rows_(o.ctx_rows_),
+                                guard_(o.guard_), bias_tok_(std::move(o.bias_tok_)), bias_val_(std::move(o.bias_val_)) { o.ctx_ = nullptr; }
     Model(const Model &) = delete;
     ~Model() { if (ctx_) nh_destroy(ctx_); }
 
@@ -396,12 +398,28 @@ class Model {
             nh_ctx *c = nullptr;
             if (nh_create_shared(ctx_, k, &c)) return backend_error();
             if (nh_set_tokens(c, &tk_, suppress_.data(), (int)suppress_.size())) { Error e{Error::Backend, nh_last_error(c)}; nh_destroy(c); return e; }
+            // ... and the same guard and bias list
+            if (nh_set_guard(c, &guard_) || nh_guard_bias(c, 0, bias_tok_.data(), bias_val_.data(), (int)bias_tok_.size())) { Error e{Error::Backend, nh_last_error(c)}; nh_destroy(c); return e; }
             nh_destroy(ctx_);
             ctx_ = c; ctx_rows_ = k;
             if (resampler_) resampler_->rebind(c);
             capture_stale_ = !align_heads_.empty();
         }
         beam_size_ = k;
+        return Error{};
+    }
+    // The repetition guard of every decode of this model (nh_set_guard, include/norma_hip.h; no counterpart in the reference):
+    // no-repeat n-gram, repetition penalty, loop exit, and whether the token bias below applies.  {0, 1.0, 0, 0, 0} (the
+    // default) is off: the calls and the bits of a model without it.  A refused value leaves the guard as it was.
+    Error set_repetition_guard(const nh_guard_params &p) {
+        if (nh_set_guard(ctx_, &p)) return backend_error();
+        guard_ = p;
+        return Error{};
+    }
+    // {token: beta} for the model's single row (nh_guard_bias), applied while the guard has bias != 0; n = 0 clears it
+    Error set_token_bias(const int32_t *ids, const float *beta, int n) {
+        if (nh_guard_bias(ctx_, 0, ids, beta, n)) return backend_error();
+        bias_tok_.assign(ids, ids + (n > 0 ? n : 0)); bias_val_.assign(beta, beta + (n > 0 ? n : 0));
         return Error{};
     }
     void set_suppress_tokens(std::vector<int32_t> ids) { suppress_ = std::move(ids); suppress_known_ = true; }   // what the context was told (the loaders call it)
@@ -436,6 +454,12 @@ class Model {
             dr.tokens.assign(toks.begin(), toks.begin() + r.n_tokens);
             dr.avg_logprob = r.avg_logprob; dr.no_speech_prob = r.no_speech_prob;
             dr.compression_ratio = 0.0 / 0.0;                                    // f64::NAN, :387
+            dr.loop_exit = false;
+            if (guard_.loop_period > 0 && !beam) {                               // the flag does not travel with a beam hypothesis
+                int32_t le = 0;
+                if (nh_guard_report(ctx_, nullptr, 1, &le)) return backend_error();
+                dr.loop_exit = le != 0;
+            }
             // :177-187 -- accept unless avg_logprob < -1 (compression_ratio is NaN, so that test is always false)
             const bool needs_fallback = dr.avg_logprob < LOGPROB_THRESHOLD;
             if (a == 0) needs_fallback_ = needs_fallback && !(dr.no_speech_prob > NO_SPEECH_THRESHOLD);
@@ -487,6 +511,9 @@ class Model {
     std::vector<int32_t> suppress_;          // the suppress list the context was told (a beam context is told again)
     bool suppress_known_ = false;            // set_suppress_tokens was called: an empty list is then a list, not an omission
     int beam_size_ = 1, ctx_rows_ = 1;       // set_beam_size; rows the context decodes (its max_batch)
+    nh_guard_params guard_{0, 1.0f, 0, 0, 0};   // set_repetition_guard; what the context was told (a beam context is told again)
+    std::vector<int32_t> bias_tok_;          // set_token_bias
+    std::vector<float> bias_val_;
 };
 
 // One tensor handed to the loader (HF name, f32 or f16 data) -- stands in for the safetensors mmap of

@@ -31,6 +31,7 @@ NH_OPT_ALIGN_KEEP = 4      # 1: align() keeps every clip's weights and matrix fo
 NH_OPT_PROMPT_STEPWISE = 5  # 1: a decode's prefix (set_prompts) goes through the decode step position by position; 0: one pass
 NH_ALIGN_MAX_HEADS = 32
 NH_MAX_BEAMS = 8           # decode_beam: hypotheses per clip at most
+NH_GUARD_MAX_BIAS = 256    # guard_bias: entries per row at most
 # NH_SAMPLE_* of include/norma_hip.h (the types of src/dtype.rs)
 SAMPLE_DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.int8): 2, np.dtype(np.int16): 3,
                  np.dtype(np.int32): 4, np.dtype(np.int64): 5, np.dtype(np.uint8): 6, np.dtype(np.uint16): 7,
@@ -85,6 +86,12 @@ class NhVadParams(C.Structure):
             return params
         v = list(params)
         return cls(*[int(x) for x in v[:5]], *[float(x) for x in v[5:8]], *[int(x) for x in v[8:]])
+
+
+class NhGuardParams(C.Structure):
+    """nh_guard_params (nh_set_guard): {0, 1.0, 0, 0, 0} is off"""
+    _fields_ = [("no_repeat_ngram", C.c_int32), ("repetition_penalty", C.c_float), ("loop_period", C.c_int32),
+                ("loop_repeats", C.c_int32), ("bias", C.c_int32)]
 
 
 class NhTimings(C.Structure):
@@ -180,6 +187,10 @@ def load_library() -> C.CDLL:
     L.nh_beam_hypotheses.argtypes = [vp, C.c_int, ip, ip, dp, ip]
     L.nh_beam_step.argtypes = [vp, C.c_int, C.c_int, fp, ip, ip, ip, ip, ip, dp, C.c_int, C.c_int, ip, ip, ip, ip, dp]
     L.nh_beam_reorder.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint16)]
+    L.nh_set_guard.argtypes = [vp, C.POINTER(NhGuardParams)]
+    L.nh_guard_bias.argtypes = [vp, C.c_int, ip, fp, C.c_int]
+    L.nh_guard_report.argtypes = [vp, ip, C.c_int, ip]
+    L.nh_guard_apply.argtypes = [vp, C.c_int, fp, ip, ip, C.c_int64, C.c_int, ip, ip, fp, ip]
     L.nh_get_timings.argtypes = [vp, C.POINTER(NhTimings)]
     L.nh_set_profile_gemm.argtypes = [vp, C.c_int]
     L.nh_set_option.argtypes = [vp, C.c_int, C.c_int]
@@ -674,6 +685,55 @@ class HipWhisper:
         self._chk(self.L.nh_beam_reorder(self._h, int(beam_size), int(batch), _ip(par), int(n_pos), int(layer), int(which),
                                          c.view(np.uint16).ctypes.data_as(C.POINTER(C.c_uint16))))
         return c
+
+    # ---- repetition guard (include/norma_hip.h: nh_set_guard ...) ----
+    def set_guard(self, no_repeat_ngram: int = 0, repetition_penalty: float = 1.0, loop_period: int = 0, loop_repeats: int = 0,
+                  bias: bool = False):
+        """The guard of this context's decode steps, kept until changed; set_guard(None) or no arguments: off."""
+        if no_repeat_ngram is None:
+            self._chk(self.L.nh_set_guard(self._h, None))
+            return
+        p = NhGuardParams(int(no_repeat_ngram), float(repetition_penalty), int(loop_period), int(loop_repeats), int(bool(bias)))
+        self._chk(self.L.nh_set_guard(self._h, C.byref(p)))
+
+    def guard_bias(self, row: int, bias: Optional[dict]):
+        """{token: beta} for context row `row` (applied while set_guard(bias=True)); None or {}: clear"""
+        items = sorted((bias or {}).items())
+        tk = np.array([k for k, _ in items], dtype=np.int32)
+        bv = np.array([v for _, v in items], dtype=np.float32)
+        self._chk(self.L.nh_guard_bias(self._h, int(row), _ip(tk) if len(tk) else None, _fp(bv) if len(tk) else None, len(tk)))
+
+    def guard_report(self, rows: Optional[Sequence[int]] = None) -> List[int]:
+        """loop-exit flags of the given rows (pool rows are named; None: every clip of the lockstep batch)"""
+        if rows is None:
+            out = np.zeros(self.batch, dtype=np.int32)
+            self._chk(self.L.nh_guard_report(self._h, None, self.batch, _ip(out)))
+        else:
+            r = np.ascontiguousarray(rows, dtype=np.int32)
+            out = np.zeros(len(r), dtype=np.int32)
+            self._chk(self.L.nh_guard_report(self._h, _ip(r), len(r), _ip(out)))
+        return out.tolist()
+
+    def guard_apply(self, logits: np.ndarray, tokens: Sequence[Sequence[int]], prompt_len: int = 3,
+                    active: Optional[Sequence[int]] = None, bias_rows: Optional[Sequence[int]] = None):
+        """The guard's edit alone on logits f32 [rows][V] and one token list per row (parity view nh_guard_apply).  Returns
+        (device rows f32 [rows][ld] with the pad columns, loop_exit [rows])."""
+        lg = np.ascontiguousarray(logits, dtype=np.float32).reshape(len(tokens), self.cfg.vocab_size)
+        R = lg.shape[0]
+        stride = max(max(len(t) for t in tokens), 1)
+        toks = np.zeros((R, stride), dtype=np.int32)
+        nt = np.zeros(R, dtype=np.int32)
+        for r, t in enumerate(tokens):
+            toks[r, :len(t)] = t
+            nt[r] = len(t)
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.int32)
+        br = None if bias_rows is None else np.ascontiguousarray(bias_rows, dtype=np.int32)
+        ld = (self.cfg.vocab_size + 63) & ~63
+        out = np.zeros((R, ld), dtype=np.float32)
+        le = np.zeros(R, dtype=np.int32)
+        self._chk(self.L.nh_guard_apply(self._h, R, _fp(lg), _ip(toks), _ip(nt), stride, int(prompt_len),
+                                        None if act is None else _ip(act), None if br is None else _ip(br), _fp(out), _ip(le)))
+        return out, le
 
     def transcribe_batch_device(self, pcm_dev_ptr: int, n_samples: Sequence[int], stride: int,
                                 max_new_tokens: int = 0) -> List[dict]:

@@ -105,6 +105,9 @@ def _lib():
         L.nm_gguf_list.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
         L.nm_model_set_temperature_fallback.argtypes = [vp, C.c_int, C.c_uint64]
         L.nm_model_set_beam_size.argtypes = [vp, C.c_int]
+        L.nm_model_set_repetition_guard.argtypes = [vp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int]
+        L.nm_model_set_token_bias.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int]
+        L.nm_model_last_loop_exit.argtypes = [vp]
         L.nm_model_free.argtypes = [vp]
         L.nm_model_transcribe.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                           C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.c_char_p, C.c_int]
@@ -242,6 +245,21 @@ class Model:
         if _lib().nm_model_set_beam_size(self._h, int(k)):
             raise WhisperError(f"set_beam_size: 1 .. 8 hypotheses (and device memory for a context of that many rows), got {k}")
 
+    def set_repetition_guard(self, no_repeat_ngram: int = 0, repetition_penalty: float = 1.0, loop_period: int = 0,
+                             loop_repeats: int = 0, bias: bool = False):
+        """The repetition guard of every decode (HipWhisper.set_guard); no arguments: off, the default."""
+        if _lib().nm_model_set_repetition_guard(self._h, int(no_repeat_ngram), float(repetition_penalty), int(loop_period),
+                                                int(loop_repeats), int(bool(bias))):
+            raise WhisperError("set_repetition_guard: refused (penalty > 0 and finite, n-gram 0 .. 16, period 0 .. 64, repeats 2 .. 16, period * repeats <= 448)")
+
+    def set_token_bias(self, bias: Optional[dict]):
+        """{token: beta} added to the logits of every decode while set_repetition_guard(bias=True); None or {}: none."""
+        items = sorted((bias or {}).items())
+        ids = np.array([k for k, _ in items], dtype=np.int32)
+        bv = np.array([v for _, v in items], dtype=np.float32)
+        if _lib().nm_model_set_token_bias(self._h, ids.ctypes.data_as(C.POINTER(C.c_int32)), bv.ctypes.data_as(C.POINTER(C.c_float)), len(ids)):
+            raise WhisperError("set_token_bias: refused (at most 256 distinct ids inside the vocabulary, each bias finite or -inf)")
+
     def set_prompt_tokens(self, ids: Sequence[int]):
         """An initial prompt (token ids; the tokenizer only decodes) every slice decodes under, behind <|startofprev|>; [] = none."""
         a = np.ascontiguousarray(ids, dtype=np.int32)
@@ -304,7 +322,8 @@ class Model:
     def last_result(self) -> dict:
         a, n, f, k = C.c_double(0), C.c_double(0), C.c_int(0), C.c_int(0)
         _lib().nm_model_last_result(self._h, C.byref(a), C.byref(n), C.byref(f), C.byref(k))
-        return dict(avg_logprob=a.value, no_speech_prob=n.value, needed_fallback=bool(f.value), n_tokens=k.value)
+        return dict(avg_logprob=a.value, no_speech_prob=n.value, needed_fallback=bool(f.value), n_tokens=k.value,
+                    loop_exit=bool(_lib().nm_model_last_loop_exit(self._h)))
 
 
 class Resampler:

@@ -47,6 +47,39 @@ def _set_prompt(hm, prompt, n: int, align: bool):
         hm.set_prompts([list(prompt)] * n)
 
 
+class _Guard:
+    """guard=<HipWhisper.set_guard's keywords> and bias=<{token: beta}, the same for every chunk> around the decodes of one call
+    (DESIGN.md 16): set on entry, switched off and cleared on exit -- the call owns the context's guard and the bias lists of
+    rows 0 .. rows-1 meanwhile, and what the caller had set there before is gone after it.  Neither given: no engine method is
+    called and the context's own guard, if any, applies.  With a loop
+    exit in the guard every result of a greedy decode carries "loop_exit" (after a beam decode guard_report refuses)."""
+
+    def __init__(self, hm, guard, bias, rows: int, beam_size: int):
+        self.hm, self.guard, self.bias, self.rows = hm, (None if guard is None else dict(guard)), bias, rows
+        self.report = self.guard is not None and int(self.guard.get("loop_period", 0)) > 0 and beam_size == 1
+
+    def __enter__(self):
+        if self.guard is not None:
+            self.hm.set_guard(**self.guard)
+        if self.bias:
+            for r in range(self.rows):
+                self.hm.guard_bias(r, self.bias)
+        return self
+
+    def __exit__(self, *exc):
+        if self.bias:
+            for r in range(self.rows):
+                self.hm.guard_bias(r, None)
+        if self.guard is not None:
+            self.hm.set_guard(None)
+        return False
+
+    def mark(self, res):
+        if self.report:
+            for r, flag in zip(res, self.hm.guard_report()):
+                r["loop_exit"] = bool(flag)
+
+
 def _score(hm, res, prompt) -> List[np.ndarray]:
     """hm.score on the sequences a group's decode returned: per clip f32 [len(tokens)], entry i = ln p(tokens[i]), 0.0 for the
     [sot, language?, task] prompt.  A prefix the decode ran under goes in front of them, as nh_score asks.  A clip that
@@ -64,7 +97,7 @@ def _score(hm, res, prompt) -> List[np.ndarray]:
 
 
 def transcribe_recording(hm, pcm, params=None, max_new_tokens: int = 0, align: bool = False, prompt=None,
-                         beam_size: int = 1, score: bool = False) -> List[dict]:
+                         beam_size: int = 1, score: bool = False, guard=None, bias=None) -> List[dict]:
     """hm: a HipWhisper with weights, filters and tokens set.  pcm: a host f32 array (16 kHz mono), or (device pointer,
     n_samples).  params: the cut parameters (HipWhisper.cut_plan).  Returns one dict per chunk: the fields of decode_greedy
     plus start_sample, n_samples and n_keys = ceil(n_samples / 320), the encoder frames that hold audio.  align=True (the
@@ -72,30 +105,34 @@ def transcribe_recording(hm, pcm, params=None, max_new_tokens: int = 0, align: b
     prompt: token ids every chunk decodes under (taken verbatim: <|startofprev|> first is the caller's to add; at most
     max_target_positions / 2 - 1 of them); the results exclude them.  Not together with align=True.
     score=True: token_logprob as well, f32 [len(tokens)]: ln p of every returned token under the model (HipWhisper.score on the
-    group's returned sequences, after its align_decoded; 0.0 for the prompt tokens)."""
+    group's returned sequences, after its align_decoded; 0.0 for the prompt tokens).
+    guard, bias: the repetition guard of the chunks' decodes and one {token: beta} list for all of them (see _Guard)."""
     if isinstance(pcm, np.ndarray):
         rec, n = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1), None
     else:
         rec, n = int(pcm[0]), int(pcm[1])
     starts, lens = hm.cut_plan(rec, n, params)
     out = []
-    for a, b in _groups(lens, _beam_rows(hm, beam_size, align)):
-        hm.logmel_chunks_rows(rec, starts[a:b], lens[a:b], 0)
-        hm.encode()
-        _set_prompt(hm, prompt, b - a, align)
-        res = hm.decode_greedy(max_new_tokens) if beam_size == 1 else hm.decode_beam(beam_size, max_new_tokens)
-        keys = [-(-int(v) // KEY_SAMPLES) for v in lens[a:b]]
-        if align:
-            first, last = hm.align_decoded(n_keys=keys)
-        if score:
-            lps = _score(hm, res, prompt)
-        for i, r in enumerate(res):
-            if score:
-                r.update(token_logprob=lps[i])
-            r.update(start_sample=int(starts[a + i]), n_samples=int(lens[a + i]), n_keys=keys[i])
+    rows = _beam_rows(hm, beam_size, align)
+    with _Guard(hm, guard, bias, rows, beam_size) as gd:
+        for a, b in _groups(lens, rows):
+            hm.logmel_chunks_rows(rec, starts[a:b], lens[a:b], 0)
+            hm.encode()
+            _set_prompt(hm, prompt, b - a, align)
+            res = hm.decode_greedy(max_new_tokens) if beam_size == 1 else hm.decode_beam(beam_size, max_new_tokens)
+            gd.mark(res)
+            keys = [-(-int(v) // KEY_SAMPLES) for v in lens[a:b]]
             if align:
-                r.update(token_first=first[i].copy(), token_last=last[i].copy())
-            out.append(r)
+                first, last = hm.align_decoded(n_keys=keys)
+            if score:
+                lps = _score(hm, res, prompt)
+            for i, r in enumerate(res):
+                if score:
+                    r.update(token_logprob=lps[i])
+                r.update(start_sample=int(starts[a + i]), n_samples=int(lens[a + i]), n_keys=keys[i])
+                if align:
+                    r.update(token_first=first[i].copy(), token_last=last[i].copy())
+                out.append(r)
     return out
 
 
@@ -141,11 +178,11 @@ def stitch(results: Sequence[dict], tokens) -> List[Tuple[float, float, List[int
 
 
 def transcribe_speech(hm, pcm, params=None, max_new_tokens: int = 0, align: bool = False, prompt=None,
-                      beam_size: int = 1, score: bool = False) -> List[dict]:
+                      beam_size: int = 1, score: bool = False, guard=None, bias=None) -> List[dict]:
     """transcribe_recording on the recording's speech alone.  params: the parameters of HipWhisper.vad_plan.  Returns one dict
     per chunk (none for a recording without speech): the fields of decode_greedy plus pieces = [(offset_in_chunk, start_sample,
     n_samples)], n_samples = the chunk's total, n_keys = ceil(n_samples / 320), and with align=True token_first / token_last.  prompt, score:
-    as for transcribe_recording."""
+    as for transcribe_recording; so are guard and bias."""
     if isinstance(pcm, np.ndarray):
         rec, n = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1), None
     else:
@@ -160,23 +197,26 @@ def transcribe_speech(hm, pcm, params=None, max_new_tokens: int = 0, align: bool
         pieces.append(row)
     totals = [row[-1][0] + row[-1][2] for row in pieces]
     out = []
-    for a, b in _groups(totals, _beam_rows(hm, beam_size, align)):
-        hm.logmel_pieces_rows(rec, starts, lens, first[a:b + 1], 0)
-        hm.encode()
-        _set_prompt(hm, prompt, b - a, align)
-        res = hm.decode_greedy(max_new_tokens) if beam_size == 1 else hm.decode_beam(beam_size, max_new_tokens)
-        keys = [-(-v // KEY_SAMPLES) for v in totals[a:b]]
-        if align:
-            tf, tl = hm.align_decoded(n_keys=keys)
-        if score:
-            lps = _score(hm, res, prompt)
-        for i, r in enumerate(res):
-            if score:
-                r.update(token_logprob=lps[i])
-            r.update(pieces=pieces[a + i], n_samples=totals[a + i], n_keys=keys[i])
+    rows = _beam_rows(hm, beam_size, align)
+    with _Guard(hm, guard, bias, rows, beam_size) as gd:
+        for a, b in _groups(totals, rows):
+            hm.logmel_pieces_rows(rec, starts, lens, first[a:b + 1], 0)
+            hm.encode()
+            _set_prompt(hm, prompt, b - a, align)
+            res = hm.decode_greedy(max_new_tokens) if beam_size == 1 else hm.decode_beam(beam_size, max_new_tokens)
+            gd.mark(res)
+            keys = [-(-v // KEY_SAMPLES) for v in totals[a:b]]
             if align:
-                r.update(token_first=tf[i].copy(), token_last=tl[i].copy())
-            out.append(r)
+                tf, tl = hm.align_decoded(n_keys=keys)
+            if score:
+                lps = _score(hm, res, prompt)
+            for i, r in enumerate(res):
+                if score:
+                    r.update(token_logprob=lps[i])
+                r.update(pieces=pieces[a + i], n_samples=totals[a + i], n_keys=keys[i])
+                if align:
+                    r.update(token_first=tf[i].copy(), token_last=tl[i].copy())
+                out.append(r)
     return out
 
 

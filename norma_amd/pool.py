@@ -34,6 +34,16 @@ fallback=True after _settle accepts, never for a rejected or dropped attempt -- 
 The result gains "token_first" / "token_last": one encoder frame (20 ms) per entry of "tokens", -1 for the prompt.  A no-speech
 exit gets none.  run(.., n_keys=[frames that hold audio per clip]) bounds each clip's alignment (None: all frames).  Without
 the keyword neither engine method is called.
+
+guard=<dict of set_guard's keywords> puts the repetition guard into the pool's steps: set_guard(**guard) once
+after pool_begin.  bias=<callable clip -> {token: beta} | None> gives a clip its own logit bias (hotwords, per-clip
+suppression): guard_bias(row, dict) right before the clip's admission, applied while guard has bias=True.  With a guard that
+has a loop exit (loop_period > 0) every result carries "loop_exit", read with guard_report(rows) at the collect.
+loop_fallback=True (with fallback=True) makes a result whose row took the exit fail the test of _settle whatever its
+avg_logprob -- the counterpart of the reference's dead `compression_ratio > threshold` half -- still subject to the
+no_speech_prob clause.  Without these keywords none of the three engine methods is called.  Like the alignment heads and the
+language table, the guard and the rows' bias lists stay set on the engine after run(): a caller that goes on to use the
+context otherwise switches them off itself (set_guard(None), guard_bias(row, None)).
 """
 from typing import Callable, List, Optional, Sequence
 
@@ -62,13 +72,25 @@ class _Fallback:
         self.align_heads = None if align_heads is None else [(int(l), int(h)) for l, h in align_heads]
         self.aligned = 0        # clips aligned
 
+    def _init_guard(self, guard, bias, loop_fallback):
+        self.guard = None if guard is None else dict(guard)
+        self.bias_of, self.loop_fallback = bias, bool(loop_fallback)
+        self._report = self.guard is not None and int(self.guard.get("loop_period", 0)) > 0
+
     def _begin(self):
         self.e.pool_begin(self.rows, self.max_new, self.per_clip_language)
+        if self.guard is not None:
+            self.e.set_guard(**self.guard)           # the fresh pool has no busy row
         if self.align_heads is not None:
             self.e.align_capture(self.align_heads)   # the fresh pool has no busy row: the steps are captured with the list
         if self.detect_languages is not None:
             self.e.pool_detect_languages(self.detect_languages)
         self._lang = [None] * self.rows     # per row: (language token, probabilities or None) of the clip it holds
+
+    def _admit_bias(self, row: int, clip: int):
+        """the clip's bias list goes to the row it is about to be admitted into (None or {}: the row's list is cleared)"""
+        if self.bias_of is not None:
+            self.e.guard_bias(row, self.bias_of(clip))
 
     def _admit_lang(self, row: int, clip: int, langs) -> int:
         """the `lang` a clip is admitted with"""
@@ -81,6 +103,9 @@ class _Fallback:
     def _collect(self, fin: List[int], attempt: List[int]) -> List[dict]:
         """pool_collect, plus the languages: detected ones are read once, with the t = 0 attempt (those rows have stepped)"""
         out = self.e.pool_collect(fin)
+        if self._report:
+            for res, flag in zip(out, self.e.guard_report(fin)):
+                res["loop_exit"] = bool(flag)
         if self.detect_languages is not None:
             det = [r for r in fin if self._lang[r] is None]
             if det:
@@ -101,7 +126,8 @@ class _Fallback:
         if not self.fallback:
             return True
         # model.rs:177-179; compression_ratio is NaN there (:383), so `compression_ratio > threshold` never holds
-        needs = res["avg_logprob"] < self.logprob_threshold
+        # ... and has this counterpart: a row that took the guard's loop exit (loop_fallback)
+        needs = res["avg_logprob"] < self.logprob_threshold or (self.loop_fallback and bool(res.get("loop_exit")))
         if not needs or res["no_speech_prob"] > self.no_speech_threshold:
             return True
         if attempt + 1 >= len(self.temperatures):
@@ -131,13 +157,15 @@ class DecodePool(_Fallback):
     def __init__(self, engine, rows: int = 64, staging: int = 32, max_new_tokens: int = 0, check_every: int = 16,
                  per_clip_language: bool = False, fallback: bool = False, seed: int = 0, clip0: int = 0,
                  temperatures: Sequence[float] = TEMPERATURES, logprob_threshold: float = -1.0, no_speech_threshold: float = 0.6,
-                 detect_languages: Optional[Sequence[int]] = None, align_heads: Optional[Sequence] = None):
+                 detect_languages: Optional[Sequence[int]] = None, align_heads: Optional[Sequence] = None,
+                 guard: Optional[dict] = None, bias: Optional[Callable[[int], Optional[dict]]] = None, loop_fallback: bool = False):
         assert rows >= 1 and staging >= 1 and check_every >= 1
         self._init_fallback(fallback, seed, clip0, temperatures, logprob_threshold, no_speech_threshold)
         self.e, self.rows, self.staging, self.check_every = engine, rows, staging, check_every
         self.max_new, self.per_clip_language = max_new_tokens, per_clip_language
         self._init_detect(detect_languages)
         self._init_align(align_heads)
+        self._init_guard(guard, bias, loop_fallback)
         self.steps = 0          # decode steps launched
         self.row_steps = 0      # sum over steps of the rows that were busy (what the step kernels' per-row work scales with)
         self.encodes = 0
@@ -167,6 +195,7 @@ class DecodePool(_Fallback):
                     break
                 if owner[r] < 0:
                     c = staged.pop(0)
+                    self._admit_bias(r, c)
                     e.pool_admit(R + (c - staged_first), r, self._admit_lang(r, c, langs))
                     owner[r], attempt[r] = c, 0
                     busy += 1
@@ -201,13 +230,15 @@ class FedDecodePool(_Fallback):
     def __init__(self, engine, encoders: Sequence, rows: int = 64, batch: int = 32, max_new_tokens: int = 0, check_every: int = 16,
                  per_clip_language: bool = False, fallback: bool = False, seed: int = 0, clip0: int = 0,
                  temperatures: Sequence[float] = TEMPERATURES, logprob_threshold: float = -1.0, no_speech_threshold: float = 0.6,
-                 detect_languages: Optional[Sequence[int]] = None, align_heads: Optional[Sequence] = None):
+                 detect_languages: Optional[Sequence[int]] = None, align_heads: Optional[Sequence] = None,
+                 guard: Optional[dict] = None, bias: Optional[Callable[[int], Optional[dict]]] = None, loop_fallback: bool = False):
         assert rows >= 1 and batch >= 1 and check_every >= 1 and len(encoders) >= 1
         self._init_fallback(fallback, seed, clip0, temperatures, logprob_threshold, no_speech_threshold)
         self.e, self.encoders, self.rows, self.batch, self.check_every = engine, list(encoders), rows, batch, check_every
         self.max_new, self.per_clip_language = max_new_tokens, per_clip_language
         self._init_detect(detect_languages)
         self._init_align(align_heads)
+        self._init_guard(guard, bias, loop_fallback)
         self.steps = self.row_steps = self.encodes = 0
 
     def run(self, n_clips: int, encode: Callable[[int, int, int], None], langs: Optional[Sequence[Optional[int]]] = None,
@@ -259,6 +290,7 @@ class FedDecodePool(_Fallback):
                         break
                     i, first, n, j = cur
                     c = first + j
+                    self._admit_bias(r, c)
                     e.pool_admit_from(self.encoders[i], j, r, self._admit_lang(r, c, langs))
                     owner[r], attempt[r] = c, 0
                     busy += 1
