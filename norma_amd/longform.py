@@ -11,6 +11,8 @@ from typing import List, Sequence, Tuple
 
 import numpy as np
 
+from .pool import _has_loop_exit
+
 SAMPLE_RATE = 16000
 KEY_SAMPLES = 320      # samples per encoder frame (20 ms): one timestamp unit
 MIN_MEL_SAMPLES = 160  # a shorter clip produces 1500 mel frames, not 3000, and cannot share a batch with longer ones
@@ -56,7 +58,7 @@ class _Guard:
 
     def __init__(self, hm, guard, bias, rows: int, beam_size: int):
         self.hm, self.guard, self.bias, self.rows = hm, (None if guard is None else dict(guard)), bias, rows
-        self.report = self.guard is not None and int(self.guard.get("loop_period", 0)) > 0 and beam_size == 1
+        self.report = _has_loop_exit(self.guard) and beam_size == 1
 
     def __enter__(self):
         if self.guard is not None:
@@ -96,6 +98,42 @@ def _score(hm, res, prompt) -> List[np.ndarray]:
     return out
 
 
+def _pcm(pcm):
+    """a host f32 array (16 kHz mono) or (device pointer, n_samples), as the plan and log-mel calls take it: (rec, n)"""
+    if isinstance(pcm, np.ndarray):
+        return np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1), None
+    return int(pcm[0]), int(pcm[1])
+
+
+def _transcribe(hm, totals, fill, annotate, max_new_tokens, align, prompt, beam_size, score, guard, bias) -> List[dict]:
+    """A planned recording through log-mel, encoder and decode, a group of chunks at a time.  totals: samples per chunk;
+    fill(a, b) puts the log-mel of chunks a .. b-1 into rows 0 ..; annotate(i, result) adds the plan's own fields of chunk i,
+    which come after token_logprob and before n_samples, n_keys and token_first / token_last."""
+    out = []
+    rows = _beam_rows(hm, beam_size, align)
+    with _Guard(hm, guard, bias, rows, beam_size) as gd:
+        for a, b in _groups(totals, rows):
+            fill(a, b)
+            hm.encode()
+            _set_prompt(hm, prompt, b - a, align)
+            res = hm.decode_greedy(max_new_tokens) if beam_size == 1 else hm.decode_beam(beam_size, max_new_tokens)
+            gd.mark(res)
+            keys = [-(-int(v) // KEY_SAMPLES) for v in totals[a:b]]
+            if align:
+                first, last = hm.align_decoded(n_keys=keys)
+            if score:
+                lps = _score(hm, res, prompt)
+            for i, r in enumerate(res):
+                if score:
+                    r.update(token_logprob=lps[i])
+                annotate(a + i, r)
+                r.update(n_samples=int(totals[a + i]), n_keys=keys[i])
+                if align:
+                    r.update(token_first=first[i].copy(), token_last=last[i].copy())
+                out.append(r)
+    return out
+
+
 def transcribe_recording(hm, pcm, params=None, max_new_tokens: int = 0, align: bool = False, prompt=None,
                          beam_size: int = 1, score: bool = False, guard=None, bias=None) -> List[dict]:
     """hm: a HipWhisper with weights, filters and tokens set.  pcm: a host f32 array (16 kHz mono), or (device pointer,
@@ -107,33 +145,10 @@ def transcribe_recording(hm, pcm, params=None, max_new_tokens: int = 0, align: b
     score=True: token_logprob as well, f32 [len(tokens)]: ln p of every returned token under the model (HipWhisper.score on the
     group's returned sequences, after its align_decoded; 0.0 for the prompt tokens).
     guard, bias: the repetition guard of the chunks' decodes and one {token: beta} list for all of them (see _Guard)."""
-    if isinstance(pcm, np.ndarray):
-        rec, n = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1), None
-    else:
-        rec, n = int(pcm[0]), int(pcm[1])
+    rec, n = _pcm(pcm)
     starts, lens = hm.cut_plan(rec, n, params)
-    out = []
-    rows = _beam_rows(hm, beam_size, align)
-    with _Guard(hm, guard, bias, rows, beam_size) as gd:
-        for a, b in _groups(lens, rows):
-            hm.logmel_chunks_rows(rec, starts[a:b], lens[a:b], 0)
-            hm.encode()
-            _set_prompt(hm, prompt, b - a, align)
-            res = hm.decode_greedy(max_new_tokens) if beam_size == 1 else hm.decode_beam(beam_size, max_new_tokens)
-            gd.mark(res)
-            keys = [-(-int(v) // KEY_SAMPLES) for v in lens[a:b]]
-            if align:
-                first, last = hm.align_decoded(n_keys=keys)
-            if score:
-                lps = _score(hm, res, prompt)
-            for i, r in enumerate(res):
-                if score:
-                    r.update(token_logprob=lps[i])
-                r.update(start_sample=int(starts[a + i]), n_samples=int(lens[a + i]), n_keys=keys[i])
-                if align:
-                    r.update(token_first=first[i].copy(), token_last=last[i].copy())
-                out.append(r)
-    return out
+    return _transcribe(hm, lens, lambda a, b: hm.logmel_chunks_rows(rec, starts[a:b], lens[a:b], 0),
+                       lambda i, r: r.update(start_sample=int(starts[i])), max_new_tokens, align, prompt, beam_size, score, guard, bias)
 
 
 def _segments(tokens, v):
@@ -183,10 +198,7 @@ def transcribe_speech(hm, pcm, params=None, max_new_tokens: int = 0, align: bool
     per chunk (none for a recording without speech): the fields of decode_greedy plus pieces = [(offset_in_chunk, start_sample,
     n_samples)], n_samples = the chunk's total, n_keys = ceil(n_samples / 320), and with align=True token_first / token_last.  prompt, score:
     as for transcribe_recording; so are guard and bias."""
-    if isinstance(pcm, np.ndarray):
-        rec, n = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1), None
-    else:
-        rec, n = int(pcm[0]), int(pcm[1])
+    rec, n = _pcm(pcm)
     starts, lens, first = hm.vad_plan(rec, n, params)
     pieces = []
     for k in range(len(first) - 1):
@@ -196,28 +208,8 @@ def transcribe_speech(hm, pcm, params=None, max_new_tokens: int = 0, align: bool
             off += int(lens[j])
         pieces.append(row)
     totals = [row[-1][0] + row[-1][2] for row in pieces]
-    out = []
-    rows = _beam_rows(hm, beam_size, align)
-    with _Guard(hm, guard, bias, rows, beam_size) as gd:
-        for a, b in _groups(totals, rows):
-            hm.logmel_pieces_rows(rec, starts, lens, first[a:b + 1], 0)
-            hm.encode()
-            _set_prompt(hm, prompt, b - a, align)
-            res = hm.decode_greedy(max_new_tokens) if beam_size == 1 else hm.decode_beam(beam_size, max_new_tokens)
-            gd.mark(res)
-            keys = [-(-v // KEY_SAMPLES) for v in totals[a:b]]
-            if align:
-                tf, tl = hm.align_decoded(n_keys=keys)
-            if score:
-                lps = _score(hm, res, prompt)
-            for i, r in enumerate(res):
-                if score:
-                    r.update(token_logprob=lps[i])
-                r.update(pieces=pieces[a + i], n_samples=totals[a + i], n_keys=keys[i])
-                if align:
-                    r.update(token_first=tf[i].copy(), token_last=tl[i].copy())
-                out.append(r)
-    return out
+    return _transcribe(hm, totals, lambda a, b: hm.logmel_pieces_rows(rec, starts, lens, first[a:b + 1], 0),
+                       lambda i, r: r.update(pieces=pieces[i]), max_new_tokens, align, prompt, beam_size, score, guard, bias)
 
 
 def to_recording(pieces: Sequence[Tuple[int, int, int]], tau_samples: float, end: bool = False) -> float:

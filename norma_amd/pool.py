@@ -4,7 +4,8 @@ The reference's decode loop ends per sequence at eot (src/models/whisper/model.r
 (src/lib.rs:462-464); a batch decoded in lockstep makes the short sequences wait for the longest one.  The pool keeps a fixed
 number of decode rows busy instead: the encoder is still fed `staging` clips at a time, every encoded clip is admitted to
 whichever row is free, finished rows are collected every `check_every` steps.  The policy is engine-agnostic (it only calls
-the methods below), so the CPU tests drive it with a counting stand-in and the GPU tests with HipWhisper.
+the methods below), so the CPU tests drive it with a counting stand-in and the GPU tests with HipWhisper.  Both pools are one
+run loop (_Pool._run) over a source of encoded clips; run(.., on_result=f) calls f(clip, result) as soon as a result is final.
 
 engine methods used: pool_begin(rows, max_new, per_clip_language), pool_admit(src_row, dst_row, lang),
 pool_step(n) -> flags per row (0 running, 1 / 2 finished, 3 empty), pool_collect(rows) -> [result],
@@ -45,6 +46,8 @@ no_speech_prob clause.  Without these keywords none of the three engine methods 
 language table, the guard and the rows' bias lists stay set on the engine after run(): a caller that goes on to use the
 context otherwise switches them off itself (set_guard(None), guard_bias(row, None)).
 """
+import queue
+import threading
 from typing import Callable, List, Optional, Sequence
 
 from .hip import NH_LANG_DETECT
@@ -52,30 +55,36 @@ from .hip import NH_LANG_DETECT
 TEMPERATURES = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0)   # m::TEMPERATURES of model.rs:175 (LOGPROB_THRESHOLD -1, NO_SPEECH_THRESHOLD 0.6)
 
 
-class _Fallback:
-    """what both pools do with a collected result"""
+def _has_loop_exit(guard: Optional[dict]) -> bool:
+    """a guard with a loop exit (loop_period > 0) has something for guard_report to say"""
+    return guard is not None and int(guard.get("loop_period", 0)) > 0
 
-    def _init_fallback(self, fallback, seed, clip0, temperatures, logprob_threshold, no_speech_threshold):
+
+class _Pool:
+    """what both pools are: the per-row policy on a collected result, and the one run loop over a source of encoded clips"""
+
+    def __init__(self, engine, rows, max_new_tokens, check_every, per_clip_language, fallback, seed, clip0, temperatures,
+                 logprob_threshold, no_speech_threshold, detect_languages, align_heads, guard, bias, loop_fallback):
+        assert rows >= 1 and check_every >= 1
+        self.e, self.rows, self.check_every = engine, rows, check_every
+        self.max_new, self.per_clip_language = max_new_tokens, per_clip_language
         self.fallback, self.seed, self.clip0 = bool(fallback), int(seed), int(clip0)
         self.temperatures = tuple(float(t) for t in temperatures)
         assert len(self.temperatures) >= 1 and self.temperatures[0] == 0.0 and all(t > 0.0 for t in self.temperatures[1:]), \
             "temperatures: 0 first (an admitted row is greedy), then the sampled retries"
         self.logprob_threshold, self.no_speech_threshold = float(logprob_threshold), float(no_speech_threshold)
-        self.retries = 0        # pool_retry calls
-
-    def _init_detect(self, detect_languages):
         self.detect_languages = None if detect_languages is None else [int(t) for t in detect_languages]
         if self.detect_languages is not None:
             self.per_clip_language = True
-
-    def _init_align(self, align_heads):
         self.align_heads = None if align_heads is None else [(int(l), int(h)) for l, h in align_heads]
-        self.aligned = 0        # clips aligned
-
-    def _init_guard(self, guard, bias, loop_fallback):
         self.guard = None if guard is None else dict(guard)
         self.bias_of, self.loop_fallback = bias, bool(loop_fallback)
-        self._report = self.guard is not None and int(self.guard.get("loop_period", 0)) > 0
+        self._report = _has_loop_exit(self.guard)
+        self.steps = 0          # decode steps launched
+        self.row_steps = 0      # sum over steps of the rows that were busy (what the step kernels' per-row work scales with)
+        self.encodes = 0
+        self.retries = 0        # pool_retry calls
+        self.aligned = 0        # clips aligned
 
     def _begin(self):
         self.e.pool_begin(self.rows, self.max_new, self.per_clip_language)
@@ -86,11 +95,6 @@ class _Fallback:
         if self.detect_languages is not None:
             self.e.pool_detect_languages(self.detect_languages)
         self._lang = [None] * self.rows     # per row: (language token, probabilities or None) of the clip it holds
-
-    def _admit_bias(self, row: int, clip: int):
-        """the clip's bias list goes to the row it is about to be admitted into (None or {}: the row's list is cleared)"""
-        if self.bias_of is not None:
-            self.e.guard_bias(row, self.bias_of(clip))
 
     def _admit_lang(self, row: int, clip: int, langs) -> int:
         """the `lang` a clip is admitted with"""
@@ -152,53 +156,30 @@ class _Fallback:
             res["token_first"], res["token_last"] = [int(v) for v in first[i][:n]], [int(v) for v in last[i][:n]]
         self.aligned += len(todo)
 
-
-class DecodePool(_Fallback):
-    def __init__(self, engine, rows: int = 64, staging: int = 32, max_new_tokens: int = 0, check_every: int = 16,
-                 per_clip_language: bool = False, fallback: bool = False, seed: int = 0, clip0: int = 0,
-                 temperatures: Sequence[float] = TEMPERATURES, logprob_threshold: float = -1.0, no_speech_threshold: float = 0.6,
-                 detect_languages: Optional[Sequence[int]] = None, align_heads: Optional[Sequence] = None,
-                 guard: Optional[dict] = None, bias: Optional[Callable[[int], Optional[dict]]] = None, loop_fallback: bool = False):
-        assert rows >= 1 and staging >= 1 and check_every >= 1
-        self._init_fallback(fallback, seed, clip0, temperatures, logprob_threshold, no_speech_threshold)
-        self.e, self.rows, self.staging, self.check_every = engine, rows, staging, check_every
-        self.max_new, self.per_clip_language = max_new_tokens, per_clip_language
-        self._init_detect(detect_languages)
-        self._init_align(align_heads)
-        self._init_guard(guard, bias, loop_fallback)
-        self.steps = 0          # decode steps launched
-        self.row_steps = 0      # sum over steps of the rows that were busy (what the step kernels' per-row work scales with)
-        self.encodes = 0
-
-    def run(self, n_clips: int, encode: Callable[[int, int, int, bool], Optional[bool]], langs: Optional[Sequence[Optional[int]]] = None,
-            on_result: Optional[Callable[[int, dict], None]] = None, n_keys: Optional[Sequence[int]] = None) -> List[dict]:
-        """Decode clips 0 .. n_clips - 1; returns their results in clip order."""
+    def _run(self, n_clips: int, src, langs, on_result, n_keys) -> List[dict]:
+        """Decode clips 0 .. n_clips - 1 as `src` has them encoded; returns their results in clip order.  src.ready(clip, wait):
+        is the next clip to admit encoded?  Asked once per pass; wait: no row is busy, there is nothing to decode meanwhile.
+        src.admit(clip, row, lang): move it into the row; is the clip after it encoded as well?"""
         e, R = self.e, self.rows
         self._begin()
         results: List[Optional[dict]] = [None] * n_clips
         owner = [-1] * R                  # clip decoding in each row
         attempt = [0] * R                 # index into temperatures of the decode that row is on
-        staged: List[int] = []            # clips encoded and waiting for a row, in order; clip c sits in staging row R + (c - staged_first)
-        staged_first = 0
-        next_clip = 0
-        busy = 0
-        while next_clip < n_clips or staged or busy:
-            if not staged and next_clip < n_clips:
-                n = min(self.staging, n_clips - next_clip)
-                if encode(next_clip, n, R, busy == 0) is not False:   # busy == 0: nothing to decode meanwhile, wait for the encoder
-                    self.encodes += 1
-                    staged_first = next_clip
-                    staged = list(range(next_clip, next_clip + n))
-                    next_clip += n
+        clip = busy = done = 0            # next clip to admit, rows decoding, clips with a result
+        while done < n_clips:
+            more = clip < n_clips and src.ready(clip, busy == 0)
             for r in range(R):            # admit in clip order into the lowest free rows
-                if not staged:
+                if not more:
                     break
                 if owner[r] < 0:
-                    c = staged.pop(0)
-                    self._admit_bias(r, c)
-                    e.pool_admit(R + (c - staged_first), r, self._admit_lang(r, c, langs))
-                    owner[r], attempt[r] = c, 0
+                    if self.bias_of is not None:   # the clip's bias list goes to its row first (None or {}: the row's list is cleared)
+                        e.guard_bias(r, self.bias_of(clip))
+                    more = src.admit(clip, r, self._admit_lang(r, clip, langs)) and clip + 1 < n_clips
+                    owner[r], attempt[r] = clip, 0
+                    clip += 1
                     busy += 1
+            if busy == 0:
+                continue
             flags = e.pool_step(self.check_every)
             self.steps += self.check_every
             self.row_steps += busy * self.check_every
@@ -217,110 +198,124 @@ class DecodePool(_Fallback):
                         on_result(c, res)
                     owner[r] = -1
                     busy -= 1
+                    done += 1
         return results  # type: ignore[return-value]
 
 
-class FedDecodePool(_Fallback):
+class _Staged:
+    """DecodePool's clips: encoded `staging` at a time into the staging rows R .. of the pool's own context, whenever those are
+    empty; clip c sits in staging row R + (c - first)"""
+
+    def __init__(self, pool, n_clips: int, encode):
+        self.p, self.n_clips, self.encode = pool, n_clips, encode
+        self.first = self.end = 0         # clips first .. end - 1 are or were staged; those from the next to admit on still are
+
+    def ready(self, clip: int, wait: bool) -> bool:
+        if clip == self.end:
+            n = min(self.p.staging, self.n_clips - clip)
+            if self.encode(clip, n, self.p.rows, wait) is not False:   # False: the encoder is busy, ask again after a step
+                self.p.encodes += 1
+                self.first, self.end = clip, clip + n
+        return clip < self.end
+
+    def admit(self, clip: int, row: int, lang: int) -> bool:
+        self.p.e.pool_admit(self.p.rows + (clip - self.first), row, lang)
+        return clip + 1 < self.end
+
+
+class DecodePool(_Pool):
+    def __init__(self, engine, rows: int = 64, staging: int = 32, max_new_tokens: int = 0, check_every: int = 16,
+                 per_clip_language: bool = False, fallback: bool = False, seed: int = 0, clip0: int = 0,
+                 temperatures: Sequence[float] = TEMPERATURES, logprob_threshold: float = -1.0, no_speech_threshold: float = 0.6,
+                 detect_languages: Optional[Sequence[int]] = None, align_heads: Optional[Sequence] = None,
+                 guard: Optional[dict] = None, bias: Optional[Callable[[int], Optional[dict]]] = None, loop_fallback: bool = False):
+        assert staging >= 1
+        super().__init__(engine, rows, max_new_tokens, check_every, per_clip_language, fallback, seed, clip0, temperatures,
+                         logprob_threshold, no_speech_threshold, detect_languages, align_heads, guard, bias, loop_fallback)
+        self.staging = staging
+
+    def run(self, n_clips: int, encode: Callable[[int, int, int, bool], Optional[bool]], langs: Optional[Sequence[Optional[int]]] = None,
+            on_result: Optional[Callable[[int, dict], None]] = None, n_keys: Optional[Sequence[int]] = None) -> List[dict]:
+        """Decode clips 0 .. n_clips - 1; returns their results in clip order."""
+        return self._run(n_clips, _Staged(self, n_clips, encode), langs, on_result, n_keys)
+
+
+class _Fed:
+    """FedDecodePool's clips: an encoder thread submits them `batch` at a time to the encoder contexts in turn and queues what
+    it has encoded; a context is handed back to it only when every clip of its submission has been moved"""
+
+    def __init__(self, pool, n_clips: int, encode):
+        self.p = pool
+        self.queue: "queue.Queue" = queue.Queue()      # (encoder index, first clip, n) in submission order; None: see errs
+        self.free = [threading.Semaphore(1) for _ in pool.encoders]   # encoder context not holding un-admitted clips
+        self.stop = threading.Event()                  # the calling thread is done, whether or not every clip was encoded
+        self.errs: List[BaseException] = []
+        self.cur = None                                # the submission being admitted
+        self.thread = threading.Thread(target=self._feed, args=(n_clips, encode))
+        self.thread.start()
+
+    def _feed(self, n_clips: int, encode):
+        try:
+            for k, first in enumerate(range(0, n_clips, self.p.batch)):
+                i = k % len(self.free)
+                self.free[i].acquire()
+                if self.stop.is_set():
+                    break
+                n = min(self.p.batch, n_clips - first)
+                encode(i, first, n)
+                self.p.encodes += 1
+                self.queue.put((i, first, n))
+        except BaseException as ex:   # noqa: BLE001 -- re-raised on the calling thread, which may be waiting for a submission
+            self.errs.append(ex)
+            self.queue.put(None)
+
+    def ready(self, clip: int, wait: bool) -> bool:
+        if self.cur is None:
+            try:
+                self.cur = self.queue.get(block=wait)
+            except queue.Empty:
+                return False
+            if self.cur is None:
+                raise self.errs[0]
+        return True
+
+    def admit(self, clip: int, row: int, lang: int) -> bool:
+        i, first, n = self.cur
+        self.p.e.pool_admit_from(self.p.encoders[i], clip - first, row, lang)
+        if clip + 1 == first + n:
+            self.free[i].release()        # every clip of that submission has been moved: the context may encode again
+            self.cur = None
+        return clip + 1 < first + n or self.ready(clip + 1, False)
+
+    def close(self):
+        self.stop.set()
+        for s_ in self.free:              # a thread that waits for a context wakes up, sees the flag and ends
+            s_.release()
+        self.thread.join()
+
+
+class FedDecodePool(_Pool):
     """One decoding context fed by encoder contexts of the same weight set (nh_pool_admit_from): the pool never stalls for an
     encoder submission -- its stream only ever runs decode steps and the device-to-device moves of admitted clips -- while an
     encoder thread keeps the encoder contexts busy one after the other.  `encode(e, first_clip, n)` must leave clips first ..
     first + n - 1 encoded in rows 0 .. n - 1 of encoder context e (called on the encoder thread; an encoder context is handed
-    out again only when every clip of its previous submission has been admitted)."""
+    out again only when every clip of its previous submission has been admitted).  When run() raises, whether the error is the
+    engine's or `encode`'s, the encoder thread has ended."""
 
     def __init__(self, engine, encoders: Sequence, rows: int = 64, batch: int = 32, max_new_tokens: int = 0, check_every: int = 16,
                  per_clip_language: bool = False, fallback: bool = False, seed: int = 0, clip0: int = 0,
                  temperatures: Sequence[float] = TEMPERATURES, logprob_threshold: float = -1.0, no_speech_threshold: float = 0.6,
                  detect_languages: Optional[Sequence[int]] = None, align_heads: Optional[Sequence] = None,
                  guard: Optional[dict] = None, bias: Optional[Callable[[int], Optional[dict]]] = None, loop_fallback: bool = False):
-        assert rows >= 1 and batch >= 1 and check_every >= 1 and len(encoders) >= 1
-        self._init_fallback(fallback, seed, clip0, temperatures, logprob_threshold, no_speech_threshold)
-        self.e, self.encoders, self.rows, self.batch, self.check_every = engine, list(encoders), rows, batch, check_every
-        self.max_new, self.per_clip_language = max_new_tokens, per_clip_language
-        self._init_detect(detect_languages)
-        self._init_align(align_heads)
-        self._init_guard(guard, bias, loop_fallback)
-        self.steps = self.row_steps = self.encodes = 0
+        assert batch >= 1 and len(encoders) >= 1
+        super().__init__(engine, rows, max_new_tokens, check_every, per_clip_language, fallback, seed, clip0, temperatures,
+                         logprob_threshold, no_speech_threshold, detect_languages, align_heads, guard, bias, loop_fallback)
+        self.encoders, self.batch = list(encoders), batch
 
     def run(self, n_clips: int, encode: Callable[[int, int, int], None], langs: Optional[Sequence[Optional[int]]] = None,
-            n_keys: Optional[Sequence[int]] = None) -> List[dict]:
-        import queue
-        import threading
-        e, R, NE = self.e, self.rows, len(self.encoders)
-        self._begin()
-        ready: "queue.Queue" = queue.Queue()                 # (encoder index, first clip, n) in submission order
-        free = [threading.Semaphore(1) for _ in range(NE)]   # encoder context not holding un-admitted clips
-        errs: List[BaseException] = []
-
-        def feeder():
-            try:
-                for k, first in enumerate(range(0, n_clips, self.batch)):
-                    i = k % NE
-                    free[i].acquire()
-                    n = min(self.batch, n_clips - first)
-                    encode(i, first, n)
-                    self.encodes += 1
-                    ready.put((i, first, n))
-            except BaseException as ex:   # noqa: BLE001 -- re-raised on the calling thread
-                errs.append(ex)
-            finally:
-                ready.put(None)
-        th = threading.Thread(target=feeder)
-        th.start()
-        results: List[Optional[dict]] = [None] * n_clips
-        owner = [-1] * R
-        attempt = [0] * R
-        cur = None          # submission being admitted: [encoder index, first clip, n, next index in it]
-        fed_all, busy, done_clips = False, 0, 0
+            n_keys: Optional[Sequence[int]] = None, on_result: Optional[Callable[[int, dict], None]] = None) -> List[dict]:
+        src = _Fed(self, n_clips, encode)
         try:
-            while done_clips < n_clips and not errs:
-                while True:                      # admit what is encoded into the lowest free rows, in clip order
-                    if cur is None and not fed_all:
-                        try:
-                            item = ready.get(block=(busy == 0))    # nothing to decode: wait for the encoder
-                        except queue.Empty:
-                            break
-                        if item is None:
-                            fed_all = True
-                            break
-                        cur = [item[0], item[1], item[2], 0]
-                    if cur is None:
-                        break
-                    r = next((r for r in range(R) if owner[r] < 0), None)
-                    if r is None:
-                        break
-                    i, first, n, j = cur
-                    c = first + j
-                    self._admit_bias(r, c)
-                    e.pool_admit_from(self.encoders[i], j, r, self._admit_lang(r, c, langs))
-                    owner[r], attempt[r] = c, 0
-                    busy += 1
-                    cur[3] += 1
-                    if cur[3] == n:
-                        free[i].release()        # every clip of that submission has been moved: the context may encode again
-                        cur = None
-                if busy == 0:
-                    continue
-                flags = e.pool_step(self.check_every)
-                self.steps += self.check_every
-                self.row_steps += busy * self.check_every
-                fin = [r for r in range(R) if owner[r] >= 0 and flags[r] in (1, 2)]
-                if fin:
-                    settled = []
-                    for r, res in zip(fin, self._collect(fin, attempt)):
-                        if not self._settle(r, owner[r], res, attempt[r]):
-                            attempt[r] += 1
-                            continue
-                        settled.append((r, owner[r], res))
-                    self._align(settled, n_keys)
-                    for r, c, res in settled:
-                        results[c] = res
-                        owner[r] = -1
-                        busy -= 1
-                        done_clips += 1
+            return self._run(n_clips, src, langs, on_result, n_keys)
         finally:
-            for s_ in free:                      # let a feeder that is waiting for a context run to its end
-                s_.release()
-            th.join()
-        if errs:
-            raise errs[0]
-        return results  # type: ignore[return-value]
+            src.close()

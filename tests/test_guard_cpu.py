@@ -12,6 +12,7 @@ import beam_fixture as F
 import common
 import guard_fixture as GF
 import guard_ref as G
+import pool_standin
 from norma_amd import hip, pool
 
 # a toy vocabulary: text 0 .. 4, eot 5, specials 6 .. 8 (no_timestamps 8), timestamps 9 .. 11
@@ -109,54 +110,10 @@ def test_new_symbols_are_declared_and_exported():
 
 
 # ---- the pool policy -------------------------------------------------------------------------------------------------------
-class Engine:
-    """counting stand-in: clip c decodes for 2 steps; clips in `loops` take the loop exit at attempt 0 (and at every attempt
-    in `always`)"""
-
-    def __init__(self, loops=(), always=(), logprob=-0.5, nsp=0.1, with_guard=True):
-        self.loops, self.always, self.logprob, self.nsp = set(loops), set(always), logprob, nsp
-        self.calls = []
-        if not with_guard:     # an engine without the guard's methods at all: the pool must not ask for them
-            self.set_guard = self.guard_bias = self.guard_report = None
-
-    def pool_begin(self, rows, max_new, per_clip_language):
-        self.rows, self.left, self.clip, self.attempt, self.staged = rows, [None] * rows, [None] * rows, [0] * rows, {}
-
-    def encode(self, first, n, row0, must):
-        self.staged = {row0 + i: first + i for i in range(n)}
-
-    def set_guard(self, **kw):
-        self.calls.append(("set_guard", kw))
-
-    def guard_bias(self, row, bias):
-        assert self.left[row] is None
-        self.calls.append(("guard_bias", row, bias))
-
-    def guard_report(self, rows):
-        self.calls.append(("guard_report", tuple(rows)))
-        return [int(self.clip[r] in self.always or (self.clip[r] in self.loops and self.attempt[r] == 0)) for r in rows]
-
-    def pool_admit(self, src, dst, lang):
-        self.clip[dst], self.left[dst], self.attempt[dst] = self.staged.pop(src), 2, 0
-        self.calls.append(("admit", self.clip[dst], dst))
-
-    def pool_retry(self, row, temperature, seed, clip, attempt):
-        self.left[row], self.attempt[row] = 2, attempt
-        self.calls.append(("retry", self.clip[row], attempt))
-
-    def pool_step(self, n):
-        flags = np.full(self.rows, 3, dtype=np.int32)
-        for r in range(self.rows):
-            if self.left[r] is not None:
-                self.left[r] = max(0, self.left[r] - n)
-                flags[r] = 1 if self.left[r] == 0 else 0
-        return flags
-
-    def pool_collect(self, rows):
-        out = [dict(avg_logprob=self.logprob, no_speech_prob=self.nsp, no_speech_exit=False, tokens=[self.clip[r], self.attempt[r]]) for r in rows]
-        for r in rows:
-            self.left[r] = None
-        return out
+def Engine(loops=(), always=(), logprob=-0.5, nsp=0.1, with_guard=True):
+    """every clip decodes for 2 steps (+ attempt) and collects as (logprob, nsp); with_guard=False: an engine without the
+    guard's methods at all -- the pool must not ask for them"""
+    return pool_standin.Engine([2] * 8, [[(logprob, nsp)] * 6] * 8, guard=with_guard, loops=loops, always=always)
 
 
 GUARD = dict(no_repeat_ngram=3, loop_period=4, loop_repeats=3)
@@ -173,23 +130,23 @@ def test_pool_sets_the_guard_once_and_reports_loop_exit():
     e = Engine(loops={1, 3})
     p = pool.DecodePool(e, rows=2, staging=2, check_every=2, guard=GUARD)
     res = p.run(5, e.encode)
-    assert [c for c in e.calls if c[0] == "set_guard"] == [("set_guard", GUARD)]
-    assert e.calls[0][0] == "set_guard"                                   # before the first admission
+    assert [c for c in e.log if c[0] == "set_guard"] == [("set_guard", GUARD)]
+    assert [c[0] for c in e.log[:2]] == ["begin", "set_guard"]          # before the first admission
     assert [r["loop_exit"] for r in res] == [False, True, False, True, False]
-    assert p.retries == 0 and not any(c[0] == "guard_bias" for c in e.calls)
+    assert p.retries == 0 and not any(c[0] == "guard_bias" for c in e.log)
     # a guard without a loop exit: nothing to report, nothing asked
     e = Engine()
     res = pool.DecodePool(e, rows=2, staging=2, check_every=2, guard=dict(no_repeat_ngram=3)).run(3, e.encode)
-    assert not any(c[0] == "guard_report" for c in e.calls) and all("loop_exit" not in r for r in res)
+    assert not any(c[0] == "guard_report" for c in e.log) and all("loop_exit" not in r for r in res)
 
 
 def test_pool_bias_goes_to_the_row_before_its_admission():
     e = Engine()
     bias = lambda c: {100 + c: -INF} if c % 2 else None
     pool.DecodePool(e, rows=2, staging=2, check_every=2, guard=dict(bias=True), bias=bias).run(4, e.encode)
-    seq = [c for c in e.calls if c[0] in ("guard_bias", "admit")]
+    seq = [c for c in e.log if c[0] in ("guard_bias", "admit")]
     for i in range(0, len(seq), 2):
-        (_, row, b), (_, clip, dst) = seq[i], seq[i + 1]
+        (_, row, b), (_, clip, dst, _lang) = seq[i], seq[i + 1]
         assert row == dst and b == bias(clip)
     assert len(seq) == 8
 
@@ -198,7 +155,7 @@ def test_loop_fallback_retries_the_looping_clip_only():
     e = Engine(loops={2}, always={4})
     p = pool.DecodePool(e, rows=2, staging=3, check_every=2, guard=GUARD, fallback=True, loop_fallback=True)
     res = p.run(6, e.encode)
-    assert sorted((c[1], c[2]) for c in e.calls if c[0] == "retry") == [(2, 1)] + [(4, a) for a in range(1, 6)]
+    assert sorted((c[1], c[6]) for c in e.log if c[0] == "retry") == [(2, 1)] + [(4, a) for a in range(1, 6)]
     assert [r["attempt"] for r in res] == [0, 0, 1, 0, 5, 0]
     assert [r["accepted"] for r in res] == [True, True, True, True, False, True]      # clip 4 loops at every temperature: dropped
     assert res[2]["loop_exit"] is False and res[4]["loop_exit"] is True
@@ -211,38 +168,22 @@ def test_loop_fallback_retries_the_looping_clip_only():
     assert [r["attempt"] for r in p.run(3, e.encode)] == [0] * 3 and p.retries == 0
 
 
-class Enc:
-    """an encoder context of the fed pool's stand-in: the clips it holds, by row"""
-    def __init__(self):
-        self.rows = {}
-
-
-class FedEngine(Engine):
-    def pool_admit_from(self, enc, src, dst, lang):
-        self.clip[dst], self.left[dst], self.attempt[dst] = enc.rows.pop(src), 2, 0
-        self.calls.append(("admit", self.clip[dst], dst))
-
-
 def test_fed_pool_guard_bias_and_loop_fallback():
-    e, encs = FedEngine(loops={1}), [Enc(), Enc()]
-
-    def encode(i, first, n):
-        assert not encs[i].rows
-        encs[i].rows = {k: first + k for k in range(n)}
+    e, encs = Engine(loops={1}), [pool_standin.Encoder(), pool_standin.Encoder()]
     bias = lambda c: {100 + c: 1.0} if c % 2 else None
     p = pool.FedDecodePool(e, encs, rows=2, batch=2, check_every=2, guard=dict(GUARD, bias=True), bias=bias, fallback=True, loop_fallback=True)
-    res = p.run(5, encode)
-    assert e.calls[0] == ("set_guard", dict(GUARD, bias=True)) and sum(c[0] == "set_guard" for c in e.calls) == 1
-    seq = [c for c in e.calls if c[0] in ("guard_bias", "admit")]
+    res = p.run(5, pool_standin.feeder(encs))
+    assert e.log[0][0] == "begin" and e.log[1] == ("set_guard", dict(GUARD, bias=True)) and sum(c[0] == "set_guard" for c in e.log) == 1
+    seq = [c for c in e.log if c[0] in ("guard_bias", "admit")]
     assert len(seq) == 10
     for i in range(0, len(seq), 2):
-        (_, row, b), (_, clip, dst) = seq[i], seq[i + 1]
+        (_, row, b), (_, clip, dst, _lang) = seq[i], seq[i + 1]
         assert row == dst and b == bias(clip)
     assert [r["attempt"] for r in res] == [0, 1, 0, 0, 0] and [r["loop_exit"] for r in res] == [False] * 5
-    assert [(c[1], c[2]) for c in e.calls if c[0] == "retry"] == [(1, 1)]
+    assert [(c[1], c[6]) for c in e.log if c[0] == "retry"] == [(1, 1)]
     # without the keywords: an engine that has none of the guard's methods
-    e, encs = FedEngine(with_guard=False), [Enc(), Enc()]
-    res = pool.FedDecodePool(e, encs, rows=2, batch=2, check_every=2).run(3, encode)
+    e, encs = Engine(with_guard=False), [pool_standin.Encoder(), pool_standin.Encoder()]
+    res = pool.FedDecodePool(e, encs, rows=2, batch=2, check_every=2).run(3, pool_standin.feeder(encs))
     assert [r["tokens"] for r in res] == [[c, 0] for c in range(3)]
 
 

@@ -1,5 +1,5 @@
-"""CPU: token-level timestamps through the decode pool (norma_amd/pool.py, align_heads=...) against a scripted stand-in for
-the engine: the pool tells the engine the heads once, after pool_begin and before anything is admitted; it aligns exactly the
+"""CPU: token-level timestamps through the decode pool (norma_amd/pool.py, align_heads=...) against the scripted stand-in for
+the engine (tests/pool_standin.py): the pool tells the engine the heads once, after pool_begin and before anything is admitted; it aligns exactly the
 attempts it accepts -- never a rejected or a dropped one, never a no-speech exit --, while the row still holds the clip (before
 anything is admitted into it or it is retried), with the clip's own n_keys; without the keyword it calls neither method.  The
 GPU side is tests/test_gpu_align_live.py."""
@@ -7,66 +7,21 @@ import numpy as np
 import pytest
 
 from norma_amd import hip, pool
-from test_pool_fallback_cpu import BAD, GOOD, FakeEncoder, FedScriptedEngine, ScriptedEngine, make_script
+from pool_standin import BAD, GOOD, MUTE, Encoder, Engine, feeder
+from test_pool_fallback_cpu import make_script
 
 HEADS = [(1, 0), (0, 1)]
-N_POS = 12
-
-
-class _Aligning:
-    """align_decoded answers with numbers made of (clip, attempt, n_keys), so a result shows which decode it was aligned on"""
-
-    def align_capture(self, heads):
-        assert all(l is None for l in self.left), "heads set while a row is busy"
-        self.heads = list(heads)
-        self.log.append(("capture", tuple(heads)))
-
-    def pool_collect(self, rows):
-        out = super().pool_collect(rows)
-        for r, res in zip(rows, out):
-            res["no_speech_exit"] = res["no_speech_prob"] > 0.95 and self.attempt[r] == 0
-            if res["no_speech_exit"]:
-                res["tokens"] = [7, 8, 9]
-            else:
-                res["tokens"] = [7, 8, 9] + [100 + res["clip"], 200 + self.attempt[r]]
-        return out
-
-    def align_decoded(self, rows, n_keys=None):
-        first = np.full((len(rows), N_POS), -1, dtype=np.int32)
-        last = np.full((len(rows), N_POS), -1, dtype=np.int32)
-        for i, r in enumerate(rows):
-            assert self.left[r] is None and self.clip[r] is not None, "aligned a busy or an empty row"
-            nk = -1 if n_keys is None else n_keys[i]
-            first[i, 3:5] = [self.clip[r], self.attempt[r]]
-            last[i, 3:5] = [nk, 1000 + self.clip[r]]
-        self.log.append(("align", tuple(rows), tuple(self.clip[r] for r in rows), tuple(self.attempt[r] for r in rows),
-                         None if n_keys is None else tuple(n_keys)))
-        return first, last
-
-
-class Engine(_Aligning, ScriptedEngine):
-    pass
-
-
-class FedEngine(_Aligning, FedScriptedEngine):
-    pass
-
-
-MUTE = (-2.0, 0.99)     # the no-speech exit: accepted at attempt 0, nothing to align
 
 
 def _run(kind, N, script, rows, feed, check, n_keys, **kw):
     lengths = [3 + (5 * c) % 11 for c in range(N)]
+    e = Engine(lengths, script, align="align_heads" in kw)
     if kind == "plain":
-        e = Engine(lengths, script)
         p = pool.DecodePool(e, rows=rows, staging=feed, check_every=check, **kw)
         return e, p, p.run(N, e.encode, n_keys=n_keys)
-    e, encs = FedEngine(lengths, script), [FakeEncoder(), FakeEncoder()]
-
-    def encode(i, first, n):
-        encs[i].rows = {k: first + k for k in range(n)}
+    encs = [Encoder(), Encoder()]
     p = pool.FedDecodePool(e, encs, rows=rows, batch=feed, check_every=check, **kw)
-    return e, p, p.run(N, encode, n_keys=n_keys)
+    return e, p, p.run(N, feeder(encs), n_keys=n_keys)
 
 
 @pytest.mark.parametrize("kind", ["plain", "fed"])

@@ -1,83 +1,12 @@
-"""CPU: the temperature fallback of the decode pool (norma_amd/pool.py, fallback=True) against a scripted stand-in for the
-engine.  decode_with_fallback (src/models/whisper/model.rs:164-191) walks TEMPERATURES until avg_logprob >= -1 or
+"""CPU: the temperature fallback of the decode pool (norma_amd/pool.py, fallback=True) against the scripted stand-in for the
+engine (tests/pool_standin.py).  decode_with_fallback (src/models/whisper/model.rs:164-191) walks TEMPERATURES until avg_logprob >= -1 or
 no_speech_prob > 0.6 and drops the clip otherwise; the pool does that per row: an admitted clip is attempt 0, every further
 attempt is a pool_retry of the row the clip already sits in.  The GPU side is tests/test_gpu_pool_fallback.py."""
 import numpy as np
 import pytest
 
 from norma_amd import pool
-
-GOOD, BAD = (-0.5, 0.1), (-2.0, 0.1)      # (avg_logprob, no_speech_prob): accepted / needs a fallback
-SILENT = (-2.0, 0.9)                      # needs a fallback by its log-prob, accepted all the same: no_speech_prob > 0.6
-
-
-class ScriptedEngine:
-    """pool_collect returns script[clip][attempt]; every call is logged.  A decode takes lengths[clip] + attempt steps."""
-
-    def __init__(self, lengths, script, clip0=0):
-        self.lengths, self.script, self.clip0 = lengths, script, clip0
-        self.log = []
-
-    def pool_begin(self, rows, max_new, per_clip_language):
-        self.rows = rows
-        self.left = [None] * rows          # steps still to run per row (None: not busy)
-        self.clip = [None] * rows          # the clip whose cross K/V the row holds
-        self.attempt = [0] * rows
-        self.retrying = [False] * rows     # the policy owes this row a pool_retry or a final answer
-        self.staged = {}
-        self.log.append(("begin", rows))
-
-    def encode(self, first, n, row0, must):
-        assert row0 == self.rows
-        self.staged = {row0 + i: first + i for i in range(n)}
-        self.log.append(("encode", first, n))
-
-    def _admit(self, c, dst, lang):
-        assert self.left[dst] is None, "admit into a busy row"
-        self.clip[dst], self.left[dst], self.attempt[dst] = c, self.lengths[c], 0
-        self.log.append(("admit", c, dst, lang))
-
-    def pool_admit(self, src, dst, lang):
-        assert src in self.staged
-        self._admit(self.staged.pop(src), dst, lang)
-
-    def pool_retry(self, row, temperature, seed, clip, attempt):
-        assert self.left[row] is None and self.clip[row] is not None, "retry of a busy or never admitted row"
-        assert clip == self.clip0 + self.clip[row]
-        self.left[row], self.attempt[row] = self.lengths[self.clip[row]] + attempt, attempt
-        self.log.append(("retry", self.clip[row], row, temperature, seed, clip, attempt))
-
-    def pool_step(self, n):
-        flags = np.zeros(self.rows, dtype=np.int32)
-        for r in range(self.rows):
-            if self.left[r] is None:
-                flags[r] = 3
-            else:
-                self.left[r] = max(0, self.left[r] - n)
-                flags[r] = 1 if self.left[r] == 0 else 0
-        self.log.append(("step", n))
-        return flags
-
-    def pool_collect(self, rows):
-        out = []
-        for r in rows:
-            assert self.left[r] == 0
-            lp, ns = self.script[self.clip[r]][self.attempt[r]]
-            out.append(dict(clip=self.clip[r], avg_logprob=lp, no_speech_prob=ns, tokens=[self.clip[r], self.attempt[r]]))
-            self.left[r] = None
-        self.log.append(("collect", tuple(rows)))
-        return out
-
-
-class FedScriptedEngine(ScriptedEngine):
-    def pool_admit_from(self, enc, src, dst, lang):
-        assert src in enc.rows
-        self._admit(enc.rows.pop(src), dst, lang)
-
-
-class FakeEncoder:
-    def __init__(self):
-        self.rows = {}
+from pool_standin import BAD, GOOD, SILENT, Encoder, Engine, feeder
 
 
 def make_script(N, rng):
@@ -97,17 +26,13 @@ def make_script(N, rng):
 
 
 def run_pool(kind, N, lengths, script, rows, feed, check, **kw):
+    e = Engine(lengths, script, clip0=kw.get("clip0", 0))
     if kind == "plain":
-        e = ScriptedEngine(lengths, script, clip0=kw.get("clip0", 0))
         p = pool.DecodePool(e, rows=rows, staging=feed, check_every=check, **kw)
         return e, p, p.run(N, e.encode, langs=list(range(1000, 1000 + N)))
-    e, encs = FedScriptedEngine(lengths, script, clip0=kw.get("clip0", 0)), [FakeEncoder(), FakeEncoder()]
-
-    def encode(i, first, n):
-        assert not encs[i].rows
-        encs[i].rows = {k: first + k for k in range(n)}
+    encs = [Encoder(), Encoder()]
     p = pool.FedDecodePool(e, encs, rows=rows, batch=feed, check_every=check, **kw)
-    return e, p, p.run(N, encode, langs=list(range(1000, 1000 + N)))
+    return e, p, p.run(N, feeder(encs), langs=list(range(1000, 1000 + N)))
 
 
 @pytest.mark.parametrize("kind", ["plain", "fed"])
@@ -142,7 +67,7 @@ def test_fallback_walks_the_temperatures_per_clip_in_the_row_the_clip_sits_in(ki
     assert [len(per_clip[c]) for c in range(N) if not want[c][1]] == [5] * sum(not ok for _, ok in want)
     assert p.retries == sum(k for k, _ in want) == sum(1 for x in e.log if x[0] == "retry")
     # a row that owes a retry is never the target of an admit: between the collect that returned a failing attempt and the
-    # clip's final answer, the only calls naming that row are the clip's own retries (ScriptedEngine also refuses an admit
+    # clip's final answer, the only calls naming that row are the clip's own retries (the stand-in also refuses an admit
     # into a busy row; this covers the moment between collect and retry)
     owner = {}
     for x in e.log:
@@ -193,7 +118,7 @@ def test_without_fallback_the_calls_are_what_they_were(kind):
         e1, p1, r1 = run_pool(kind, N, lengths, good, 4, 3, 2, fallback=True)
         assert e0.log == e1.log and (p0.steps, p0.row_steps, p0.encodes) == (p1.steps, p1.row_steps, p1.encodes)
         # today's sequence, spelled out for the head of the run: begin, encode 3, admit 3, step, ...
-        assert e0.log[:6] == [("begin", 4), ("encode", 0, 3), ("admit", 0, 0, 1000), ("admit", 1, 1, 1001), ("admit", 2, 2, 1002), ("step", 2)]
+        assert e0.log[:6] == [("begin", 4, False), ("encode", 0, 3), ("admit", 0, 0, 1000), ("admit", 1, 1, 1001), ("admit", 2, 2, 1002), ("step", 2)]
     assert {x[0] for x in e0.log} == {"begin", "encode", "admit", "step", "collect"} - ({"encode"} if kind == "fed" else set())
 
 
