@@ -30,14 +30,11 @@ static int align_head_set(nh_ctx *ctx, const char *who, const nh_align_head *hea
 // moves makes them stale (StepKey::align_gen), and what a decode kept in the old one is gone.  A failure changes nothing.
 static int align_q_buffer(nh_ctx *ctx, const char *who, int A) {
     if (A <= ctx->align_q_heads) return NH_OK;
-    HIPCHK(hipStreamSynchronize(ctx->st));   // a finished decode may still be copying into the buffer that goes
-    half_t *q = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&q), (size_t)A * (ctx->c.max_target_positions - 1) * ctx->B * NH_DH * sizeof(half_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        return ctx->fail(NH_ERR_NOMEM, std::string(who) + ": hipMalloc failed");
-    }
-    if (ctx->align_q) hipFree(ctx->align_q);
-    ctx->align_q = q; ctx->align_q_heads = A;
+    // reserve drains the stream first: a finished decode may still be copying into the buffer that goes
+    DevBuf q;
+    if (int rc = q.reserve(ctx, (size_t)A * (ctx->c.max_target_positions - 1) * ctx->B * NH_DH * sizeof(half_t), who)) return rc;
+    ctx->align_q.swap(q);   // ... and the old one goes with q
+    ctx->align_q_heads = A;
     ctx->live.gen++; ctx->live.lock_valid = false;
     return NH_OK;
 }
@@ -56,28 +53,23 @@ static int align_prepare(nh_ctx *ctx, int A, int n) {
         const size_t room = NH_ALIGN_BUDGET > fixed ? NH_ALIGN_BUDGET - fixed : 0;
         group = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, room / per_clip));
     }
-    // kept whenever it is large enough: the rows a pool hands back differ from collect to collect, and making it again costs a
-    // stream synchronise and device-wide hipFree / hipMalloc pairs on the path the pool exists for
+    // kept whenever it is large enough: the rows a pool hands back differ from collect to collect.  Another shape carves the
+    // buffer again, and only one that needs more than any before costs a stream synchronise and a new allocation.
     if (al.heads == A && al.group >= group && al.S == (int)S) return NH_OK;
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    for (void *p : al.allocs) hipFree(p);
-    al = AlignState{};
-    al.n_rows = dalloc_into<int32_t>(al.allocs, B);
-    al.n_keys = dalloc_into<int32_t>(al.allocs, B);
-    al.row_map = dalloc_into<int32_t>(al.allocs, B);
-    al.first = dalloc_into<int32_t>(al.allocs, B * (C + 1));
-    al.last = dalloc_into<int32_t>(al.allocs, B * (C + 1));
-    al.W = dalloc_into<float>(al.allocs, (size_t)group * A * NP * S, false);
-    al.stats = dalloc_into<float>(al.allocs, (size_t)group * A * 2 * S, false);
-    al.M = dalloc_into<float>(al.allocs, (size_t)group * C * S, false);
-    al.trace = dalloc_into<uint8_t>(al.allocs, (size_t)group * C * S, false);
-    if (!al.n_rows || !al.n_keys || !al.row_map || !al.first || !al.last || !al.W || !al.stats || !al.M || !al.trace) {
-        for (void *p : al.allocs) hipFree(p);
-        al = AlignState{};
-        (void)hipGetLastError();
-        return ctx->fail(NH_ERR_NOMEM, "nh_align: the workspace for " + std::to_string(group) + " clips x " + std::to_string(A) +
+    Carve cv;
+    const size_t o_rows = cv.take(4 * B), o_keys = cv.take(4 * B), o_map = cv.take(4 * B);
+    const size_t o_first = cv.take(4 * B * (C + 1)), o_last = cv.take(4 * B * (C + 1)), zeroed = cv.off;
+    const size_t o_W = cv.take(sizeof(float) * group * A * NP * S), o_stats = cv.take(sizeof(float) * group * A * 2 * S);
+    const size_t o_M = cv.take(sizeof(float) * group * C * S), o_trace = cv.take((size_t)group * C * S);
+    al.heads = al.group = al.S = 0; al.kept = false;   // what the views showed is cut up differently from here on
+    if (int rc = al.buf.reserve(ctx, cv.off, "alignment workspace"))
+        return rc != NH_ERR_NOMEM ? rc : ctx->fail(rc, "nh_align: the workspace for " + std::to_string(group) + " clips x " + std::to_string(A) +
                                            " heads does not fit (NH_OPT_ALIGN_KEEP = 1 holds the whole batch)");
-    }
+    HIPCHK(hipMemsetAsync(al.buf.p, 0, zeroed, ctx->st));   // the rows, keys, row map and paths start as zeros
+    al.n_rows = al.buf.at<int32_t>(o_rows); al.n_keys = al.buf.at<int32_t>(o_keys); al.row_map = al.buf.at<int32_t>(o_map);
+    al.first = al.buf.at<int32_t>(o_first); al.last = al.buf.at<int32_t>(o_last);
+    al.W = al.buf.at<float>(o_W); al.stats = al.buf.at<float>(o_stats); al.M = al.buf.at<float>(o_M);
+    al.trace = al.buf.at<uint8_t>(o_trace);
     al.heads = A; al.group = group; al.S = (int)S;
     return NH_OK;
 }
@@ -118,7 +110,7 @@ static int align_run(nh_ctx *ctx, const char *who, const AlignHeadSet &hs, int P
     al.kept = false;
     AlignHeadPtrs hp{};
     for (int a = 0; a < hs.A; a++) {
-        hp.q[a] = ctx->align_q + (size_t)a * NP * ctx->B * NH_DH;
+        hp.q[a] = ctx->align_q.at<half_t>() + (size_t)a * NP * ctx->B * NH_DH;
         hp.k[a] = ctx->kv[hs.heads[a].layer].ck + (size_t)hs.heads[a].head * S * NH_DH;
     }
     std::vector<int32_t> rows(n);
@@ -246,25 +238,25 @@ extern "C" int nh_align_path(nh_ctx *ctx, const float *matrix, int R, int nk, in
     if (R < 1 || R > ctx->c.max_target_positions || nk < 1 || nk > Smax) return ctx->fail(NH_ERR_INVALID, "nh_align_path: R or nk out of range");
     hipSetDevice(ctx->dev);
     // a parity view with buffers of its own: the workspace of the last nh_align (and its views) stays as it is
-    std::vector<void *> tmp;
-    float *M = dalloc_into<float>(tmp, (size_t)R * nk, false);
-    uint8_t *trace = dalloc_into<uint8_t>(tmp, (size_t)R * nk, false);
-    int32_t *meta = dalloc_into<int32_t>(tmp, 2 + 2 * (size_t)(R + 1));   // n_rows, n_keys, first [R + 1], last [R + 1]
-    auto done = [&](int rc) { for (void *p : tmp) hipFree(p); return rc; };
-    if (!M || !trace || !meta) return done(ctx->fail(NH_ERR_NOMEM, "nh_align_path: hipMalloc failed"));
+    DevBuf tmp;
+    Carve cv;
+    const size_t o_M = cv.take(sizeof(float) * (size_t)R * nk), o_trace = cv.take((size_t)R * nk);
+    const size_t o_meta = cv.take(4 * (2 + 2 * (size_t)(R + 1)));   // n_rows, n_keys, first [R + 1], last [R + 1]
+    if (int rc = tmp.reserve(ctx, cv.off, "nh_align_path", true)) return rc;
+    float *M = tmp.at<float>(o_M);
+    int32_t *meta = tmp.at<int32_t>(o_meta);
     const int32_t rk[2] = {R, nk};
     std::vector<int32_t> fl(2 * (size_t)(R + 1));
-    hipError_t e = hipMemcpyAsync(M, matrix, (size_t)R * nk * 4, hipMemcpyHostToDevice, ctx->st);
-    if (e == hipSuccess) e = hipMemcpyAsync(meta, rk, 8, hipMemcpyHostToDevice, ctx->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->st);
+    HIPCHK(hipMemcpyAsync(M, matrix, (size_t)R * nk * 4, hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipMemcpyAsync(meta, rk, 8, hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));
     // prompt_len 1 and n - 1 = R rows: row r of the matrix is token 1 + r
-    if (e == hipSuccess && !launch_align_dtw(M, (long)R * nk, nk, meta, meta + 1, 1, R, nk, 1, 0, trace, (long)R * nk, meta + 2, meta + 2 + (R + 1), R + 1, nullptr, ctx->st))
-        return done(ctx->fail(NH_ERR_INVALID, "nh_align_path: the DTW kernel covers R <= 512"));
-    if (e == hipSuccess) e = hipMemcpyAsync(fl.data(), meta + 2, fl.size() * 4, hipMemcpyDeviceToHost, ctx->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->st);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return done(ctx->fail(NH_ERR_HIP, std::string("nh_align_path: ") + hipGetErrorString(e)));
+    if (!launch_align_dtw(M, (long)R * nk, nk, meta, meta + 1, 1, R, nk, 1, 0, tmp.at<uint8_t>(o_trace), (long)R * nk, meta + 2, meta + 2 + (R + 1), R + 1, nullptr, ctx->st))
+        return ctx->fail(NH_ERR_INVALID, "nh_align_path: the DTW kernel covers R <= 512");
+    HIPCHK(hipMemcpyAsync(fl.data(), meta + 2, fl.size() * 4, hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    HIPCHK(hipGetLastError());
     memcpy(out_first, fl.data() + 1, sizeof(int32_t) * R);
     memcpy(out_last, fl.data() + (R + 1) + 1, sizeof(int32_t) * R);
-    return done(NH_OK);
+    return NH_OK;
 }

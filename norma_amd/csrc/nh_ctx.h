@@ -1,8 +1,10 @@
 // nh_ctx.h -- the state behind the C ABI of include/norma_hip.h, shared by the files that implement it: nh_model.hip
 // (create / destroy, weights, tokens, options, timings), nh_encode.hip (log-mel, encoder), nh_decode.hip (decoder step,
 // lockstep decode, decode pool, parity views), nh_prefill.hip (decoder prompts, the one-pass forward), nh_score.hip (transcript scoring), nh_align.hip (token-level timestamps), nh_resample.hip (audio ingest),
-// nh_cut.hip (cutting long recordings), nh_vad.hip (their speech map).  It also holds the two things every audio route into the PCM rows shares: the
-// grow-on-demand device buffer (DevBuf: the one staging of host audio, the cut workspaces) and the batch check
+// nh_cut.hip (cutting long recordings), nh_vad.hip (their speech map).  Device memory has two owners and no third: an
+// Arena for what is made once and kept until its owner dies (the model's tables, the workspaces build_context makes), and
+// DevBuf for everything made lazily, grown, replaced or living for one call -- a feature's lazy buffers are ONE DevBuf cut
+// with Carve, so a group is there or not there.  Both release themselves: ~nh_ctx names neither.  Also here: the batch check
 // (check_batch) that runs before anything is queued.  No torch, no candle, no CPU fallback: an entry point runs the HIP
 // path or fails.
 #pragma once
@@ -29,6 +31,24 @@
         }                                                                                     \
     } while (0)
 
+// Device buffers made once and kept until their owner dies: they never move and are never replaced.
+struct Arena {
+    std::vector<void *> ptrs;
+    Arena() = default;
+    Arena(const Arena &) = delete;
+    Arena &operator=(const Arena &) = delete;
+    ~Arena() { for (void *p : ptrs) hipFree(p); }   // the owner's destructor has made the device current
+    template <typename T>
+    T *dalloc_into(size_t n, bool zero = true) {
+        void *p = nullptr;
+        if (n == 0) n = 1;
+        if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) return nullptr;
+        if (zero) hipMemset(p, 0, n * sizeof(T));
+        ptrs.push_back(p);
+        return reinterpret_cast<T *>(p);
+    }
+};
+
 struct LinW { half_t *w = nullptr; float *b = nullptr; half_t *wt = nullptr; /* tile-major repack (decoder GEMVs) */ };
 struct LnW { float *w = nullptr, *b = nullptr; };
 struct EncLayer { LnW ln1, ln2; LinW qkv, o, fc1, fc2; };
@@ -44,7 +64,7 @@ struct KvCache { half_t *ck = nullptr, *cv = nullptr, *sk = nullptr, *sv = nullp
 struct nh_model {
     int dev = 0;
     nh_config c{};
-    std::vector<void *> allocs;
+    Arena allocs;                    // the tables below; lazy additions (repacks, resample and mel filter tables) under mu
     LinW conv1, conv2;
     float *enc_pos = nullptr;
     std::vector<EncLayer> enc;
@@ -64,10 +84,7 @@ struct nh_model {
     // hipStreamWaitEvent fails ("dependency created on uncaptured work in another stream") on an event whose stream is capturing
     // at that moment, even one recorded before: a step capture and the encoders' waits on kv_readers exclude each other
     std::mutex capture_mu;
-    ~nh_model() {
-        hipSetDevice(dev);
-        for (void *p : allocs) hipFree(p);
-    }
+    ~nh_model() { hipSetDevice(dev); }   // ... and allocs frees the tables
 };
 
 struct PoolRow {   // one row of a decode pool, as the host knows it
@@ -107,10 +124,34 @@ struct StepGraphs {
     hipGraphExec_t multi = nullptr; // NH_GRAPH_STEPS consecutive steps (one launch gap instead of NH_GRAPH_STEPS)
 };
 
+// A device buffer that grows on demand: empty until the first call that needs it (a context that never stages, plans or
+// aligns holds nothing), released with whatever it is a member or a local of.
+struct nh_ctx;
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) hipFree(p); }   // ~nh_ctx has made the device current and drained the stream
+    // room for `need` bytes (contents are not kept; zero: a buffer made here starts as zeros, in stream order); on failure the
+    // buffer is empty and NH_ERR_NOMEM names `what`
+    int reserve(nh_ctx *ctx, size_t need, const char *what, bool zero = false);
+    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(bytes, o.bytes); }
+    template <typename T>
+    T *at(size_t off = 0) const { return reinterpret_cast<T *>(static_cast<char *>(p) + off); }
+};
+// One DevBuf carved into 16-byte aligned pieces: take(bytes) is the piece's offset, `off` ends as the bytes to reserve
+static inline size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
+struct Carve {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off += up16(bytes); return o; }
+};
+
 // The workspace of stages 2 - 6 (nh_align, nh_align_decoded): allocated by the first alignment (contexts that never align pay
-// nothing), freed by nh_destroy.  The last call's shape is kept for the views (nh_align_weights / nh_align_matrix).
+// nothing).  The last call's shape is kept for the views (nh_align_weights / nh_align_matrix).
 struct AlignState {
-    std::vector<void *> allocs;      // everything below; released and re-made when a call needs more
+    DevBuf buf;                      // everything below, carved again when the shape changes; it only grows
     int32_t *n_rows = nullptr, *n_keys = nullptr;   // [max_batch]
     int32_t *row_map = nullptr;                     // [max_batch] context row of every clip of a call (nh_align_decoded on a pool)
     int32_t *first = nullptr, *last = nullptr;      // [max_batch][C + 1]
@@ -142,26 +183,6 @@ struct AlignLive {
     std::vector<int32_t> n, done;
 };
 
-// A device scratch buffer that grows on demand: empty until the first call that needs it (a context that never stages or
-// plans holds nothing), released with the context it is a member of -- nh_destroy names none of them.
-struct nh_ctx;
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p) hipFree(p); }   // nh_destroy has made the device current and drained the stream
-    // room for `need` bytes (contents are not kept); on failure the buffer is empty and NH_ERR_NOMEM names `what`
-    int reserve(nh_ctx *ctx, size_t need, const char *what);
-};
-// One DevBuf carved into 16-byte aligned pieces: take(bytes) is the piece's offset, `off` ends as the bytes to reserve
-static inline size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
-struct Carve {
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off += up16(bytes); return o; }
-};
-
 // nh_cut_plan: everything it owns.  Two (e, E) workspaces: a plan computes into the one that is not the view of nh_cut_energy
 // and becomes the view only when it succeeds, so a refused call -- cap too small is known only after the search -- leaves the
 // view of the plan before as it was.
@@ -169,8 +190,7 @@ struct CutState {
     DevBuf ws[2];                // e[F] then E[F] of the plan computed there
     int view = -1;               // the workspace of the last successful plan; -1: none yet
     long long F = 0;             // its frames
-    DevBuf out;                  // the search's outputs: starts[cap] (64-bit) then lens[cap]
-    int32_t *count = nullptr;    // [1], in ctx->allocs
+    DevBuf out;                  // the search's outputs: starts[cap] (64-bit), lens[cap], the count; cut again by every plan
 };
 
 // nh_vad_plan: everything it owns, beside and apart from CutState (the view of nh_cut_energy is not its to change).  Two view
@@ -217,10 +237,18 @@ struct GuardState {
     GuardSpec spec{0, 1.0f, 0, 0, 0};
     bool on = false;
     int gen = 0;                    // in StepKey; bumped whenever spec changes or a table is made
+    DevBuf flags, table;            // loop_exit; the four pieces of the bias table.  Both start as zeros.
     int32_t *loop_exit = nullptr;   // [max_batch]
     int32_t *bias_tok = nullptr, *bias_n = nullptr, *bias_map = nullptr;   // [max_batch][NH_GUARD_MAX_BIAS], [max_batch], [max_batch] (nh_guard_apply)
     float *bias_val = nullptr;
     bool after_beam = false;        // the last lockstep decode was a beam search: nh_guard_report refuses
+};
+
+// NH_OPT_ABSORBED_XATTN: the scratch of the absorbed cross-attention, made by the first nh_set_option that switches it on
+struct AbsorbedState {
+    DevBuf u;                    // fp16 [max_batch][32][d] (heads padded to 32; made as zeros, and the pad rows stay zero)
+    DevBuf parts;                // the key-range partials of the one-pass form (value 2): z, then ml
+    float *z = nullptr, *ml = nullptr;
 };
 
 struct nh_ctx {
@@ -237,7 +265,7 @@ struct nh_ctx {
     nh_config c{};
     int B = 1;
     std::string err;
-    std::vector<void *> allocs;
+    Arena allocs;               // the workspaces and caches below: build_context makes them all, nothing joins them later
     std::vector<KvCache> kv;    // [decoder_layers]; the weights are read from mdl
     // mel
     float *pcm = nullptr;
@@ -246,7 +274,7 @@ struct nh_ctx {
     // context's stream with the kernel that reads it queued right behind, so the stream orders the next copy, whoever
     // makes it, behind the kernel that read the bytes before.
     DevBuf stage;
-    ResampleClip *rs_clips = nullptr;   // [max_batch] per-clip records of a resample call, made by the first one
+    DevBuf rs_clips;            // ResampleClip [max_batch]: per-clip records of a resample call, made by the first one
     CutState cut;               // nh_cut_plan, nh_cut_energy
     VadState vad;               // nh_vad_plan, nh_vad_view, nh_logmel_pieces_rows
     int32_t *nsamp = nullptr;
@@ -274,8 +302,7 @@ struct nh_ctx {
     int token_gen = 0;  // bumped by nh_set_tokens; part of the graph key
     bool opt_graphs = true, opt_fuse_ln = true;  // nh_set_option
     int opt_absorbed = 0;        // NH_OPT_ABSORBED_XATTN: 1 = numerics prototype, 2 = one-pass kernels
-    half_t *xabs_u = nullptr;    // [max_batch][32][d] scratch (heads padded to 32, pad rows zero)
-    float *xabs_z = nullptr, *xabs_ml = nullptr;   // key-range partials of the one-pass form
+    AbsorbedState xabs;
     bool opt_align_keep = false; // NH_OPT_ALIGN_KEEP
     AlignState al;               // nh_align, nh_align_decoded
     AlignLive live;              // nh_align_capture
@@ -283,8 +310,8 @@ struct nh_ctx {
     ScoreState score;            // nh_score
     GuardState guard;            // nh_set_guard, nh_guard_bias, nh_guard_report, nh_guard_apply
     // The context's one query buffer, fp16 [align_q_heads][C - 1][max_batch][64]: nh_align's teacher-forced pass and the decodes
-    // under nh_align_capture both write it, stages 2 - 6 read it.  Grown by align_q_buffer alone, freed by nh_destroy.
-    half_t *align_q = nullptr;
+    // under nh_align_capture both write it, stages 2 - 6 read it.  Grown by align_q_buffer alone.
+    DevBuf align_q;
     int align_q_heads = 0;
     int dec_layer_limit = 0;    // parity view (NH_OPT_DECODER_LAYER_LIMIT): run only the first n decoder blocks; 0 = all
     std::vector<int32_t> seq_lang;  // per-sequence language tokens (LanguageState::Detect), empty = tk.lang for all
@@ -312,29 +339,24 @@ struct nh_ctx {
     double gemm_flops_acc = 0.0;
 
     int fail(int code, const std::string &msg) { err = msg; return code; }
+    // Device current, stream drained, step graphs, events, h_done, stream (nh_model.hip); the members -- the arena, every
+    // DevBuf, then the model -- release themselves after that.  A context whose stream or events were never made destructs too.
+    ~nh_ctx();
 };
-
-template <typename T>
-static T *dalloc_into(std::vector<void *> &allocs, size_t n, bool zero = true) {
-    void *p = nullptr;
-    if (n == 0) n = 1;
-    if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) return nullptr;
-    if (zero) hipMemset(p, 0, n * sizeof(T));
-    allocs.push_back(p);
-    return reinterpret_cast<T *>(p);
-}
-template <typename T>
-static T *dalloc(nh_ctx *ctx, size_t n, bool zero = true) { return dalloc_into<T>(ctx->allocs, n, zero); }
 
 #define NH_STAGE_BYTES (256ull << 20)   // ctx->stage per group of clips or frames (the alignment workspace's figure)
 
-inline int DevBuf::reserve(nh_ctx *ctx, size_t need, const char *what) {
+inline int DevBuf::reserve(nh_ctx *ctx, size_t need, const char *what, bool zero) {
     if (bytes >= need) return NH_OK;
     HIPCHK(hipStreamSynchronize(ctx->st));   // nothing may still read what goes away
     if (p) hipFree(p);
     p = nullptr; bytes = 0;
-    if (hipMalloc(&p, need) != hipSuccess) { p = nullptr; return ctx->fail(NH_ERR_NOMEM, std::string("hipMalloc(") + what + ")"); }
+    if (hipMalloc(&p, need) != hipSuccess) {
+        p = nullptr; (void)hipGetLastError();
+        return ctx->fail(NH_ERR_NOMEM, std::string("hipMalloc(") + what + ")");
+    }
     bytes = need;
+    if (zero) HIPCHK(hipMemsetAsync(p, 0, need, ctx->st));
     return NH_OK;
 }
 

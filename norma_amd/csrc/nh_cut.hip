@@ -41,18 +41,19 @@ extern "C" int nh_cut_plan(nh_ctx *ctx, const float *pcm, int on_device, int64_t
     // a chunk that is not the last holds at least min_frames frames; the device records at most what the caller can take
     const long long bound = F / q.min_frames + 1;
     const long long kcap = std::min(bound, (long long)std::max(cap, 1));
-    if (!cs.count && !(cs.count = dalloc<int32_t>(ctx, 1, false))) return ctx->fail(NH_ERR_NOMEM, "hipMalloc(chunk count)");
-    if (int rc = cs.out.reserve(ctx, (sizeof(long long) + sizeof(int32_t)) * (size_t)kcap, "chunk records")) return rc;
-    long long *const d_starts = static_cast<long long *>(cs.out.p);
-    int32_t *const d_lens = reinterpret_cast<int32_t *>(d_starts + kcap);
+    Carve cv;
+    const size_t o_starts = cv.take(sizeof(long long) * (size_t)kcap), o_lens = cv.take(sizeof(int32_t) * (size_t)kcap), o_count = cv.take(sizeof(int32_t));
+    if (int rc = cs.out.reserve(ctx, cv.off, "chunk records")) return rc;
+    long long *const d_starts = cs.out.at<long long>(o_starts);
+    int32_t *const d_lens = cs.out.at<int32_t>(o_lens), *const d_count = cs.out.at<int32_t>(o_count);
     if (int rc = cut_energies(ctx, pcm, on_device, N, e, E, F, q.half_window)) return rc;
     CutSearch s{};
     s.E = E; s.F = F; s.min_frames = q.min_frames; s.max_frames = q.max_frames; s.n_samples = N;
-    s.starts = d_starts; s.lens = d_lens; s.count = cs.count; s.cap = kcap;
+    s.starts = d_starts; s.lens = d_lens; s.count = d_count; s.cap = kcap;
     launch_cut_search(s, ctx->st);
     HIPCHK(hipGetLastError());
     int32_t n = 0;
-    HIPCHK(hipMemcpyAsync(&n, cs.count, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipMemcpyAsync(&n, d_count, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipStreamSynchronize(ctx->st));
     *n_chunks = n;
     if (n > cap) return ctx->fail(NH_ERR_INVALID, "nh_cut_plan: the plan has " + std::to_string(n) + " chunks, cap is " + std::to_string(cap));

@@ -69,9 +69,9 @@ void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr, bool final_ln, b
         launch_dec_attention(ctx->dq, kv.sk, kv.sv, ctx->datt, B, 1, H, d, C, pos + 1, pos_ptr, ctx->st, 1, done);  // head-major cache
         skinny(ctx, ctx->datt, d, L.o, B, d, d, SK_RESID_F32, ctx->dx, nullptr, nullptr, d, 0, C);
         ln_skinny(ctx, L.ln2, L.cq, B, d, d, SK_F16, ctx->dq, nullptr, nullptr, d, 0, C, nullptr);
-        if (keep && keep->layer[l].n) launch_align_qsave(ctx->dq, ctx->align_q, keep->layer[l], B, ctx->B, d, pos, pos_ptr, done, C - 1, ctx->st);
-        if (ctx->opt_absorbed == 2) launch_xabs_attention_fast(ctx->dq, L.ckv.wt, L.ckv.w, L.ckv.b, ctx->xa16, ctx->xabs_u, ctx->xabs_z, ctx->xabs_ml, ctx->datt, B, H, d, ctx->S, done, ctx->st);
-        else if (ctx->opt_absorbed) launch_xabs_attention(ctx->dq, L.ckv.w, L.ckv.b, ctx->xa16, ctx->xabs_u, ctx->datt, B, H, d, ctx->S, done, ctx->st);
+        if (keep && keep->layer[l].n) launch_align_qsave(ctx->dq, ctx->align_q.at<half_t>(), keep->layer[l], B, ctx->B, d, pos, pos_ptr, done, C - 1, ctx->st);
+        if (ctx->opt_absorbed == 2) launch_xabs_attention_fast(ctx->dq, L.ckv.wt, L.ckv.w, L.ckv.b, ctx->xa16, ctx->xabs.u.at<half_t>(), ctx->xabs.z, ctx->xabs.ml, ctx->datt, B, H, d, ctx->S, done, ctx->st);
+        else if (ctx->opt_absorbed) launch_xabs_attention(ctx->dq, L.ckv.w, L.ckv.b, ctx->xa16, ctx->xabs.u.at<half_t>(), ctx->datt, B, H, d, ctx->S, done, ctx->st);
         else launch_dec_attention(ctx->dq, kv.ck, kv.cv, ctx->datt, B, 1, H, d, ctx->S, ctx->S, nullptr, ctx->st, 1, done);  // head-major cross K/V
         skinny(ctx, ctx->datt, d, L.co, B, d, d, SK_RESID_F32, ctx->dx, nullptr, nullptr, d, 0, C);
         ln_skinny(ctx, L.ln3, L.fc1, B, 4 * d, d, SK_GELU_F16, ctx->dhid, nullptr, nullptr, 4 * d, 0, C, nullptr);
@@ -650,8 +650,11 @@ extern "C" int nh_apply_rules(nh_ctx *ctx, const float *probs, const int32_t *to
     hipSetDevice(ctx->dev);
     const int V = ctx->c.vocab_size;
     float *d_in = ctx->logits, *d_out = ctx->logits + ctx->VP * (ctx->B > 1 ? 1 : 0);
-    float *tmp_out = nullptr;
-    if (ctx->B == 1) { if (hipMalloc(reinterpret_cast<void **>(&tmp_out), sizeof(float) * V) != hipSuccess) return ctx->fail(NH_ERR_NOMEM, "hipMalloc"); d_out = tmp_out; }
+    DevBuf tmp_out;   // a max_batch 1 context has no second row of logits
+    if (ctx->B == 1) {
+        if (int rc = tmp_out.reserve(ctx, sizeof(float) * V, "masked row")) return rc;
+        d_out = tmp_out.at<float>();
+    }
     int32_t *d_tok = ctx->ds.tokens;
     HIPCHK(hipMemcpyAsync(d_in, probs, sizeof(float) * V, hipMemcpyHostToDevice, ctx->st));
     HIPCHK(hipMemcpyAsync(d_tok, tokens, sizeof(int32_t) * n_tokens, hipMemcpyHostToDevice, ctx->st));
@@ -659,7 +662,6 @@ extern "C" int nh_apply_rules(nh_ctx *ctx, const float *probs, const int32_t *to
     HIPCHK(hipMemcpyAsync(masked_out, d_out, sizeof(float) * V, hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipMemcpyAsync(argmax_out, ctx->ds.n_active, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipStreamSynchronize(ctx->st));
-    if (tmp_out) hipFree(tmp_out);
     HIPCHK(hipGetLastError());
     return NH_OK;
 }

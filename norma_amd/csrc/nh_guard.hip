@@ -19,17 +19,17 @@ static int ensure_guard_buffers(nh_ctx *ctx, bool want_bias) {
     GuardState &g = ctx->guard;
     hipSetDevice(ctx->dev);
     if (!g.loop_exit) {
-        if (!(g.loop_exit = dalloc<int32_t>(ctx, ctx->B))) return ctx->fail(NH_ERR_NOMEM, "hipMalloc(guard flags)");
+        if (int rc = g.flags.reserve(ctx, sizeof(int32_t) * (size_t)ctx->B, "guard flags", true)) return rc;
+        g.loop_exit = g.flags.at<int32_t>();
         g.gen++;
     }
     if (want_bias && !g.bias_tok) {
         const size_t n = (size_t)ctx->B * NH_GUARD_MAX_BIAS;
-        g.bias_tok = dalloc<int32_t>(ctx, n); g.bias_val = dalloc<float>(ctx, n);
-        g.bias_n = dalloc<int32_t>(ctx, ctx->B); g.bias_map = dalloc<int32_t>(ctx, ctx->B);
-        if (!g.bias_tok || !g.bias_val || !g.bias_n || !g.bias_map) {
-            g.bias_tok = g.bias_n = g.bias_map = nullptr; g.bias_val = nullptr;
-            return ctx->fail(NH_ERR_NOMEM, "hipMalloc(guard bias table)");
-        }
+        Carve cv;
+        const size_t o_tok = cv.take(4 * n), o_val = cv.take(4 * n), o_n = cv.take(4 * (size_t)ctx->B), o_map = cv.take(4 * (size_t)ctx->B);
+        if (int rc = g.table.reserve(ctx, cv.off, "guard bias table", true)) return rc;   // bias_n starts at zero
+        g.bias_tok = g.table.at<int32_t>(o_tok); g.bias_val = g.table.at<float>(o_val);
+        g.bias_n = g.table.at<int32_t>(o_n); g.bias_map = g.table.at<int32_t>(o_map);
         g.gen++;
     }
     return NH_OK;

@@ -41,29 +41,25 @@ extern "C" int nh_device_count(void) {
 
 extern "C" const char *nh_last_error(const nh_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
-extern "C" void nh_destroy(nh_ctx *ctx) {
-    if (!ctx) return;
-    hipSetDevice(ctx->dev);
-    if (ctx->st) hipStreamSynchronize(ctx->st);
-    for (void *p : ctx->allocs) hipFree(p);
-    for (void *p : ctx->al.allocs) hipFree(p);
-    if (ctx->align_q) hipFree(ctx->align_q);
-    drop_graphs(ctx);
-    if (ctx->h_done) hipHostFree(ctx->h_done);
-    for (auto &e : ctx->ev) if (e) hipEventDestroy(e);
-    for (auto &e : ctx->gemm_ev) hipEventDestroy(e);
-    if (ctx->enc_done) hipEventDestroy(ctx->enc_done);
-    if (ctx->st) hipStreamDestroy(ctx->st);
-    ctx->mdl.reset();  // the last context of a model frees its weights (~nh_model)
-    delete ctx;        // ... and every DevBuf of the context frees itself
-}
+nh_ctx::~nh_ctx() {
+    hipSetDevice(dev);
+    if (st) hipStreamSynchronize(st);
+    drop_graphs(this);
+    for (auto &e : ev) if (e) hipEventDestroy(e);
+    for (auto &e : gemm_ev) hipEventDestroy(e);
+    if (enc_done) hipEventDestroy(enc_done);
+    if (h_done) hipHostFree(h_done);
+    if (st) hipStreamDestroy(st);
+}   // ... then the arena and every DevBuf free themselves, and the last context of a model frees its weights (~nh_model)
+
+extern "C" void nh_destroy(nh_ctx *ctx) { delete ctx; }
 
 static bool build_mel_tables(nh_model *m, std::string &err) {
     // host tables with libm, the same f32 expressions candle evaluates (mel_host.h, see k_mel.hip)
     std::vector<float> hann(MEL_N_HANN), dc(MEL_N_DFT), dsn(MEL_N_DFT), twc(MEL_N_TW), tws(MEL_N_TW);
     mel_host_tables(hann.data(), dc.data(), dsn.data(), twc.data(), tws.data());
-    float *d_h = dalloc_into<float>(m->allocs, 400), *d_dc = dalloc_into<float>(m->allocs, 625), *d_ds = dalloc_into<float>(m->allocs, 625);
-    float *d_tc = dalloc_into<float>(m->allocs, 375), *d_ts = dalloc_into<float>(m->allocs, 375);
+    float *d_h = m->allocs.dalloc_into<float>(400), *d_dc = m->allocs.dalloc_into<float>(625), *d_ds = m->allocs.dalloc_into<float>(625);
+    float *d_tc = m->allocs.dalloc_into<float>(375), *d_ts = m->allocs.dalloc_into<float>(375);
     if (!d_h || !d_dc || !d_ds || !d_tc || !d_ts) { err = "hipMalloc(mel tables)"; return false; }
     if (hipMemcpy(d_h, hann.data(), 400 * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_dc, dc.data(), 625 * 4, hipMemcpyHostToDevice) != hipSuccess ||
@@ -81,8 +77,8 @@ static std::shared_ptr<nh_model> build_model(int device_ordinal, const nh_config
     const int d = cfg->d_model, V = cfg->vocab_size, nm = cfg->num_mel_bins, ctxlen = cfg->max_target_positions;
     build_expected(m.get());
     bool ok = true;
-#define MA(field, T, n) ok = ok && ((m->field = dalloc_into<T>(m->allocs, (size_t)(n))) != nullptr)
-#define ML(f, T, n) ok = ok && ((L.f = dalloc_into<T>(m->allocs, (size_t)(n))) != nullptr)
+#define MA(field, T, n) ok = ok && ((m->field = m->allocs.dalloc_into<T>((size_t)(n))) != nullptr)
+#define ML(f, T, n) ok = ok && ((L.f = m->allocs.dalloc_into<T>((size_t)(n))) != nullptr)
     MA(conv1.w, half_t, (long)d * 3 * NH_MELP); MA(conv1.b, float, d);
     MA(conv2.w, half_t, (long)d * 3 * d); MA(conv2.b, float, d);
     MA(enc_pos, float, 1500L * d);
@@ -130,7 +126,7 @@ static int build_context(std::shared_ptr<nh_model> mdl, int max_batch, nh_ctx **
     const int d = cfg->d_model;
     nh_ctx *ctx = new nh_ctx();
     ctx->dev = mdl->dev; ctx->c = *cfg; ctx->B = max_batch; ctx->mdl = mdl;
-    auto bail = [&](int code) { g_create_error = ctx->err; nh_destroy(ctx); return code; };
+    auto bail = [&](int code) { g_create_error = ctx->err; delete ctx; return code; };
     if (hipSetDevice(ctx->dev) != hipSuccess) { ctx->err = "hipSetDevice failed"; return bail(NH_ERR_HIP); }
     // ONE stream per context.  r02 gave the decode loop a stream of its own at the highest priority; r03
     // measured what that costs: the runtime backs every stream with an HSA queue, the queues are spread over the command
@@ -150,11 +146,11 @@ static int build_context(std::shared_ptr<nh_model> mdl, int max_batch, nh_ctx **
     const long M = (long)B * 1500;
     ctx->VP = nh_logits_ld(V);
     bool ok = true;
-#define DA(field, T, n) ok = ok && ((ctx->field = dalloc<T>(ctx, (size_t)(n))) != nullptr)
+#define DA(field, T, n) ok = ok && ((ctx->field = ctx->allocs.dalloc_into<T>((size_t)(n))) != nullptr)
     // this context's K/V caches: cross K/V of the current batch, self-attention cache
     ctx->kv.resize(cfg->decoder_layers);
     for (auto &L : ctx->kv) {
-#define DL(f, T, n) ok = ok && ((L.f = dalloc<T>(ctx, (size_t)(n))) != nullptr)
+#define DL(f, T, n) ok = ok && ((L.f = ctx->allocs.dalloc_into<T>((size_t)(n))) != nullptr)
         DL(ck, half_t, M * d); DL(cv, half_t, M * d);
         DL(sk, half_t, (long)B * ctxlen * d); DL(sv, half_t, (long)B * ctxlen * d);
 #undef DL
@@ -357,7 +353,7 @@ int ensure_decoder_repack(nh_ctx *ctx) {
         if (!m.dec_tiled_valid) {
             const int d = ctx->c.d_model, V = ctx->c.vocab_size;
             auto one = [&](half_t *&dst, const half_t *src, int N, int K) -> bool {
-                if (!dst) { dst = dalloc_into<half_t>(m.allocs, (size_t)((N + 15) / 16) * 16 * K, false); }
+                if (!dst) { dst = m.allocs.dalloc_into<half_t>((size_t)((N + 15) / 16) * 16 * K, false); }
                 if (!dst) return false;
                 launch_repack_tiles(src, dst, N, K, ctx->st);
                 return true;
@@ -367,7 +363,7 @@ int ensure_decoder_repack(nh_ctx *ctx) {
                 ok = ok && one(L.qkv.wt, L.qkv.w, 3 * d, d) && one(L.o.wt, L.o.w, d, d) && one(L.cq.wt, L.cq.w, d, d) &&
                      one(L.co.wt, L.co.w, d, d) && one(L.fc1.wt, L.fc1.w, 4 * d, d) && one(L.fc2.wt, L.fc2.w, d, 4 * d);
                 // the cross K projection transposed ([feature][head dim]; NH_OPT_ABSORBED_XATTN reads Wk_h^T q from it)
-                if (ok && !L.ckv.wt) L.ckv.wt = dalloc_into<half_t>(m.allocs, (size_t)d * d, false);
+                if (ok && !L.ckv.wt) L.ckv.wt = m.allocs.dalloc_into<half_t>((size_t)d * d, false);
                 ok = ok && L.ckv.wt;
                 if (ok) launch_transpose_sq(L.ckv.w, L.ckv.wt, d, ctx->st);
             }
@@ -392,7 +388,7 @@ extern "C" int nh_set_mel_filters(nh_ctx *ctx, const float *filters, int n_mel) 
     hipSetDevice(ctx->dev);
     nh_model &m = *ctx->mdl;
     std::lock_guard<std::mutex> lk(m.mu);
-    float *df = dalloc_into<float>(m.allocs, (size_t)n_mel * 201);
+    float *df = m.allocs.dalloc_into<float>((size_t)n_mel * 201);
     if (!df) return ctx->fail(NH_ERR_NOMEM, "hipMalloc(mel filters)");
     HIPCHK(hipMemcpy(df, filters, (size_t)n_mel * 201 * 4, hipMemcpyHostToDevice));
     std::vector<int32_t> grp(2 * n_mel);
@@ -459,14 +455,16 @@ extern "C" int nh_set_option(nh_ctx *ctx, int option, int value) {
         if (value && ctx->pool.rows > 0) return ctx->fail(NH_ERR_STATE, "nh_set_option: NH_OPT_ABSORBED_XATTN covers lockstep decodes only, and the context runs a decode pool");
         if (value == 2 && !xabs_fast_supported(ctx->c.d_model, ctx->c.decoder_attention_heads)) value = 1;   // widths the one-pass kernel is not built for
         hipSetDevice(ctx->dev);
-        if (value && !ctx->xabs_u) {
-            ctx->xabs_u = dalloc<half_t>(ctx, (size_t)ctx->B * 32 * ctx->c.d_model);
-            if (!ctx->xabs_u) return ctx->fail(NH_ERR_NOMEM, "nh_set_option: hipMalloc failed");
-        }
-        if (value == 2 && !ctx->xabs_z) {
-            ctx->xabs_z = dalloc<float>(ctx, (size_t)ctx->B * 4 * ctx->c.decoder_attention_heads * ctx->c.d_model);
-            ctx->xabs_ml = dalloc<float>(ctx, (size_t)ctx->B * 4 * 32 * 2);
-            if (!ctx->xabs_z || !ctx->xabs_ml) return ctx->fail(NH_ERR_NOMEM, "nh_set_option: hipMalloc failed");
+        AbsorbedState &xs = ctx->xabs;
+        // the launcher needs u's rows of heads >= H to be zero, and xabs_u_fast_kernel writes only the heads it has
+        if (value)
+            if (int rc = xs.u.reserve(ctx, sizeof(half_t) * (size_t)ctx->B * 32 * ctx->c.d_model, "absorbed attention scratch", true)) return rc;
+        if (value == 2) {
+            Carve cv;
+            const size_t o_z = cv.take(sizeof(float) * (size_t)ctx->B * 4 * ctx->c.decoder_attention_heads * ctx->c.d_model);
+            const size_t o_ml = cv.take(sizeof(float) * (size_t)ctx->B * 4 * 32 * 2);
+            if (int rc = xs.parts.reserve(ctx, cv.off, "absorbed attention partials", true)) return rc;
+            xs.z = xs.parts.at<float>(o_z); xs.ml = xs.parts.at<float>(o_ml);
         }
         ctx->opt_absorbed = value; drop_graphs(ctx);
         ctx->live.gen++; ctx->live.lock_valid = false;

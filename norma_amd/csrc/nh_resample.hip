@@ -54,7 +54,7 @@ static int resample_table(nh_ctx *ctx, int src_hz, const RsDesign &d, const floa
         std::vector<float> h((size_t)d.L * d.T);
         for (int p = 0; p < d.L; p++)
             for (int j = 0; j < d.T; j++) h[(size_t)p * d.T + j] = (float)resample_h(d, (double)p / (double)d.L - (double)(j - Wc + 1));
-        dev = dalloc_into<float>(m.allocs, h.size(), false);
+        dev = m.allocs.dalloc_into<float>(h.size(), false);
         if (!dev) return ctx->fail(NH_ERR_NOMEM, "hipMalloc(resampling filter)");
         HIPCHK(hipMemcpy(dev, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice));
     }
@@ -131,14 +131,14 @@ static int resample_rows(nh_ctx *ctx, const char *who, const RsDesign &d, const 
     }
     const float *coef = nullptr;
     if (int rc = resample_table(ctx, src_hz, d, &coef)) return rc;
-    if (!ctx->rs_clips && !(ctx->rs_clips = dalloc<ResampleClip>(ctx, (size_t)ctx->B, false)))
-        return ctx->fail(NH_ERR_NOMEM, "hipMalloc(resample clip records)");
+    if (int rc = ctx->rs_clips.reserve(ctx, sizeof(ResampleClip) * (size_t)ctx->B, "resample clip records")) return rc;
+    ResampleClip *const d_clips = ctx->rs_clips.at<ResampleClip>();
     ResampleParams p{};
     p.dtype = dt; p.channels = channels; p.coef = coef; p.L = d.L; p.M = d.M; p.T = d.T; p.out_stride = NH_N_SAMPLES;
     const size_t fb = (size_t)nh_sample_size(dt) * (size_t)channels;   // bytes per frame
     if (on_device) {
-        HIPCHK(hipMemcpyAsync(ctx->rs_clips, clips.data(), sizeof(ResampleClip) * (size_t)batch, hipMemcpyHostToDevice, ctx->st));
-        p.frames = frames; p.clips = ctx->rs_clips; p.batch = batch; p.max_out = max_out;
+        HIPCHK(hipMemcpyAsync(d_clips, clips.data(), sizeof(ResampleClip) * (size_t)batch, hipMemcpyHostToDevice, ctx->st));
+        p.frames = frames; p.clips = d_clips; p.batch = batch; p.max_out = max_out;
         p.out = ctx->pcm + (size_t)row0 * NH_N_SAMPLES;
         if (!launch_resample(p, ctx->st)) return ctx->fail(NH_ERR_INVALID, w + ": launch refused");
         HIPCHK(hipGetLastError());
@@ -160,7 +160,7 @@ static int resample_rows(nh_ctx *ctx, const char *who, const RsDesign &d, const 
         long long off = 0;
         for (int b = g.first; b < g.second; b++) { clips[b].off = off; off += n_frames[b]; }
     }
-    HIPCHK(hipMemcpyAsync(ctx->rs_clips, clips.data(), sizeof(ResampleClip) * (size_t)batch, hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipMemcpyAsync(d_clips, clips.data(), sizeof(ResampleClip) * (size_t)batch, hipMemcpyHostToDevice, ctx->st));
     for (const auto &g : groups) {
         int gmax = 0;
         for (int b = g.first; b < g.second; b++) {
@@ -169,7 +169,7 @@ static int resample_rows(nh_ctx *ctx, const char *who, const RsDesign &d, const 
                                   (size_t)n_frames[b] * fb, hipMemcpyHostToDevice, ctx->st));
             gmax = std::max(gmax, clips[b].n_out);
         }
-        p.frames = ctx->stage.p; p.clips = ctx->rs_clips + g.first; p.batch = g.second - g.first; p.max_out = gmax;
+        p.frames = ctx->stage.p; p.clips = d_clips + g.first; p.batch = g.second - g.first; p.max_out = gmax;
         p.out = ctx->pcm + (size_t)(row0 + g.first) * NH_N_SAMPLES;
         if (!launch_resample(p, ctx->st)) return ctx->fail(NH_ERR_INVALID, w + ": launch refused");
     }

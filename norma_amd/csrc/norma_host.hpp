@@ -242,12 +242,7 @@ class Model {
   public:
     typedef float Data;                               // Model::Data = f32 (model.rs:49)
     Model(nh_ctx *ctx, nh_config cfg, nh_tokens tk) : ctx_(ctx), cfg_(cfg), tk_(tk) {}
-    Model(Model &&o) noexcept : ctx_(o.ctx_), cfg_(o.cfg_), tk_(o.tk_), buf_(std::move(o.buf_)), detok_(std::move(o.detok_)),
-                                align_heads_(std::move(o.align_heads_)), checkpoint_heads_(std::move(o.checkpoint_heads_)), capture_stale_(o.capture_stale_),
-                                src_hz_(o.src_hz_), channels_(o.channels_), resampler_(std::move(o.resampler_)),
-                                prompt_tokens_(std::move(o.prompt_tokens_)), history_(std::move(o.history_)), condition_(o.condition_), sop_token_(o.sop_token_),
-                                suppress_(std::move(o.suppress_)), suppress_known_(o.suppress_known_), beam_size_(o.beam_size_), ctx_rows_(o.ctx_rows_),
-                                guard_(o.guard_), bias_tok_(std::move(o.bias_tok_)), bias_val_(std::move(o.bias_val_)) { o.ctx_ = nullptr; }
+    Model(Model &&) = delete;   // the nh_ctx * is raw, and nothing moves a Model
     Model(const Model &) = delete;
     ~Model() { if (ctx_) nh_destroy(ctx_); }
 

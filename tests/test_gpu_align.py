@@ -327,6 +327,82 @@ def test_refusals(fx):
     assert first[0, P_LEN] == 0
 
 
+# ---- the workspace after a larger one ---------------------------------------------------------------------------------------
+HEADS3 = [(0, 1), (1, 0), (0, 0)]
+# (heads, batch) of the calls one context takes in turn: one head, three, one again; then one clip, three, one again
+CALLS = [(HEADS3[:1], 3), (HEADS3, 3), (HEADS3[:1], 3), (HEADS, 1), (HEADS, 3), (HEADS, 1)]
+
+
+class Scripted:
+    """test-d128 with scripted weights, three clips, and given tokens of three lengths over three key counts; every context is
+    a fresh one over the weights of `base`"""
+
+    def __init__(self):
+        from norma_amd import hip, synth
+        self.hip = hip
+        self.cfg, self.tk = common.make_config(NAME), common.tokens_for(NAME)
+        script = common.transcript_script(self.tk, n_segments=3, words_per_segment=6)
+        self.base = common.build_hip(self.cfg, self.tk, overrides=common.scripted_overrides(self.cfg, self.tk, script), max_batch=1)
+        self.clips = [synth.synth_pcm(0), synth.synth_pcm(1), synth.synth_pcm(2, 400000)]
+        seq = [self.tk.sot, self.tk.en, self.tk.transcribe] + script
+        self.tokens = [seq[:6], seq[:14], seq]
+        self.fresh = {}
+
+    def context(self):
+        hm = self.hip.HipWhisper(self.cfg, max_batch=3, share_with=self.base)
+        hm.set_tokens(self.tk, self.tk.en, self.tk.transcribe)
+        return hm
+
+    def call(self, hm, heads, B, keep):
+        """(first, last, views or None) of one nh_align over the first B clips"""
+        hm.set_option(self.hip.NH_OPT_ALIGN_KEEP, keep)
+        hm.logmel(self.clips[:B])
+        hm.encode()
+        first, last = hm.align(self.tokens[:B], prompt_len=P_LEN, heads=heads, n_keys=N_KEYS[:B])
+        views = [([hm.align_weights(b, a) for a in range(len(heads))], hm.align_matrix(b)) for b in range(B)] if keep else None
+        return first, last, views
+
+    def fresh_answer(self, heads, B, keep):
+        key = (len(heads), B, keep)
+        if key not in self.fresh:
+            hm = self.context()
+            self.fresh[key] = self.call(hm, heads, B, keep)
+            hm.close()
+        return self.fresh[key]
+
+
+@pytest.fixture(scope="module")
+def sc():
+    s = Scripted()
+    yield s
+    s.base.close()
+
+
+@pytest.mark.parametrize("keep", [0, 1])
+def test_a_smaller_shape_after_a_larger_one_equals_a_fresh_context(sc, keep):
+    """One context takes CALLS in turn: the workspace of a small shape is cut out of the buffer a larger shape sized (fewer
+    heads after more; fewer clips after more reuses the larger carve as it is).  After every call the paths are integer-equal
+    to what a context that never aligned before gives for the same call, and under NH_OPT_ALIGN_KEEP = 1 so are the views, as
+    bit patterns."""
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint32)
+    hm = sc.context()
+    try:
+        for i, (heads, B) in enumerate(CALLS):
+            first, last, views = sc.call(hm, heads, B, keep)
+            f0, l0, v0 = sc.fresh_answer(heads, B, keep)
+            assert first.dtype == np.int32 and np.array_equal(first, f0) and np.array_equal(last, l0), (i, len(heads), B)
+            for b in range(B):
+                n = len(sc.tokens[b])
+                assert first[b, P_LEN] == 0 and last[b, n - 1] == N_KEYS[b] - 1 and (first[b, n:] == -1).all()
+            if keep:
+                for b in range(B):
+                    for a in range(len(heads)):
+                        assert views[b][0][a].shape == v0[b][0][a].shape and np.array_equal(bits(views[b][0][a]), bits(v0[b][0][a])), (i, b, a)
+                    assert views[b][1].shape == v0[b][1].shape and np.array_equal(bits(views[b][1]), bits(v0[b][1])), (i, b)
+    finally:
+        hm.close()
+
+
 # ---- the host layer ---------------------------------------------------------------------------------------------------------
 def _scripted_model(script):
     from norma_amd import host, synth
