@@ -27,22 +27,13 @@
 #endif
 #define KT 64              // keys per tile
 #define QW 32              // queries per wave
-#ifndef ENC_ATTN_WAVES
 #define ENC_ATTN_WAVES 8   // waves per workgroup
-#endif
 #define QB (QW * ENC_ATTN_WAVES)   // queries per workgroup
-#define NTHR (64 * ENC_ATTN_WAVES)
-#define NSLOT (NTHR >= 512 ? 1 : 512 / NTHR)   // 16-byte staging slots per thread per tile (a tile is 512 slots; threads >= 512 stage nothing)
+#define NTHR (64 * ENC_ATTN_WAVES) // 512: one 16-byte staging slot per thread per K or V^T tile
 #define TILE_B 8192        // bytes per K or V^T tile
 
-#ifndef ENC_ATTN_MINWAVES
-#ifdef ENC_ATTN_PIPE
-#define ENC_ATTN_MINWAVES 2   // one 8-wave workgroup per CU: 256 VGPRs for two tiles of scores in flight
-#else
-#define ENC_ATTN_MINWAVES 4   // two 8-wave workgroups per CU need <= 128 VGPRs
-#endif
-#endif
-__global__ __launch_bounds__(NTHR, (NTHR <= 512 ? ENC_ATTN_MINWAVES : 1)) void ENC_ATTN_KERNEL(const half_t *__restrict__ q, const half_t *__restrict__ k,
+// two 8-wave workgroups per CU need <= 128 VGPRs
+__global__ __launch_bounds__(512, 4) void ENC_ATTN_KERNEL(const half_t *__restrict__ q, const half_t *__restrict__ k,
                                                          long ld, const half_t *__restrict__ vt,
                                                          half_t *__restrict__ out, long ldo, int S, int H) {
     __shared__ __attribute__((aligned(16))) char smem[2 * 2 * TILE_B];
@@ -60,52 +51,25 @@ __global__ __launch_bounds__(NTHR, (NTHR <= 512 ? ENC_ATTN_MINWAVES : 1)) void E
 #pragma unroll
         for (int ks = 0; ks < 4; ks++) qf[ks] = *reinterpret_cast<const half8 *>(qp + 16 * ks);
     }
-    // staging: slot s = tid + NTHR i (i < NSLOT): LDS row = s >> 3, chunk' = s & 7
-    const half_t *kg[NSLOT]; const half_t *vg[NSLOT];
-    int krow_off[NSLOT];
-#pragma unroll
-    for (int i = 0; i < NSLOT; i++) {
-        int row = (tid >> 3) + (NTHR / 8) * i;
-        int c = (tid & 7) ^ ((row >> 1) & 7);
-        krow_off[i] = swap23(row);  // LDS row `row` holds key key0 + swap23(row)
-        kg[i] = k + (long)b * S * ld + h * NH_DH + c * 8;
-        vg[i] = vt + ((long)(b * H + h) * NH_DH + row) * NH_SP + c * 8;
-    }
-    u32x4 rk[NSLOT], rv[NSLOT];
-    const bool stager = NTHR <= 512 || tid < 512;
-    auto load_k = [&](int t) {
-        if (!stager) return;
-#pragma unroll
-        for (int i = 0; i < NSLOT; i++) {
-            int key = t * KT + krow_off[i]; if (key >= S) key = S - 1;
-            rk[i] = *reinterpret_cast<const u32x4 *>(kg[i] + (long)key * ld);
-        }
-    };
-    auto load_v = [&](int t) {
-        if (!stager) return;
-#pragma unroll
-        for (int i = 0; i < NSLOT; i++) rv[i] = *reinterpret_cast<const u32x4 *>(vg[i] + t * KT);
+    // staging: thread tid moves slot tid of a tile: LDS row = tid >> 3, chunk' = tid & 7
+    const int srow = tid >> 3;
+    const int sc = (tid & 7) ^ ((srow >> 1) & 7);
+    const int krow_off = swap23(srow);  // LDS row `srow` holds key key0 + swap23(srow)
+    const half_t *kg = k + (long)b * S * ld + h * NH_DH + sc * 8;
+    const half_t *vg = vt + ((long)(b * H + h) * NH_DH + srow) * NH_SP + sc * 8;
+    u32x4 rk, rv;
+    auto load_tile = [&](int t) {
+        int key = t * KT + krow_off; if (key >= S) key = S - 1;
+        rk = *reinterpret_cast<const u32x4 *>(kg + (long)key * ld);
+        rv = *reinterpret_cast<const u32x4 *>(vg + t * KT);
     };
     // LDS: K tiles of buffer 0 / 1 at 0 / 2 TILE_B, V^T tiles at TILE_B / 3 TILE_B
-    auto store_k = [&](int buf) {
-        if (!stager) return;
-        u32x4 *lk = reinterpret_cast<u32x4 *>(smem + buf * 2 * TILE_B);
-#pragma unroll
-        for (int i = 0; i < NSLOT; i++) lk[tid + NTHR * i] = rk[i];
+    auto store_tile = [&](int buf) {
+        reinterpret_cast<u32x4 *>(smem + buf * 2 * TILE_B)[tid] = rk;
+        reinterpret_cast<u32x4 *>(smem + buf * 2 * TILE_B + TILE_B)[tid] = rv;
     };
-    auto store_v = [&](int buf) {
-        if (!stager) return;
-        u32x4 *lv = reinterpret_cast<u32x4 *>(smem + buf * 2 * TILE_B + TILE_B);
-#pragma unroll
-        for (int i = 0; i < NSLOT; i++) lv[tid + NTHR * i] = rv[i];
-    };
-    auto load_tile = [&](int t) { load_k(t); load_v(t); };
-    auto store_tile = [&](int buf) { store_k(buf); store_v(buf); };
     load_tile(0);
     store_tile(0);
-#ifdef ENC_ATTN_PIPE
-    if (nT > 1) { load_k(1); store_k(1); }
-#endif
     __syncthreads();
 
     // fragment byte offsets inside a tile (before adding the per-step chunk xor)
@@ -221,10 +185,10 @@ __global__ __launch_bounds__(NTHR, (NTHR <= 512 ? ENC_ATTN_MINWAVES : 1)) void E
     // (r03, tools/abench, one box: a schedule in which waves 4-7 run half a tile behind waves 0-3 -- two barriers per tile, one
     // half multiplying K Q^T while the other does softmax + P V -- measured 640-670 us against 446-454 for this loop; four
     // independent max / sum chains, v_dot2_f32_f16 row sums and s_setprio around the MFMA clusters all within +-1.5 %.  Later in
-    // r03: workgroups of 4 and 16 waves 856 / 501 us; the second workgroup of a CU started 1000-3000 cycles late: no change; the
-    // software-pipelined form below (ENC_ATTN_PIPE: one 8-wave workgroup per CU, 161 VGPRs, K Q^T of tile t + 1 issued between
-    // the exponentials of tile t) 577-609 us: two waves per SIMD do not cover the dependent-MFMA and LDS latencies that four do.)
-#ifndef ENC_ATTN_PIPE
+    // r03: workgroups of 4 and 16 waves 856 / 501 us; the second workgroup of a CU started 1000-3000 cycles late: no change; a
+    // software-pipelined loop (one 8-wave workgroup per CU, 161 VGPRs, K Q^T of tile t + 1 issued between the exponentials of
+    // tile t) 577-609 us: two waves per SIMD do not cover the dependent-MFMA and LDS latencies that four do.  None of these
+    // forms is kept in the source.)
     int cur = 0;
     for (int t = 0; t < nT; t++) {
         const bool more = (t + 1 < nT);
@@ -236,30 +200,6 @@ __global__ __launch_bounds__(NTHR, (NTHR <= 512 ? ENC_ATTN_MINWAVES : 1)) void E
         __syncthreads();
         cur ^= 1;
     }
-#else
-    // Software-pipelined form: the matrix pipe and the vector ALU of a SIMD work at the same time only when ONE instruction
-    // stream offers both (waves do not fill each other's gaps here: 576 MFMA + 540 VALU cycles per wave-tile took 1090), so
-    // the K Q^T products of tile t + 1 are issued between the exponentials of tile t.  At the top of iteration t the LDS holds
-    // K(t + 1) and V^T(t); K(t + 2) and V^T(t + 1) are fetched during the iteration into the buffers of K(t) and V^T(t - 1).
-    f32x16 n0, n1;
-    qk_phase(smem, s0, s1);
-    for (int t = 0; t < nT; t++) {
-        if (t + 2 < nT) load_k(t + 2);
-        if (t + 1 < nT) load_v(t + 1);
-        sm_head(t);                                                   // mask, maximum, (rare) rebase: moves qx before it is used below
-        qk_phase(smem + ((t + 1) & 1) * 2 * TILE_B, n0, n1);         // tile t + 1 (after the last tile: a stale buffer, result unused)
-        sm_body(smem + (t & 1) * 2 * TILE_B + TILE_B);               // exp2, row sums, P, O^T += V^T P^T of tile t
-#pragma unroll
-        for (int i = 0; i < 18; i++) {                                // one MFMA, then its share of the 100-odd vector instructions
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, ENC_ATTN_PIPE, 0);
-        }
-        if (t + 2 < nT) store_k(t & 1);
-        if (t + 1 < nT) store_v((t + 1) & 1);
-        __syncthreads();
-        s0 = n0; s1 = n1;
-    }
-#endif
     const float l_tot = l_run + __shfl_xor(l_run, 32);
     const float inv = 1.0f / l_tot;
     const int qrow = q0 + r;

@@ -79,5 +79,5 @@ __device__ __forceinline__ float f32_from_ordered(unsigned u) {
 }
 
 // ---- swap23 ---------------------------------------------------------------------------------------------------------------
-// x with bits 2 and 3 exchanged: the key order of the attention kernels' LDS tiles (k_attn_enc.hip, k_dec_attn.hip)
+// x with bits 2 and 3 exchanged: the key order of the attention kernels' LDS tiles (k_attn_enc.hip, k_xabs.hip)
 __device__ __forceinline__ int swap23(int x) { return (x & ~12) | ((x & 4) << 1) | ((x & 8) >> 1); }

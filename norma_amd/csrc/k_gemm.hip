@@ -170,9 +170,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(GemmParams p) {
 // ---------------------------------------------------------------------------------------------------
 #define G2_BM 256
 #define G2_BN 256
-#ifndef G2_GM
 #define G2_GM 4           // M-panels per group of the tile order (2 and 8 measured: within +-3 %, 4 best overall)
-#endif
 #define PP_BUF 65536
 #define PP_HT 16384
 #define PP_RING (2 * PP_BUF)
@@ -332,13 +330,6 @@ __global__ __launch_bounds__(512) void gemm256_f16_kernel(GemmParams p) {
     pp_tile(vb, ntn, ntm, tm, tn);
     PPSource sg = pp_source(p, tm * G2_BM, tn * G2_BN);
     pp_prologue(p, wbase, sg);
-#ifdef G2_STAMPS   // diagnostic build (tools/gstamps): when does every workgroup start, finish each tile, and on which XCD
-    int stamp_n = 0;
-    if (threadIdx.x == 0 && p.dbg) {
-        p.dbg[blockIdx.x * 32 + 0] = __builtin_amdgcn_s_memrealtime();
-        p.dbg[blockIdx.x * 32 + 1] = __builtin_amdgcn_s_getreg(6164);   // HW_REG_XCC_ID[3:0]
-    }
-#endif
     for (;;) {
         const int m0 = tm * G2_BM, n0 = tn * G2_BN;
         f32x4 acc[8][4];
@@ -351,9 +342,6 @@ __global__ __launch_bounds__(512) void gemm256_f16_kernel(GemmParams p) {
         if (vt) pp_main<false>(p, smem, wbase, sg, acc);
         else pp_main<true>(p, smem, wbase, sg, acc);
 
-#ifdef G2_STAMPS
-        if (threadIdx.x == 0 && p.dbg) p.dbg[blockIdx.x * 32 + 3] += __builtin_amdgcn_s_memrealtime() - (stamp_n ? p.dbg[blockIdx.x * 32 + 4 + stamp_n - 1] : p.dbg[blockIdx.x * 32]);   // time from tile start to the end of its main loop, summed
-#endif
         // EPI_RESID_F32: residual values of four 16-row blocks (64 VGPRs: the fragment registers are dead here), fetched through a
         // buffer descriptor over x[M][ldo]: rows >= M of the last, partial M-panel fall outside it, so their loads return 0 and
         // their stores are dropped by the hardware -- no per-row guard (a guard makes hipcc wrap each row block's stores in an
@@ -463,7 +451,7 @@ __global__ __launch_bounds__(512) void gemm256_f16_kernel(GemmParams p) {
         } else if (EPI == EPI_RESID_F32) {
             // x[m][n] += acc + bias.  r01/r02 took the residual tile as the INITIAL accumulator: 32 loads per lane queued behind the
             // twelve prologue DMAs and waited for before the first MFMA -- 12.8 us of every 57 us out-proj tile with the matrix
-            // pipe idle (tools/gstamps, profiles/r03_gstamps.txt).  Now the tile is fetched here, after the main loop, 16 loads per
+            // pipe idle (profiles/r03_gstamps.txt).  Now the tile is fetched here, after the main loop, 16 loads per
             // lane at a time into the registers the fragments no longer need (the first sixteen were issued BEFORE the next tile's
             // prologue DMAs, see above), added in the reference's order x + (A.W + bias), and stored: the residual traffic runs
             // under the next tile's first fetches instead of in front of this tile's first MFMA.

@@ -66,13 +66,13 @@ void decoder_step(nh_ctx *ctx, int pos, const int32_t *pos_ptr, bool final_ln, b
         const DecLayer &L = m.dec[l];
         const KvCache &kv = ctx->kv[l];
         ln_skinny(ctx, L.ln1, L.qkv, B, 3 * d, d, SK_QKV, ctx->dq, kv.sk, kv.sv, d, pos, C, pos_ptr);
-        launch_dec_attention(ctx->dq, kv.sk, kv.sv, ctx->datt, B, 1, H, d, C, pos + 1, pos_ptr, ctx->st, 1, done);  // head-major cache
+        launch_dec_attention(ctx->dq, kv.sk, kv.sv, ctx->datt, B, H, d, C, pos + 1, pos_ptr, ctx->st, done);  // head-major cache
         skinny(ctx, ctx->datt, d, L.o, B, d, d, SK_RESID_F32, ctx->dx, nullptr, nullptr, d, 0, C);
         ln_skinny(ctx, L.ln2, L.cq, B, d, d, SK_F16, ctx->dq, nullptr, nullptr, d, 0, C, nullptr);
         if (keep && keep->layer[l].n) launch_align_qsave(ctx->dq, ctx->align_q.at<half_t>(), keep->layer[l], B, ctx->B, d, pos, pos_ptr, done, C - 1, ctx->st);
         if (ctx->opt_absorbed == 2) launch_xabs_attention_fast(ctx->dq, L.ckv.wt, L.ckv.w, L.ckv.b, ctx->xa16, ctx->xabs.u.at<half_t>(), ctx->xabs.z, ctx->xabs.ml, ctx->datt, B, H, d, ctx->S, done, ctx->st);
         else if (ctx->opt_absorbed) launch_xabs_attention(ctx->dq, L.ckv.w, L.ckv.b, ctx->xa16, ctx->xabs.u.at<half_t>(), ctx->datt, B, H, d, ctx->S, done, ctx->st);
-        else launch_dec_attention(ctx->dq, kv.ck, kv.cv, ctx->datt, B, 1, H, d, ctx->S, ctx->S, nullptr, ctx->st, 1, done);  // head-major cross K/V
+        else launch_dec_attention(ctx->dq, kv.ck, kv.cv, ctx->datt, B, H, d, ctx->S, ctx->S, nullptr, ctx->st, done);  // head-major cross K/V
         skinny(ctx, ctx->datt, d, L.co, B, d, d, SK_RESID_F32, ctx->dx, nullptr, nullptr, d, 0, C);
         ln_skinny(ctx, L.ln3, L.fc1, B, 4 * d, d, SK_GELU_F16, ctx->dhid, nullptr, nullptr, 4 * d, 0, C, nullptr);
         skinny(ctx, ctx->dhid, 4 * d, L.fc2, B, d, 4 * d, SK_RESID_F32, ctx->dx, nullptr, nullptr, d, 0, C);

@@ -48,7 +48,6 @@ struct GemmParams {
     int S, H;                                   // rows per clip / heads (V^T and conv2 epilogues)
     const float *pos;                           // conv2: positional embedding [S][N]
     int cus;                                    // workgroups of the persistent grid; 0 = one per CU (tools/cumask runs it on CU-masked streams)
-    unsigned long long *dbg;                    // -DG2_STAMPS diagnostic builds only (tools/gstamps): per-workgroup time stamps; else unused
     // filled in by launch_gemm: multipliers for the kernels' integer divisions by a_rpb, o_rpb and S (nh_magic / nh_div below)
     unsigned a_magic, o_magic, s_magic;
 };
@@ -161,7 +160,7 @@ bool launch_layernorm_sliced(const float *x, const float *w, const float *b, hal
 void launch_repack_tiles(const half_t *W, half_t *out, int N, int K, hipStream_t st);
 
 // ---- kernels that do not share their CU's LDS: skinny_lds_kernel, skinny_ldsp_kernel (k_skinny.hip: the "two logits kernels
-// above" of the finding below, written beside them), xabs_main_kernel (k_dec_attn.hip) and prefill_attn_kernel (k_prefill.hip) -------
+// above" of the finding below, written beside them), xabs_main_kernel (k_xabs.hip) and prefill_attn_kernel (k_prefill.hip) -------
 // The two logits kernels above keep their activations in LDS and feed every MFMA from a `ds_read_b128` -- 512 threads, 288-358
 // of a SIMD's 512 registers, 40-120 KB of LDS: other kernels' workgroups fit beside them on a CU.  r03 found that they must not:
 // the log-mel kernel of ANOTHER context (37 KB of LDS, 4 waves) gave wrong spectra in 1-250 frames of a clip whenever one of these
@@ -383,14 +382,13 @@ void launch_mel_finish_ex(float *mel32, const unsigned *chunk_max, half_t *img, 
 void launch_enc_attention(const half_t *q, const half_t *k, long ld, const half_t *vt, half_t *out, long ldo,
                           int B, int S, int H, hipStream_t st);
 
-// ---- decoder attention (one query row per (b, h, i)) -------------------------------------------------
-// q: fp16 [B*Tn][d]; kc,vc: fp16 [B][ctx][d]; keys visible to new row i: t0 + i + 1 (causal) or Tk (cross)
+// ---- decoder attention of a decode step (one query row per (b, h)) ------------------------------------
+// q: fp16 [B][d]; kc,vc: fp16 head-major [B][H][ctx][64] (the self-attention cache, or the cross K/V written with
+// GemmParams::head_major); out: fp16 [B][d]; keys visible to the row: Tk
 // pos_ptr != nullptr: i32 [B]; sequence b attends causally over pos_ptr[b] + 1 keys (device-side positions)
-// kv_head_major: K/V are [b][h][ctx][64] (the cross K/V written with GemmParams::head_major) instead of [b][ctx][d]
-// done: optional i32 [B]; sequences with done[b] != 0 are skipped (their output row is left untouched)
-void launch_dec_attention(const half_t *q, const half_t *kc, const half_t *vc, half_t *out, int B, int Tn,
-                          int H, int d, int ctx, int Tk, const int32_t *pos_ptr, hipStream_t st, int kv_head_major = 0,
-                          const int32_t *done = nullptr);
+// done: i32 [B] or nullptr; sequences with done[b] != 0 are skipped (their output row is left untouched)
+void launch_dec_attention(const half_t *q, const half_t *kc, const half_t *vc, half_t *out, int B, int H, int d, int ctx, int Tk,
+                          const int32_t *pos_ptr, hipStream_t st, const int32_t *done);
 
 // ---- attention of the one-pass decoder forward (k_prefill.hip): T query positions per clip at once ---------------------
 // q, k, v: fp16 [B*T][ld] as the qkv GEMM leaves them (head h at column 64 h); out fp16 [B*T][ldo].  Query i of a clip sees
@@ -402,7 +400,7 @@ bool launch_prefill_self_attention(const half_t *q, const half_t *k, const half_
 bool launch_prefill_cross_attention(const half_t *q, long ldq, const half_t *ck, const half_t *cv, half_t *out, long ldo, int B, int T,
                                     int H, int S, hipStream_t st);
 
-// numerics prototype of cross-attention on the encoder output itself (NH_OPT_ABSORBED_XATTN; k_dec_attn.hip): Wkv = the fused
+// numerics prototype of cross-attention on the encoder output itself (NH_OPT_ABSORBED_XATTN; k_xabs.hip): Wkv = the fused
 // [2 d][d] cross K/V projection (K rows first), bkv its bias, xa fp16 [B][S][d], U scratch fp16 [B][H][d]
 void launch_xabs_attention(const half_t *q, const half_t *Wkv, const float *bkv, const half_t *xa, half_t *U, half_t *out, int B, int H, int d, int S,
                            const int32_t *done, hipStream_t st);

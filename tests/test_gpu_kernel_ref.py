@@ -287,14 +287,14 @@ def _attn_case(r, B, H, T, scale=1.0):
     return q, k, v
 
 
-def _dec_run(q, k, v, H, Tk, pos=None, done=None, head_major=True, out=None):
+def _dec_run(q, k, v, H, Tk, pos=None, done=None, out=None):
     L = K.lib()
     B, d = q.shape
     ctx = k.shape[1]
-    kk = K.head_major(k, H) if head_major else k
-    vv = K.head_major(v, H) if head_major else v
+    kk = K.head_major(k, H)
+    vv = K.head_major(v, H)
     out = np.full((B, d), np.float16(7.25), np.float16) if out is None else out
-    rc = L.kref_dec_attention(K.ptr(q), K.ptr(kk), K.ptr(vv), K.ptr(out), B, H, d, ctx, Tk, K.ptr(pos), int(head_major), K.ptr(done))
+    rc = L.kref_dec_attention(K.ptr(q), K.ptr(kk), K.ptr(vv), K.ptr(out), B, H, d, ctx, Tk, K.ptr(pos), 1, K.ptr(done))
     K.check_rc(rc, f"launch_dec_attention B={B} H={H} Tk={Tk}")
     return out
 
@@ -329,9 +329,6 @@ def test_dec_attention_self_matches_fp64(B, H):
             K.discriminates(ref, bound, _dec_mutations(q, k, v, H, [Tk] * B, CTX))
         got = _dec_run(q, k, v, H, Tk)
         K.within(got, ref, bound, f"dec self B={B} H={H} Tk={Tk}")
-    # the [b][ctx][d] layout (kv_head_major = 0)
-    ref, sabs, vst = K.dec_attention(q, k, v, H, [33] * B)
-    K.within(_dec_run(q, k, v, H, 33, head_major=False), ref, K.attn_bound(ref, sabs, [33] * B, vst), "dec self row-major")
 
 
 def test_dec_attention_per_row_positions_match_fp64():

@@ -102,9 +102,8 @@ int main(int argc, char **argv) {
     bench("skinny fc1   N=5120 K=1280 (GELU)", R, [&] { sk_call(xn, d, W(4ul * d * d), 4 * d, d, SK_GELU_F16, hid, 4 * d); }, 4.0 * d * d * 2);
     bench("skinny fc2   N=1280 K=5120 (RESID)", R, [&] { sk_call(hid, 4 * d, W(4ul * d * d), d, 4 * d, SK_RESID_F32, x, d); }, 4.0 * d * d * 2);
     bench("skinny logits N=51866 K=1280 (F32)", 9, [&] { SkinnyParams p{}; p.x = xn; p.ldx = d; p.W = W((size_t)V * d); p.R = B; p.N = V; p.K = d; p.epi = SK_F32; p.out[0] = logits; p.ldo = VP; (void)launch_skinny(p, st); }, (double)V * d * 2);
-    bench("dec_attn self Tk=200", R, [&] { launch_dec_attention(q, sk, sv, att, B, 1, H, d, C, 200, nullptr, st); }, 2.0 * B * 200 * d * 2);
-    bench("dec_attn cross Tk=1500", 9, [&] { size_t o = (size_t)(kvr++ % 3) * B * S * d; launch_dec_attention(q, kc + o, vc + o, att, B, 1, H, d, S, S, nullptr, st); }, 2.0 * B * S * d * 2);
-    bench("dec_attn cross Tk=1500, head-major K/V", 9, [&] { size_t o = (size_t)(kvr++ % 3) * B * S * d; launch_dec_attention(q, kc + o, vc + o, att, B, 1, H, d, S, S, nullptr, st, 1); }, 2.0 * B * S * d * 2);
+    bench("dec_attn self Tk=200", R, [&] { launch_dec_attention(q, sk, sv, att, B, H, d, C, 200, nullptr, st, nullptr); }, 2.0 * B * 200 * d * 2);
+    bench("dec_attn cross Tk=1500", 9, [&] { size_t o = (size_t)(kvr++ % 3) * B * S * d; launch_dec_attention(q, kc + o, vc + o, att, B, H, d, S, S, nullptr, st, nullptr); }, 2.0 * B * S * d * 2);
     bench("logit_step mode 1", R, [&] { launch_logit_step(logits, V, ds, tk, B, 4096, 1 << 30, 0, 3, 1, lpart, ltick, nullptr, st); }, (double)B * V * 4);
     {   // the sampled rows of a decode pool: every row at t = 0.2 and at a generation position (eot suppressed, so no row ends)
         PoolSampling ps{};

@@ -103,9 +103,11 @@ int kref_skinny_plan(int R, int N, int K, int epi, int wt, int ln, int32_t out[1
     return pl.kind != SKP_NONE;
 }
 
-// launch_dec_attention: q [B][d]; kc, vc [B][ctx][d] or head-major [B][H][ctx][64]; out [B][d] (copied in: done rows stay)
+// launch_dec_attention: q [B][d]; kc, vc head-major [B][H][ctx][64]; out [B][d] (copied in: done rows stay).  head_major must
+// be 1: 0 was the row-major [B][ctx][d] layout, which dec_attn_kernel no longer reads (-1, shape refused)
 int kref_dec_attention(const void *q, const void *kc, const void *vc, void *out, int B, int H, int d, int ctx, int Tk,
-                       const int32_t *pos_ptr, int kv_head_major, const int32_t *done) {
+                       const int32_t *pos_ptr, int head_major, const int32_t *done) {
+    if (!head_major) return -1;
     Bufs b;
     Stream st;
     const size_t kv = (size_t)B * ctx * d * 2;
@@ -113,7 +115,7 @@ int kref_dec_attention(const void *q, const void *kc, const void *vc, void *out,
     half_t *dout = b.in<half_t>(out, (size_t)B * d * 2);
     const int32_t *dpos = b.in<int32_t>(pos_ptr, (size_t)B * 4), *ddone = b.in<int32_t>(done, (size_t)B * 4);
     KREF_CHECK(b);
-    launch_dec_attention(dq, dk, dv, dout, B, 1, H, d, ctx, Tk, dpos, st.s, kv_head_major, ddone);
+    launch_dec_attention(dq, dk, dv, dout, B, H, d, ctx, Tk, dpos, st.s, ddone);
     if (hipError_t e = st.finish()) return (int)e;
     b.out(out, dout, (size_t)B * d * 2);
     return (int)b.err;

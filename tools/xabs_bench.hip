@@ -1,5 +1,5 @@
-// xabs_bench: the one-pass "absorbed" cross-attention kernels of k_dec_attn.hip (NH_OPT_ABSORBED_XATTN = 2) on random data, next to
-// the K/V kernel they replace: time per launch group, and (built with -DXA_STAMPS) the cycle counter at eight points of one tile.
+// xabs_bench: the one-pass "absorbed" cross-attention kernels of k_xabs.hip (NH_OPT_ABSORBED_XATTN = 2) on random data, next to
+// the K/V kernel they replace: time per launch group.
 #include "../norma_amd/csrc/nh_kernels.h"
 #include <cstdio>
 #include <cstdlib>
@@ -18,8 +18,8 @@ int main(int argc, char **argv) {
     CK(hipMalloc(&q, (size_t)R * d * 2)); CK(hipMalloc(&WkT, (size_t)d * d * 2)); CK(hipMalloc(&Wkv, (size_t)2 * d * d * 2));
     CK(hipMalloc(&xa, (size_t)R * S * d * 2)); CK(hipMalloc(&U, (size_t)R * 32 * d * 2)); CK(hipMalloc(&out, (size_t)R * d * 2)); CK(hipMalloc(&out2, (size_t)R * d * 2));
     CK(hipMalloc(&kc, (size_t)R * S * d * 2)); CK(hipMalloc(&vc, (size_t)R * S * d * 2));
-    CK(hipMalloc(&bkv, 2 * d * 4)); CK(hipMalloc(&zpart, (size_t)R * 4 * H * d * 4)); CK(hipMalloc(&mlpart, (size_t)R * 4 * 32 * 2 * 4 + 4096));
-    CK(hipMemset(U, 0, (size_t)R * 32 * d * 2)); CK(hipMemset(bkv, 0, 2 * d * 4)); CK(hipMemset(mlpart, 0, (size_t)R * 4 * 32 * 2 * 4 + 4096));
+    CK(hipMalloc(&bkv, 2 * d * 4)); CK(hipMalloc(&zpart, (size_t)R * 4 * H * d * 4)); CK(hipMalloc(&mlpart, (size_t)R * 4 * 32 * 2 * 4));
+    CK(hipMemset(U, 0, (size_t)R * 32 * d * 2)); CK(hipMemset(bkv, 0, 2 * d * 4)); CK(hipMemset(mlpart, 0, (size_t)R * 4 * 32 * 2 * 4));
     fill(q, (size_t)R * d, 1.0f, 1); fill(Wkv, (size_t)2 * d * d, 0.03f, 2); fill(xa, (size_t)R * S * d, 1.0f, 3);
     fill(kc, (size_t)R * S * d, 1.0f, 4); fill(vc, (size_t)R * S * d, 1.0f, 5);
     hipStream_t st; CK(hipStreamCreate(&st));
@@ -31,14 +31,8 @@ int main(int argc, char **argv) {
         std::sort(ms.begin(), ms.end());
         printf("%-52s rows %3d: median %7.1f us  min %7.1f us\n", name, R, ms[6] * 1e3, ms[0] * 1e3); fflush(stdout);
     };
-    timeit("K/V cross-attention (dec_attn_kernel, head-major)", [&] { launch_dec_attention(q, kc, vc, out2, R, 1, H, d, S, S, nullptr, st, 1, nullptr); });
+    timeit("K/V cross-attention (dec_attn_kernel, head-major)", [&] { launch_dec_attention(q, kc, vc, out2, R, H, d, S, S, nullptr, st, nullptr); });
     timeit("absorbed: u + main + z-merge + o-projection", [&] { launch_xabs_attention_fast(q, WkT, Wkv, bkv, xa, U, zpart, mlpart, out, R, H, d, S, nullptr, st); });
     CK(hipStreamSynchronize(st));
-    std::vector<float> stamps(64);
-    CK(hipMemcpy(stamps.data(), mlpart + (size_t)R * 4 * 32 * 2, 64 * 4, hipMemcpyDeviceToHost));
-    if (stamps[1] > 0.f) {
-        printf("cycle counter of tile 5 per wave: top | stored+barrier | S partial done | barrier | reduced+barrier | softmax done | z updated | barrier\n");
-        for (int w = 0; w < 8; w++) { printf("wave %d:", w); for (int k = 0; k < 8; k++) printf(" %7.0f", stamps[w * 8 + k]); printf("\n"); }
-    }
     return 0;
 }
