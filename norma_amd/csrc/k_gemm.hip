@@ -176,6 +176,10 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(GemmParams p) {
 #define PP_RING (2 * PP_BUF)
 #define PP_EPI_PITCH 136  // bytes per image row (64 fp16 + 8 pad)
 #define PP_EPI_WAVE (16 * PP_EPI_PITCH)
+#define PP_BIAS (PP_RING + 8 * PP_EPI_WAVE)  // two rows of 256 f32: the bias of this tile's and the next tile's columns
+#define PP_LDS (PP_BIAS + 2 * 1024)
+#define PP_VT_OOB 0xf0000000u  // V^T epilogue: offset of a row that must not be written; beyond any image launch_gemm admits, and
+                               // still so (no wrap) with a column offset added
 
 struct PPSource { unsigned ag[2][2], wg[2][2]; };  // [h][i]: 32-bit element offsets of this lane's eight source rows
 
@@ -194,7 +198,10 @@ __device__ __forceinline__ PPSource pp_source(const GemmParams &p, int m0, int n
     for (int h = 0; h < 2; h++)
 #pragma unroll
         for (int i = 0; i < 2; i++) {
-            sg.ag[h][i] = (unsigned)(a_row_ptr(p, m0 + i * 128 + h * 64 + lrow) - p.A) + csrc;
+            // a_row_ptr(p, m) - p.A in 32 bits (launch_gemm sends a map that does not fit to the 128 x 128 kernel): tail rows
+            // clamped, the clip index as one multiply-high (a_magic is 0 or exact here)
+            const unsigned m = (unsigned)min(m0 + i * 128 + h * 64 + lrow, p.M - 1), b = __umulhi(m, p.a_magic);
+            sg.ag[h][i] = b * (unsigned)p.a_bstride + (m - b * (unsigned)p.a_rpb) * (unsigned)p.lda + csrc;
             const int l = lrow + 64 * i;
             sg.wg[h][i] = (unsigned)(n0 + (l >> 5) * 64 + h * 32 + (l & 31)) * (unsigned)p.K + csrc;
         }
@@ -316,31 +323,216 @@ __device__ __forceinline__ void pp_tile(int vb, int ntn, int ntm, int &tm, int &
     grouped_tile(xcd_contiguous(vb, ntn * ntm), ntn, ntm, G2_GM, tm, tn);
 }
 
+// ---- the tile hand-over: next tile's first fetches, then the finished tile's epilogue ----
+// Everything a store of the fp16 epilogues needs is decided per launch (launch_gemm: the e_* row map, one form for row-major,
+// row-mapped and head-major outputs) or per tile (segment, V^T or not, scaled or not, the sixteen row offsets of a lane), so
+// that the 128 outputs of a lane run as one straight line of bias add / scale / GELU / conversion, LDS image and stores.
+
+// The bias of a tile's 256 columns travels with the tile's first fetches: one more LDS-DMA (4 bytes per lane) in front of the
+// twelve of the prologue, into one of two 1 KiB rows behind the images (tiles alternate), and the epilogue reads it with
+// ds_read.  An ordinary load of the bias in the hand-over makes hipcc wait vmcnt(0) where the value is used -- it does not count
+// past LDS-DMAs in flight -- and that is the drain of the next tile's twelve DMAs in front of the epilogue, wherever the load is
+// issued.  Being the oldest operation of its batch the extra DMA has retired at every counted wait of the main loop.  The two waves
+// of a wave column fetch the same 64 values to the same place.  Without a bias both rows are zero (gemm256_f16_kernel).
+__device__ __forceinline__ void pp_bias_stage(const GemmParams &p, char *smem, int w, int n0, int par) {
+    if (!p.bias) return;
+    int ln = threadIdx.x;
+    asm volatile("" : "+v"(ln));
+    __builtin_amdgcn_global_load_lds((gbl_void *)(p.bias + n0 + (w & 3) * 64 + (ln & 63)), (lds_void *)(smem + PP_BIAS + par * 1024 + (w & 3) * 256), 4, 0, 0);
+}
+
+// starts the fetches of the workgroup's next tile, if it has one (the ring is free: every wave is through its last phase)
+__device__ __forceinline__ bool pp_next(const GemmParams &p, char *smem, int w, int par, int &vb, int ntn, int ntm, int &tm, int &tn, PPSource &sg) {
+    const int nvb = vb + gridDim.x;
+    if (nvb >= ntn * ntm) return false;
+    vb = nvb;
+    pp_tile(nvb, ntn, ntm, tm, tn);
+    pp_bias_stage(p, smem, w, tn * G2_BN, par ^ 1);
+    sg = pp_source(p, tm * G2_BM, tn * G2_BN);
+    pp_prologue(p, smem + w * 1024, sg);
+    return true;
+}
+
+// byte offsets of the sixteen 8-row groups a lane stores (rows m0 + wm * 128 + 8 k + (lane >> 3), k = 0 .. 15) from the wave's
+// base: row m lies ((m / rpb) * bstride + m % rpb) * e_rs bytes in = ((m / rpb) * e_db + m) * e_rs (plan_gemm256).  A tile whose rows
+// are one clip (every tile of a launch whose rows are one batch) has the quotient as a scalar and adds 8 k e_rs per group; a tile
+// that holds a clip end or the end of M divides per group.  Rows >= M continue the last clip, so their offsets lie at or beyond
+// the last row's and the buffer descriptor (e_bound) drops them: no guard, no exec-masked region around the stores.
+__device__ __forceinline__ void pp_row_offsets(const GemmParams &p, int m0, int wm, int ln, unsigned (&off)[16]) {
+    const unsigned ml = (unsigned)(m0 + wm * 128 + ((ln >> 3) & 7)), lc = (unsigned)(ln & 7) * 16u;
+    const unsigned b0 = __umulhi((unsigned)m0, p.e_magic);
+    if (m0 + G2_BM <= p.M && b0 == __umulhi((unsigned)m0 + G2_BM - 1, p.e_magic)) {
+        const unsigned base = (b0 * p.e_db + ml) * p.e_rs + lc;
+#pragma unroll
+        for (int k = 0; k < 16; k++) off[k] = base + (unsigned)(8 * k) * p.e_rs;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            const unsigned m = ml + 8 * k;
+            off[k] = (__umulhi(m, p.e_magic) * p.e_db + m) * p.e_rs + lc;
+        }
+    }
+}
+
+// bias of the lane's four 4-column pieces (columns wn * 64 + 16 j + 4 fq + r of the tile) from the tile's bias row
+__device__ __forceinline__ void pp_bias4(const char *smem, int par, int wn, int ln, f32x4 (&bv)[4]) {
+    const char *const src = smem + PP_BIAS + par * 1024 + wn * 256 + ((ln >> 4) & 3) * 16;
+#pragma unroll
+    for (int j = 0; j < 4; j++) bv[j] = *reinterpret_cast<const f32x4 *>(src + 64 * j);
+}
+
+// fp16 / GELU epilogue: lane holds columns n = nb + 4 fq + r of row m = mb + fr: per 16-row block i a [16 m][64 n] fp16 image,
+// read back as 128-byte row segments (8 lanes x 16 B; 8 rows per store instruction)
+template <bool GELU, bool SCALED>
+__device__ __forceinline__ void pp_epi_f16(const f32x4 (&acc)[8][4], const f32x4 (&bv)[4], float scale, char *img, int ln,
+                                           __amdgpu_buffer_rsrc_t ors, const unsigned (&off)[16]) {
+    char *const wr = img + (ln & 15) * PP_EPI_PITCH + ((ln >> 4) & 3) * 8;
+    const char *const rd = img + ((ln >> 3) & 7) * PP_EPI_PITCH + (ln & 7) * 16;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            f32x4 v = acc[i][j] + bv[j];
+            if (SCALED) v *= scale;
+            if (GELU) {
+                v[0] = gelu_tanh_f(v[0]); v[1] = gelu_tanh_f(v[1]); v[2] = gelu_tanh_f(v[2]); v[3] = gelu_tanh_f(v[3]);
+            }
+            half4 hv = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
+            *reinterpret_cast<half4 *>(wr + 32 * j) = hv;
+        }
+#pragma unroll
+        for (int it = 0; it < 2; it++) {
+            const half4 lo = *reinterpret_cast<const half4 *>(rd + 8 * it * PP_EPI_PITCH);
+            const half4 hi = *reinterpret_cast<const half4 *>(rd + 8 * it * PP_EPI_PITCH + 8);
+            const half8 o = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), ors, off[2 * i + it], 0, 0);
+        }
+    }
+}
+
+// V^T epilogue: lane holds rows m = mb + 4 fq + r of column n = nb + fr: per 16-column block j and 64-row half a [16 n][64 m]
+// image, read back as 16-byte runs of 8 consecutive m.  one_clip (tile-uniform): the tile's 256 rows are one clip b0 and all below
+// M, so every run is a whole 16-byte store; otherwise a run that crosses a clip end or M goes out element by element.  One body
+// with a scalar branch at each store, not one body per case: hipcc hoists what two bodies have in common above the branch
+// between them -- every bias add of the tile, 128 more live registers, and accumulators get spilled.
+__device__ __forceinline__ void pp_epi_vt(const GemmParams &p, const f32x4 (&acc)[8][4], const float (&bv)[4], char *img, int ln,
+                                          half_t *dst, int m0, int wm, int nl0, bool one_clip, unsigned b0) {
+    char *const wr = img + (ln & 15) * PP_EPI_PITCH + ((ln >> 4) & 3) * 8;
+    const char *const rd = img + ((ln >> 3) & 7) * PP_EPI_PITCH + (ln & 7) * 16;
+    const int nl = nl0 + ((ln >> 3) & 7), ml = m0 + wm * 128 + (ln & 7) * 8;  // + 16 j + 8 it, + 64 hh
+    __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(dst, 0, (int)p.vt_bytes, 0x00020000);
+    const unsigned voff = ((b0 * (unsigned)(p.H * NH_DH) + (unsigned)nl) * NH_SP + ((unsigned)ml - b0 * (unsigned)p.S)) * 2u;
+    // !one_clip: the lane's two runs (hh = 0, 1) are the same rows for every column: decided once.  whole: the eight rows are one
+    // clip and below M; otherwise every row goes to its own offset, or beyond the descriptor when it is >= M (dropped)
+    bool whole[2];
+    unsigned wo[2];
+    if (!one_clip) {
+#pragma unroll
+        for (int hh = 0; hh < 2; hh++) {
+            const int m = ml + 64 * hh;
+            const unsigned b = __umulhi((unsigned)m, p.s_magic), ss = (unsigned)m - b * (unsigned)p.S;
+            whole[hh] = (int)ss + 7 < p.S && m + 7 < p.M;
+            wo[hh] = ((b * (unsigned)(p.H * NH_DH) + (unsigned)nl) * NH_SP + ss) * 2u;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+#pragma unroll
+        for (int hh = 0; hh < 2; hh++) {
+#pragma unroll
+            for (int ii = 0; ii < 4; ii++) {
+                const f32x4 a = acc[4 * hh + ii][j];
+                half4 v = {(half_t)(a[0] + bv[j]), (half_t)(a[1] + bv[j]), (half_t)(a[2] + bv[j]), (half_t)(a[3] + bv[j])};
+                *reinterpret_cast<half4 *>(wr + 32 * ii) = v;
+            }
+#pragma unroll
+            for (int it = 0; it < 2; it++) {
+                const half4 lo = *reinterpret_cast<const half4 *>(rd + 8 * it * PP_EPI_PITCH);
+                const half4 hi = *reinterpret_cast<const half4 *>(rd + 8 * it * PP_EPI_PITCH + 8);
+                if (one_clip) {
+                    const half8 o = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), vrs, voff + (unsigned)(((16 * j + 8 * it) * NH_SP + 64 * hh) * 2), 0, 0);
+                } else {
+                    const unsigned c = (unsigned)((16 * j + 8 * it) * NH_SP * 2);
+                    if (whole[hh]) {
+                        const half8 o = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), vrs, wo[hh] + c, 0, 0);
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 8; r++) {   // recomputed at every run: rare tiles, and sixteen offsets held across the epilogue cost spills
+                            const unsigned mm = (unsigned)(ml + 64 * hh + r), bb = __umulhi(mm, p.s_magic);
+                            const unsigned eo = (int)mm < p.M ? ((bb * (unsigned)(p.H * NH_DH) + (unsigned)nl) * NH_SP + (mm - bb * (unsigned)p.S)) * 2u : PP_VT_OOB;
+                            __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(short, r < 4 ? lo[r] : hi[r - 4]), vrs, eo + c, 0, 0);
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm256_f16_kernel(GemmParams p) {
-    __shared__ __attribute__((aligned(16))) char smem[PP_RING + 8 * PP_EPI_WAVE];
-    const int ntn = p.N / G2_BN, ntm = (p.M + G2_BM - 1) / G2_BM, nwg = ntn * ntm;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __shared__ __attribute__((aligned(16))) char smem[PP_LDS];
+    const int ntn = p.N / G2_BN, ntm = (p.M + G2_BM - 1) / G2_BM;
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // the wave index is a scalar
     const int wm = w >> 2, wn = w & 3;
     const int fr = lane & 15, fq = lane >> 4;
-    char *const wbase = smem + __builtin_amdgcn_readfirstlane(w) * 1024;  // this wave's 1 KiB run of every 8 KiB DMA group
+    char *const wbase = smem + w * 1024;  // this wave's 1 KiB run of every 8 KiB DMA group
     char *const img = smem + PP_RING + w * PP_EPI_WAVE;
 
     int vb = blockIdx.x, tm, tn;
     pp_tile(vb, ntn, ntm, tm, tn);
+    if (!p.bias) *reinterpret_cast<float *>(smem + PP_BIAS + threadIdx.x * 4) = 0.f;  // both bias rows; read after pp_main's barriers
+    pp_bias_stage(p, smem, w, tn * G2_BN, 0);
     PPSource sg = pp_source(p, tm * G2_BM, tn * G2_BN);
     pp_prologue(p, wbase, sg);
-    for (;;) {
+    for (int par = 0;; par ^= 1) {   // par: which bias row this tile's columns use
         const int m0 = tm * G2_BM, n0 = tn * G2_BN;
         f32x4 acc[8][4];
 #pragma unroll
         for (int i = 0; i < 8; i++)
 #pragma unroll
             for (int j = 0; j < 4; j++) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const int seg = (EPI == EPI_F16 || EPI == EPI_GELU_F16) ? n0 / p.seg_n : 0;
-        const bool vt = (EPI == EPI_F16 && seg == p.vt_seg);
-        if (vt) pp_main<false>(p, smem, wbase, sg, acc);
-        else pp_main<true>(p, smem, wbase, sg, acc);
+        if (EPI == EPI_F16 || EPI == EPI_GELU_F16) {
+            // the tile's segment (at most three; seg_n is a multiple of the tile width), its destination and its wave's columns
+            const int stn = p.seg_n / G2_BN, seg = (tn >= stn) + (tn >= 2 * stn);
+            half_t *const ob = reinterpret_cast<half_t *>(seg == 0 ? p.out[0] : seg == 1 ? p.out[1] : p.out[2]);
+            const int nl0 = n0 - seg * p.seg_n + wn * 64;
+            if (EPI == EPI_F16 && seg == p.vt_seg) {
+                pp_main<false>(p, smem, wbase, sg, acc);
+                int ln = threadIdx.x;
+                asm volatile("" : "+v"(ln));   // lane constants are recomputed per tile (hoisted, they are spilled: pp_source)
+                const unsigned b0 = __umulhi((unsigned)m0, p.s_magic);
+                const bool one_clip = m0 + G2_BM <= p.M && b0 == __umulhi((unsigned)m0 + G2_BM - 1, p.s_magic);
+                const bool more = pp_next(p, smem, w, par, vb, ntn, ntm, tm, tn, sg);
+                asm volatile("" : "+v"(ln));
+                float bv[4];   // columns wn * 64 + 16 j + fr of the tile
+#pragma unroll
+                for (int j = 0; j < 4; j++) bv[j] = *reinterpret_cast<const float *>(smem + PP_BIAS + par * 1024 + wn * 256 + 64 * j + (ln & 15) * 4);
+                pp_epi_vt(p, acc, bv, img, ln, ob, m0, wm, nl0, one_clip, b0);
+                if (!more) break;
+            } else {
+                pp_main<true>(p, smem, wbase, sg, acc);
+                int ln = threadIdx.x;
+                asm volatile("" : "+v"(ln));
+                f32x4 bv[4];
+                pp_bias4(smem, par, wn, ln, bv);
+                // the wave's 64 columns start e_off0 + nl0 * e_cs bytes into the segment (row-major: column nl0 of row o_off;
+                // head-major: row 0 of head nl0 / 64); the descriptor ends with the launch's last row, not with the allocation:
+                // in a joint decode the next encoder batch's rows follow directly
+                const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char *>(ob) + p.e_off0 + (long)nl0 * p.e_cs, 0, (int)p.e_bound, 0x00020000);
+                unsigned off[16];
+                pp_row_offsets(p, m0, wm, ln, off);
+                const bool more = pp_next(p, smem, w, par, vb, ntn, ntm, tm, tn, sg);
+                if (EPI == EPI_GELU_F16) pp_epi_f16<true, false>(acc, bv, 0.f, img, ln, ors, off);
+                else if (seg == 0 && p.seg0_scale != 0.f) pp_epi_f16<false, true>(acc, bv, p.seg0_scale, img, ln, ors, off);
+                else pp_epi_f16<false, false>(acc, bv, 0.f, img, ln, ors, off);
+                if (!more) break;
+            }
+            continue;
+        }
+        pp_main<true>(p, smem, wbase, sg, acc);
 
         // EPI_RESID_F32: residual values of four 16-row blocks (64 VGPRs: the fragment registers are dead here), fetched through a
         // buffer descriptor over x[M][ldo]: rows >= M of the last, partial M-panel fall outside it, so their loads return 0 and
@@ -362,105 +554,18 @@ __global__ __launch_bounds__(512) void gemm256_f16_kernel(GemmParams p) {
                     rs[ii][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, xoff + (unsigned)(64 * ii * p.ldo + 64 * j), 0, 0));
         }
         // every wave is through its last phase: the ring is free.  Start the next tile's first fetches now.
-        const int nvb = vb + gridDim.x;
-        const bool more = nvb < nwg;
-        if (more) {
-            pp_tile(nvb, ntn, ntm, tm, tn);
-            sg = pp_source(p, tm * G2_BM, tn * G2_BN);
-            pp_prologue(p, wbase, sg);
-        }
+        const bool more = pp_next(p, smem, w, par, vb, ntn, ntm, tm, tn, sg);
+        f32x4 bv[4];
+        pp_bias4(smem, par, wn, lane, bv);
 
         // ---- epilogue of tile (m0, n0) ----
-        if (vt) {
-            // lane holds rows m = mb + 4 fq + r of column n = nb + fr: per 16-column block j and 64-row half, a
-            // [16 n][64 m] image (V^T); read back as 128-byte runs of 64 consecutive m
-            half_t *dst = reinterpret_cast<half_t *>(seg == 0 ? p.out[0] : seg == 1 ? p.out[1] : p.out[2]);
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const float bv = p.bias ? p.bias[n0 + wn * 64 + 16 * j + fr] : 0.f;
-#pragma unroll
-                for (int hh = 0; hh < 2; hh++) {
-#pragma unroll
-                    for (int ii = 0; ii < 4; ii++) {
-                        const f32x4 a = acc[4 * hh + ii][j];
-                        half4 v = {(half_t)(a[0] + bv), (half_t)(a[1] + bv), (half_t)(a[2] + bv), (half_t)(a[3] + bv)};
-                        *reinterpret_cast<half4 *>(img + fr * PP_EPI_PITCH + (16 * ii + 4 * fq) * 2) = v;
-                    }
-#pragma unroll
-                    for (int it = 0; it < 2; it++) {
-                        const int nrow = 8 * it + (lane >> 3), mc = (lane & 7) * 8;
-                        const half4 lo = *reinterpret_cast<const half4 *>(img + nrow * PP_EPI_PITCH + mc * 2);
-                        const half4 hi = *reinterpret_cast<const half4 *>(img + nrow * PP_EPI_PITCH + mc * 2 + 8);
-                        const int n = n0 + wn * 64 + 16 * j + nrow, nl = n - seg * p.seg_n, h = nl >> 6, dh = nl & 63;
-                        const int m = m0 + wm * 128 + 64 * hh + mc;
-                        if (m >= p.M) continue;
-                        const int b = nh_div(m, p.S, p.s_magic), ss = m - b * p.S;
-                        if (ss + 7 < p.S && m + 7 < p.M) {
-                            half8 o = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                            *reinterpret_cast<half8 *>(dst + ((long)(b * p.H + h) * NH_DH + dh) * NH_SP + ss) = o;
-                        } else {
-                            for (int r = 0; r < 8; r++) {
-                                const int mm = m + r;
-                                if (mm >= p.M) break;
-                                const int bb = nh_div(mm, p.S, p.s_magic), s2 = mm - bb * p.S;
-                                dst[((long)(bb * p.H + h) * NH_DH + dh) * NH_SP + s2] = r < 4 ? lo[r] : hi[r - 4];
-                            }
-                        }
-                    }
-                }
-            }
-        } else if (EPI == EPI_F16 || EPI == EPI_GELU_F16) {
-            // lane holds columns n = nb + 4 fq + r of row m = mb + fr: per 16-row block i a [16 m][64 n] fp16 image
-            half_t *ob = reinterpret_cast<half_t *>(seg == 0 ? p.out[0] : seg == 1 ? p.out[1] : p.out[2]);
-            f32x4 bv[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                bv[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                if (p.bias) bv[j] = *reinterpret_cast<const f32x4 *>(p.bias + n0 + wn * 64 + 16 * j + 4 * fq);
-            }
-            const int ncol = n0 + wn * 64 - seg * p.seg_n + (lane & 7) * 8;
-            const bool q_scaled = EPI == EPI_F16 && seg == 0 && p.seg0_scale != 0.f;   // tile-uniform
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    f32x4 v = acc[i][j] + bv[j];
-                    if (EPI == EPI_F16 && q_scaled) v *= p.seg0_scale;
-                    if (EPI == EPI_GELU_F16) {
-                        v[0] = gelu_tanh_f(v[0]); v[1] = gelu_tanh_f(v[1]); v[2] = gelu_tanh_f(v[2]); v[3] = gelu_tanh_f(v[3]);
-                    }
-                    half4 hv = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
-                    *reinterpret_cast<half4 *>(img + fr * PP_EPI_PITCH + (16 * j + 4 * fq) * 2) = hv;
-                }
-                // read back: 8 lanes x 16 B = one 128-byte output row segment; 8 rows per instruction
-#pragma unroll
-                for (int it = 0; it < 2; it++) {
-                    const int mr = 8 * it + (lane >> 3);
-                    const int m = m0 + wm * 128 + 16 * i + mr;
-                    const half4 lo = *reinterpret_cast<const half4 *>(img + mr * PP_EPI_PITCH + (lane & 7) * 16);
-                    const half4 hi = *reinterpret_cast<const half4 *>(img + mr * PP_EPI_PITCH + (lane & 7) * 16 + 8);
-                    if (m < p.M) {
-                        half8 o = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                        // head-major: the wave's 64 columns are one head (seg_n and the tile base are multiples of 64)
-                        half_t *dst = p.head_major ? ob + (((long)nh_div(m, p.S, p.s_magic) * p.H + (ncol >> 6)) * p.S + (m - nh_div(m, p.S, p.s_magic) * p.S)) * NH_DH + (lane & 7) * 8
-                                                   : ob + out_row(p, m) * p.ldo + ncol;
-                        *reinterpret_cast<half8 *>(dst) = o;
-                    }
-                }
-            }
-        } else if (EPI == EPI_RESID_F32) {
+        if (EPI == EPI_RESID_F32) {
             // x[m][n] += acc + bias.  r01/r02 took the residual tile as the INITIAL accumulator: 32 loads per lane queued behind the
             // twelve prologue DMAs and waited for before the first MFMA -- 12.8 us of every 57 us out-proj tile with the matrix
             // pipe idle (profiles/r03_gstamps.txt).  Now the tile is fetched here, after the main loop, 16 loads per
             // lane at a time into the registers the fragments no longer need (the first sixteen were issued BEFORE the next tile's
             // prologue DMAs, see above), added in the reference's order x + (A.W + bias), and stored: the residual traffic runs
             // under the next tile's first fetches instead of in front of this tile's first MFMA.
-            f32x4 bv[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                bv[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                if (p.bias) bv[j] = *reinterpret_cast<const f32x4 *>(p.bias + n0 + wn * 64 + 16 * j + 4 * fq);
-            }
 #pragma unroll
             for (int ii = 0; ii < 4; ii++)
 #pragma unroll
@@ -481,14 +586,12 @@ __global__ __launch_bounds__(512) void gemm256_f16_kernel(GemmParams p) {
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const int n = n0 + wn * 64 + 16 * j + 4 * fq;
-                f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-                if (p.bias) bv = *reinterpret_cast<const f32x4 *>(p.bias + n);
 #pragma unroll
                 for (int i = 0; i < 8; i++) {
                     const int m = m0 + wm * 128 + 16 * i + fr;
                     if (m >= p.M) continue;
-                    const f32x4 v = acc[i][j] + bv;
-                    const int s = m - nh_div(m, p.S, p.s_magic) * p.S;
+                    const f32x4 v = acc[i][j] + bv[j];
+                    const int s = m - (int)__umulhi((unsigned)m, p.s_magic) * p.S;
                     const f32x4 pe = *reinterpret_cast<const f32x4 *>(p.pos + (long)s * p.N + n);
                     f32x4 o = {gelu_tanh_f(v[0]) + pe[0], gelu_tanh_f(v[1]) + pe[1], gelu_tanh_f(v[2]) + pe[2],
                                gelu_tanh_f(v[3]) + pe[3]};
@@ -497,7 +600,6 @@ __global__ __launch_bounds__(512) void gemm256_f16_kernel(GemmParams p) {
             }
         }
         if (!more) break;
-        vb = nvb;
     }
 }
 
@@ -521,10 +623,45 @@ static GemmParams with_magics(const GemmParams &p_in) {
     return p;
 }
 
+// What the 256 x 256 kernel assumes beyond its shape: every row division is one multiply-high (no magic of the "divide" class),
+// operand and output offsets fit 32 bits for every row of the last, partial M-panel too, and a row-mapped output does not
+// overlap itself.  Fills in the fp16 epilogues' row map (GemmParams::e_*).  A launch that does not fit runs the 128 x 128 kernel.
+static bool plan_gemm256(GemmParams &p) {
+    const bool f16 = p.epi == EPI_F16 || p.epi == EPI_GELU_F16;
+    if (p.N % G2_BN != 0 || p.K % 128 != 0 || p.M < G2_BM || (f16 && p.seg_n % G2_BN != 0)) return false;
+    const unsigned long long lim = 0xffffffffull;
+    const long rows = ((long)p.M + G2_BM - 1) / G2_BM * G2_BM;   // rows the tiles cover
+    if (p.a_magic == ~0u || p.s_magic == ~0u) return false;
+    if ((unsigned long long)(p.a_magic ? (p.M - 1) / p.a_rpb : 0) * p.a_bstride + (unsigned long long)p.M * p.lda + p.K > lim) return false;
+    if (p.s_magic != 0u) {   // the V^T epilogue asks for the clip of a tile's last row, which may lie beyond M
+        p.s_magic = nh_magic(p.S, rows - 1);
+        if (p.s_magic == ~0u) return false;
+    }
+    if (!f16) return true;
+    const bool hm = p.epi == EPI_F16 && p.head_major;
+    const long rpb = hm ? p.S : p.o_rpb, bstride = hm ? (long)p.H * p.S : p.o_bstride;
+    p.e_rs = hm ? NH_DH * 2 : (unsigned)(p.ldo * 2);
+    p.e_cs = hm ? 2L * p.S : 2L;
+    p.e_off0 = hm ? 0L : p.o_off * p.ldo * 2;
+    p.e_magic = (rpb <= 0 || rpb >= p.M) ? 0u : nh_magic((int)rpb, rows - 1);
+    if (p.e_magic == ~0u || (p.e_magic != 0u && bstride < rpb) || p.ldo * 2 > (long)lim || p.e_rs < 128u) return false;
+    p.e_db = p.e_magic ? (unsigned)(bstride - rpb) : 0u;
+    const unsigned long long last = ((unsigned long long)(p.e_magic ? (p.M - 1) / rpb : 0) * p.e_db + (unsigned long long)(p.M - 1)) * p.e_rs + 128;
+    const unsigned long long far = ((unsigned long long)(p.e_magic ? (rows - 1) / rpb : 0) * p.e_db + (unsigned long long)(rows - 1)) * p.e_rs + 128;
+    if (far > lim) return false;
+    p.e_bound = (unsigned)last;
+    if (p.epi == EPI_F16 && p.vt_seg >= 0) {
+        if (p.S <= 0) return false;
+        const unsigned long long vb = (unsigned long long)((p.M + p.S - 1) / p.S) * p.H * NH_DH * NH_SP * 2;
+        if (vb > PP_VT_OOB) return false;
+        p.vt_bytes = (unsigned)vb;
+    }
+    return true;
+}
+
 void launch_gemm(const GemmParams &p_in, hipStream_t st) {
-    const GemmParams p = with_magics(p_in);
-    const bool seg_ok = (p.epi != EPI_F16 && p.epi != EPI_GELU_F16) || (p.seg_n % G2_BN == 0);
-    if (p.N % G2_BN == 0 && p.K % 128 == 0 && seg_ok && p.M >= G2_BM) {
+    GemmParams p = with_magics(p_in);
+    if (plan_gemm256(p)) {
         const int nwg = (p.N / G2_BN) * ((p.M + G2_BM - 1) / G2_BM);
         int cus = p.cus > 0 ? p.cus : device_cu_count();  // persistent grid: one workgroup per CU the stream can reach
         cus -= cus % 8;  // the tile order assumes workgroups b and b + gridDim.x sit on the same XCD

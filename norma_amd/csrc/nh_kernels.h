@@ -50,6 +50,13 @@ struct GemmParams {
     int cus;                                    // workgroups of the persistent grid; 0 = one per CU (tools/cumask runs it on CU-masked streams)
     // filled in by launch_gemm: multipliers for the kernels' integer divisions by a_rpb, o_rpb and S (nh_magic / nh_div below)
     unsigned a_magic, o_magic, s_magic;
+    // filled in by launch_gemm for the 256 x 256 kernel's fp16 epilogues: ONE row map for the row-major, row-mapped (conv1) and
+    // head-major outputs.  A wave's 64 columns start e_off0 + (first column in the segment) * e_cs bytes into out[seg]; from
+    // there row m of batch b = m / rows-per-batch lies (b * e_db + m) * e_rs bytes on (e_magic: the multiplier of that division,
+    // 0 when the rows are one batch; e_db = batch stride - rows per batch, in rows), and e_bound is where the launch's last row
+    // ends: the buffer descriptor's size, so rows >= M of the last tile are dropped by the hardware.  vt_bytes: size of the V^T image
+    unsigned e_magic, e_db, e_rs, e_bound, vt_bytes;
+    long e_off0, e_cs;
 };
 // m / d for 0 <= m <= max_m as one multiply-high: magic = ceil(2^32 / d), exact while m * d < 2^32.  magic == 0 encodes
 // "d > every m" (quotient 0: a GEMM whose rows are one batch), magic == ~0u "outside the exact range: divide" (no shape of
