@@ -6,11 +6,11 @@ when candle cannot open the device, `src/models/mod.rs:47-55`).
 """
 import ctypes as C
 import os
-import re
 from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import cabi
 from .config import Config
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -20,22 +20,14 @@ LIB_PATH = os.environ.get("NORMA_HIP_LIB") or os.path.join(_HERE, "libnorma_hip.
 STRICT_LIB_PATH = os.path.join(_HERE, "libnorma_hip_strict.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "norma_hip.h")
 
-N_SAMPLES = 480000
-N_FRAMES = 3000
-NH_CUT_HOP = 160     # samples per analysis frame of cut_plan
-NH_DTYPE_F32, NH_DTYPE_F16 = 0, 1
-NH_ERR_NOMEM = 4
-NH_LANG_DETECT = -2   # `lang` of pool_admit*: the row detects its language in its first step (pool_detect_languages)
-NH_OPT_DECODE_GRAPHS, NH_OPT_FUSE_DECODE_LAYERNORM, NH_OPT_DECODER_LAYER_LIMIT, NH_OPT_ABSORBED_XATTN = 0, 1, 2, 3
-NH_OPT_ALIGN_KEEP = 4      # 1: align() keeps every clip's weights and matrix for align_weights / align_matrix
-NH_OPT_PROMPT_STEPWISE = 5  # 1: a decode's prefix (set_prompts) goes through the decode step position by position; 0: one pass
-NH_ALIGN_MAX_HEADS = 32
-NH_MAX_BEAMS = 8           # decode_beam: hypotheses per clip at most
-NH_GUARD_MAX_BIAS = 256    # guard_bias: entries per row at most
-# NH_SAMPLE_* of include/norma_hip.h (the types of src/dtype.rs)
-SAMPLE_DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.int8): 2, np.dtype(np.int16): 3,
-                 np.dtype(np.int32): 4, np.dtype(np.int64): 5, np.dtype(np.uint8): 6, np.dtype(np.uint16): 7,
-                 np.dtype(np.uint32): 8, np.dtype(np.uint64): 9}
+_H = cabi.read(HEADER_PATH)
+# every integer #define of the header under its own name: NH_OPT_*, NH_DTYPE_*, NH_SAMPLE_*, NH_ERR_*, NH_LANG_DETECT, NH_CUT_HOP, ...
+globals().update(_H.constants)
+N_SAMPLES, N_FRAMES = NH_N_SAMPLES, NH_N_FRAMES
+# the NH_SAMPLE_* code of each numpy dtype (the types of src/dtype.rs)
+SAMPLE_DTYPES = {np.dtype(t): _H.constants["NH_SAMPLE_" + s] for s, t in (
+    ("F32", np.float32), ("F64", np.float64), ("I8", np.int8), ("I16", np.int16), ("I32", np.int32), ("I64", np.int64),
+    ("U8", np.uint8), ("U16", np.uint16), ("U32", np.uint32), ("U64", np.uint64))}
 
 
 class HipError(RuntimeError):
@@ -46,65 +38,33 @@ class HipError(RuntimeError):
         self.code = code
 
 
-class NhConfig(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in (
-        "num_mel_bins", "max_source_positions", "d_model", "encoder_attention_heads", "encoder_layers",
-        "vocab_size", "max_target_positions", "decoder_attention_heads", "decoder_layers")]
+# the header's structs, fields in the header's names and order
+NhConfig, NhTokens, NhDecodeResult, NhAlignHead = (_H.structs[n] for n in ("nh_config", "nh_tokens", "nh_decode_result", "nh_align_head"))
+# nh_cut_params: analysis frames of 160 samples (nh_cut_plan), defaults {3000, 2000, 15}; nh_vad_params (nh_vad_plan): the same,
+# then the levels' ranks and ratios, then the shaping in frames, defaults {3000, 2000, 15, 100, 900, 4.0, 0.01, 0.0, 10, 20, 100};
+# nh_guard_params (nh_set_guard): {0, 1.0, 0, 0, 0} is off
+NhCutParams, NhVadParams, NhGuardParams, NhTimings = (_H.structs[n] for n in ("nh_cut_params", "nh_vad_params", "nh_guard_params", "nh_timings"))
 
 
-class NhTokens(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in
-                ("sot", "eot", "lang", "task", "no_speech", "no_timestamps", "zero_sec", "one_sec")]
+def _vad_params_of(cls, params):
+    """an NhVadParams as is, or a tuple in field order"""
+    if isinstance(params, cls):
+        return params
+    return cls(*[(float if t is C.c_float else int)(x) for x, (_, t) in zip(params, cls._fields_)])
 
 
-class NhDecodeResult(C.Structure):
-    _fields_ = [("n_tokens", C.c_int32), ("no_speech_exit", C.c_int32), ("avg_logprob", C.c_double),
-                ("no_speech_prob", C.c_double)]
+NhVadParams.of = classmethod(_vad_params_of)
 
-
-class NhAlignHead(C.Structure):
-    _fields_ = [("layer", C.c_int32), ("head", C.c_int32)]
-
-
-class NhCutParams(C.Structure):
-    """nh_cut_params: analysis frames of 160 samples (nh_cut_plan); the defaults are {3000, 2000, 15}"""
-    _fields_ = [("max_frames", C.c_int32), ("min_frames", C.c_int32), ("half_window", C.c_int32)]
-
-
-class NhVadParams(C.Structure):
-    """nh_vad_params (nh_vad_plan): nh_cut_params, then the levels' ranks and ratios, then the shaping in frames of 160 samples;
-    the defaults are {3000, 2000, 15, 100, 900, 4.0, 0.01, 0.0, 10, 20, 100}"""
-    _fields_ = [("max_frames", C.c_int32), ("min_frames", C.c_int32), ("half_window", C.c_int32),
-                ("lo_permille", C.c_int32), ("hi_permille", C.c_int32),
-                ("lo_ratio", C.c_float), ("hi_ratio", C.c_float), ("abs_floor", C.c_float),
-                ("min_speech_frames", C.c_int32), ("pad_frames", C.c_int32), ("min_gap_frames", C.c_int32)]
-
-    @classmethod
-    def of(cls, params):
-        """an NhVadParams as is, or a tuple in field order"""
-        if isinstance(params, cls):
-            return params
-        v = list(params)
-        return cls(*[int(x) for x in v[:5]], *[float(x) for x in v[5:8]], *[int(x) for x in v[8:]])
-
-
-class NhGuardParams(C.Structure):
-    """nh_guard_params (nh_set_guard): {0, 1.0, 0, 0, 0} is off"""
-    _fields_ = [("no_repeat_ngram", C.c_int32), ("repetition_penalty", C.c_float), ("loop_period", C.c_int32),
-                ("loop_repeats", C.c_int32), ("bias", C.c_int32)]
-
-
-class NhTimings(C.Structure):
-    _fields_ = [("mel_ms", C.c_float), ("encoder_ms", C.c_float), ("cross_kv_ms", C.c_float),
-                ("decode_ms", C.c_float), ("decode_steps", C.c_int32), ("gemm_ms", C.c_float),
-                ("gemm_launches", C.c_int32), ("gemm_flops", C.c_double)]
+# PCM the header types `const float *` that may live in device memory: callers hand these over as bare addresses (c_void_p).
+# The one list kept by hand beside the header: a new entry point that takes host-or-device PCM needs its line here, and says
+# so itself if it is forgotten -- its first call with a c_void_p raises ctypes.ArgumentError, nothing is passed wrongly.
+_ADDRESSES = {"nh_logmel_device": ("pcm_dev",), "nh_logmel_device_rows": ("pcm_dev",), "nh_transcribe_batch": ("pcm_dev",),
+              "nh_cut_plan": ("pcm",), "nh_logmel_chunks_rows": ("pcm",), "nh_vad_plan": ("pcm",), "nh_logmel_pieces_rows": ("pcm",)}
 
 
 def declared_symbols() -> List[str]:
     """Every function include/norma_hip.h declares (used by the CPU-side ABI test)."""
-    with open(HEADER_PATH) as f:
-        text = f.read()
-    return sorted(set(re.findall(r"\b(nh_[a-z_0-9]+)\s*\(", text)))
+    return sorted(_H.prototypes)
 
 
 _lib = None
@@ -119,81 +79,7 @@ def load_library() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  norma_amd has no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    vp, fp, ip = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32)
-    L.nh_create.argtypes = [C.c_int, C.POINTER(NhConfig), C.c_int, C.POINTER(vp)]
-    L.nh_create_shared.argtypes = [vp, C.c_int, C.POINTER(vp)]
-    L.nh_destroy.argtypes = [vp]
-    L.nh_destroy.restype = None
-    L.nh_last_error.argtypes = [vp]
-    L.nh_last_error.restype = C.c_char_p
-    L.nh_device_count.argtypes = []
-    L.nh_load_tensor.argtypes = [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.c_int, vp]
-    L.nh_set_mel_filters.argtypes = [vp, fp, C.c_int]
-    L.nh_set_tokens.argtypes = [vp, C.POINTER(NhTokens), ip, C.c_int]
-    L.nh_missing_tensors.argtypes = [vp]
-    L.nh_logmel.argtypes = [vp, fp, ip, C.c_int64, C.c_int]
-    L.nh_logmel_device.argtypes = [vp, vp, ip, C.c_int64, C.c_int]
-    L.nh_logmel_rows.argtypes = [vp, fp, ip, C.c_int64, C.c_int, C.c_int]
-    L.nh_logmel_device_rows.argtypes = [vp, vp, ip, C.c_int64, C.c_int, C.c_int]
-    L.nh_encode_rows.argtypes = [vp, C.c_int, C.c_int]
-    L.nh_pool_begin.argtypes = [vp, C.c_int, C.c_int, C.c_int]
-    L.nh_pool_admit.argtypes = [vp, C.c_int, C.c_int, C.c_int32]
-    L.nh_pool_admit_from.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int32]
-    L.nh_pool_step.argtypes = [vp, C.c_int, ip]
-    L.nh_pool_collect.argtypes = [vp, ip, C.c_int, ip, C.POINTER(NhDecodeResult)]
-    L.nh_pool_retry.argtypes = [vp, C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_uint32]
-    L.nh_pool_detect_languages.argtypes = [vp, ip, C.c_int]
-    L.nh_pool_languages.argtypes = [vp, ip, C.c_int, ip, fp]
-    L.nh_logmel_samples.argtypes = [vp, vp, C.c_int, ip, C.c_int64, C.c_int]
-    L.nh_sample_size.argtypes = [C.c_int]
-    i64p = C.POINTER(C.c_int64)
-    L.nh_resample_len.argtypes = [C.c_int, C.c_int64]
-    L.nh_resample_table.argtypes = [vp, C.c_int, fp, ip, ip, ip]
-    L.nh_resample.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int64, C.c_int, i64p, ip, fp, C.c_int64]
-    L.nh_logmel_resampled_rows.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int64, C.c_int, C.c_int]
-    L.nh_cut_plan.argtypes = [vp, vp, C.c_int, C.c_int64, C.POINTER(NhCutParams), i64p, ip, C.c_int, ip]
-    L.nh_cut_energy.argtypes = [vp, fp, fp, C.c_int64]
-    L.nh_logmel_chunks_rows.argtypes = [vp, vp, C.c_int, i64p, ip, C.c_int, C.c_int]
-    u8p = C.POINTER(C.c_uint8)
-    L.nh_vad_plan.argtypes = [vp, vp, C.c_int, C.c_int64, C.POINTER(NhVadParams), i64p, ip, C.c_int, ip, ip, C.c_int, ip]
-    L.nh_vad_view.argtypes = [vp, fp, u8p, C.c_int64, fp, i64p, C.c_int, ip]
-    L.nh_logmel_pieces_rows.argtypes = [vp, vp, C.c_int, i64p, ip, ip, C.c_int, C.c_int]
-    L.nh_encode.argtypes = [vp]
-    L.nh_decode_greedy.argtypes = [vp, ip, C.POINTER(NhDecodeResult), C.c_int]
-    L.nh_decode_sampled.argtypes = [vp, ip, C.POINTER(NhDecodeResult), C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_uint32]
-    L.nh_sample_rules.argtypes = [vp, fp, ip, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_uint32, ip]
-    L.nh_transcribe_batch.argtypes = [vp, vp, ip, C.c_int64, C.c_int, ip, C.POINTER(NhDecodeResult), C.c_int]
-    L.nh_detect_language.argtypes = [vp, ip, C.c_int, ip, fp]
-    L.nh_set_languages.argtypes = [vp, ip]
-    L.nh_reset.argtypes = [vp]
-    L.nh_synchronize.argtypes = [vp]
-    L.nh_get_mel.argtypes = [vp, C.c_int, fp]
-    L.nh_set_mel.argtypes = [vp, fp, C.c_int]
-    L.nh_encoder_output.argtypes = [vp, C.c_int, fp]
-    L.nh_decoder_forward.argtypes = [vp, ip, C.c_int, fp]
-    L.nh_decoder_forward_onepass.argtypes = [vp, ip, C.c_int, fp]
-    L.nh_set_prompts.argtypes = [vp, ip, C.c_int, C.c_int64, C.c_int]
-    L.nh_final_linear.argtypes = [vp, fp, C.c_int, fp]
-    L.nh_apply_rules.argtypes = [vp, fp, ip, C.c_int, C.c_int, fp, ip]
-    L.nh_align.argtypes = [vp, ip, ip, C.c_int, C.POINTER(NhAlignHead), C.c_int, ip, ip, ip]
-    L.nh_align_capture.argtypes = [vp, C.POINTER(NhAlignHead), C.c_int]
-    L.nh_align_decoded.argtypes = [vp, ip, C.c_int, ip, ip, ip]
-    L.nh_align_weights.argtypes = [vp, C.c_int, C.c_int, fp]
-    L.nh_align_matrix.argtypes = [vp, C.c_int, fp]
-    L.nh_align_path.argtypes = [vp, fp, C.c_int, C.c_int, ip, ip]
-    L.nh_score.argtypes = [vp, ip, ip, C.c_int, fp]
-    dp = C.POINTER(C.c_double)
-    L.nh_decode_beam.argtypes = [vp, C.c_int, ip, C.POINTER(NhDecodeResult), C.c_int]
-    L.nh_beam_hypotheses.argtypes = [vp, C.c_int, ip, ip, dp, ip]
-    L.nh_beam_step.argtypes = [vp, C.c_int, C.c_int, fp, ip, ip, ip, ip, ip, dp, C.c_int, C.c_int, ip, ip, ip, ip, dp]
-    L.nh_beam_reorder.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint16)]
-    L.nh_set_guard.argtypes = [vp, C.POINTER(NhGuardParams)]
-    L.nh_guard_bias.argtypes = [vp, C.c_int, ip, fp, C.c_int]
-    L.nh_guard_report.argtypes = [vp, ip, C.c_int, ip]
-    L.nh_guard_apply.argtypes = [vp, C.c_int, fp, ip, ip, C.c_int64, C.c_int, ip, ip, fp, ip]
-    L.nh_get_timings.argtypes = [vp, C.POINTER(NhTimings)]
-    L.nh_set_profile_gemm.argtypes = [vp, C.c_int]
-    L.nh_set_option.argtypes = [vp, C.c_int, C.c_int]
+    cabi.bind(L, HEADER_PATH, _ADDRESSES)
     _lib = L
     return L
 
@@ -235,7 +121,7 @@ class DeviceBuffer:
         self.ptr, self.nbytes = int(p.value), a.nbytes
         if rt.hipMemcpy(C.c_void_p(self.ptr), a.ctypes.data_as(C.c_void_p), a.nbytes, 1) != 0:   # hipMemcpyHostToDevice
             self.free()
-            raise HipError(2, "hipMemcpy to the device failed")
+            raise HipError(NH_ERR_HIP, "hipMemcpy to the device failed")
 
     def free(self):
         if getattr(self, "ptr", 0):
@@ -320,7 +206,7 @@ class HipWhisper:
             self.load_tensor(name, arr)
         missing = self.L.nh_missing_tensors(self._h)
         if missing:
-            raise HipError(3, f"{missing} tensors missing after load_weights")
+            raise HipError(NH_ERR_STATE, f"{missing} tensors missing after load_weights")
 
     def set_mel_filters(self, filters: np.ndarray):
         f = np.ascontiguousarray(filters, dtype=np.float32)
@@ -346,14 +232,20 @@ class HipWhisper:
         self.batch = B
 
     def _filled(self, row0: int, n: int):
-        """what an accepted nh_logmel*_rows call leaves as the context's batch: row 0 starts a batch, higher rows join one"""
-        self.batch = row0 + n if row0 > 0 else n
+        """what an accepted nh_logmel*_rows call leaves as the context's batch (commit_batch of nh_encode.hip): row 0 starts a
+        batch, higher rows join one -- and refilling rows in its middle does not shorten it"""
+        self.batch = max(self.batch, row0 + n) if row0 > 0 else n
+
+    @staticmethod
+    def _lens(given: Optional[Sequence[int]], n: int, whole: int) -> np.ndarray:
+        """i32 [n]: the clips' lengths as given, or `whole` for each"""
+        return np.full(n, whole, dtype=np.int32) if given is None else np.ascontiguousarray(given, dtype=np.int32)
 
     def logmel_array(self, pcm: np.ndarray, n_samples: Optional[Sequence[int]] = None):
         """pcm: contiguous f32 [batch][stride] in HOST memory, handed to nh_logmel as is (no staging copy here)."""
         assert pcm.dtype == np.float32 and pcm.ndim == 2 and pcm.flags.c_contiguous
         B, stride = pcm.shape
-        ns = np.full(B, stride, dtype=np.int32) if n_samples is None else np.asarray(n_samples, dtype=np.int32)
+        ns = self._lens(n_samples, B, stride)
         self._chk(self.L.nh_logmel(self._h, _fp(pcm), _ip(ns), stride, B))
         self.batch = B
 
@@ -362,7 +254,7 @@ class HipWhisper:
         GPU with dasp_sample's formulas (nh_logmel_samples)."""
         assert pcm.ndim == 2 and pcm.flags.c_contiguous and pcm.dtype in SAMPLE_DTYPES
         B, stride = pcm.shape
-        ns = np.full(B, stride, dtype=np.int32) if n_samples is None else np.asarray(n_samples, dtype=np.int32)
+        ns = self._lens(n_samples, B, stride)
         self._chk(self.L.nh_logmel_samples(self._h, pcm.ctypes.data_as(C.c_void_p), SAMPLE_DTYPES[pcm.dtype], _ip(ns), stride, B))
         self.batch = B
 
@@ -374,7 +266,7 @@ class HipWhisper:
             assert frames.ndim in (2, 3) and frames.dtype in SAMPLE_DTYPES
             a = np.ascontiguousarray(frames)
             ch = 1 if a.ndim == 2 else a.shape[2]
-            nf = np.full(a.shape[0], a.shape[1], dtype=np.int32) if n_frames is None else np.ascontiguousarray(n_frames, dtype=np.int32)
+            nf = self._lens(n_frames, a.shape[0], a.shape[1])
             assert len(nf) == a.shape[0]
             return a.ctypes.data_as(C.c_void_p), 0, SAMPLE_DTYPES[a.dtype], ch, nf, a.shape[1], a
         nf = np.ascontiguousarray(n_frames, dtype=np.int32)
@@ -432,7 +324,7 @@ class HipWhisper:
         (max_frames, min_frames, half_window)."""
         ptr, dev, n, keep = self._recording(pcm, n_samples)
         q = None if params is None else params if isinstance(params, NhCutParams) else NhCutParams(*[int(v) for v in params])
-        cap = max(4, 2 * (n // (NH_CUT_HOP * (q.max_frames if q is not None and q.max_frames > 0 else N_FRAMES))) + 2)
+        cap = self._plan_cap(n, q)
         while True:
             starts, lens, cnt = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int32), C.c_int32(0)
             rc = self.L.nh_cut_plan(self._h, ptr, dev, n, None if q is None else C.byref(q),
@@ -443,6 +335,12 @@ class HipWhisper:
             self._chk(rc)
             self._cut_frames = -(-n // NH_CUT_HOP)
             return starts[:cnt.value].copy(), lens[:cnt.value].copy()
+
+    @staticmethod
+    def _plan_cap(n: int, q) -> int:
+        """room for the records of a plan over n samples that is right unless the cuts fall early: two per max_frames
+        (q: the plan's parameters or None, the defaults); a plan that needs more says so and runs again (cut_plan, vad_plan)"""
+        return max(4, 2 * (n // (NH_CUT_HOP * (q.max_frames if q is not None and q.max_frames > 0 else N_FRAMES))) + 2)
 
     def cut_energy(self):
         """(e, E) f32 [F] of the last cut_plan: frame and window energies (nh_cut_energy)"""
@@ -470,7 +368,7 @@ class HipWhisper:
         NhVadParams, or a tuple in its field order."""
         ptr, dev, n, keep = self._recording(pcm, n_samples)
         q = None if params is None else NhVadParams.of(params)
-        cap_p = cap_c = max(4, 2 * (n // (NH_CUT_HOP * (q.max_frames if q is not None and q.max_frames > 0 else N_FRAMES))) + 2)
+        cap_p = cap_c = self._plan_cap(n, q)
         while True:
             starts, lens, first = np.zeros(cap_p, dtype=np.int64), np.zeros(cap_p, dtype=np.int32), np.zeros(cap_c + 1, dtype=np.int32)
             n_p, n_c = C.c_int32(0), C.c_int32(0)
@@ -525,8 +423,7 @@ class HipWhisper:
         """pcm: contiguous f32 [batch][stride] in HOST memory -> rows [row0, row0 + batch)."""
         assert pcm.dtype == np.float32 and pcm.ndim == 2 and pcm.flags.c_contiguous
         B, stride = pcm.shape
-        ns = np.full(B, stride, dtype=np.int32)
-        self._chk(self.L.nh_logmel_rows(self._h, _fp(pcm), _ip(ns), stride, B, row0))
+        self._chk(self.L.nh_logmel_rows(self._h, _fp(pcm), _ip(self._lens(None, B, stride)), stride, B, row0))
         self._filled(row0, B)
 
     def encode_rows(self, row0: int, batch: int):
@@ -536,7 +433,7 @@ class HipWhisper:
     # encoder output; norma_amd/pool.py holds the refill policy
     def pool_begin(self, rows: int, max_new_tokens: int = 0, per_clip_language: bool = False):
         self._chk(self.L.nh_pool_begin(self._h, rows, max_new_tokens, int(per_clip_language)))
-        self.pool_rows = rows
+        self.pool_rows = self.batch = rows   # nh_pool_begin: the rows filled so far are the pool's; staging rows join above them
         self._decoded_rows = {}
 
     def pool_admit(self, src_row: int, dst_row: int, lang: int = -1):
@@ -554,13 +451,11 @@ class HipWhisper:
 
     def pool_collect(self, rows: Sequence[int]) -> List[dict]:
         rows = np.asarray(rows, dtype=np.int32)
-        toks = np.zeros((len(rows), self.cfg.max_target_positions), dtype=np.int32)
-        res = (NhDecodeResult * len(rows))()
+        toks, res = self._decode_out(len(rows))
         self._chk(self.L.nh_pool_collect(self._h, _ip(rows), len(rows), _ip(toks), res))
-        for i, r in enumerate(rows):   # what align_decoded aligns for these rows
-            self._decoded_rows[int(r)] = (int(res[i].n_tokens), bool(res[i].no_speech_exit), int(toks[i, 1]))
-        return [dict(tokens=toks[i, :res[i].n_tokens].tolist(), avg_logprob=res[i].avg_logprob,
-                     no_speech_prob=res[i].no_speech_prob, no_speech_exit=bool(res[i].no_speech_exit)) for i in range(len(rows))]
+        seqs, out = self._sequences(toks, res)
+        self._decoded_rows.update(zip(rows.tolist(), seqs))
+        return out
 
     def pool_retry(self, row: int, temperature: float, seed: int, clip: int, attempt: int):
         """the clip that row `row` last decoded (collected, not refilled since) decodes again, sampled at `temperature` under
@@ -601,43 +496,45 @@ class HipWhisper:
         self._chk(self.L.nh_encoder_output(self._h, b, _fp(out)))
         return out
 
+    def _decode_out(self, n: int):
+        """(tokens i32 [n][max_target_positions], nh_decode_result [n]) for a decode or a collect of n rows to fill"""
+        return np.zeros((n, self.cfg.max_target_positions), dtype=np.int32), (NhDecodeResult * n)()
+
+    @staticmethod
+    def _sequences(toks: np.ndarray, res):
+        """per row of a filled _decode_out: (n_tokens, no-speech exit, tokens[1]), what align_decoded aligns afterwards, and the
+        dict the decodes and pool_collect return"""
+        seqs = [(int(r.n_tokens), bool(r.no_speech_exit), int(t[1])) for t, r in zip(toks, res)]
+        return seqs, [dict(tokens=t[:r.n_tokens].tolist(), avg_logprob=r.avg_logprob, no_speech_prob=r.no_speech_prob,
+                           no_speech_exit=bool(r.no_speech_exit)) for t, r in zip(toks, res)]
+
     def _results(self, toks: np.ndarray, res) -> List[dict]:
-        out = []
-        # what align_decoded aligns after this decode: (n_tokens, no-speech exit, tokens[1]) per clip
-        self._decoded = [(int(res[b].n_tokens), bool(res[b].no_speech_exit), int(toks[b, 1])) for b in range(self.batch)]
-        for b in range(self.batch):
-            n = res[b].n_tokens
-            out.append(dict(tokens=toks[b, :n].tolist(), avg_logprob=res[b].avg_logprob,
-                            no_speech_prob=res[b].no_speech_prob, no_speech_exit=bool(res[b].no_speech_exit)))
+        """the dicts of a lockstep decode, whose sequences align_decoded aligns from now on"""
+        self._decoded, out = self._sequences(toks, res)
         return out
 
-    def decode_greedy(self, max_new_tokens: int = 0) -> List[dict]:
-        B = self.batch
-        toks = np.zeros((B, self.cfg.max_target_positions), dtype=np.int32)
-        res = (NhDecodeResult * B)()
-        self._chk(self.L.nh_decode_greedy(self._h, _ip(toks), res, max_new_tokens))
+    def _decode(self, fn, *args) -> List[dict]:
+        """fn(ctx, out_tokens, results, *args) on the lockstep batch"""
+        toks, res = self._decode_out(self.batch)
+        self._chk(fn(self._h, _ip(toks), res, *args))
         return self._results(toks, res)
+
+    def decode_greedy(self, max_new_tokens: int = 0) -> List[dict]:
+        return self._decode(self.L.nh_decode_greedy, max_new_tokens)
 
     def decode_sampled(self, temperature: float, seed: int, clip0: int = 0, attempt: int = 1,
                        max_new_tokens: int = 0) -> List[dict]:
         """Model::decode at t > 0 (model.rs:340-348) under the seeded sampling contract of include/norma_hip.h."""
-        B = self.batch
-        toks = np.zeros((B, self.cfg.max_target_positions), dtype=np.int32)
-        res = (NhDecodeResult * B)()
-        self._chk(self.L.nh_decode_sampled(self._h, _ip(toks), res, max_new_tokens, float(temperature), int(seed),
-                                           int(clip0), int(attempt)))
-        return self._results(toks, res)
+        return self._decode(self.L.nh_decode_sampled, max_new_tokens, float(temperature), int(seed), int(clip0), int(attempt))
 
     def decode_beam(self, beam_size: int, max_new_tokens: int = 0) -> List[dict]:
         """Beam search at t = 0 (include/norma_hip.h): decode_greedy's dicts for the best hypothesis of every
         clip, plus `hypotheses`: the clip's finished list [(tokens, sum_logprob)] in finishing order, untrimmed."""
-        B, Cn = self.batch, self.cfg.max_target_positions
-        toks = np.zeros((B, Cn), dtype=np.int32)
-        res = (NhDecodeResult * B)()
+        toks, res = self._decode_out(self.batch)
         self._chk(self.L.nh_decode_beam(self._h, int(beam_size), _ip(toks), res, max_new_tokens))
         out = self._results(toks, res)
-        for b in range(B):
-            out[b]["hypotheses"] = self.beam_hypotheses(b)
+        for b, o in enumerate(out):
+            o["hypotheses"] = self.beam_hypotheses(b)
         return out
 
     def beam_hypotheses(self, b: int) -> List[Tuple[List[int], float]]:
@@ -739,12 +636,10 @@ class HipWhisper:
                                 max_new_tokens: int = 0) -> List[dict]:
         """pcm already resident in HBM (device pointer, f32 [batch][stride])."""
         ns = np.asarray(n_samples, dtype=np.int32)
-        B = len(ns)
-        toks = np.zeros((B, self.cfg.max_target_positions), dtype=np.int32)
-        res = (NhDecodeResult * B)()
-        self._chk(self.L.nh_transcribe_batch(self._h, C.c_void_p(pcm_dev_ptr), _ip(ns), stride, B, _ip(toks), res,
+        toks, res = self._decode_out(len(ns))
+        self._chk(self.L.nh_transcribe_batch(self._h, C.c_void_p(pcm_dev_ptr), _ip(ns), stride, len(ns), _ip(toks), res,
                                              max_new_tokens))
-        self.batch = B
+        self.batch = len(ns)
         return self._results(toks, res)
 
     def detect_language(self, lang_tokens: Sequence[int], want_probs: bool = True):
@@ -782,22 +677,20 @@ class HipWhisper:
         self._chk(self.L.nh_synchronize(self._h))
 
     # -- fine-grained parity views ---------------------------------------------------------------
-    def decoder_forward(self, tokens: np.ndarray) -> np.ndarray:
+    def _decoder_forward(self, fn, tokens: np.ndarray) -> np.ndarray:
         tokens = np.ascontiguousarray(tokens, dtype=np.int32)
         B, T = tokens.shape
         assert B == self.batch
         out = np.zeros((B, T, self.cfg.d_model), dtype=np.float32)
-        self._chk(self.L.nh_decoder_forward(self._h, _ip(tokens), T, _fp(out)))
+        self._chk(fn(self._h, _ip(tokens), T, _fp(out)))
         return out
+
+    def decoder_forward(self, tokens: np.ndarray) -> np.ndarray:
+        return self._decoder_forward(self.L.nh_decoder_forward, tokens)
 
     def decoder_forward_onepass(self, tokens: np.ndarray) -> np.ndarray:
         """decoder_forward's contract computed in one pass over the T positions (nh_decoder_forward_onepass)"""
-        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
-        B, T = tokens.shape
-        assert B == self.batch
-        out = np.zeros((B, T, self.cfg.d_model), dtype=np.float32)
-        self._chk(self.L.nh_decoder_forward_onepass(self._h, _ip(tokens), T, _fp(out)))
-        return out
+        return self._decoder_forward(self.L.nh_decoder_forward_onepass, tokens)
 
     def final_linear(self, x: np.ndarray) -> np.ndarray:
         x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, self.cfg.d_model)
@@ -824,6 +717,28 @@ class HipWhisper:
         return int(tok.value)
 
     # -- token-level timestamps -------------------------------------------------------------------
+    def _token_rows(self, tokens, n_tokens: Optional[Sequence[int]], whole: bool):
+        """(tokens i32 [batch][max_target_positions], n_tokens i32 [batch]) of one token list per clip of the batch, or of an
+        array of that shape with n_tokens.  whole: such an array goes in as given, what lies past n_tokens included; otherwise
+        the rows are zero past n_tokens."""
+        B, Cn = self.batch, self.cfg.max_target_positions
+        if n_tokens is None:
+            n_tokens = [len(t) for t in tokens]
+        nt = np.ascontiguousarray(n_tokens, dtype=np.int32)
+        assert len(nt) == B and len(tokens) == B
+        if whole and isinstance(tokens, np.ndarray) and tokens.shape == (B, Cn):
+            return np.ascontiguousarray(tokens, dtype=np.int32), nt
+        toks = np.zeros((B, Cn), dtype=np.int32)
+        for b in range(B):
+            n = max(0, min(int(nt[b]), Cn))
+            toks[b, :n] = np.asarray(tokens[b], dtype=np.int32)[:n]
+        return toks, nt
+
+    @staticmethod
+    def _heads(heads: Sequence[Tuple[int, int]]):
+        """nh_align_head [len(heads)] (one entry at least, so that an empty list is still a pointer)"""
+        return (NhAlignHead * max(1, len(heads)))(*[NhAlignHead(int(l), int(h)) for l, h in heads])
+
     def align(self, tokens: Sequence[Sequence[int]], n_tokens: Optional[Sequence[int]] = None, prompt_len: int = 3,
               heads: Sequence[Tuple[int, int]] = (), n_keys: Optional[Sequence[int]] = None):
         """nh_align for every clip of the batch: tokens = the sequences as decode_* returned them (lists, or an i32 array
@@ -831,15 +746,8 @@ class HipWhisper:
         (None: all).  Returns (first, last): i32 [batch][max_target_positions], the first and last 20 ms encoder frame of every
         token, -1 for the prompt and past the end."""
         B, Cn = self.batch, self.cfg.max_target_positions
-        if n_tokens is None:
-            n_tokens = [len(t) for t in tokens]
-        nt = np.ascontiguousarray(n_tokens, dtype=np.int32)
-        toks = np.zeros((B, Cn), dtype=np.int32)
-        assert len(nt) == B and len(tokens) == B
-        for b in range(B):
-            n = max(0, min(int(nt[b]), Cn))
-            toks[b, :n] = np.asarray(tokens[b], dtype=np.int32)[:n]
-        hs = (NhAlignHead * max(1, len(heads)))(*[NhAlignHead(int(l), int(h)) for l, h in heads])
+        toks, nt = self._token_rows(tokens, n_tokens, whole=False)
+        hs = self._heads(heads)
         nk = None if n_keys is None else np.ascontiguousarray(n_keys, dtype=np.int32)
         assert nk is None or len(nk) == B
         first = np.full((B, Cn), -2, dtype=np.int32)
@@ -859,17 +767,7 @@ class HipWhisper:
         A prefix that stood in front of sot goes in front of `tokens`, with prompt_len = len(prefix) + 2 or 3.
         out: the array to write (a refused call leaves it as it is)."""
         B, Cn = self.batch, self.cfg.max_target_positions
-        if n_tokens is None:
-            n_tokens = [len(t) for t in tokens]
-        nt = np.ascontiguousarray(n_tokens, dtype=np.int32)
-        assert len(nt) == B and len(tokens) == B
-        if isinstance(tokens, np.ndarray) and tokens.shape == (B, Cn):
-            toks = np.ascontiguousarray(tokens, dtype=np.int32)   # as given, what lies past n_tokens included
-        else:
-            toks = np.zeros((B, Cn), dtype=np.int32)
-            for b in range(B):
-                n = max(0, min(int(nt[b]), Cn))
-                toks[b, :n] = np.asarray(tokens[b], dtype=np.int32)[:n]
+        toks, nt = self._token_rows(tokens, n_tokens, whole=True)
         if out is None:
             out = np.zeros((B, Cn), dtype=np.float32)
         assert out.dtype == np.float32 and out.shape == (B, Cn) and out.flags.c_contiguous
@@ -879,8 +777,7 @@ class HipWhisper:
     def align_capture(self, heads: Sequence[Tuple[int, int]]):
         """nh_align_capture: every following decode of this context (decode_greedy, decode_sampled, the rows of a pool) keeps
         the cross-attention queries of `heads` = [(decoder layer, head)] for align_decoded; [] turns it off (the default)."""
-        hs = (NhAlignHead * max(1, len(heads)))(*[NhAlignHead(int(l), int(h)) for l, h in heads])
-        self._chk(self.L.nh_align_capture(self._h, hs, len(heads)))
+        self._chk(self.L.nh_align_capture(self._h, self._heads(heads), len(heads)))
 
     def align_decoded(self, rows: Optional[Sequence[int]] = None, n_keys: Optional[Sequence[int]] = None):
         """nh_align_decoded: (first, last) i32 [n][max_target_positions] of the sequences this context has just decoded, from

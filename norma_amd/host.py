@@ -12,57 +12,48 @@ the C ABI; nothing here computes anything.
 """
 import ctypes as C
 import enum
+import os
 from dataclasses import dataclass
 from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import assets_io, hip
+from . import assets_io, cabi, hip
 from .config import Config
+
+
+HEADER_PATH = os.path.join(os.path.dirname(hip.HEADER_PATH), "norma_host.h")
+_K = cabi.read(HEADER_PATH).constants   # NM_DEVICE_*, NM_MODEL_*
 
 
 @dataclass(frozen=True)
 class SelectedDevice:
-    """`enum SelectedDevice { Cpu, Cuda(usize), Metal }` (src/models/mod.rs:36-43) + `Rocm(usize)`."""
-    kind: int = 0
+    """`enum SelectedDevice { Cpu, Cuda(usize), Metal }` (src/models/mod.rs:36-43) + `Rocm(usize)`; kind is an NM_DEVICE_*."""
+    kind: int = _K["NM_DEVICE_CPU"]
     ordinal: int = 0
 
     @staticmethod
     def Cpu():
-        return SelectedDevice(0, 0)
+        return SelectedDevice(_K["NM_DEVICE_CPU"], 0)
 
     @staticmethod
     def Cuda(n: int):
-        return SelectedDevice(1, n)
+        return SelectedDevice(_K["NM_DEVICE_CUDA"], n)
 
     @staticmethod
     def Metal():
-        return SelectedDevice(2, 0)
+        return SelectedDevice(_K["NM_DEVICE_METAL"], 0)
 
     @staticmethod
     def Rocm(n: int):
-        return SelectedDevice(3, n)
+        return SelectedDevice(_K["NM_DEVICE_ROCM"], n)
 
 
-class ModelType(enum.IntEnum):
-    """monolingual::ModelType (monolingual.rs:32-46) and multilingual::ModelType (multilingual.rs:47-57)."""
-    TinyEn = 0
-    BaseEn = 1
-    SmallEn = 2
-    MediumEn = 3
-    DistilMediumEn = 4
-    DistilLargeEnV2 = 5
-    DistilLargeEnV3 = 6
-    QuantizedTinyEn = 7     # q8_0 GGUF checkpoint (monolingual.rs), files *-tiny-en*
-    QuantizedTiny = 8       # q8_0 GGUF checkpoint (multilingual.rs:49), files *-tiny*
-    # multilingual::ModelType (multilingual.rs:47-57): language=None detects the language, a fixed "<|xx|>" is MultiAsMono
-    Tiny = 9
-    Base = 10
-    Small = 11
-    Medium = 12
-    Large = 13
-    LargeV2 = 14
-    LargeV3 = 15
+# monolingual::ModelType (monolingual.rs:32-46), its q8_0 GGUF checkpoints (Quantized*), then multilingual::ModelType
+# (multilingual.rs:47-57: language=None detects the language, a fixed "<|xx|>" is MultiAsMono).  The members are the header's
+# NM_MODEL_* under the reference's names: NM_MODEL_DISTIL_LARGE_EN_V3 is ModelType.DistilLargeEnV3.
+ModelType = enum.IntEnum("ModelType", {"".join(w.capitalize() for w in n[len("NM_MODEL_"):].split("_")): v
+                                       for n, v in _K.items() if n.startswith("NM_MODEL_")}, module=__name__)
 
 
 QUANTIZED_EXT = {ModelType.QuantizedTinyEn: "tiny-en", ModelType.QuantizedTiny: "tiny"}
@@ -76,71 +67,12 @@ _bound = False
 
 
 def _lib():
+    """the library with every function of include/norma_host.h bound (its nh_config / nh_tokens are hip's classes: the header
+    includes norma_hip.h)"""
     global _bound
     L = hip.load_library()
     if not _bound:
-        vp = C.c_void_p
-        L.nm_definition_new.restype = vp
-        L.nm_definition_new.argtypes = [C.c_int, C.c_int, C.c_size_t]
-        L.nm_definition_free.argtypes = [vp]
-        L.nm_definition_set_responsiveness.argtypes = [vp, C.c_uint64]
-        L.nm_definition_max_chunk_len.restype = C.c_size_t
-        L.nm_definition_max_chunk_len.argtypes = [vp]
-        L.nm_definition_data_buffer_size.restype = C.c_size_t
-        L.nm_definition_data_buffer_size.argtypes = [vp]
-        L.nm_definition_set_data_buffer_size.argtypes = [vp, C.c_size_t]
-        L.nm_tensors_new.restype = vp
-        L.nm_tensors_add.argtypes = [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.c_int, vp]
-        L.nm_tensors_free.argtypes = [vp]
-        L.nm_definition_blocking_try_to_model.restype = vp
-        L.nm_definition_blocking_try_to_model.argtypes = [vp, C.POINTER(hip.NhConfig), C.POINTER(hip.NhTokens),
-                                                          C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.c_int,
-                                                          vp, C.c_char_p, C.c_int]
-        L.nm_definition_blocking_try_to_model_from_dir.restype = vp
-        L.nm_definition_blocking_try_to_model_from_dir.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float), C.c_int, C.c_char_p,
-                                                                   C.c_int, C.c_char_p, C.c_int]
-        L.nm_model_last_text.argtypes = [vp, C.c_char_p, C.c_int]
-        L.nm_model_enable_language_detection.argtypes = [vp, C.POINTER(C.c_int32), C.c_int]
-        L.nm_model_language_token.argtypes = [vp]
-        L.nm_gguf_list.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
-        L.nm_model_set_temperature_fallback.argtypes = [vp, C.c_int, C.c_uint64]
-        L.nm_model_set_beam_size.argtypes = [vp, C.c_int]
-        L.nm_model_set_repetition_guard.argtypes = [vp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int]
-        L.nm_model_set_token_bias.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int]
-        L.nm_model_last_loop_exit.argtypes = [vp]
-        L.nm_model_free.argtypes = [vp]
-        L.nm_model_transcribe.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_int32), C.c_int,
-                                          C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.c_char_p, C.c_int]
-        L.nm_model_set_alignment_heads.argtypes = [vp, C.POINTER(C.c_int32), C.c_int]
-        L.nm_model_checkpoint_alignment_heads.argtypes = [vp, C.POINTER(C.c_int32), C.c_int]
-        L.nm_model_set_prompt_tokens.argtypes = [vp, C.POINTER(C.c_int32), C.c_int]
-        L.nm_model_set_prompt_tokens.restype = None
-        L.nm_model_set_condition_on_previous.argtypes = [vp, C.c_int]
-        L.nm_model_set_condition_on_previous.restype = None
-        L.nm_model_set_startofprev_token.argtypes = [vp, C.c_int32]
-        L.nm_model_set_startofprev_token.restype = None
-        L.nm_model_prompt_prefix.argtypes = [vp, C.POINTER(C.c_int32), C.c_int]
-        L.nm_model_last_token_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]
-        L.nm_model_last_result.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),
-                                           C.POINTER(C.c_int)]
-        i64, i64p = C.c_int64, C.POINTER(C.c_int64)
-        L.nm_definition_set_input_format.argtypes = [vp, C.c_uint32, C.c_int]
-        L.nm_definition_set_input_format.restype = None
-        L.nm_model_set_input_format.argtypes = [vp, C.c_uint32, C.c_int]
-        L.nm_model_set_input_format.restype = None
-        L.nm_model_transcribe_frames.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_int32), C.c_int,
-                                                 C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.c_char_p, C.c_int]
-        L.nm_resample_plan.argtypes = [C.c_int, i64, i64, i64, C.c_int, i64p, i64p, i64p, i64p]
-        L.nm_resampler_new.restype = vp
-        L.nm_resampler_new.argtypes = [vp, C.c_int, C.c_int, C.c_int]
-        L.nm_resampler_free.argtypes = [vp]
-        L.nm_resampler_free.restype = None
-        L.nm_resampler_push.restype = i64
-        L.nm_resampler_push.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_char_p, C.c_int]
-        L.nm_resampler_read.restype = i64
-        L.nm_resampler_read.argtypes = [vp, C.POINTER(C.c_float), i64]
-        L.nm_resampler_state.argtypes = [vp, i64p, i64p, i64p]
-        L.nm_resampler_state.restype = None
+        cabi.bind(L, HEADER_PATH)
         _bound = True
     return L
 
@@ -425,7 +357,6 @@ class Definition:
         fetches through hf-hub, monolingual.rs:323-345).  language=None: multilingual Definition, the language is
         detected (multilingual.rs:463-466)."""
         import json
-        import os
         ext = QUANTIZED_EXT.get(self.model)   # quantised checkpoints: config-{ext}.json, tokenizer-{ext}.json, model-{ext}-q80.gguf
         with open(os.path.join(path, f"config-{ext}.json" if ext else "config.json")) as f:
             n_mel = json.load(f)["num_mel_bins"]

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import common
-from norma_amd import hip
+from norma_amd import host
 
 GOLD = os.path.join(common.ROOT, "tests", "golden")
 ASSETS = os.path.join(GOLD, "assets")
@@ -21,16 +21,7 @@ ASSETS = os.path.join(GOLD, "assets")
 
 @pytest.fixture(scope="module")
 def L():
-    lib = hip.load_library()
-    lib.nm_tokenizer_open.restype = C.c_void_p
-    lib.nm_tokenizer_open.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
-    lib.nm_tokenizer_free.argtypes = [C.c_void_p]
-    lib.nm_tokenizer_token_to_id.argtypes = [C.c_void_p, C.c_char_p]
-    lib.nm_tokenizer_decode.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.c_int, C.c_char_p, C.c_int]
-    lib.nm_safetensors_list.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
-    lib.nm_language_code.restype = C.c_char_p
-    lib.nm_language_code.argtypes = [C.c_int]
-    return lib
+    return host._lib()
 
 
 def _decode(L, t, ids, skip):
@@ -113,7 +104,6 @@ def test_malformed_checkpoints_are_rejected_not_read_past_the_mapping(L, tmp_pat
     good = tmp_path / "ok.gguf"
     gguf_writer.write_gguf(str(good), [("a.weight", np.arange(64, dtype=np.float32).reshape(2, 32))])
     lib_buf = C.create_string_buffer(4096)
-    L.nm_gguf_list.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
     assert L.nm_gguf_list(str(good).encode(), lib_buf, len(lib_buf)) == 1
     raw = bytearray(good.read_bytes())
     bad = tmp_path / "trunc.gguf"

@@ -516,3 +516,43 @@ def test_encoder_batches_decoded_together_give_what_they_give_alone():
         with pytest.raises(hip.HipError):
             hm.logmel_array_rows(np.ascontiguousarray(clips[:2]), groups[0] + 1)
         hm.close(); h1.close()
+
+
+def test_refilling_a_middle_row_keeps_the_batch_the_library_decodes():
+    """HipWhisper.batch sizes every output array, so it has to be the library's own count of rows (commit_batch of
+    nh_encode.hip: rows above 0 only ever extend the batch; nh_pool_begin: the pool's rows).  Rows [0,1), [1,3), then [1,2)
+    again: the library decodes 3 rows, clips 0, 3 and 2, each bit for bit what it gives alone."""
+    hip = _hip()
+    name = "test-d256-mel128"
+    cfg = config.preset(name)
+    tk = common.tokens_for(name)
+    script = common.transcript_script(tk, n_segments=3, words_per_segment=5, seed=17)
+    hm = common.build_hip(cfg, tk, overrides=common.scripted_overrides(cfg, tk, script), max_batch=3)
+    h1 = hip.HipWhisper(cfg, device=0, max_batch=1, share_with=hm)
+    h1.set_tokens(tk, tk.en, tk.transcribe)
+    clips = np.stack([synth.synth_pcm(k) for k in range(4)])
+    alone, enc_alone = [], []
+    for k in range(4):
+        h1.logmel_array(np.ascontiguousarray(clips[k:k + 1])); h1.encode()
+        alone.extend(h1.decode_greedy())
+        enc_alone.append(h1.encoder_output(0))
+    for row0, first, n in ((0, 0, 1), (1, 1, 2), (1, 3, 1)):
+        hm.logmel_array_rows(np.ascontiguousarray(clips[first:first + n]), row0)
+        hm.encode_rows(row0, n)
+    assert hm.batch == 3
+    joint = hm.decode_greedy()
+    assert len(joint) == 3
+    for row, clip in enumerate((0, 3, 2)):
+        a, b = joint[row], alone[clip]
+        assert a["tokens"] == b["tokens"] == [tk.sot, tk.en, tk.transcribe] + script
+        assert a["avg_logprob"] == b["avg_logprob"] and a["no_speech_prob"] == b["no_speech_prob"]
+        assert np.array_equal(hm.encoder_output(row), enc_alone[clip])
+    assert not np.array_equal(enc_alone[1], enc_alone[3])   # row 1 does hold the refill, not what it held before
+    # the same shadow under a pool: its rows, then the staging rows above them
+    hm.pool_begin(1)
+    assert hm.batch == 1
+    hm.logmel_array_rows(np.ascontiguousarray(clips[1:3]), 1)
+    assert hm.batch == 3
+    hm.logmel_array_rows(np.ascontiguousarray(clips[3:4]), 1)
+    assert hm.batch == 3
+    hm.close(); h1.close()
