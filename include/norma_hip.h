@@ -43,6 +43,8 @@
  *   nh_set_prompts, nh_decoder_forward_onepass
  *                                 (no counterpart: every reference decode starts from [sot, lang?, task], model.rs:285-289)
  *                                 tokens in front of the prompt, consumed in one pass
+ *   nh_pool_prefix                the same per row of a decode pool, every row its own length, one ragged pass: declared in
+ *                                 norma_hip_pool.h
  */
 #ifndef NORMA_HIP_H
 #define NORMA_HIP_H
@@ -361,6 +363,7 @@ int nh_pool_collect(nh_ctx *ctx, const int32_t *rows, int n, int32_t *out_tokens
  * clip - clip0, whatever the other rows of the pool do meanwhile.  Refused (NH_ERR_INVALID / NH_ERR_STATE, nothing is
  * launched): no pool, row out of range, row busy, row never admitted since nh_pool_begin, temperature <= 0 or not finite. */
 int nh_pool_retry(nh_ctx *ctx, int row, float temperature, uint64_t seed, uint32_t clip, uint32_t attempt);
+/* A prompt prefix per pool row, every row its own length (nh_pool_prefix): include/norma_hip_pool.h, which includes this header. */
 /* Language detection inside the pool.  Model::detect_language (model.rs:194-210) is one decoder forward on [sot] and a softmax
  * over the language-token logits; the first step of a pooled row is that forward (position 0 consumes sot against the clip's
  * cross K/V), and the language token is first consumed one step later.  So a row admitted with lang = NH_LANG_DETECT detects

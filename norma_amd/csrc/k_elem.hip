@@ -78,6 +78,15 @@ void launch_layernorm(const float *x, const float *w, const float *b, half_t *y,
 }
 
 // TextDecoder::forward input: token_embedding(x) + positional_embedding[0..T]  
+__device__ __forceinline__ void embed_row(const half_t *__restrict__ e, const half_t *__restrict__ p, float *__restrict__ xr, int d) {
+    for (int c = threadIdx.x * 4; c < d; c += 256 * 4) {
+        half4 ev = *reinterpret_cast<const half4 *>(e + c), pv = *reinterpret_cast<const half4 *>(p + c);
+        f32x4 o = {(float)ev[0] + (float)pv[0], (float)ev[1] + (float)pv[1], (float)ev[2] + (float)pv[2],
+                   (float)ev[3] + (float)pv[3]};
+        *reinterpret_cast<f32x4 *>(xr + c) = o;
+    }
+}
+
 __global__ __launch_bounds__(256) void embed_kernel(const int32_t *__restrict__ tokens, int tok_stride,
                                                     const half_t *__restrict__ E, const half_t *__restrict__ P,
                                                     float *__restrict__ x, int Tn, int t0,
@@ -86,16 +95,26 @@ __global__ __launch_bounds__(256) void embed_kernel(const int32_t *__restrict__ 
     const int b = r / Tn, i = r - b * Tn;
     if (pos_ptr) t0 = pos_ptr[b];  // per-sequence position
     const int tok = tokens[(long)b * tok_stride + t0 + i];
-    const half_t *e = E + (long)tok * d, *p = P + (long)(t0 + i) * d;
-    for (int c = threadIdx.x * 4; c < d; c += 256 * 4) {
-        half4 ev = *reinterpret_cast<const half4 *>(e + c), pv = *reinterpret_cast<const half4 *>(p + c);
-        f32x4 o = {(float)ev[0] + (float)pv[0], (float)ev[1] + (float)pv[1], (float)ev[2] + (float)pv[2],
-                   (float)ev[3] + (float)pv[3]};
-        *reinterpret_cast<f32x4 *>(x + (long)r * d + c) = o;
-    }
+    embed_row(E + (long)tok * d, P + (long)(t0 + i) * d, x + (long)r * d, d);
+}
+
+// the ragged rows of the one-pass forward: workgroup (i, z) is position i of clip z of the table, where the clip has one
+__global__ __launch_bounds__(256) void embed_ragged_kernel(const int32_t *__restrict__ tokens, int tok_stride,
+                                                           const half_t *__restrict__ E, const half_t *__restrict__ P,
+                                                           float *__restrict__ x, const PfClip *__restrict__ clips, int d) {
+    const PfClip c = clips[blockIdx.y];
+    const int i = blockIdx.x;
+    if (i >= c.T) return;
+    const int tok = tokens[(long)c.row * tok_stride + i];
+    embed_row(E + (long)tok * d, P + (long)i * d, x + ((long)c.off + i) * d, d);
 }
 
 void launch_embed(const int32_t *tokens, int tok_stride, const half_t *E, const half_t *P, float *x, int B,
                   int Tn, int t0, const int32_t *pos_ptr, int d, hipStream_t st) {
     hipLaunchKernelGGL(embed_kernel, dim3(B * Tn), dim3(256), 0, st, tokens, tok_stride, E, P, x, Tn, t0, pos_ptr, d);
+}
+
+void launch_embed_ragged(const int32_t *tokens, int tok_stride, const half_t *E, const half_t *P, float *x, const PfClip *clips, int n,
+                         int Tmax, int d, hipStream_t st) {
+    hipLaunchKernelGGL(embed_ragged_kernel, dim3(Tmax, n), dim3(256), 0, st, tokens, tok_stride, E, P, x, clips, d);
 }

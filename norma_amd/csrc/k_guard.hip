@@ -13,7 +13,7 @@ static_assert(GUARD_THREADS == 256 && NH_GUARD_MAX_PERIOD * 4 == GUARD_THREADS, 
 
 __global__ __launch_bounds__(GUARD_THREADS) void guard_kernel(float *__restrict__ logits, int V, int ldl, DecodeState s, RuleTokens tk,
                                                               int ctx, int prompt_len, const int32_t *__restrict__ pos, GuardSpec g,
-                                                              GuardBufs gb) {
+                                                              GuardBufs gb, const int32_t *__restrict__ pfx) {
     // h[m .. m + 3] is padding for the 16-byte reads of stage 1
     __shared__ __attribute__((aligned(16))) int32_t h[NH_GUARD_MAX_HISTORY + 4];
     __shared__ int wave_cnt[GUARD_THREADS / 64];
@@ -21,6 +21,7 @@ __global__ __launch_bounds__(GUARD_THREADS) void guard_kernel(float *__restrict_
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     // everything up to the first barrier is the same in every thread: whole workgroups leave
     if (s.done[b]) return;
+    if (pos && pfx) prompt_len += pfx[b];         // decode pool: the row's prefix (nh_pool_prefix) is part of its physical prompt
     if (pos && pos[b] < prompt_len - 1) return;   // decode pool: the row is at its probe or inside its prompt
     const int n = s.n_tokens[b];
     if (n < prompt_len) return;
@@ -126,6 +127,6 @@ __global__ __launch_bounds__(GUARD_THREADS) void guard_kernel(float *__restrict_
 }
 
 void launch_guard(float *logits, int V, DecodeState s, RuleTokens tk, int R, int ctx, int prompt_len, const int32_t *pos, GuardSpec g,
-                  GuardBufs gb, hipStream_t st) {
-    hipLaunchKernelGGL(guard_kernel, dim3(R), dim3(GUARD_THREADS), 0, st, logits, V, nh_logits_ld(V), s, tk, ctx, prompt_len, pos, g, gb);
+                  GuardBufs gb, hipStream_t st, const int32_t *pfx) {
+    hipLaunchKernelGGL(guard_kernel, dim3(R), dim3(GUARD_THREADS), 0, st, logits, V, nh_logits_ld(V), s, tk, ctx, prompt_len, pos, g, gb, pfx);
 }

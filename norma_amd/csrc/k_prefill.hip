@@ -21,6 +21,11 @@
 //                                 up to the order of the 32 keys inside a k-step, and the V^T fragment is read in that order
 // and at the end O / l in f32, rounded once to fp16.  Everything a query's result depends on -- its clip's rows, the order
 // of the key blocks, the reduction trees -- is fixed by its position alone: bit-identical whatever the batch around the clip.
+// The ragged form (PrefillAttn::clips; a decode pool's prefixes, nh_pool_prefix): clip z of the launch has its own length, its
+// rows packed at its own offset, and its caches in its own context row, all read from a table; grid x covers the longest clip
+// and a workgroup past its clip's last query leaves before its first barrier.  The uniform form is the same kernel with no
+// table: length T, offset z * T, row z.  Nothing above looks at the grid or at the block size except the staging loops, which
+// only move data: a clip's bits are the same in either form, whatever is packed around it.
 // The kernel feeds MFMAs from LDS, so it takes its CU's whole LDS (nh_kernels.h, "kernels that do not share their CU's LDS").
 #include "nh_kernels.h"
 
@@ -32,12 +37,13 @@
 #define PF_LDS_BYTES (PF_LDS_K + NH_DH * PF_VT_LD * 2)
 
 struct PrefillAttn {
-    const half_t *q; long ldq;                  // query of (clip b, position i, head h) at q + (b * T + i) * ldq + 64 h
-    const half_t *k, *v;                        // key j of (b, h) at k + b * kv_clip + h * kv_head + j * kv_key (64 halfs)
-    long kv_clip, kv_head, kv_key;
+    const half_t *q; long ldq;                  // query of (clip b, position i, head h) at q + (off_b + i) * ldq + 64 h, off_b = b * T
+    const half_t *k, *v;                        // key j of (b, h): causal -- the packed rows, k + (off_b + j) * kv_key + h * kv_head;
+    long kv_clip, kv_head, kv_key;              //   cross -- k + row_b * kv_clip + h * kv_head + j * kv_key (64 halfs), row_b = b
     half_t *out; long ldo;                      // like q
     int T, nk;                                  // queries per clip; keys per clip (the causal form: T)
-    half_t *ck, *cv; int C;                     // the causal form: self cache [b][h][C][64], slots 0 .. T-1 are written
+    half_t *ck, *cv; int C;                     // the causal form: self cache [row_b][h][C][64], slots 0 .. T-1 are written
+    const PfClip *clips;                        // ragged: (row_b, T_b, off_b) of clip b = blockIdx.z; nullptr: uniform, as above
 };
 
 template <bool CAUSAL>
@@ -48,18 +54,25 @@ __global__ __launch_bounds__(64 * PF_MAX_WAVES) void prefill_attn_kernel(Prefill
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
     const int h = blockIdx.y, b = blockIdx.z, H = gridDim.y;
     const int q0 = blockIdx.x * (PF_QW * PF_MAX_WAVES);           // first query of the workgroup
+    int T = p.T, crow = b;                                        // the clip's queries, its context row (caches),
+    long off = (long)b * p.T;                                     // and the packed row of its position 0
+    if (p.clips) {
+        const PfClip c = p.clips[b];
+        T = c.T; crow = c.row; off = c.off;
+        if (q0 >= T) return;                                      // the grid covers the longest clip: nothing here for a shorter one
+    }
     const int nwaves = blockDim.x >> 6;
     const int wq0 = q0 + wave * PF_QW;                            // first query of the wave
-    const bool active = wq0 < p.T;                                // waves past the clip's last query only help staging
+    const bool active = wq0 < T;                                  // waves past the clip's last query only help staging
     // keys the workgroup needs: causal -- up to its last query; cross -- all
-    const int wg_last_q = min(p.T, q0 + nwaves * PF_QW) - 1;
+    const int wg_last_q = min(T, q0 + nwaves * PF_QW) - 1;
     const int nkeys = CAUSAL ? wg_last_q + 1 : p.nk;
-    const bool writer = CAUSAL && blockIdx.x == gridDim.x - 1;    // stages every key of the clip: it fills the self cache
-    const int myq = min(wq0 + fr, p.T - 1);                       // rows past the clip's last are clamped (computed, never stored)
-    const half_t *qp = p.q + ((long)b * p.T + myq) * p.ldq + h * NH_DH + 8 * fq;
+    const bool writer = CAUSAL && q0 + PF_QW * PF_MAX_WAVES >= T; // the clip's own last tile stages every key of the clip: it fills the self cache
+    const int myq = min(wq0 + fr, T - 1);                         // rows past the clip's last are clamped (computed, never stored)
+    const half_t *qp = p.q + (off + myq) * p.ldq + h * NH_DH + 8 * fq;
     const half8 qf0 = *reinterpret_cast<const half8 *>(qp), qf1 = *reinterpret_cast<const half8 *>(qp + 32);
-    const half_t *kb = p.k + (long)b * p.kv_clip + (long)h * p.kv_head;
-    const half_t *vb = p.v + (long)b * p.kv_clip + (long)h * p.kv_head;
+    const long kv0 = (CAUSAL ? off * p.kv_key : (long)crow * p.kv_clip) + (long)h * p.kv_head;
+    const half_t *kb = p.k + kv0, *vb = p.v + kv0;
     const float ninf = -INFINITY;
     float m = ninf, l = 0.f;
     f32x4 o[4];
@@ -75,8 +88,8 @@ __global__ __launch_bounds__(64 * PF_MAX_WAVES) void prefill_attn_kernel(Prefill
             *reinterpret_cast<half8 *>(lk + key * 128 + ((c ^ ((key >> 1) & 7)) << 4)) = kk;
 #pragma unroll
             for (int j = 0; j < 8; j++) lvt[(8 * c + j) * PF_VT_LD + key] = vv[j];
-            if (writer && kg < p.T) {
-                const long dst = (((long)b * H + h) * p.C + kg) * NH_DH + 8 * c;
+            if (writer && kg < T) {
+                const long dst = (((long)crow * H + h) * p.C + kg) * NH_DH + 8 * c;
                 *reinterpret_cast<half8 *>(p.ck + dst) = kk;
                 *reinterpret_cast<half8 *>(p.cv + dst) = vv;
             }
@@ -139,9 +152,9 @@ __global__ __launch_bounds__(64 * PF_MAX_WAVES) void prefill_attn_kernel(Prefill
     l += __shfl_xor(l, 16);
     l += __shfl_xor(l, 32);
     const int qrow = wq0 + fr;
-    if (qrow >= p.T) return;
+    if (qrow >= T) return;
     const float inv = 1.0f / l;
-    half_t *op = p.out + ((long)b * p.T + qrow) * p.ldo + h * NH_DH + 4 * fq;
+    half_t *op = p.out + (off + qrow) * p.ldo + h * NH_DH + 4 * fq;
 #pragma unroll
     for (int dt = 0; dt < 4; dt++) {
         // o[dt][r]: dim 16 dt + 4 fq + r of query qrow
@@ -163,17 +176,17 @@ static bool prefill_attn_launch(bool causal, const PrefillAttn &p, int B, int H,
 }
 
 bool launch_prefill_self_attention(const half_t *q, const half_t *k, const half_t *v, long ld, half_t *out, long ldo, half_t *ck,
-                                   half_t *cv, int B, int T, int H, int C, hipStream_t st) {
+                                   half_t *cv, int B, int T, int H, int C, hipStream_t st, const PfClip *clips) {
     PrefillAttn p{};
     p.q = q; p.ldq = ld; p.k = k; p.v = v; p.kv_clip = (long)T * ld; p.kv_head = NH_DH; p.kv_key = ld;
-    p.out = out; p.ldo = ldo; p.T = T; p.nk = T; p.ck = ck; p.cv = cv; p.C = C;
+    p.out = out; p.ldo = ldo; p.T = T; p.nk = T; p.ck = ck; p.cv = cv; p.C = C; p.clips = clips;
     return prefill_attn_launch(true, p, B, H, st);
 }
 
 bool launch_prefill_cross_attention(const half_t *q, long ldq, const half_t *ck, const half_t *cv, half_t *out, long ldo, int B, int T,
-                                    int H, int S, hipStream_t st) {
+                                    int H, int S, hipStream_t st, const PfClip *clips) {
     PrefillAttn p{};
     p.q = q; p.ldq = ldq; p.k = ck; p.v = cv; p.kv_clip = (long)H * S * NH_DH; p.kv_head = (long)S * NH_DH; p.kv_key = NH_DH;
-    p.out = out; p.ldo = ldo; p.T = T; p.nk = S; p.C = 0;
+    p.out = out; p.ldo = ldo; p.T = T; p.nk = S; p.C = 0; p.clips = clips;
     return prefill_attn_launch(false, p, B, H, st);
 }

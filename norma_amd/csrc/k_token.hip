@@ -205,10 +205,11 @@ void launch_sample_step(const float *logits, int V, DecodeState s, RuleTokens tk
 // kernels never decide that through pos[b], which one of them has moved by then.
 __global__ __launch_bounds__(1024) void pool_sample_step_kernel(const float *__restrict__ logits, int V, int ldl, DecodeState s,
                                                                 RuleTokens tk, int ctx, int cap, int max_new, int prompt_len,
-                                                                PoolSampling ps, int32_t *pos) {
+                                                                PoolSampling ps, int32_t *pos, const int32_t *pfx) {
     __shared__ SampleShared sh;
     const int b = blockIdx.x, tid = threadIdx.x;
     const float inv_t = ps.inv_t[b];
+    if (pfx) prompt_len += pfx[b];   // nh_pool_prefix: the row's physical prompt
     const int my_pos = pos[b];  // read by every thread ahead of the first barrier; thread 0 moves it after the last
     const bool mine = inv_t > 0.f && !s.done[b] && my_pos >= prompt_len - 1;
     if (tid == 0) ps.handled[b] = mine ? 1 : 0;
@@ -244,9 +245,9 @@ __global__ __launch_bounds__(1024) void pool_sample_step_kernel(const float *__r
 }
 
 void launch_pool_sample_step(const float *logits, int V, DecodeState s, RuleTokens tk, int B, int ctx, int cap, int max_new,
-                             int prompt_len, PoolSampling ps, int32_t *pos, hipStream_t st) {
+                             int prompt_len, PoolSampling ps, int32_t *pos, hipStream_t st, const int32_t *pfx) {
     hipLaunchKernelGGL(pool_sample_step_kernel, dim3(B), dim3(1024), 0, st, logits, V, nh_logits_ld(V), s, tk, ctx, cap, max_new, prompt_len,
-                       ps, pos);
+                       ps, pos, pfx);
 }
 
 // parity view of the sampler: rules + one draw on an already soft-maxed probability vector
@@ -295,7 +296,7 @@ __device__ __forceinline__ void merge_ms(float &m, float &s, float &ts, float m2
 __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict__ logits, int V, int ldl,
                                                          DecodeState s, RuleTokens tk, int ctx, int cap, int max_new,
                                                          int prompt_len, int mode, float *partials, unsigned *tickets,
-                                                         int32_t *pos_ptr, const int32_t *handled) {
+                                                         int32_t *pos_ptr, const int32_t *handled, const int32_t *pfx) {
     __shared__ float sh_f[4][6];
     __shared__ int sh_i[4][2];
     __shared__ int sh_last;
@@ -322,11 +323,14 @@ __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict
     const float l_nt = lg[tk.no_timestamps];           // no_timestamps is text to supress_past_timestamps only (see below)
     const int sup_nt = s.suppress[tk.no_timestamps];
     const int taken = handled ? handled[b] : 0;  // decode pool: pool_sample_step_kernel generated this sequence's token in this step
+    const int npfx = pfx ? pfx[b] : 0;           // decode pool: the row's prefix (nh_pool_prefix); lockstep launches pass no array
     if (done || taken) return;                   // (all LSPLIT workgroups leave before any takes a ticket)
-    // mode 2 (decode pool): sequences join a running decode, so each is in its own phase -- position 0 of its prompt is the
-    // no-speech probe, the other prompt positions only feed the caches (their next token is given), then it generates
+    // mode 2 (decode pool): sequences join a running decode, so each is in its own phase -- the position of sot (0, or behind the
+    // row's prefix) is the no-speech probe, the other prompt positions, and those of a prefix that goes through the steps, only
+    // feed the caches (their next token is given), then it generates
     if (mode == 2) {
-        mode = my_pos == 0 ? 0 : (my_pos < prompt_len - 1 ? 3 : 1);
+        prompt_len += npfx;
+        mode = my_pos == npfx ? 0 : (my_pos < prompt_len - 1 ? 3 : 1);
         if (mode == 3) {  // the position moves only when all LSPLIT workgroups of the sequence have read it: same ticket as below
             if (tid == 0 && __hip_atomic_fetch_add(tickets + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == LSPLIT - 1) {
                 __hip_atomic_store(tickets + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -457,44 +461,54 @@ __global__ __launch_bounds__(256) void logit_step_kernel(const float *__restrict
 
 void launch_logit_step(const float *logits, int V, DecodeState s, RuleTokens tk, int B, int ctx, int cap,
                        int max_new, int prompt_len, int mode, float *partials, unsigned *tickets, int32_t *pos_ptr,
-                       hipStream_t st, const int32_t *handled) {
+                       hipStream_t st, const int32_t *handled, const int32_t *pfx) {
     hipLaunchKernelGGL(logit_step_kernel, dim3(LSPLIT, B), dim3(256), 0, st, logits, V, nh_logits_ld(V), s, tk, ctx, cap, max_new,
-                       prompt_len, mode, partials, tickets, pos_ptr, handled);
+                       prompt_len, mode, partials, tickets, pos_ptr, handled, mode == 2 ? pfx : nullptr);
 }
 
-// decode pool: what admission and retry both clear -- row `row` stands at position 0 with its P prompt tokens and no history
-__device__ __forceinline__ void pool_row_reset(const DecodeState &s, int32_t *pos, unsigned *tickets, int row, int P) {
-    s.n_tokens[row] = P; s.done[row] = 0; s.have_last[row] = 0; s.last_ts[row] = 0;
+// decode pool: what admission and retry both clear -- row `row` stands at position pos0 with its n prefix and P prompt tokens
+// and no history
+__device__ __forceinline__ void pool_row_reset(const DecodeState &s, int32_t *pos, unsigned *tickets, int row, int P, int n, int pos0) {
+    s.n_tokens[row] = n + P; s.done[row] = 0; s.have_last[row] = 0; s.last_ts[row] = 0;
     s.sum_logprob[row] = 0.0; s.no_speech[row] = 0.0;
-    pos[row] = 0; tickets[row] = 0u;
+    pos[row] = pos0; tickets[row] = 0u;
 }
 
-// decode pool: sequence `row` starts over with the prompt [t0, t1, (t2)] (model.rs:285-289) at position 0.  detect_flag
-// (i32 [B] or null): whether the row detects its language in its first step (t1 is a placeholder until then).
+// decode pool: sequence `row` starts over with the prompt [t0, t1, (t2)] (model.rs:285-289), at position 0 unless pfx says otherwise.  detect_flag
+// (i32 [B] or null): whether the row detects its language in its first step (t1 is a placeholder until then).  pfx (i32 [B] or
+// null; nh_pool_prefix): the row's prefix length n_prefix is recorded there, the prompt sits behind the n_prefix ids (which
+// the caller copies into the row) and the row starts at pos0: 0, or n_prefix when one pass consumes the prefix.
 __global__ void pool_admit_kernel(DecodeState s, int32_t *pos, unsigned *tickets, int row, int ctx, int t0, int t1, int t2, int P,
-                                  int32_t *detect_flag, int detect) {
-    int32_t *t = s.tokens + (long)row * ctx;
+                                  int32_t *detect_flag, int detect, int32_t *pfx, int n_prefix, int pos0) {
+    int32_t *t = s.tokens + (long)row * ctx + n_prefix;
     t[0] = t0; t[1] = t1; if (P == 3) t[2] = t2;
-    pool_row_reset(s, pos, tickets, row, P);
+    pool_row_reset(s, pos, tickets, row, P, n_prefix, pos0);
     if (detect_flag) detect_flag[row] = detect;
+    if (pfx) pfx[row] = n_prefix;
 }
 void launch_pool_admit(DecodeState s, int32_t *pos, unsigned *tickets, int row, int ctx, int t0, int t1, int t2, int P, hipStream_t st,
-                       int32_t *detect_flag, int detect) {
-    hipLaunchKernelGGL(pool_admit_kernel, dim3(1), dim3(1), 0, st, s, pos, tickets, row, ctx, t0, t1, t2, P, detect_flag, detect);
+                       int32_t *detect_flag, int detect, int32_t *pfx, int n_prefix, int pos0) {
+    if (!pfx) n_prefix = pos0 = 0;
+    hipLaunchKernelGGL(pool_admit_kernel, dim3(1), dim3(1), 0, st, s, pos, tickets, row, ctx, t0, t1, t2, P, detect_flag, detect, pfx,
+                       n_prefix, pos0);
 }
 
 // decode pool: sequence `row` decodes the clip it holds once more, sampled.  The prompt tokens [0, P) are still in place
 // (generation writes from P on; the trimming of finish_sequence works on the host copy), so is the clip's cross K/V.
 // A language the row detected in its t = 0 attempt is one of those prompt tokens: the retry does not detect again.
+// Under a prefix (pfx[row] = n > 0) the row restarts at position n: the self K/V of positions 0 .. n-1 are still in its cache,
+// whichever route wrote them, because generation wrote only from n on.
 __global__ void pool_retry_kernel(DecodeState s, int32_t *pos, unsigned *tickets, PoolSampling ps, int row, int P, float inv_t,
-                                  unsigned long long seed, unsigned clip, unsigned attempt, int32_t *detect_flag) {
-    pool_row_reset(s, pos, tickets, row, P);
+                                  unsigned long long seed, unsigned clip, unsigned attempt, int32_t *detect_flag, const int32_t *pfx) {
+    const int n = pfx ? pfx[row] : 0;
+    pool_row_reset(s, pos, tickets, row, P, n, n);
     ps.inv_t[row] = inv_t; ps.seed[row] = seed; ps.clip[row] = clip; ps.attempt[row] = attempt;
     if (detect_flag) detect_flag[row] = 0;
 }
 void launch_pool_retry(DecodeState s, int32_t *pos, unsigned *tickets, PoolSampling ps, int row, int P, float inv_t,
-                       unsigned long long seed, unsigned clip, unsigned attempt, hipStream_t st, int32_t *detect_flag) {
-    hipLaunchKernelGGL(pool_retry_kernel, dim3(1), dim3(1), 0, st, s, pos, tickets, ps, row, P, inv_t, seed, clip, attempt, detect_flag);
+                       unsigned long long seed, unsigned clip, unsigned attempt, hipStream_t st, int32_t *detect_flag,
+                       const int32_t *pfx) {
+    hipLaunchKernelGGL(pool_retry_kernel, dim3(1), dim3(1), 0, st, s, pos, tickets, ps, row, P, inv_t, seed, clip, attempt, detect_flag, pfx);
 }
 
 // Model::detect_language (model.rs:194-210) on the position-0 logits of a [sot] prompt: softmax over the language

@@ -193,6 +193,7 @@ extern "C" int nh_align_decoded(nh_ctx *ctx, const int32_t *rows, int n, const i
             const PoolRow &r = ctx->pool.row[rows[i]];
             if (r.busy) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: that row is busy (nh_pool_collect hands it back first)");
             if (!r.held) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: no clip was admitted into that row since nh_pool_begin");
+            if (r.pfx > 0) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: that row's last decode had a prefix (nh_pool_prefix): the kept queries sit at physical positions");
             if (r.align_gen != lv.gen) return ctx->fail(NH_ERR_STATE, "nh_align_decoded: that row has not been collected since it was admitted or retried under the current alignment heads");
             nt = r.n; done = r.done;
         } else { nt = lv.n[i]; done = lv.done[i]; }

@@ -20,7 +20,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/norma_hip.h"
+#include "../../include/norma_hip_pool.h"   // ... which includes norma_hip.h
 #include "nh_kernels.h"
 
 #define HIPCHK(expr)                                                                          \
@@ -94,6 +94,7 @@ struct PoolRow {   // one row of a decode pool, as the host knows it
     bool inv_t_set = false;  // the row's device-side inv_t is > 0 (its last decode was a retry): the next admit zeroes it
     bool detect = false;     // the row's clip was admitted with NH_LANG_DETECT; an admit sets or clears it
     bool detected = false;   // ... and has taken a step since: d_lang_out / d_lang_probs hold its language
+    int pfx = 0;             // prefix length of the clip the row holds (nh_pool_prefix; the device side is nh_ctx::d_pfx)
     // what nh_pool_collect last read off the row (nh_align_decoded): tokens after finish_sequence's trim, the done flag, and
     // the alignment generation its queries were kept under (-1: none; an admit or a retry clears it)
     int n = 0, done = 0, align_gen = -1;
@@ -104,6 +105,10 @@ struct Pool {
     int lang_n = 0;          // entries of the pool's language table in d_lang_tokens (nh_pool_detect_languages); 0: none
     bool per_clip_language = false;
     std::vector<PoolRow> row;
+    // nh_pool_prefix: pending[r] ids wait in pfx_host row r for the next admission into row r (0: none); todo: the rows admitted
+    // on the one-pass route since the last ragged prefill, which the head of the next nh_pool_step that runs steps issues
+    std::vector<int> pending;
+    std::vector<PfClip> todo;
 };
 
 // Everything a captured decode step takes by value (batch, encoder length, max_new_tokens, prompt length, the rule token ids,
@@ -296,6 +301,15 @@ struct nh_ctx {
     Pool pool;                       // decode pool (nh_pool_*)
     PoolSampling psamp{};            // [max_batch] each: per-row temperature, seed, clip, attempt, and the step's handled flags
     int32_t *d_lang_flag = nullptr;  // [max_batch] device side of PoolRow::detect, cleared by a retry (the token is in the prompt by then)
+    // nh_pool_prefix.  d_pfx: [max_batch] device side of PoolRow::pfx, which the pool-mode selection kernels and the guard read
+    // through the pointer (zero at creation and at nh_pool_begin; the admit kernel writes a row's).  d_pfclips: [max_batch] the
+    // clip table of a ragged one-pass forward.  pfx_host: pinned, [max_batch][max_target_positions / 2] pending ids, then
+    // max_batch PfClip: the host side of the two async copies (ids at an admission, the table at a prefill); a row's ids are
+    // rewritten only while the row is free and the table only by nh_pool_step, both behind a drained stream.  Made by the
+    // first nh_pool_prefix: a context that never takes a prefix holds no host buffer.
+    int32_t *d_pfx = nullptr;
+    PfClip *d_pfclips = nullptr;
+    int32_t *pfx_host = nullptr;
     // [0]: greedy steps, lockstep or pool; [1]: pool steps with at least one sampled row busy (pool_sample_step_kernel ahead of
     // logit_step_kernel).  Kept side by side, so a pool that goes back and forth between the two states captures each once.
     StepGraphs graphs[2];
@@ -398,7 +412,10 @@ bool prefill_supported(const nh_ctx *ctx);
 // 0.17 / 0.36 / 0.73 ms stepwise at 1 / 2 / 4 tokens (tools/dbg/prompt_cost.py, profiles/prompt_cost.json): the crossover
 // lies between 2 and 4.
 #define NH_PREFILL_MIN_PREFIX 4
-int prefill_forward(nh_ctx *ctx, int T, float *hidden, bool keep_rows = false);
+// The ragged form (clips != nullptr: n host entries, rows and lengths; the offsets are filled in here): the given context rows,
+// clip i over its own positions 0 .. T_i - 1, packed; T is ignored, hidden and keep_rows are not offered.  The table goes up
+// in one copy from pfx_host.  A decode pool's prefixes (nh_pool_step).
+int prefill_forward(nh_ctx *ctx, int T, float *hidden, bool keep_rows = false, PfClip *clips = nullptr, int n = 0);
 inline void clear_prompt(nh_ctx *ctx) { ctx->prompt.clear(); ctx->n_prefix = 0; ctx->prompt_batch = 0; }
 // nh_encode.hip: may `batch` clips of these lengths become rows row0 .. of the context's mel batch?  Row range, clip lengths,
 // equal mel frames, the pool and row-gap rules.  Changes nothing in the context: every entry point that fills PCM rows

@@ -135,7 +135,9 @@ static int read_results(nh_ctx *ctx, const int32_t *rows, int n, int32_t *out_to
     if (!rows) { ctx->live.n.assign(n, 0); ctx->live.done.assign(n, 0); }
     for (int i = 0; i < n; i++) {
         const int b = rows ? rows[i] : i;
-        finish_sequence(ctx, h.toks.data() + (size_t)i * C, h.nt[b], h.done[b], h.slp[b], h.nsp[b], out_tokens + (size_t)i * C, results[i], skip);
+        // a pool row's skip is its own prefix (nh_pool_prefix)
+        finish_sequence(ctx, h.toks.data() + (size_t)i * C, h.nt[b], h.done[b], h.slp[b], h.nsp[b], out_tokens + (size_t)i * C, results[i],
+                        rows ? ctx->pool.row[b].pfx : skip);
         // what nh_align_decoded aligns: the sequence as returned
         if (rows) { PoolRow &r = ctx->pool.row[b]; r.n = results[i].n_tokens; r.done = h.done[b]; }
         else { ctx->live.n[i] = results[i].n_tokens; ctx->live.done[i] = h.done[b]; }
@@ -163,15 +165,16 @@ static void emit_token_step(nh_ctx *ctx, const StepSpec &s) {
     logits_from_dx(ctx, s.B);
     if (pool && ctx->pool.lang_n > 0)
         launch_pool_lang_detect(ctx->logits, V, ctx->ds, s.B, C, s.pos_ptr, PoolDetect{ctx->d_lang_flag, ctx->d_lang_tokens, ctx->pool.lang_n, ctx->d_lang_out, ctx->d_lang_probs}, ctx->st);
+    const int32_t *pfx = pool ? ctx->d_pfx : nullptr;   // a pool's per-row prefix lengths: the pointer, so a prefix never recaptures
     if (ctx->guard.on) emit_guard(ctx, s.B, s.P, pool ? s.pos_ptr : nullptr, s.B);   // nh_set_guard; off: nothing is launched
     if (s.sampled && !pool) {  // lockstep sampled: every sequence draws its token
         launch_sample_step(ctx->logits, V, ctx->ds, ctx->tk, s.B, C, cap, s.max_new, s.P, s.inv_t, s.seed, s.clip0, s.attempt, ctx->st);
         return;
     }
     // greedy.  In a pool with a row on a sampled retry, the kernel of those rows goes first and tells the greedy one which it took.
-    if (s.sampled) launch_pool_sample_step(ctx->logits, V, ctx->ds, ctx->tk, s.B, C, cap, s.max_new, s.P, ctx->psamp, s.pos_ptr, ctx->st);
+    if (s.sampled) launch_pool_sample_step(ctx->logits, V, ctx->ds, ctx->tk, s.B, C, cap, s.max_new, s.P, ctx->psamp, s.pos_ptr, ctx->st, pfx);
     launch_logit_step(ctx->logits, V, ctx->ds, ctx->tk, s.B, C, cap, s.max_new, s.P, s.mode, ctx->lpart, ctx->ltick, s.pos_ptr, ctx->st,
-                      s.sampled ? ctx->psamp.handled : nullptr);
+                      s.sampled ? ctx->psamp.handled : nullptr, pfx);
 }
 
 // The graphs of `key`, captured unless the slot holds them already.  A key that the greedy slot does not hold drops both
@@ -359,10 +362,17 @@ extern "C" int nh_pool_begin(nh_ctx *ctx, int rows, int max_new_tokens, int per_
     for (int b = 0; b < rows; b++) ctx->h_done[128 + b] = 3;  // 3: empty row (skipped like a finished one)
     HIPCHK(hipMemcpyAsync(ctx->ds.done, ctx->h_done + 128, sizeof(int32_t) * rows, hipMemcpyHostToDevice, ctx->st));
     HIPCHK(hipMemsetAsync(ctx->d_pos, 0, sizeof(int32_t) * rows, ctx->st));
+    HIPCHK(hipMemsetAsync(ctx->d_pfx, 0, sizeof(int32_t) * ctx->B, ctx->st));   // no row has a prefix, none is pending (the fresh Pool)
     HIPCHK(hipMemsetAsync(ctx->ltick, 0, sizeof(unsigned) * rows, ctx->st));
     if (was_sampled) HIPCHK(hipMemsetAsync(ctx->psamp.inv_t, 0, sizeof(float) * ctx->B, ctx->st));  // rows an earlier pool left on a retry: greedy again
     HIPCHK(hipStreamSynchronize(ctx->st));
     return NH_OK;
+}
+
+// A row that is admitted again or handed back leaves the list of the next ragged prefill: the list never holds a row twice,
+// so it never outgrows the pool
+static void drop_pending_prefill(Pool &pl, int row) {
+    pl.todo.erase(std::remove_if(pl.todo.begin(), pl.todo.end(), [row](const PfClip &c) { return c.row == row; }), pl.todo.end());
 }
 
 static int pool_admit_impl(nh_ctx *ctx, nh_ctx *src, int src_row, int dst_row, int32_t lang) {
@@ -375,6 +385,11 @@ static int pool_admit_impl(nh_ctx *ctx, nh_ctx *src, int src_row, int dst_row, i
     // a detecting row holds sot in slot 1 until its first step has written the language there; nothing reads the slot before
     int32_t lg = detect ? ctx->tk.sot : lang >= 0 ? lang : ctx->tk.lang;
     if (P == 3 && (lg < 0 || lg >= ctx->c.vocab_size)) return ctx->fail(NH_ERR_INVALID, "nh_pool_admit: language token outside the vocabulary");
+    // nh_pool_prefix: the ids this admission consumes.  Every refusal above and this one leave them pending.
+    const int NP = ctx->pool.pending.empty() ? 0 : ctx->pool.pending[dst_row];
+    if (NP > 0 && detect) return ctx->fail(NH_ERR_INVALID, "nh_pool_admit: NH_LANG_DETECT into a row with a pending prefix (the probe step behind a prefix is not nh_detect_language's forward)");
+    // the route: one ragged pass at the head of the next nh_pool_step, or the pool's own steps from position 0
+    const bool onepass = NP >= NH_PREFILL_MIN_PREFIX && !ctx->opt_prompt_stepwise && prefill_supported(ctx);
     hipSetDevice(ctx->dev);
     const size_t per = (size_t)ctx->S * ctx->c.d_model;  // cross K / V of one clip and layer, head-major [h][S][64]
     if (src != ctx) HIPCHK(hipStreamWaitEvent(ctx->st, src->enc_done, 0));   // the other context's encoder ran on its own stream
@@ -389,9 +404,16 @@ static int pool_admit_impl(nh_ctx *ctx, nh_ctx *src, int src_row, int dst_row, i
         if (std::find(src->kv_readers.begin(), src->kv_readers.end(), ctx->kv_copied) == src->kv_readers.end()) src->kv_readers.push_back(ctx->kv_copied);
     }
     // model.rs:285-289: prompt = [sot, lang?, task]
-    launch_pool_admit(ctx->ds, ctx->d_pos, ctx->ltick, dst_row, ctx->c.max_target_positions, ctx->tk.sot, P == 3 ? lg : ctx->tk.task,
-                      ctx->tk.task, P, ctx->st, ctx->d_lang_flag, detect ? 1 : 0);
+    const int C = ctx->c.max_target_positions;
+    if (NP > 0)   // the ids, verbatim, in front of the prompt: one copy out of the context's pinned buffer
+        HIPCHK(hipMemcpyAsync(ctx->ds.tokens + (size_t)dst_row * C, ctx->pfx_host + (size_t)dst_row * (C / 2), sizeof(int32_t) * NP, hipMemcpyHostToDevice, ctx->st));
+    launch_pool_admit(ctx->ds, ctx->d_pos, ctx->ltick, dst_row, C, ctx->tk.sot, P == 3 ? lg : ctx->tk.task,
+                      ctx->tk.task, P, ctx->st, ctx->d_lang_flag, detect ? 1 : 0, ctx->d_pfx, NP, onepass ? NP : 0);
     HIPCHK(hipGetLastError());
+    if (NP > 0) ctx->pool.pending[dst_row] = 0;   // one-shot
+    drop_pending_prefill(ctx->pool, dst_row);   // the row names at most one clip of the next ragged pass: this one
+    if (onepass) ctx->pool.todo.push_back(PfClip{dst_row, NP, 0, 0});
+    row.pfx = NP;
     row.detect = detect; row.detected = false;
     if (row.inv_t_set) {  // an admitted row is greedy (a pool that never retried launches nothing here)
         HIPCHK(hipMemsetAsync(ctx->psamp.inv_t + dst_row, 0, sizeof(float), ctx->st));
@@ -403,7 +425,8 @@ static int pool_admit_impl(nh_ctx *ctx, nh_ctx *src, int src_row, int dst_row, i
 
 // The clip in `row` once more, sampled (the fallback of decode_with_fallback, model.rs:164-191, for one row of a pool): the row
 // restarts at position 0 on the cross K/V and the prompt it still holds -- nothing is copied, where an admission copies the
-// clip's cross K/V of every layer.
+// clip's cross K/V of every layer.  A row with a prefix of n ids restarts at position n, on the self K/V of positions 0 .. n-1
+// that its first decode left in the cache: nothing is computed again either.
 extern "C" int nh_pool_retry(nh_ctx *ctx, int row, float temperature, uint64_t seed, uint32_t clip, uint32_t attempt) {
     if (!ctx) return NH_ERR_INVALID;
     if (ctx->pool.rows < 1) return ctx->fail(NH_ERR_STATE, "nh_pool_retry: no decode pool (nh_pool_begin)");
@@ -414,7 +437,7 @@ extern "C" int nh_pool_retry(nh_ctx *ctx, int row, float temperature, uint64_t s
     if (!(temperature > 0.f && temperature < INFINITY)) return ctx->fail(NH_ERR_INVALID, "nh_pool_retry: temperature must be > 0 and finite (an admitted row decodes at t = 0)");
     hipSetDevice(ctx->dev);
     launch_pool_retry(ctx->ds, ctx->d_pos, ctx->ltick, ctx->psamp, row, ctx->pool.prompt, 1.0f / temperature, seed, clip, attempt, ctx->st,
-                      ctx->d_lang_flag);
+                      ctx->d_lang_flag, ctx->d_pfx);
     HIPCHK(hipGetLastError());
     r.busy = true; r.sampled = true; r.inv_t_set = true; r.align_gen = -1;
     return NH_OK;
@@ -450,6 +473,16 @@ extern "C" int nh_pool_step(nh_ctx *ctx, int n_steps, int32_t *done_out) {
     for (const PoolRow &r : pl.row) { any = any || r.busy; sampled = sampled || (r.busy && r.sampled); }
     if (any && n_steps > 0) {
         if (ctx->S < 1) return ctx->fail(NH_ERR_STATE, "nh_pool_step: rows are busy but nothing was ever encoded");
+        // the prefixes of the rows admitted since the last one, in ONE ragged pass: eager, ahead of the graph launches, and on
+        // this stream behind the admissions' copies of cross K/V and ids.  Those rows stand at their sot already.
+        if (!pl.todo.empty()) {
+            std::vector<PfClip> todo;
+            todo.swap(pl.todo);
+            if (int rc = prefill_forward(ctx, 0, nullptr, false, todo.data(), (int)todo.size())) {
+                pl.todo.swap(todo);   // refused before anything ran: the prefixes are still owed
+                return rc;
+            }
+        }
         const StepGraphs &g = ctx->graphs[sampled];
         for (int s = 0; ctx->opt_graphs && s <= (int)sampled; s++)   // the greedy pair also when this call replays the sampled one
             if (int rc = ensure_step_graphs(ctx, StepKey{B, ctx->S, pl.max_new, pl.prompt, ctx->token_gen, pl.lang_n, true, s == 1, ctx->live.gen, ctx->guard.gen})) return rc;
@@ -478,6 +511,7 @@ extern "C" int nh_pool_collect(nh_ctx *ctx, const int32_t *rows, int n, int32_t 
     hipSetDevice(ctx->dev);
     if (int rc = read_results(ctx, rows, n, out_tokens, results)) return rc;
     // heads cannot change while a row is busy (nh_align_capture refuses), so the whole decode ran under the current list
+    for (int i = 0; i < n; i++) drop_pending_prefill(ctx->pool, rows[i]);
     for (int i = 0; i < n; i++) { PoolRow &r = ctx->pool.row[rows[i]]; r.busy = false; r.sampled = false; r.align_gen = kept_heads(ctx) ? ctx->live.gen : -1; }
     return NH_OK;
 }

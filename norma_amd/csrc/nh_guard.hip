@@ -10,7 +10,7 @@ static GuardBufs guard_bufs(const nh_ctx *ctx, const int32_t *bias_map, int clip
 
 void emit_guard(nh_ctx *ctx, int R, int prompt_len, const int32_t *pos, int clips) {
     launch_guard(ctx->logits, ctx->c.vocab_size, ctx->ds, ctx->tk, R, ctx->c.max_target_positions, prompt_len, pos, ctx->guard.spec,
-                 guard_bufs(ctx, nullptr, clips), ctx->st);
+                 guard_bufs(ctx, nullptr, clips), ctx->st, pos && ctx->pool.rows > 0 ? ctx->d_pfx : nullptr);
 }
 
 // the flags, and with want_bias the bias table: made once, zeroed.  A table that appears is something the captured steps

@@ -210,6 +210,10 @@ void launch_layernorm(const float *x, const float *w, const float *b, half_t *y,
 // decoder input: x[(b*Tn+i)][:] = E[tokens[b*tok_stride + t0 + i]][:] + P[t0+i][:]
 void launch_embed(const int32_t *tokens, int tok_stride, const half_t *E, const half_t *P, float *x, int B,
                   int Tn, int t0, const int32_t *pos_ptr, int d, hipStream_t st);
+// the ragged rows of the one-pass forward (PfClip below; n clips, Tmax the longest): x[off_z + i][:] = E[tokens[row_z * tok_stride + i]][:] + P[i][:], i < T_z
+struct PfClip;
+void launch_embed_ragged(const int32_t *tokens, int tok_stride, const half_t *E, const half_t *P, float *x, const PfClip *clips, int n,
+                         int Tmax, int d, hipStream_t st);
 
 // ---- sample conversion (src/dtype.rs / dasp_sample): native capture samples -> f32 PCM -------------------------------
 #ifdef __HIPCC__
@@ -401,11 +405,16 @@ void launch_dec_attention(const half_t *q, const half_t *kc, const half_t *vc, h
 // q, k, v: fp16 [B*T][ld] as the qkv GEMM leaves them (head h at column 64 h); out fp16 [B*T][ldo].  Query i of a clip sees
 // the clip's keys 0 .. i; softmax(q . k / 8) in f32.  Also writes K and V of positions 0 .. T-1 into the head-major self
 // cache ck / cv [b][h][C][64].  false (nothing launched): a shape it does not cover (T < 1, T > C).
+// The ragged form (clips != nullptr, a device table of B entries): clip z has T_z <= T positions, its q / k / v / out rows
+// packed at rows off_z .. off_z + T_z - 1, and its caches -- the self cache written, the cross K/V read -- in context row row_z;
+// T is the largest T_z and sizes the grid.  The caller answers for the table: 1 <= T_z <= min(T, C), rows inside the caches,
+// offsets that keep the clips' rows apart.  A clip's bits are those of the uniform launch of that clip alone.
+struct PfClip { int32_t row, T, off, pad; };
 bool launch_prefill_self_attention(const half_t *q, const half_t *k, const half_t *v, long ld, half_t *out, long ldo, half_t *ck,
-                                   half_t *cv, int B, int T, int H, int C, hipStream_t st);
+                                   half_t *cv, int B, int T, int H, int C, hipStream_t st, const PfClip *clips = nullptr);
 // q: fp16 [B*T][ldq]; ck, cv: the head-major cross K/V [b][h][S][64]; every query sees the S keys of its clip
 bool launch_prefill_cross_attention(const half_t *q, long ldq, const half_t *ck, const half_t *cv, half_t *out, long ldo, int B, int T,
-                                    int H, int S, hipStream_t st);
+                                    int H, int S, hipStream_t st, const PfClip *clips = nullptr);
 
 // numerics prototype of cross-attention on the encoder output itself (NH_OPT_ABSORBED_XATTN; k_xabs.hip): Wkv = the fused
 // [2 d][d] cross K/V projection (K rows first), bkv its bias, xa fp16 [B][S][d], U scratch fp16 [B][H][d]
@@ -441,13 +450,18 @@ inline int nh_logits_ld(int V) { return (V + 63) & ~63; }
 // pos_ptr != nullptr: i32 [B], the position of every sequence; the kernel advances those it stepped
 // 1 <= V <= NH_MAX_VOCAB (nh_create refuses larger vocabularies)
 // handled != nullptr: i32 [B], written by launch_pool_sample_step earlier in the same step; a sequence whose flag is set is left alone
+// pfx != nullptr (mode 2 only; nh_pool_prefix): i32 [B], the prefix length n of every row.  Row b probes at pos_ptr[b] == n, is
+// inside its prompt while pos_ptr[b] < n + prompt_len - 1 (positions below n consume the prefix: nothing is selected, the
+// position moves), and max_new counts from n + prompt_len.  The pointer goes by value, the lengths are read by the kernel.
 void launch_logit_step(const float *logits, int V, DecodeState s, RuleTokens tk, int B, int ctx, int cap,
                        int max_new, int prompt_len, int mode, float *partials, unsigned *tickets, int32_t *pos_ptr,
-                       hipStream_t st, const int32_t *handled = nullptr);
-// decode pool: sequence `row` restarts at position 0 with the prompt [t0, t1] (P = 2) or [t0, t1, t2] (P = 3);
+                       hipStream_t st, const int32_t *handled = nullptr, const int32_t *pfx = nullptr);
+// decode pool: sequence `row` restarts with the prompt [t0, t1] (P = 2) or [t0, t1, t2] (P = 3), at position 0 when pfx == nullptr;
 // detect_flag != nullptr: detect_flag[row] = detect (see PoolDetect)
+// pfx != nullptr: pfx[row] = n_prefix, the prompt goes to slots n_prefix .. of the row (ctx >= n_prefix + P; the caller copies
+// the n_prefix ids in front of it) and the row starts at position pos0 (0: the steps consume the prefix; n_prefix: one pass does)
 void launch_pool_admit(DecodeState s, int32_t *pos, unsigned *tickets, int row, int ctx, int t0, int t1, int t2, int P, hipStream_t st,
-                       int32_t *detect_flag = nullptr, int detect = 0);
+                       int32_t *detect_flag = nullptr, int detect = 0, int32_t *pfx = nullptr, int n_prefix = 0, int pos0 = 0);
 // decode pool, sampled rows: how each row draws its tokens.  All device pointers, [B]; inv_t == 0: the row is greedy.
 struct PoolSampling {
     float *inv_t;
@@ -456,14 +470,17 @@ struct PoolSampling {
     int32_t *handled;       // written every step by pool_sample_step_kernel: 1 = it generated this row's token
 };
 // decode pool: sequence `row` decodes its clip again from position 0, sampled at 1 / inv_t; its prompt tokens [0, P) stay
-// (a detected language among them: detect_flag[row], when given, is cleared)
+// (a detected language among them: detect_flag[row], when given, is cleared).  pfx != nullptr: from position pfx[row], on the
+// self K/V its prefix left in the cache
 void launch_pool_retry(DecodeState s, int32_t *pos, unsigned *tickets, PoolSampling ps, int row, int P, float inv_t,
-                       unsigned long long seed, unsigned clip, unsigned attempt, hipStream_t st, int32_t *detect_flag = nullptr);
+                       unsigned long long seed, unsigned clip, unsigned attempt, hipStream_t st, int32_t *detect_flag = nullptr,
+                       const int32_t *pfx = nullptr);
 // decode pool: launch_sample_step for the rows that are sampled (inv_t > 0), running and at a generation position
 // (pos[b] >= prompt_len - 1); advances pos[b] of those and writes ps.handled[b] for every row.  Runs ahead of
 // launch_logit_step(mode 2, handled = ps.handled), which does the probe, the prompt positions and the greedy rows.
+// pfx: as launch_logit_step's (row b's prompt_len is pfx[b] + prompt_len).
 void launch_pool_sample_step(const float *logits, int V, DecodeState s, RuleTokens tk, int B, int ctx, int cap, int max_new,
-                             int prompt_len, PoolSampling ps, int32_t *pos, hipStream_t st);
+                             int prompt_len, PoolSampling ps, int32_t *pos, hipStream_t st, const int32_t *pfx = nullptr);
 // t > 0: one SAMPLED token per sequence (model.rs:340-348) under the seeded contract of include/norma_hip.h;
 // sequence b draws with clip id clip0 + b, step = its current token count
 void launch_sample_step(const float *logits, int V, DecodeState s, RuleTokens tk, int B, int ctx, int cap, int max_new,
@@ -504,8 +521,9 @@ struct GuardBufs {
 // Goes between the step's logits [R][nh_logits_ld(V)] and the selection kernels.  Edits the rows with done == 0 that stand at
 // a generation position (pos == nullptr: all of them; decode pool: pos[r] >= prompt_len - 1); the pad columns, every other
 // row and all decode state but loop_exit stay as they are.  max_target_positions <= NH_GUARD_MAX_HISTORY.
+// pfx (with pos only; nh_pool_prefix): i32 [R], row r's prompt_len is pfx[r] + prompt_len.
 void launch_guard(float *logits, int V, DecodeState s, RuleTokens tk, int R, int ctx, int prompt_len, const int32_t *pos, GuardSpec g,
-                  GuardBufs gb, hipStream_t st);
+                  GuardBufs gb, hipStream_t st, const int32_t *pfx = nullptr);
 // parity helper: apply rules to one already soft-maxed probability vector
 void launch_rules_only(const float *probs_in, float *masked_out, int32_t *argmax_out, const int32_t *tokens,
                        int n_tokens, int last_ts, const uint8_t *suppress, RuleTokens tk, int V, hipStream_t st);

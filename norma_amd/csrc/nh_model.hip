@@ -49,6 +49,7 @@ nh_ctx::~nh_ctx() {
     for (auto &e : gemm_ev) hipEventDestroy(e);
     if (enc_done) hipEventDestroy(enc_done);
     if (h_done) hipHostFree(h_done);
+    if (pfx_host) hipHostFree(pfx_host);
     if (st) hipStreamDestroy(st);
 }   // ... then the arena and every DevBuf free themselves, and the last context of a model frees its weights (~nh_model)
 
@@ -170,6 +171,7 @@ static int build_context(std::shared_ptr<nh_model> mdl, int max_batch, nh_ctx **
     DA(ds.n_active, int32_t, 1); DA(suppress, uint8_t, V); DA(lpart, float, (long)B * 64); DA(ltick, unsigned, B); DA(d_pos, int32_t, B);
     DA(psamp.inv_t, float, B); DA(psamp.seed, unsigned long long, B); DA(psamp.clip, unsigned, B); DA(psamp.attempt, unsigned, B); DA(psamp.handled, int32_t, B);
     DA(d_lang_tokens, int32_t, 256); DA(d_lang_out, int32_t, B); DA(d_lang_flag, int32_t, B); DA(d_lang_probs, float, (long)B * 256);
+    DA(d_pfx, int32_t, B); DA(d_pfclips, PfClip, B);
 #undef DA
     if (!ok) { ctx->err = "hipMalloc failed while sizing the context (out of device memory?)"; return bail(NH_ERR_NOMEM); }
     ctx->ds.suppress = ctx->suppress;

@@ -19,6 +19,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NORMA_HIP_LIB") or os.path.join(_HERE, "libnorma_hip.so")
 STRICT_LIB_PATH = os.path.join(_HERE, "libnorma_hip_strict.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "norma_hip.h")
+# the decode pool's extensions to that ABI (nh_pool_prefix): a header of its own that includes the first, same library (the
+# first header's prototype list is pinned by tests/test_cabi_cpu.py; why, in full: the top of norma_hip_pool.h)
+POOL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "norma_hip_pool.h")
 
 _H = cabi.read(HEADER_PATH)
 # every integer #define of the header under its own name: NH_OPT_*, NH_DTYPE_*, NH_SAMPLE_*, NH_ERR_*, NH_LANG_DETECT, NH_CUT_HOP, ...
@@ -67,6 +70,11 @@ def declared_symbols() -> List[str]:
     return sorted(_H.prototypes)
 
 
+def pool_declared_symbols() -> List[str]:
+    """Every function include/norma_hip_pool.h declares on top of those"""
+    return sorted(cabi.read(POOL_HEADER_PATH).prototypes)
+
+
 _lib = None
 
 
@@ -80,6 +88,7 @@ def load_library() -> C.CDLL:
             "(hipcc --offload-arch=gfx950).  norma_amd has no CPU fallback.")
     L = C.CDLL(LIB_PATH)
     cabi.bind(L, HEADER_PATH, _ADDRESSES)
+    cabi.bind(L, POOL_HEADER_PATH)
     _lib = L
     return L
 
@@ -461,6 +470,12 @@ class HipWhisper:
         """the clip that row `row` last decoded (collected, not refilled since) decodes again, sampled at `temperature` under
         the seeded contract of decode_sampled with this clip id and attempt; the row is busy again"""
         self._chk(self.L.nh_pool_retry(self._h, int(row), float(temperature), int(seed), int(clip), int(attempt)))
+
+    def pool_prefix(self, row: int, ids: Optional[Sequence[int]]):
+        """nh_pool_prefix (include/norma_hip_pool.h): the token ids (taken verbatim) that the next admission into the free row `row` puts in front of
+        [sot, lang?, task]; one-shot; None or an empty list clears the row's pending prefix.  The row's result excludes them."""
+        a = np.ascontiguousarray(ids if ids is not None else [], dtype=np.int32).reshape(-1)
+        self._chk(self.L.nh_pool_prefix(self._h, int(row), _ip(a) if len(a) else None, len(a)))
 
     def pool_detect_languages(self, lang_tokens: Sequence[int]):
         """the pool's language table (Language::iter() order), after pool_begin(per_clip_language=True) and while no row is

@@ -9,7 +9,7 @@ run loop (_Pool._run) over a source of encoded clips; run(.., on_result=f) calls
 
 engine methods used: pool_begin(rows, max_new, per_clip_language), pool_admit(src_row, dst_row, lang),
 pool_step(n) -> flags per row (0 running, 1 / 2 finished, 3 empty), pool_collect(rows) -> [result],
-pool_retry(row, temperature, seed, clip, attempt) (only with fallback=True),
+pool_retry(row, temperature, seed, clip, attempt) (only with fallback=True), pool_prefix(row, ids) (only with prefix=...),
 pool_detect_languages(lang_tokens) and pool_languages(rows) -> (tokens, probs) (only with detect_languages=...),
 and the caller's encode(first_clip, n_clips, row0, must) which must leave clips first .. first + n - 1 encoded in rows
 row0 ... -- or, when `must` is false, may return False to say "the encoder is busy, ask again" (several pools share one GPU:
@@ -45,6 +45,20 @@ avg_logprob -- the counterpart of the reference's dead `compression_ratio > thre
 no_speech_prob clause.  Without these keywords none of the three engine methods is called.  Like the alignment heads and the
 language table, the guard and the rows' bias lists stay set on the engine after run(): a caller that goes on to use the
 context otherwise switches them off itself (set_guard(None), guard_bias(row, None)).
+
+prefix=<callable (clip, prev) -> token ids | None> gives a clip its own decoder prompt prefix ("Pool rows"; the
+engine's nh_pool_prefix): asked right before the clip's admission, after its bias; a non-empty answer goes to
+pool_prefix(row, ids), and the clip's result is the sequence from sot on, as under set_prompts.  Every row has its own
+length; the engine consumes the prefixes of the rows admitted between two steps in one ragged pass.  A clip that has a prefix
+cannot detect its language (the engine refuses NH_LANG_DETECT into such a row): give it one in `langs`.  prefix together with
+align_heads is a ValueError: nh_align_decoded does not cover prompted decodes.
+after=<callable clip -> earlier clip index | None> orders clips that depend on one another -- the chunks of one recording, each
+decoded under the text of the chunk before it, among many recordings in flight: clip c is admitted only once that clip's
+result is final (under fallback=True: once _settle accepted or dropped it), and `prev` of the prefix callable is that result
+(None without `after`, or where it answers None).  Admission stays in clip order: the pool holds c and everything behind it
+meanwhile, which cannot deadlock, since the predecessor was admitted earlier.  An index >= clip is a ValueError.
+condition_on_previous(startofprev, eot) below is the prefix callable of host.Model's history rule.  Without the two keywords
+neither callable exists and pool_prefix is never called.
 """
 import queue
 import threading
@@ -53,6 +67,25 @@ from typing import Callable, List, Optional, Sequence
 from .hip import NH_LANG_DETECT
 
 TEMPERATURES = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0)   # m::TEMPERATURES of model.rs:175 (LOGPROB_THRESHOLD -1, NO_SPEECH_THRESHOLD 0.6)
+
+
+def condition_on_previous(startofprev: int, eot: int, max_prefix: int = 223):
+    """The `prefix` callable that conditions a clip on the text of the clip `after` names: [startofprev] + the text ids (< eot)
+    of prev["tokens"] behind its prompt, cut to the last max_prefix - 1 (223 = max_target_positions / 2 - 1 of every Whisper).
+    None -- no prefix -- without a prev, and when prev was a no-speech exit, was not accepted, was accepted above t = 0.5 (what
+    it says is not to be trusted as context: host.Model's history rule, DESIGN.md 13 "Layers above"), or holds no text."""
+    assert max_prefix >= 2
+
+    def prefix(clip: int, prev: Optional[dict]):
+        if prev is None or prev.get("no_speech_exit") or not prev.get("accepted", True) or prev.get("temperature", 0.0) > 0.5:
+            return None
+        toks = list(prev["tokens"])
+        p = 0
+        while p < len(toks) and toks[p] > eot:   # [sot, lang?, task]: the special ids above eot that open every result
+            p += 1
+        text = [int(t) for t in toks[p:] if t < eot]
+        return [int(startofprev)] + text[-(max_prefix - 1):] if text else None
+    return prefix
 
 
 def _has_loop_exit(guard: Optional[dict]) -> bool:
@@ -64,8 +97,12 @@ class _Pool:
     """what both pools are: the per-row policy on a collected result, and the one run loop over a source of encoded clips"""
 
     def __init__(self, engine, rows, max_new_tokens, check_every, per_clip_language, fallback, seed, clip0, temperatures,
-                 logprob_threshold, no_speech_threshold, detect_languages, align_heads, guard, bias, loop_fallback):
+                 logprob_threshold, no_speech_threshold, detect_languages, align_heads, guard, bias, loop_fallback,
+                 prefix=None, after=None):
         assert rows >= 1 and check_every >= 1
+        if prefix is not None and align_heads is not None:
+            raise ValueError("align_heads with prefix: nh_align_decoded does not cover prompted decodes")
+        self.prefix_of, self.after_of = prefix, after
         self.e, self.rows, self.check_every = engine, rows, check_every
         self.max_new, self.per_clip_language = max_new_tokens, per_clip_language
         self.fallback, self.seed, self.clip0 = bool(fallback), int(seed), int(clip0)
@@ -172,8 +209,21 @@ class _Pool:
                 if not more:
                     break
                 if owner[r] < 0:
+                    prev = None
+                    if self.after_of is not None:
+                        p = self.after_of(clip)
+                        if p is not None:
+                            if not 0 <= p < clip:
+                                raise ValueError(f"after({clip}) = {p}: a clip can only follow an earlier clip")
+                            prev = results[p]
+                            if prev is None:       # its predecessor decodes still (or is on a retry): hold this clip and all behind it
+                                break
                     if self.bias_of is not None:   # the clip's bias list goes to its row first (None or {}: the row's list is cleared)
                         e.guard_bias(r, self.bias_of(clip))
+                    if self.prefix_of is not None:
+                        ids = self.prefix_of(clip, prev)
+                        if ids is not None and len(ids):
+                            e.pool_prefix(r, [int(t) for t in ids])
                     more = src.admit(clip, r, self._admit_lang(r, clip, langs)) and clip + 1 < n_clips
                     owner[r], attempt[r] = clip, 0
                     clip += 1
@@ -228,10 +278,13 @@ class DecodePool(_Pool):
                  per_clip_language: bool = False, fallback: bool = False, seed: int = 0, clip0: int = 0,
                  temperatures: Sequence[float] = TEMPERATURES, logprob_threshold: float = -1.0, no_speech_threshold: float = 0.6,
                  detect_languages: Optional[Sequence[int]] = None, align_heads: Optional[Sequence] = None,
-                 guard: Optional[dict] = None, bias: Optional[Callable[[int], Optional[dict]]] = None, loop_fallback: bool = False):
+                 guard: Optional[dict] = None, bias: Optional[Callable[[int], Optional[dict]]] = None, loop_fallback: bool = False,
+                 prefix: Optional[Callable[[int, Optional[dict]], Optional[Sequence[int]]]] = None,
+                 after: Optional[Callable[[int], Optional[int]]] = None):
         assert staging >= 1
         super().__init__(engine, rows, max_new_tokens, check_every, per_clip_language, fallback, seed, clip0, temperatures,
-                         logprob_threshold, no_speech_threshold, detect_languages, align_heads, guard, bias, loop_fallback)
+                         logprob_threshold, no_speech_threshold, detect_languages, align_heads, guard, bias, loop_fallback,
+                         prefix=prefix, after=after)
         self.staging = staging
 
     def run(self, n_clips: int, encode: Callable[[int, int, int, bool], Optional[bool]], langs: Optional[Sequence[Optional[int]]] = None,
@@ -306,10 +359,13 @@ class FedDecodePool(_Pool):
                  per_clip_language: bool = False, fallback: bool = False, seed: int = 0, clip0: int = 0,
                  temperatures: Sequence[float] = TEMPERATURES, logprob_threshold: float = -1.0, no_speech_threshold: float = 0.6,
                  detect_languages: Optional[Sequence[int]] = None, align_heads: Optional[Sequence] = None,
-                 guard: Optional[dict] = None, bias: Optional[Callable[[int], Optional[dict]]] = None, loop_fallback: bool = False):
+                 guard: Optional[dict] = None, bias: Optional[Callable[[int], Optional[dict]]] = None, loop_fallback: bool = False,
+                 prefix: Optional[Callable[[int, Optional[dict]], Optional[Sequence[int]]]] = None,
+                 after: Optional[Callable[[int], Optional[int]]] = None):
         assert batch >= 1 and len(encoders) >= 1
         super().__init__(engine, rows, max_new_tokens, check_every, per_clip_language, fallback, seed, clip0, temperatures,
-                         logprob_threshold, no_speech_threshold, detect_languages, align_heads, guard, bias, loop_fallback)
+                         logprob_threshold, no_speech_threshold, detect_languages, align_heads, guard, bias, loop_fallback,
+                         prefix=prefix, after=after)
         self.encoders, self.batch = list(encoders), batch
 
     def run(self, n_clips: int, encode: Callable[[int, int, int], None], langs: Optional[Sequence[Optional[int]]] = None,

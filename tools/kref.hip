@@ -203,6 +203,65 @@ int kref_prefill_cross_attention(const void *q, long ldq, void *ck, void *cv, vo
     return launched ? (int)b.err : -1;
 }
 
+// The ragged forms of the two launches above.  clips i32 [n][4] = {context row, T, packed offset, 0} per clip; q (k, v) hold
+// m_rows packed rows of ld halfs and out m_rows rows of ldo (m_rows >= the rows the table covers: the rest are a test's
+// canaries); the caches have cache_rows context rows.  -1, nothing launched: a table that would read or write outside those
+// buffers, or whose clips' rows overlap.
+static bool kref_clip_table(const int32_t *clips, int n, int m_rows, int cache_rows, int limit, int &Tmax) {
+    Tmax = 0;
+    if (!clips || n < 1) return false;
+    for (int i = 0; i < n; i++) {
+        const int32_t *c = clips + 4 * i;
+        if (c[0] < 0 || c[0] >= cache_rows || c[1] < 1 || c[1] > limit || c[2] < 0 || (long)c[2] + c[1] > m_rows) return false;
+        for (int j = 0; j < i; j++) {
+            const int32_t *e = clips + 4 * j;
+            if (e[0] == c[0] || (c[2] < e[2] + e[1] && e[2] < c[2] + c[1])) return false;
+        }
+        Tmax = c[1] > Tmax ? c[1] : Tmax;
+    }
+    return true;
+}
+
+int kref_prefill_self_attention_ragged(const void *q, const void *k, const void *v, long ld, void *out, long ldo, void *ck, void *cv,
+                                       const int32_t *clips, int n, int m_rows, int cache_rows, int H, int C) {
+    int Tmax = 0;
+    if (H < 1 || C < 1 || m_rows < 1 || ld < (long)H * NH_DH || ldo < (long)H * NH_DH || !kref_clip_table(clips, n, m_rows, cache_rows, C, Tmax)) return -1;
+    Bufs b;
+    Stream st;
+    const size_t in_bytes = (size_t)((m_rows - 1) * ld + (long)H * NH_DH) * 2, out_bytes = (size_t)m_rows * ldo * 2;
+    const size_t cache_bytes = (size_t)cache_rows * H * C * NH_DH * 2;
+    const half_t *dq = b.in<half_t>(q, in_bytes), *dk = b.in<half_t>(k, in_bytes), *dv = b.in<half_t>(v, in_bytes);
+    half_t *dout = b.in<half_t>(out, out_bytes), *dck = b.in<half_t>(ck, cache_bytes), *dcv = b.in<half_t>(cv, cache_bytes);
+    const PfClip *dtab = b.in<PfClip>(clips, sizeof(PfClip) * n);
+    KREF_CHECK(b);
+    const bool launched = launch_prefill_self_attention(dq, dk, dv, ld, dout, ldo, dck, dcv, n, Tmax, H, C, st.s, dtab);
+    if (hipError_t e = st.finish()) return (int)e;
+    b.out(out, dout, out_bytes);
+    b.out(ck, dck, cache_bytes);
+    b.out(cv, dcv, cache_bytes);
+    return launched ? (int)b.err : -1;
+}
+
+int kref_prefill_cross_attention_ragged(const void *q, long ldq, void *ck, void *cv, void *out, long ldo, const int32_t *clips, int n,
+                                        int m_rows, int cache_rows, int H, int S) {
+    int Tmax = 0;
+    if (H < 1 || S < 1 || m_rows < 1 || ldq < (long)H * NH_DH || ldo < (long)H * NH_DH || !kref_clip_table(clips, n, m_rows, cache_rows, 1 << 20, Tmax)) return -1;
+    Bufs b;
+    Stream st;
+    const size_t q_bytes = (size_t)((m_rows - 1) * ldq + (long)H * NH_DH) * 2, out_bytes = (size_t)m_rows * ldo * 2;
+    const size_t kv_bytes = (size_t)cache_rows * H * S * NH_DH * 2;
+    const half_t *dq = b.in<half_t>(q, q_bytes);
+    half_t *dck = b.in<half_t>(ck, kv_bytes), *dcv = b.in<half_t>(cv, kv_bytes), *dout = b.in<half_t>(out, out_bytes);
+    const PfClip *dtab = b.in<PfClip>(clips, sizeof(PfClip) * n);
+    KREF_CHECK(b);
+    const bool launched = launch_prefill_cross_attention(dq, ldq, dck, dcv, dout, ldo, n, Tmax, H, S, st.s, dtab);
+    if (hipError_t e = st.finish()) return (int)e;
+    b.out(out, dout, out_bytes);
+    b.out(ck, dck, kv_bytes);
+    b.out(cv, dcv, kv_bytes);
+    return launched ? (int)b.err : -1;
+}
+
 // launch_gemm (kernel128 = 0) or launch_gemm_128: A is a buffer of a_bytes that the row map (a_rpb, a_bstride, lda) reads,
 // out0..2 buffers of out_bytes each (copied in and back), pos f32 [S][N] for EPI_CONV2_F32
 int kref_gemm(int kernel128, const void *A, size_t a_bytes, long lda, int a_rpb, long a_bstride, const void *W, const float *bias,
