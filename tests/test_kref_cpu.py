@@ -159,11 +159,14 @@ def _make_wrapper_library():
 
 
 def test_make_builds_the_wrapper_library_with_every_entry_point():
+    import pool_ref
     _make_wrapper_library()
-    assert os.path.exists(K.LIB_PATH)
-    syms = subprocess.run(["nm", "-D", "--defined-only", K.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in syms.splitlines() if " T " in line}
-    assert set(K.WRAPPERS) <= exported, set(K.WRAPPERS) - exported
+    subprocess.check_call(["make", "-C", os.path.join(K.ROOT, "tools"), "bin/libnh_kref_pool.so"], stdout=subprocess.DEVNULL)
+    for path, wrappers in ((K.LIB_PATH, K.WRAPPERS), (pool_ref.LIB_PATH, pool_ref.WRAPPERS)):   # the pool step's library too
+        assert os.path.exists(path)
+        syms = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        exported = {line.split()[-1] for line in syms.splitlines() if " T " in line}
+        assert set(wrappers) <= exported, set(wrappers) - exported
 
 
 # ---- the decode GEMV dispatch (norma_amd/csrc/skinny_plan.h), asked through the wrapper library: pure host code, no GPU ------
